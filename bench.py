@@ -18,8 +18,10 @@ region (counters are summed by a separate kernel before and after it).  `rooflin
 kernel against the 8 TB/s HBM roofline with SURVEY §8(d)'s algorithmic bytes (389 B per 1-player
 env-step, 774 B per 2-player one) over the SAME wall clock as `value`; `launch_us_events` /
 `frac_kernel` give the same two figures from HIP events on the launch stream.
-`cpu_baseline` times the reference C++ backend itself (oracle/_ref, built in the container from
-/root/reference) or, without it, the C restatement, on the host cores of this box.
+`--full` adds what takes runs of its own beside the timed launches: `cpu_baseline` (the reference C++ backend itself,
+oracle/_ref, when it was built, or else the C restatement, on the host cores of this box) and the GPU-paced extra run
+(`roofline.launch_us_gpu_paced`).  A plain run leaves them out (`cpu_baseline` is null).
+`--dump-outputs DIR` writes what the K timed launches left behind, as a caller of the rollout receives it (see dump_outputs).
 """
 import argparse
 import json
@@ -37,6 +39,27 @@ import __graft_entry__ as ge  # noqa: E402
 
 ALGO_BYTES = {1: 389, 2: 774}       # P*(192 read + 192 write) + 2 action + (P+2) outputs
 HBM_PEAK_GBS = 8000.0               # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_GAMES = 8192                   # --dump-outputs: games observed (a fixed, seeded sample where the batch is larger)
+DUMP_FIELDS = ("field", "grid", "x", "y", "next", "dead", "reward", "inc_count", "combo_count", "combo_remaining", "time_ms",
+               "incoming", "piece_draws", "hole_draws", "lines_sent", "lines_cleared")     # the record fields smoke() checks
+
+
+def dump_outputs(out_dir, batch, counters):
+    """--dump-outputs: the state the timed launches left, read back through TetrisBatch.observe as a caller would, for
+    DUMP_GAMES games (all games of a smaller batch; else a sample drawn with a fixed seed, so every run picks the same games),
+    plus the rollout counters of the timed launches.  One DIR/<name>.npy per array: float32, or float64 where float32 would
+    round (counters, clocks, draw counts).  `field` is cut to the board's height."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = batch.n_games
+    idx = np.arange(n) if n <= DUMP_GAMES else np.sort(np.random.default_rng(0).choice(n, DUMP_GAMES, replace=False))
+    rec, round_over, last_winner = batch.observe(idx.astype(np.int32))
+    out = {"counters": np.asarray(counters, np.float64),            # env-steps, episodes, lines cleared, garbage sent
+           "round_over": round_over.astype(np.float32), "last_winner": last_winner.astype(np.float32)}
+    for f in DUMP_FIELDS:
+        a = rec[f][:, :, :batch.height] if f == "field" else rec[f]
+        out[f] = a.astype(np.float64 if a.dtype.itemsize >= 4 else np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(n_players, height, budget_s):
@@ -112,6 +135,8 @@ def bench_split(args, mod, dist, rank, world, local_rank):
     before = [int(x) for x in so.batch.rollout_totals()]
     dist.barrier()
     wall = so.rollout(args.steps, first_step=args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, so.batch, [int(x) - b for x, b in zip(so.batch.rollout_totals(), before)])
     dist.barrier()
     dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
     t = torch.tensor([wall], dtype=torch.float64, device=dev)
@@ -216,14 +241,18 @@ def main():
     ap.add_argument("--players", type=int, default=1)
     ap.add_argument("--height", type=int, default=20)
     ap.add_argument("--steps-per-launch", type=int, default=1, help=">1 = fused rollout (state stays in registers)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: cpu_baseline and the GPU-paced extra run (a plain run does neither)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they left (sampled games) and their counters as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: budget of the cpu_baseline leg (0 = skip)")
     ap.add_argument("--precondition-ms", type=float, default=40.0,
                     help="before the W warm-up steps: this many ms of the same launches on a SCRATCH batch (device clocks take tens of ms "
                          "to leave their idle state; the measured batch, its W warm-up steps and its K timed steps are untouched by it). 0 = off")
     ap.add_argument("--workload", choices=["sharded", "split"], default="sharded",
                     help="sharded (default): every rank owns whole games, no collective.  split: BASELINE config 5 — ranks 2k and 2k+1 "
                          "hold player 0 / player 1 of the same games, garbage exchange by three RCCL all-gathers per step (even N only)")
-    ap.add_argument("--no-gpu-paced", action="store_true", help="skip the extra GPU-paced run after the timed region (profiling runs)")
+    ap.add_argument("--no-gpu-paced", action="store_true", help="with --full: skip the extra GPU-paced run after the timed region (profiling runs)")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -299,6 +328,8 @@ def main():
         shard.run(args.warmup, S)                     # untimed warm-up
     res = shard.run(args.steps, S)                    # exactly K timed launches
     counters, wall, ev_ms = res["counters"], res["wall_s"], res["event_ms"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, shard.batch, counters)     # before anything else steps the batch
     direct = bool(shard.batch.rollout_was_direct())       # (asked now: the GPU-paced extra run below goes through the streams)
     affine = bool(shard.batch.rollout_was_affine())       # the XCD-affine kernels (include/tetris_hip.h: tetris_set_xcd_affine)
     batch = shard
@@ -307,7 +338,7 @@ def main():
     # cost (2.5-5 us per launch, it varies between processes and boxes and sets the pace where it exceeds the GPU's period)
     # does not enter.  Reported beside the wall-clock figures, never as `value`.
     gpu_paced_us = None
-    if world == 1 and S == 1 and not args.no_gpu_paced and shard.batch.rollout_is_chained(S) and os.environ.get("BENCH_LIB_PATH") is None:
+    if args.full and world == 1 and S == 1 and not args.no_gpu_paced and shard.batch.rollout_is_chained(S) and os.environ.get("BENCH_LIB_PATH") is None:
         os.environ["TETRIS_PREQUEUE"] = "1"
         try:
             shard.run(64, S)
@@ -415,7 +446,7 @@ def main():
             "library": os.path.relpath(lib_path, ROOT) if lib_path.startswith(ROOT) else lib_path,
             "device": capi.device_name(local_rank, os.environ.get("BENCH_LIB_PATH")),
         }
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             line["cpu_baseline"] = cpu_baseline(P, args.height, args.cpu_seconds)
         else:
             line["cpu_baseline"] = None

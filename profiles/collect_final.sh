@@ -1,9 +1,9 @@
 #!/bin/bash
-# Copies the judged summaries of a profiles/final_round.sh run from gpurun_out/final (scratch) into profiles/<round>/final
+# Copies the judged summaries of a profiles/final_round.sh run from its output folder (OUT, default profiles/_final) into profiles/<round>/final
 # and refreshes profiles/pmc_p{1,2}_s1.json (read by bench.py for roofline.traffic).   usage: profiles/collect_final.sh r01
 set -e
 cd "$(dirname "$0")/.."
-R=${1:-r01}; SRC=gpurun_out/final; DST=profiles/$R/final
+R=${1:-r01}; SRC=${OUT:-profiles/_final}; DST=profiles/$R/final
 mkdir -p $DST
 cp $SRC/bench_p1_s1.json $SRC/bench_p2_s1.json $SRC/bench_p1_s32.json $SRC/bench_configs.json $DST/
 cp $SRC/pytest_gpu.log $DST/pytest_gpu.txt

@@ -9,20 +9,20 @@ mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1 || { tail -30 $O/pytest_gpu.log; exit 1; }
 tail -1 $O/pytest_gpu.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout -k 10 300 python bench.py > $O/bench_p1_s1.json 2> $O/bench_p1_s1.err
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_p1_s1_driver_flags.json 2>/dev/null
+timeout -k 10 300 python bench.py --full > $O/bench_p1_s1.json 2> $O/bench_p1_s1.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_p1_s1_driver_flags.json 2>/dev/null
 timeout -k 10 200 python bench.py --players 2 --cpu-seconds 0 > $O/bench_p2_s1.json 2>/dev/null
 timeout -k 10 200 python bench.py --steps 256 --warmup 8 --steps-per-launch 32 --cpu-seconds 0 > $O/bench_p1_s32.json 2>/dev/null
 timeout -k 10 400 python profiles/bench_configs.py > $O/bench_configs.json 2> $O/bench_configs.err
 R=$GRAFT_REPO_ROOT
 prof() { (cd /tmp; export TMPDIR=/tmp; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/$1 -- python3 "${@:2}" > $R/$O/$1.log 2>&1); }
-prof prof_p1 $R/bench.py --cpu-seconds 0
-prof prof_p2 $R/bench.py --cpu-seconds 0 --players 2
+prof prof_p1 $R/bench.py --full --cpu-seconds 0
+prof prof_p2 $R/bench.py --full --cpu-seconds 0 --players 2
 # one stream, launches replayed from HIP graphs (TETRIS_GRAPH=1): under the profiler a plain launch costs the host ~8 us, more
 # than the kernel takes; from a graph the kernels of the profiled run are back to back like those of the un-profiled one
 export TETRIS_NO_CHAIN=1 TETRIS_GRAPH=1
-prof prof_p1_unchained $R/bench.py --cpu-seconds 0
-prof prof_p2_unchained $R/bench.py --cpu-seconds 0 --players 2
+prof prof_p1_unchained $R/bench.py --full --cpu-seconds 0
+prof prof_p2_unchained $R/bench.py --full --cpu-seconds 0 --players 2
 unset TETRIS_NO_CHAIN TETRIS_GRAPH
 for c in enum_planar enum_rows enum_noafter_planar observe step_auto_1p step_auto_2p loop_1p step_obs_1p loop_2p step_obs_2p; do
   timeout -k 10 200 python profiles/kernel_prof.py $c > $O/kernel_$c.json 2>/dev/null

@@ -10,8 +10,8 @@ R=$GRAFT_REPO_ROOT
 timeout -k 10 1000 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1 || { tail -40 $O/pytest_gpu.log; exit 1; }
 tail -1 $O/pytest_gpu.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout -k 10 300 python bench.py > $O/bench_p1_s1.json 2> $O/bench_p1_s1.err
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_p1_s1_driver_flags.json 2>/dev/null
+timeout -k 10 300 python bench.py --full > $O/bench_p1_s1.json 2> $O/bench_p1_s1.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_p1_s1_driver_flags.json 2>/dev/null
 timeout -k 10 200 python bench.py --players 2 --cpu-seconds 0 > $O/bench_p2_s1.json 2>/dev/null
 # the same lines without the XCD-affine kernels (direct dispatch, write-through hand-over), then through hipLaunchKernel on streams
 TETRIS_AFFINE=0 timeout -k 10 300 python bench.py --cpu-seconds 0 > $O/bench_p1_s1_write_through.json 2>/dev/null
@@ -31,16 +31,16 @@ TETRIS_NO_CHAIN=1 timeout -k 10 200 python bench.py --cpu-seconds 0 > $O/bench_p
 TETRIS_NO_CHAIN=1 timeout -k 10 200 python bench.py --players 2 --cpu-seconds 0 > $O/bench_p2_s1_unchained.json 2>/dev/null
 timeout -k 10 200 python bench.py --steps 256 --warmup 8 --steps-per-launch 32 --cpu-seconds 0 > $O/bench_p1_s32.json 2>/dev/null
 prof() { (cd /tmp; export TMPDIR=/tmp; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/$1 -- python3 "${@:2}" > $R/$O/$1.log 2>&1); }
-prof prof_p1 $R/bench.py --cpu-seconds 0
-prof prof_p2 $R/bench.py --cpu-seconds 0 --players 2
+prof prof_p1 $R/bench.py --full --cpu-seconds 0
+prof prof_p2 $R/bench.py --full --cpu-seconds 0 --players 2
 python profiles/chain_period_from_trace.py $O/prof_p1 $O/chain_period_from_trace_p1.json > /dev/null
 # (under the profiler the launches stay on the streams: forced onto the library's queues — TETRIS_DIRECT_UNDER_TOOLS=1 — the --pmc passes of
 # r03_final_c.sh went through, a --kernel-trace --stats run died inside the tool's doorbell handler: profiles/r03/direct_dispatch.txt (5))
 python profiles/chain_period_from_trace.py $O/prof_p2 $O/chain_period_from_trace_p2.json > /dev/null
 grep -h period_us_of $O/chain_period_from_trace_p1.json $O/chain_period_from_trace_p2.json
 export TETRIS_NO_CHAIN=1 TETRIS_GRAPH=1
-prof prof_p1_unchained $R/bench.py --cpu-seconds 0
-prof prof_p2_unchained $R/bench.py --cpu-seconds 0 --players 2
+prof prof_p1_unchained $R/bench.py --full --cpu-seconds 0
+prof prof_p2_unchained $R/bench.py --full --cpu-seconds 0 --players 2
 unset TETRIS_NO_CHAIN TETRIS_GRAPH
 timeout -k 10 200 python profiles/split_stages.py > $O/split_stages.json 2>/dev/null; cat $O/split_stages.json
 prof prof_split $R/profiles/split_stages.py 256

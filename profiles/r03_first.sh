@@ -10,11 +10,11 @@ timeout -k 10 300 python -m pytest tests/test_chain_fallback.py -m gpu -q -x > $
 tail -1 $O/pytest_fallback.log
 timeout -k 10 1000 python -m pytest tests -m gpu -q -x > $O/pytest_gpu.log 2>&1 || { tail -40 $O/pytest_gpu.log; exit 1; }
 tail -1 $O/pytest_gpu.log
-timeout -k 10 300 python bench.py > $O/bench_p1_s1.json 2> $O/bench_p1_s1.err
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_p1_s1_driver_flags.json 2>/dev/null
+timeout -k 10 300 python bench.py --full > $O/bench_p1_s1.json 2> $O/bench_p1_s1.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_p1_s1_driver_flags.json 2>/dev/null
 cut -c1-300 $O/bench_p1_s1.json
 prof() { (cd /tmp; export TMPDIR=/tmp; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/$1 -- python3 "${@:2}" > $R/$O/$1.log 2>&1); }
-prof prof_p1 $R/bench.py --cpu-seconds 0
+prof prof_p1 $R/bench.py --full --cpu-seconds 0
 python profiles/chain_period_from_trace.py $O/prof_p1 $O/chain_period_from_trace.json > /dev/null
 grep -h period_us $O/chain_period_from_trace.json | head -8
 (cd /tmp; rocprofv3 -L > $R/$O/counters_list.txt 2>&1 || true)

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 import __graft_entry__ as ge
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,10 +47,37 @@ def _check(line, world, games, steps, warmup, spl):
 
 
 def test_single_process_line_with_cpu_baseline():
-    line = _run([sys.executable, "bench.py", "--games", "1024", "--steps", "6", "--warmup", "2", "--cpu-seconds", "0.3"], {})
+    line = _run([sys.executable, "bench.py", "--full", "--games", "1024", "--steps", "6", "--warmup", "2", "--cpu-seconds", "0.3"], {})
     _check(line, 1, 1024, 6, 2, 1)
     cb = line["cpu_baseline"]
     assert cb["value"] > 0 and cb["cores"] >= 1 and cb["kind"] in ("reference", "port") and cb["unit"] == "env-steps/s" and cb["sample"]
+
+
+def test_plain_run_measures_the_timed_steps_only():
+    """Without --full the line carries the same headline fields, and neither cpu_baseline nor the GPU-paced extra run."""
+    line = _run([sys.executable, "bench.py", "--games", "1024", "--steps", "6", "--warmup", "2"], {})
+    _check(line, 1, 1024, 6, 2, 1)
+    assert line["cpu_baseline"] is None and "launch_us_gpu_paced" not in line["roofline"]
+
+
+def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: float32 / float64 .npy files of the state the timed steps left, identical for identical arguments,
+    and --steps sets the number of timed steps (the dumped counters count them)."""
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        line = _run([sys.executable, "bench.py", "--games", "1024", "--steps", "7", "--warmup", "2", "--dump-outputs", str(d)], {})
+        _check(line, 1, 1024, 7, 2, 1)
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == sorted(p.name for p in dirs[1].iterdir()) and {"counters.npy", "field.npy", "dead.npy"} <= set(names)
+    total = 0
+    for name in names:
+        a, b = np.load(dirs[0] / name), np.load(dirs[1] / name)
+        assert a.dtype in (np.float32, np.float64), name
+        assert a.shape == b.shape and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(dirs[0] / "counters.npy")[0] == 1024 * 7
+    assert np.load(dirs[0] / "field.npy").shape == (1024, 1, 20, 10)
 
 
 def test_two_ranks_under_torch_distributed_run():
