@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tetris_kernels.h"
+#include "tetris_plan.h"
 
 namespace te {}
 using namespace te;
@@ -41,5 +42,34 @@ __global__ __launch_bounds__(256) void k_game(KArgs a) {
     TE_STAMP(14); TE_STAMP_RT(15);
 }
 
+// The planning kernels (tetris_plan.h), one wave per workgroup with its own LDS copy of the shape table.
+// k_plan_sim: grid (ceil(N / 64), max_lists): wave = 64 consecutive games of one list index k, so that a wave whose k is past
+// every count in it leaves at once and the state loads and the column stores of a wave are coalesced rows.
+template <int P, bool TINT>
+__global__ __launch_bounds__(64) void k_plan_sim(PlanArgs pa, int fin) {
+    __shared__ uint32_t s_shapes[SHAPE_WORDS];
+    s_shapes[threadIdx.x] = d_shape_table.s[threadIdx.x];
+    __syncthreads();
+    const int i = blockIdx.x * 64 + threadIdx.x, k = blockIdx.y;
+    if (i < pa.a.n) plan_sim_lane<P, TINT>(pa, i, k, fin != 0, s_shapes, true);
+}
+// k_plan_step: one lane per game
+template <int P, bool TINT, bool AUTO>
+__global__ __launch_bounds__(64) void k_plan_step(PlanArgs pa) {
+    __shared__ uint32_t s_shapes[SHAPE_WORDS];
+    s_shapes[threadIdx.x] = d_shape_table.s[threadIdx.x];
+    __syncthreads();
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < pa.a.n) plan_step_lane<P, TINT, AUTO>(pa, i, s_shapes, true);
+}
+template <int P, bool TINT>
+static void launch_plan(int which, dim3 grid, hipStream_t st, const PlanArgs& pa, int fin) {
+    if (which == 0) hipLaunchKernelGGL((k_plan_sim<P, TINT>), grid, dim3(64), 0, st, pa, fin);
+    else if (which == 1) hipLaunchKernelGGL((k_plan_step<P, TINT, false>), grid, dim3(64), 0, st, pa);
+    else hipLaunchKernelGGL((k_plan_step<P, TINT, true>), grid, dim3(64), 0, st, pa);
+}
+
 // launches k_game<P, mode, tint> for P = 3, 4 (tetris_hip_multi.hip)
 __attribute__((visibility("hidden"))) int tetris_launch_game_multi(int n_players, int tint, int mode, dim3 grid, dim3 block, hipStream_t stream, const te::KArgs& a);
+// launches the planning kernels for P = 3, 4 (tetris_hip_multi.hip); which: 0 simulate, 1 step, 2 step with auto-reset
+__attribute__((visibility("hidden"))) int tetris_launch_plan_multi(int n_players, int tint, int which, dim3 grid, hipStream_t stream, const te::PlanArgs& pa, int fin);

@@ -687,6 +687,88 @@ __global__ __launch_bounds__(64) void k_actions(Geo geo, int n, const int32_t* i
         actions_body<P>(geo, t, idx, player, H, d_shape_table.s, count, lens, keys, max_lists, max_keys, status);
 }
 
+// tetris_action_lists_dev: the slabs k_actions wrote for games g0 .. g0 + m - 1 -> the caller's [N][L][K] lists, one wave per
+// game (plan_compact_serial is the serial form of the same steps): prefix sum of the 40 slab counts in the reference's order,
+// every raw list hashed into LDS, each lane tests its lists against all earlier ones (hash first), ballots give the output
+// positions.  Nothing is written for a game that does not fit (count -1, F_LISTS).
+__global__ __launch_bounds__(64) void k_plan_lists(const uint8_t* cnt, const uint8_t* slab_lens, const uint8_t* slab_keys, int KS, int g0,
+                                                   int L, int K, int keep_null, int32_t* count, uint8_t* lens, uint8_t* keys,
+                                                   uint32_t* status) {
+    __shared__ int s_off[41];
+    __shared__ uint32_t s_hash[PLAN_RAW_MAX];
+    __shared__ uint16_t s_src[PLAN_RAW_MAX];           // slab entry of raw list m: (r * 10 + xi) * PLAN_LANE_LISTS + list
+    __shared__ uint8_t s_len[PLAN_RAW_MAX];
+    __shared__ uint8_t s_keep[PLAN_RAW_MAX];
+    const int lane = threadIdx.x;
+    const size_t t0 = (size_t)blockIdx.x * 40, g = (size_t)g0 + blockIdx.x;
+    const uint8_t* gkeys = slab_keys + t0 * PLAN_LANE_LISTS * (size_t)KS;
+    int c = lane < 40 ? cnt[t0 + plan_slab_lane(lane)] : 0;
+    const bool over = c > PLAN_LANE_LISTS;
+    if (over) c = 0;
+    int incl = c;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int v = __shfl_up(incl, d);
+        if (lane >= d) incl += v;
+    }
+    if (lane < 40) s_off[lane] = incl - c;
+    if (lane == 39) s_off[40] = incl;
+    bool bad = __ballot(over) != 0;
+    __syncthreads();
+    const int M = s_off[40];
+    bool my_bad = false, my_null = false;
+    for (int m = lane; m < M; m += 64) {
+        int lo = 0, hi = 40;                           // s_off[lo] <= m < s_off[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_off[mid] <= m) lo = mid; else hi = mid;
+        }
+        const int src = plan_slab_lane(lo) * PLAN_LANE_LISTS + (m - s_off[lo]);
+        const int len = slab_lens[t0 * PLAN_LANE_LISTS + src];
+        const uint8_t* k = gkeys + (size_t)src * KS;
+        my_bad |= len > K;
+        my_null |= plan_is_null(k, len);
+        s_hash[m] = plan_list_hash(k, len);
+        s_src[m] = (uint16_t)src;
+        s_len[m] = (uint8_t)len;
+    }
+    bad |= __ballot(my_bad) != 0;
+    const bool has_null = __ballot(my_null) != 0;
+    __syncthreads();
+    int n_sel = 0;
+    for (int base = 0; base < M && !bad; base += 64) {     // (bad and M are uniform)
+        const int m = base + lane;
+        bool sel = false;
+        if (m < M) {
+            const int len = s_len[m];
+            const uint32_t h = s_hash[m];
+            const uint8_t* k = gkeys + (size_t)s_src[m] * KS;
+            sel = keep_null || !plan_is_null(k, len);
+            for (int e = 0; e < m && sel; e++)
+                if (s_hash[e] == h && s_len[e] == len && plan_same_list(k, len, gkeys + (size_t)s_src[e] * KS, len)) sel = false;
+            s_keep[m] = (uint8_t)sel;
+        }
+        n_sel += __popcll(__ballot(sel));
+    }
+    const int o0 = (!keep_null || has_null) ? 0 : 1;
+    const int n_out = (o0 + n_sel) ? o0 + n_sel : 1;
+    if (bad || n_out > L) {
+        if (lane == 0) { count[g] = -1; plan_report_overflow(status); }
+        return;
+    }
+    int o = o0;
+    for (int base = 0; base < M; base += 64) {
+        const int m = base + lane;
+        const bool sel = m < M && s_keep[m];
+        const unsigned long long bal = __ballot(sel);
+        if (sel) plan_write_list(lens, keys, g, L, K, o + __popcll(bal & __lanemask_lt()), gkeys + (size_t)s_src[m] * KS, s_len[m]);
+        o += __popcll(bal);
+    }
+    if (lane == 0) {
+        if (o0 || !n_sel) plan_write_null(lens, keys, g, L, K);
+        count[g] = n_out;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_snapshot(Geo geo, int n, const int32_t* idx, uint32_t* blob, int restore) {
     size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < (size_t)n * (NGWORDS + geo.P * geo.nw)) snapshot_body(geo, t, idx, blob, restore);
@@ -893,6 +975,13 @@ struct tetris_batch {
     int gate_slot = 0;                   // event to record next
     int gate_pending[2] = {0, 0};        // event has been recorded and not waited for
     Stage s_idx, s_in0, s_in1, s_in2, s_out0, s_out1, s_out2, s_big, s_act0, s_act1, s_act2;
+    // tetris_action_lists_dev: device scratch for the slabs of one chunk of games (grown on demand), the identity index the
+    // chunks' k_actions launches read their game numbers from, and the status words k_actions writes its own overflow flag to
+    // (the compaction finds every overflow itself, per game, and reports it as F_LISTS instead)
+    uint8_t* d_plan_slabs = nullptr;
+    size_t plan_slab_cap = 0;
+    int32_t* d_iota = nullptr;
+    uint32_t* d_plan_status = nullptr;
 };
 // (TETRIS_GATE_GROUP in the environment: experiment knob, 8..120)
 static const int GATE_GROUP = [] { const char* e = getenv("TETRIS_GATE_GROUP"); const int v = e ? atoi(e) : TE_GATE_GROUP; return v < 8 ? 8 : (v > 120 ? 120 : v); }();
@@ -1186,6 +1275,7 @@ int tetris_destroy(tetris_batch* b) {
     free(b->h_chain);
     if (b->stall_stream) { (void)hipStreamSynchronize(b->stall_stream); (void)hipStreamDestroy(b->stall_stream); }
     if (b->direct_used) { aql::Device* dev = aql::device_for(b->device); if (dev->ok) aql::quiesce(dev->qs); }      // (a test's idle kernel may still sit there)
+    (void)hipFree(b->d_plan_slabs); (void)hipFree(b->d_iota); (void)hipFree(b->d_plan_status);
     Stage* all[] = {&b->s_idx, &b->s_in0, &b->s_in1, &b->s_in2, &b->s_out0, &b->s_out1, &b->s_out2, &b->s_big, &b->s_act0, &b->s_act1, &b->s_act2};
     for (Stage* s : all) s->release();
     if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -1518,8 +1608,9 @@ int tetris_take_errors(tetris_batch* b, uint32_t* bits) {
     if (!bits) return fail(TETRIS_E_ARG, "bits is NULL");
     if ((rc = finish_call(b))) return rc;
     volatile uint32_t* f = b->flags;
-    *bits = (f[F_FIFO] ? TETRIS_ERR_FIFO : 0u) | (f[F_EXHAUSTED] ? TETRIS_ERR_STREAM : 0u) | (b->chain_fell_back ? TETRIS_ERR_CHAIN_FELL_BACK : 0u);
-    f[F_FIFO] = 0; f[F_EXHAUSTED] = 0; b->chain_fell_back = false;
+    *bits = (f[F_FIFO] ? TETRIS_ERR_FIFO : 0u) | (f[F_EXHAUSTED] ? TETRIS_ERR_STREAM : 0u) | (b->chain_fell_back ? TETRIS_ERR_CHAIN_FELL_BACK : 0u) |
+            (f[F_LISTS] ? TETRIS_ERR_LISTS : 0u);
+    f[F_FIFO] = 0; f[F_EXHAUSTED] = 0; f[F_LISTS] = 0; b->chain_fell_back = false;
     return TETRIS_OK;
 }
 
@@ -2037,6 +2128,119 @@ int tetris_get_actions(tetris_batch* b, const int32_t* idx, int n, const uint8_t
         }
     }
     return result;
+}
+
+// ---------------------------------------------------------------- planning: action lists, simulated afterstates, list steps
+// Games per k_actions + k_plan_lists pair: bounds the slab scratch (40 x 16 slab entries of max_keys + 1 bytes per game: 128 MB
+// at 4 096 games and 48 keys); a batch of more games enqueues one pair per chunk, ordered by the stream.
+static const int PLAN_CHUNK = 4096;
+
+static int plan_check(tetris_batch* b, const char* what) {
+    if (b->split) return fail(TETRIS_E_ARG, std::string(what) + " is not available on split batches");
+    return TETRIS_OK;
+}
+
+static PlanArgs plan_args(tetris_batch* b, const uint8_t* d_player, const int32_t* d_count, const uint8_t* d_lens, const uint8_t* d_keys,
+                          int max_lists, int max_keys, int ms) {
+    PlanArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.a = base_args(b, b->N, nullptr);
+    pa.a.ms = ms;
+    pa.player = d_player; pa.count = d_count; pa.lens = d_lens; pa.keys = d_keys;
+    pa.max_lists = max_lists; pa.max_keys = max_keys;
+    return pa;
+}
+
+// which: 0 simulate, 1 step, 2 step with auto-reset
+static int launch_plan_kernel(tetris_batch* b, int which, dim3 grid, const PlanArgs& pa, int fin) {
+    if (b->P == 1) { if (b->tint) launch_plan<1, true>(which, grid, b->stream, pa, fin); else launch_plan<1, false>(which, grid, b->stream, pa, fin); }
+    else if (b->P == 2) { if (b->tint) launch_plan<2, true>(which, grid, b->stream, pa, fin); else launch_plan<2, false>(which, grid, b->stream, pa, fin); }
+    else if (tetris_launch_plan_multi(b->P, b->tint, which, grid, b->stream, pa, fin)) return fail(TETRIS_E_ARG, "no planning kernel for this player count");
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+int tetris_action_lists_dev(tetris_batch* b, const uint8_t* d_player, int max_lists, int max_keys, int flags, int32_t* d_count,
+                            uint8_t* d_lens, uint8_t* d_keys) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = plan_check(b, "tetris_action_lists_dev"))) return rc;
+    if (!d_count || !d_lens || !d_keys) return fail(TETRIS_E_ARG, "count/lens/keys are NULL");
+    if (max_lists < 1 || max_keys < 1 || max_keys > 254) return fail(TETRIS_E_ARG, "max_lists >= 1, 1 <= max_keys <= 254");
+    if (flags & ~TETRIS_LISTS_KEEP_NULL) return fail(TETRIS_E_ARG, "unknown flag");
+    const int chunk = b->N < PLAN_CHUNK ? b->N : PLAN_CHUNK;
+    const int KS = max_keys + 1;                 // one key more than the caller takes: a list that does not fit shows as one
+    const size_t lanes = (size_t)chunk * 40;
+    const size_t need = lanes + lanes * PLAN_LANE_LISTS + lanes * PLAN_LANE_LISTS * KS;
+    if (!b->d_iota) {
+        std::vector<int32_t> iota((size_t)b->N);
+        for (int i = 0; i < b->N; i++) iota[i] = i;
+        HIP_TRY(hipMalloc((void**)&b->d_iota, (size_t)b->N * 4));
+        HIP_TRY(hipMemcpy(b->d_iota, iota.data(), (size_t)b->N * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc((void**)&b->d_plan_status, NFLAGS * 4));
+    }
+    if (need > b->plan_slab_cap) {
+        if (b->d_plan_slabs) { HIP_TRY(hipStreamSynchronize(b->stream)); (void)hipFree(b->d_plan_slabs); }
+        b->d_plan_slabs = nullptr; b->plan_slab_cap = 0;
+        HIP_TRY(hipMalloc((void**)&b->d_plan_slabs, need));
+        b->plan_slab_cap = need;
+    }
+    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
+    uint8_t* s_cnt = b->d_plan_slabs;
+    uint8_t* s_len = s_cnt + lanes;
+    uint8_t* s_key = s_len + lanes * PLAN_LANE_LISTS;
+    const Geo geo = geo_of_batch(b);
+    for (int g0 = 0; g0 < b->N; g0 += chunk) {
+        const int m = b->N - g0 < chunk ? b->N - g0 : chunk;
+        const int32_t* d_idx = b->d_iota + g0;
+        const uint8_t* pl = d_player ? d_player + g0 : nullptr;
+        const dim3 grid((unsigned)(((size_t)m * 40 + 63) / 64)), block(64);
+#define LAUNCH_ACTIONS(PP) hipLaunchKernelGGL(k_actions<PP>, grid, block, 0, b->stream, geo, m, d_idx, pl, b->H, s_cnt, s_len, s_key, \
+                                              PLAN_LANE_LISTS, KS, b->d_plan_status)
+        if (b->P == 1) LAUNCH_ACTIONS(1);
+        else if (b->P == 2) LAUNCH_ACTIONS(2);
+        else if (b->P == 3) LAUNCH_ACTIONS(3);
+        else LAUNCH_ACTIONS(4);
+#undef LAUNCH_ACTIONS
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_plan_lists, dim3((unsigned)m), block, 0, b->stream, s_cnt, s_len, s_key, KS, g0, max_lists, max_keys,
+                           (flags & TETRIS_LISTS_KEEP_NULL) ? 1 : 0, d_count, d_lens, d_keys, b->flags);
+        HIP_TRY(hipGetLastError());
+    }
+    return TETRIS_OK;
+}
+
+int tetris_simulate_lists_dev(tetris_batch* b, const uint8_t* d_player, const int32_t* d_count, const uint8_t* d_lens, const uint8_t* d_keys,
+                              int max_lists, int max_keys, int ms, int flags, uint32_t* d_cols, uint8_t* d_done, uint8_t* d_lines,
+                              uint8_t* d_dead) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = plan_check(b, "tetris_simulate_lists_dev"))) return rc;
+    if (!d_count || !d_lens || !d_keys || !d_cols) return fail(TETRIS_E_ARG, "count/lens/keys/cols are NULL");
+    if (max_lists < 1 || max_lists > 65535 || max_keys < 1 || max_keys > 255) return fail(TETRIS_E_ARG, "1 <= max_lists <= 65535, 1 <= max_keys <= 255");
+    if (flags & ~TETRIS_SIM_FINALIZE) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
+    PlanArgs pa = plan_args(b, d_player, d_count, d_lens, d_keys, max_lists, max_keys, ms);
+    pa.cols = d_cols;
+    const int fin = (flags & TETRIS_SIM_FINALIZE) ? 1 : 0;
+    if (fin) { pa.a.done = d_done; pa.a.lines = d_lines; pa.a.dead = d_dead; }
+    return launch_plan_kernel(b, 0, dim3((unsigned)((b->N + 63) / 64), (unsigned)max_lists), pa, fin);
+}
+
+int tetris_step_lists_dev(tetris_batch* b, const uint8_t* d_player, const int32_t* d_choice, const int32_t* d_count, const uint8_t* d_lens,
+                          const uint8_t* d_keys, int max_lists, int max_keys, int ms, int flags, uint8_t* d_done, uint8_t* d_lines,
+                          uint8_t* d_dead) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = plan_check(b, "tetris_step_lists_dev"))) return rc;
+    if (!d_choice || !d_count || !d_lens || !d_keys) return fail(TETRIS_E_ARG, "choice/count/lens/keys are NULL");
+    if (max_lists < 1 || max_keys < 1 || max_keys > 255) return fail(TETRIS_E_ARG, "max_lists >= 1, 1 <= max_keys <= 255");
+    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
+    PlanArgs pa = plan_args(b, d_player, d_count, d_lens, d_keys, max_lists, max_keys, ms);
+    pa.choice = d_choice;
+    pa.a.done = d_done; pa.a.lines = d_lines; pa.a.dead = d_dead;
+    return launch_plan_kernel(b, (flags & TETRIS_STEP_AUTO_RESET) ? 2 : 1, dim3((unsigned)((b->N + 63) / 64)), pa, 0);
 }
 
 // Chained launches of two batches at once would need room for four launches; only one batch per device chains at a time

@@ -1,5 +1,6 @@
-// libtetris_hip.so, second translation unit: the step kernel for three and four players per game (tetris_game_kernel.h).
-// Nothing else lives here; the two files are compiled in parallel (__graft_entry__.build_hip).
+// libtetris_hip.so, second translation unit: the step kernel for three and four players per game (tetris_game_kernel.h) and,
+// beside it, the planning kernels for three and four players (k_plan_sim, k_plan_step; tetris_plan.h).  Nothing else lives
+// here; the two files are compiled in parallel (__graft_entry__.build_hip).
 #include "tetris_game_kernel.h"
 
 template <int P, bool TINT>
@@ -16,5 +17,11 @@ static int launch_mode(int mode, dim3 grid, dim3 block, hipStream_t st, const KA
 __attribute__((visibility("hidden"))) int tetris_launch_game_multi(int n_players, int tint, int mode, dim3 grid, dim3 block, hipStream_t st, const KArgs& a) {
     if (n_players == 3) return tint ? launch_mode<3, true>(mode, grid, block, st, a) : launch_mode<3, false>(mode, grid, block, st, a);
     if (n_players == 4) return tint ? launch_mode<4, true>(mode, grid, block, st, a) : launch_mode<4, false>(mode, grid, block, st, a);
+    return -1;
+}
+
+__attribute__((visibility("hidden"))) int tetris_launch_plan_multi(int n_players, int tint, int which, dim3 grid, hipStream_t st, const PlanArgs& pa, int fin) {
+    if (n_players == 3) { if (tint) launch_plan<3, true>(which, grid, st, pa, fin); else launch_plan<3, false>(which, grid, st, pa, fin); return 0; }
+    if (n_players == 4) { if (tint) launch_plan<4, true>(which, grid, st, pa, fin); else launch_plan<4, false>(which, grid, st, pa, fin); return 0; }
     return -1;
 }

@@ -80,6 +80,7 @@ enum Flag : int {
     F_CHAIN = 4,       // != 0: a wave of a chained launch gave up waiting for its predecessor (the host finishes its games un-chained)
     F_GO = 5,          // written by the HOST: releases the blocker kernel of a pre-queued rollout (TETRIS_PREQUEUE)
     F_PLACE = 6,       // != 0: a workgroup of an XCD-affine chained launch found itself on another XCD than the host expected for its queue
+    F_LISTS = 7,       // != 0: a game's key lists did not fit the caller's buffers (tetris_action_lists_dev; TETRIS_ERR_LISTS)
     F_XCC0 = 8,        // [3] 0x100 | the XCD that block 0 of the last affine launch on queue k landed on (the host's expectation for the next call)
     NFLAGS = 16
 };

@@ -1,0 +1,219 @@
+// Kernel bodies of the planning entry points (include/tetris_hip.h: tetris_action_lists_dev, tetris_simulate_lists_dev,
+// tetris_step_lists_dev): the afterstate loop of a planning agent on the device.  The reference's sherlock agent asks the
+// environment, per decision and game, for the ordered key lists of the current piece (get_actions), for the afterstate of
+// every list (simulate_all_actions) and then performs the one it picked (perform_action)
+// (agents/sherlock_agent/sherlock_agent.py:94-120, sherlock_utils.py:9-20).
+//
+// `__host__ __device__` like tetris_kernels.h: tetris_hip.hip / tetris_hip_multi.hip wrap these in gfx950 kernels,
+// tests/cpu_harness/harness_plan.cpp in plain host loops.
+//
+// Lists of one game live at lens[i][L] and keys[i][L][K] (L = max_lists, K = max_keys), count[i] of them (-1: the game's
+// lists did not fit).  The per-(game, x, rotation) search is actions_body (k_actions), which writes "slabs": for lane
+// t = (game, r * 10 + xi), cnt[t] lists at slab_lens[t][PLAN_LANE_LISTS], slab_keys[t][PLAN_LANE_LISTS][KS].
+#pragma once
+#include "tetris_kernels.h"
+
+namespace te {
+
+constexpr int PLAN_LANE_LISTS = 16;     // lists one (x, rotation) start can produce (<= H / 2 + 1 for H <= 31; as tetris_get_actions)
+constexpr int PLAN_RAW_MAX = 40 * PLAN_LANE_LISTS;
+
+struct PlanArgs {
+    KArgs a;                    // state, tables, status words, H, N (a.n = N), ms, done / lines / dead outputs, game offset
+    const uint8_t* player;      // [N] acting player (NULL: player 0; clamped)
+    const int32_t* count;       // [N] lists per game (as tetris_action_lists_dev wrote them)
+    const uint8_t* lens;        // [N][L]
+    const uint8_t* keys;        // [N][L][K]
+    const int32_t* choice;      // [N] (step)
+    uint32_t* cols;             // [L][P][10][N] (simulate)
+    int max_lists, max_keys;
+};
+
+// ---------------------------------------------------------------- lists: compaction of the slabs of one game
+// The reference enumerates x-major, rotation-minor (tetris_get_actions): raw list order j = xi * 4 + r, slab lane r * 10 + xi.
+TE_HD int plan_slab_lane(int j) { return (j & 3) * 10 + (j >> 2); }
+
+// key list equality, the test data_types.action_list's `in` makes on two actions
+TE_HD bool plan_same_list(const uint8_t* ka, int la, const uint8_t* kb, int lb) {
+    if (la != lb) return false;
+    for (int j = 0; j < la; j++)
+        if (ka[j] != kb[j]) return false;
+    return true;
+}
+TE_HD bool plan_is_null(const uint8_t* k, int len) { return len == 1 && k[0] == 0; }    // data_types.null_action = [0]
+
+// FNV-1a over the keys and the length: the GPU compaction compares hashes before keys
+TE_HD uint32_t plan_list_hash(const uint8_t* k, int len) {
+    uint32_t h = 2166136261u ^ (uint32_t)len;
+    for (int j = 0; j < len; j++) h = (h ^ k[j]) * 16777619u;
+    return h;
+}
+
+// writes list `o` of game g (lens / keys of the caller's [N][L][K] arrays)
+TE_HD void plan_write_list(uint8_t* lens, uint8_t* keys, size_t g, int L, int K, int o, const uint8_t* src, int len) {
+    lens[g * (size_t)L + o] = (uint8_t)len;
+    uint8_t* dst = keys + (g * (size_t)L + o) * (size_t)K;
+    for (int j = 0; j < len; j++) dst[j] = src[j];
+}
+TE_HD void plan_write_null(uint8_t* lens, uint8_t* keys, size_t g, int L, int K) {
+    lens[g * (size_t)L] = 1;
+    keys[g * (size_t)L * K] = 0;
+}
+
+// A game's lists did not fit the caller's buffers: count -1, TETRIS_ERR_LISTS (plain store to the flag words, as report_status)
+TE_HD void plan_report_overflow(uint32_t* status) { ((volatile uint32_t*)status)[F_LISTS] = 1u; }
+
+// Serial form of the compaction of game `g` (CPU harness; the GPU kernel k_plan_lists spreads the same steps over a wave).
+// Slabs of the game start at lane t0 = local game * 40; KS = slab key width (max_keys + 1, so that a list longer than
+// max_keys shows as one).  data_types.action_list(lists, remove_null) (action_list.py:3-37, data_types.py:27-51):
+//   - the null action [0] goes in front unless the lists already hold it; duplicates are dropped, first occurrence kept;
+//   - remove_null: every null action is dropped again, unless nothing else is left (then the list is [[0]]).
+TE_HD void plan_compact_serial(const uint8_t* cnt, const uint8_t* slab_lens, const uint8_t* slab_keys, int KS, size_t t0, size_t g,
+                               int L, int K, bool keep_null, int32_t* count, uint8_t* lens, uint8_t* keys, uint32_t* status) {
+    int off[41];
+    bool bad = false;
+    off[0] = 0;
+    for (int j = 0; j < 40; j++) {
+        const int c = cnt[t0 + plan_slab_lane(j)];
+        bad |= c > PLAN_LANE_LISTS;
+        off[j + 1] = off[j] + (c > PLAN_LANE_LISTS ? 0 : c);
+    }
+    const int M = off[40];
+    // raw list m -> its keys and length
+    auto raw = [&](int m, int& len) -> const uint8_t* {
+        int j = 0;
+        while (off[j + 1] <= m) j++;
+        const size_t s = (t0 + plan_slab_lane(j)) * PLAN_LANE_LISTS + (m - off[j]);
+        len = slab_lens[s];
+        return slab_keys + s * KS;
+    };
+    bool has_null = false;
+    int n_out = 0;
+    for (int m = 0; m < M; m++) {
+        int len;
+        const uint8_t* k = raw(m, len);
+        bad |= len > K;
+        has_null |= plan_is_null(k, len);
+    }
+    // pass 1 counts, pass 2 writes (nothing is written for a game that does not fit)
+    for (int pass = 0; pass < 2; pass++) {
+        int o = (!keep_null || has_null) ? 0 : 1;
+        for (int m = 0; m < M && !bad; m++) {
+            int len;
+            const uint8_t* k = raw(m, len);
+            if (!keep_null && plan_is_null(k, len)) continue;
+            bool first = true;
+            for (int e = 0; e < m && first; e++) {
+                int le;
+                const uint8_t* ke = raw(e, le);
+                first = !plan_same_list(k, len, ke, le);
+            }
+            if (!first) continue;
+            if (pass == 1) plan_write_list(lens, keys, g, L, K, o, k, len);
+            o++;
+        }
+        if (o == 0) {                         // nothing but nulls (or nothing): [[0]]
+            if (pass == 1) plan_write_null(lens, keys, g, L, K);
+            o = 1;
+        } else if (pass == 1 && keep_null && !has_null)
+            plan_write_null(lens, keys, g, L, K);
+        if (pass == 0) {
+            n_out = o;
+            bad |= n_out > L;
+            if (bad) break;
+        }
+    }
+    count[g] = bad ? -1 : n_out;
+    if (bad) plan_report_overflow(status);
+}
+
+// ---------------------------------------------------------------- simulate / step: the key interpreter on a list
+// PythonHandle.cpp:138-147 make_action with `len` keys at `kp` (NULL: the null action [0]) for `player` and [0] for everyone
+// else (tetris_environment.py:106-108), as make_keys does for the staged [K][P][n] keys.
+template <int P>
+TE_HD void plan_make_keys(const Ctx& cx, Game<P>& g, int player, const uint8_t* kp, int len) {
+    if (g.round_over) return;
+    TE_UNROLL
+    for (int p = 0; p < P; p++) {
+        Player& q = g.pl[p];
+        if (q.dead) continue;
+        if (p == player && kp) for (int k = 0; k < len; k++) press_key(cx, q, kp[k]);
+        else press_key(cx, q, 0);
+    }
+}
+
+// list k of game i; its length is clamped to the caller's max_keys
+TE_HD const uint8_t* plan_list(const PlanArgs& pa, int i, int k, int& len) {
+    len = pa.lens[(size_t)i * pa.max_lists + k];
+    if (len > pa.max_keys) len = pa.max_keys;
+    return pa.keys + ((size_t)i * pa.max_lists + k) * (size_t)pa.max_keys;
+}
+
+// simulate_actions(lists, player, finalize) (tetris_environment.py:87-100) of list k of game i, on a register copy of the
+// game: loads as game_load does, runs make_keys (and with `fin`, finish_game as M_STEP_KEYS does), stores the columns of
+// every player to cols[k][p][c][i] and, with `fin`, done[k][i] / lines[k][p][i] / dead[k][p][i].  Nothing of the batch's
+// state is written.  `uniform`: the 64 lanes of the calling wave hold 64 consecutive games of one k.
+template <int P, bool TINT>
+TE_HD void plan_sim_lane(const PlanArgs& pa, int i, int k, bool fin, const uint32_t* shapes, bool uniform) {
+    const KArgs& a = pa.a;
+    const int c = pa.count[i];
+    if (k >= c) return;                                    // (count -1: nothing)
+    Game<P> g;
+    load_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, false, MEM_STREAM, uniform);
+    const Ctx cx = make_ctx(a, shapes, TINT, P > 1);
+    const int player = safe_player(pa.player, i, P);
+    if (fin) {
+        TE_UNROLL
+        for (int p = 0; p < P; p++) prefetch_next(cx, g.pl[p], g.seed16, g.status);
+    }
+    int len;
+    const uint8_t* kp = plan_list(pa, i, k, len);
+    plan_make_keys<P>(cx, g, player, kp, len);
+    const size_t n = (size_t)a.n;
+    if (fin) {
+        const int done = finish_game<P>(cx, g, a.ms);
+        if (a.done) a.done[(size_t)k * n + i] = (uint8_t)done;
+        TE_UNROLL
+        for (int p = 0; p < P; p++) {
+            if (a.lines) a.lines[((size_t)k * P + p) * n + i] = (uint8_t)g.pl[p].reward;
+            if (a.dead) a.dead[((size_t)k * P + p) * n + i] = (uint8_t)g.pl[p].dead;
+        }
+    }
+    TE_UNROLL
+    for (int p = 0; p < P; p++)
+        for (int col = 0; col < NCOL; col++) pa.cols[(((size_t)k * P + p) * NCOL + col) * n + i] = g.pl[p].col[col];
+    report_status(a, g.status);
+}
+
+// perform_action(lists[choice[i]], player) (tetris_environment.py:102-116): the step of M_STEP_KEYS with the chosen list for
+// the acting player and [0] for the others; AUTO: the reset of M_STEP_RT_AUTO in the same pass (seed schedule of
+// include/tetris_hip.h); done / lines / dead describe the step before the reset.  choice is clamped into [0, count - 1]; a
+// game whose lists did not fit (count < 1) performs the null action.
+template <int P, bool TINT, bool AUTO>
+TE_HD void plan_step_lane(const PlanArgs& pa, int i, const uint32_t* shapes, bool uniform) {
+    const KArgs& a = pa.a;
+    Game<P> g;
+    load_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, false, MEM_STREAM, uniform);
+    const Ctx cx = make_ctx(a, shapes, TINT, P > 1);
+    TE_UNROLL
+    for (int p = 0; p < P; p++) prefetch_next(cx, g.pl[p], g.seed16, g.status);
+    ResetPrefetch rpf;
+    rpf.ok = 0; rpf.seed16 = 0; rpf.word = 0;
+    if (AUTO) prefetch_reset(cx, episode_seed(a.game_offset + (uint32_t)i, g.episode + 1), rpf);
+    const int player = safe_player(pa.player, i, P);
+    const int c = imin(pa.count[i], pa.max_lists);
+    int len = 1;
+    const uint8_t* kp = nullptr;
+    if (c >= 1) kp = plan_list(pa, i, imax(0, imin(pa.choice[i], c - 1)), len);
+    plan_make_keys<P>(cx, g, player, kp, len);
+    const int done = finish_game<P>(cx, g, a.ms);
+    write_outputs<P>(a, i, g, done);
+    if (AUTO && done) {                                    // worker.py:157-166 reset_envs, without the host round trip
+        g.episode++;
+        reset_game<P>(cx, g, episode_seed(a.game_offset + (uint32_t)i, g.episode), &rpf);
+    }
+    store_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, false, MEM_STREAM, uniform);
+    report_status(a, g.status);
+}
+
+}  // namespace te

@@ -6,6 +6,35 @@ import ctypes as C
 import numpy as np
 
 
+def columns_to_deltas(cols, player, before, count, height, out=None, small_fill=1e-3):
+    """The deltas of a planning agent from simulated column bitboards (torch tensors, any device):
+    cols   int32 [L, P, 10, N]  every player's columns after list k (tetris_simulate_lists_dev without finalize)
+    player int64 / uint8 [N]    the acting player of each game
+    before uint8 [N, H, W]      the acting player's field > 0 now (observe(player)[0][0])
+    count  int32 [N]            lists per game
+    -> (deltas float32 [N, H, W, L], sums float32 [N, H, W, 1]).
+    Restates sherlock_utils.deltas / generate_deltas (agents/sherlock_agent/sherlock_utils.py:9-20): per list, the acting
+    player's field after the list minus the field before; a list whose difference adds up to less than 4 (the piece did not
+    land whole, or the player could not move) becomes `small_fill` everywhere; lists past count[i] are zero, which is the
+    reference's zero padding to the longest list; sums = the sum over the list axis.  (The reference's state_dict field is
+    uint8, and np.full_like on it turns 1e-3 into 0: small_fill=0.0 gives those numbers.)  Fields are occupancy (field > 0)."""
+    import torch
+
+    L, P, W, N = cols.shape
+    idx = player.to(torch.int64).view(N, 1, 1, 1).expand(N, L, 1, W)
+    sel = torch.gather(cols.permute(3, 0, 1, 2), 2, idx).squeeze(2)                       # [N, L, W]
+    rows = torch.arange(height, dtype=torch.int32, device=cols.device).view(1, 1, height, 1)
+    bits = torch.bitwise_and(torch.bitwise_right_shift(sel.unsqueeze(2), rows), 1)          # [N, L, H, W]
+    if out is None:
+        out = torch.empty((N, height, W, L), dtype=torch.float32, device=cols.device)
+    torch.sub(bits.permute(0, 2, 3, 1), before.unsqueeze(-1), out=out)
+    lists = torch.arange(L, device=cols.device).view(1, L)
+    small = out.sum(dim=(1, 2)) < 4.0                                                        # [N, L]
+    out.masked_fill_(small.view(N, 1, 1, L), small_fill)
+    out.masked_fill_((lists >= count.view(N, 1)).view(N, 1, 1, L), 0.0)
+    return out, out.sum(dim=-1, keepdim=True)
+
+
 class TorchEnv:
     def __init__(self, batch, device=None):
         import torch
@@ -61,3 +90,74 @@ class TorchEnv:
         self.b._check(self.b.lib.tetris_observe_packed_dev(self.b._h, None, self.b.n_games, self._ptr(player), self._ptr(self.visual),
                                                           self._ptr(self.vector), self._ptr(self.piece)))
         return self.visual, self.vector, self.piece
+
+    # ---- planning on the device: the afterstate loop of a planning agent (agents/sherlock_agent/sherlock_agent.py:94-120)
+    def _plan_buffers(self, max_lists, max_keys):
+        torch, n, P = self.torch, self.b.n_games, self.b.n_players
+        if getattr(self, "_plan_shape", None) == (max_lists, max_keys):
+            return
+        u8 = dict(dtype=torch.uint8, device=self.dev)
+        self._plan_shape = (max_lists, max_keys)
+        self.list_count = torch.zeros(n, dtype=torch.int32, device=self.dev)
+        self.list_lens = torch.zeros(n, max_lists, **u8)
+        self.list_keys = torch.zeros(n, max_lists, max_keys, **u8)
+        self.sim_cols = torch.zeros(max_lists, P, 10, n, dtype=torch.int32, device=self.dev)
+        self.sim_done = torch.zeros(max_lists, n, **u8)
+        self.sim_lines = torch.zeros(max_lists, P, n, **u8)
+        self.sim_dead = torch.zeros(max_lists, P, n, **u8)
+        self.plan_deltas = torch.zeros(n, self.b.height, 10, max_lists, dtype=torch.float32, device=self.dev)
+        self._plan_visual = torch.zeros(P, n, self.b.height, 10, **u8)
+        self._plan_vector = torch.zeros(P, n, 12, **u8)
+        self._plan_piece = torch.zeros(P, n, **u8)
+
+    def _check_player(self, player):
+        if player is not None:
+            assert player.dtype == self.torch.uint8 and player.is_cuda and player.is_contiguous() and player.numel() == self.b.n_games
+
+    def _lists(self):
+        assert getattr(self, "_plan_shape", None) is not None, "call action_lists() first"
+        return self._plan_shape
+
+    def action_lists(self, player=None, keep_null=False, max_lists=64, max_keys=48):
+        """tetris_environment_vector.get_actions(player) for every game on the device: -> (count int32 [n], lens uint8 [n, L],
+        keys uint8 [n, L, K]) device tensors (reused; list k of game i = keys[i, k, :lens[i, k]], count -1 = did not fit:
+        take_errors() reports 8).  keep_null: bar_null_moves=False.  player: uint8 device tensor [n] or None (player 0)."""
+        self._check_player(player)
+        self._plan_buffers(int(max_lists), int(max_keys))
+        self.b.action_lists_dev(self._ptr(self.list_count), self._ptr(self.list_lens), self._ptr(self.list_keys), max_lists=max_lists,
+                                max_keys=max_keys, player=self._ptr(player), keep_null=keep_null)
+        return self.list_count, self.list_lens, self.list_keys
+
+    def simulate(self, player=None, finalize=False, ms=400):
+        """simulate_actions of every list of the last action_lists(player) call: -> (cols, done, lines, dead) device tensors
+        (reused): cols int32 [L, P, 10, n] = every player's column bitboards (bit y = row y) after list k; with finalize also
+        done [L, n], lines / dead [L, P, n].  Entries of lists k >= count[i] are left as they were.  The games are not changed."""
+        self._check_player(player)
+        L, K = self._lists()
+        self.b.simulate_lists_dev(self._ptr(self.list_count), self._ptr(self.list_lens), self._ptr(self.list_keys), self._ptr(self.sim_cols),
+                                  max_lists=L, max_keys=K, player=self._ptr(player), finalize=finalize, ms=ms, done=self._ptr(self.sim_done),
+                                  lines=self._ptr(self.sim_lines), dead=self._ptr(self.sim_dead))
+        return self.sim_cols, self.sim_done, self.sim_lines, self.sim_dead
+
+    def deltas(self, player=None, small_fill=1e-3):
+        """sherlock_utils.generate_deltas for every game (lists of the last action_lists(player) call): -> (deltas float32
+        [n, H, W, L], sums float32 [n, H, W, 1]) device tensors; see columns_to_deltas.  One or two players (the field before is
+        read through the packed observation)."""
+        self._check_player(player)
+        cols = self.simulate(player, finalize=False)[0]
+        self.b._check(self.b.lib.tetris_observe_packed_dev(self.b._h, None, self.b.n_games, self._ptr(player), self._ptr(self._plan_visual),
+                                                          self._ptr(self._plan_vector), self._ptr(self._plan_piece)))
+        who = player if player is not None else self.torch.zeros(self.b.n_games, dtype=self.torch.uint8, device=self.dev)
+        return columns_to_deltas(cols, who, self._plan_visual[0], self.list_count, self.b.height, out=self.plan_deltas, small_fill=small_fill)
+
+    def step_lists(self, choice, player=None, ms=400, auto_reset=False):
+        """perform_action(lists[choice[i]], player) for every game (lists of the last action_lists(player) call); choice: int32
+        device tensor [n], clamped into [0, count - 1].  -> (done [n], lines [P, n], dead [P, n]) device tensors (reused).
+        auto_reset as for step_rt."""
+        assert choice.dtype == self.torch.int32 and choice.is_cuda and choice.is_contiguous() and choice.numel() == self.b.n_games
+        self._check_player(player)
+        L, K = self._lists()
+        self.b.step_lists_dev(self._ptr(choice), self._ptr(self.list_count), self._ptr(self.list_lens), self._ptr(self.list_keys),
+                              self._ptr(self.done), self._ptr(self.lines), self._ptr(self.dead), max_lists=L, max_keys=K,
+                              player=self._ptr(player), ms=ms, auto_reset=auto_reset)
+        return self.done, self.lines, self.dead

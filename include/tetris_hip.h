@@ -52,6 +52,7 @@ extern "C" {
  * to finish some of its games un-chained (see tetris_set_chained) — the results are the same, the call was slow, and chained
  * launches are off for the batch from then on.                                                                          */
 #define TETRIS_ERR_CHAIN_FELL_BACK 4u
+#define TETRIS_ERR_LISTS 8u      /* tetris_action_lists_dev: a game had more lists / keys than the caller's buffers (its count is -1) */
 
 #define TETRIS_MAX_H 32
 #define TETRIS_MAX_PLAYERS 4   /* players per game (PythonHandle(n_players, ...): PythonHandle.cpp:5-25) */
@@ -213,6 +214,38 @@ int tetris_enumerate_drops_dev_ex(tetris_batch *b, const int32_t *d_idx, int n, 
  * or a list more than max_keys keys (64 / 48 always suffice for 10-wide boards up to 31 rows).                   */
 int tetris_get_actions(tetris_batch *b, const int32_t *idx, int n, const uint8_t *player, uint8_t *keys,
                        uint8_t *lens, int32_t *count, int max_lists, int max_keys);
+
+/* ---- planning on the device: the afterstate loop of a planning agent without host round trips --------------------------
+ * A planning agent asks, per decision and game, for the ordered key lists of the current piece, the afterstate of every list,
+ * and then performs the list it picked (the reference's sherlock agent: agents/sherlock_agent/sherlock_agent.py:94-120,
+ * sherlock_utils.py:9-20).  These three entry points do that for games 0..N-1 of a batch: device pointers, asynchronous on
+ * the batch's stream, run-ahead bounded and RNG-table requests serviced as for tetris_step_rt_dev_ex.  Not on split batches.
+ * Lists: count[N] int32, lens[N][L] uint8, keys[N][L][K] uint8 (L = max_lists, K = max_keys); entries past lens / count are
+ * left as they were.  d_player[N] = acting player (NULL: player 0; out-of-range entries are clamped).                       */
+#define TETRIS_LISTS_KEEP_NULL 1   /* bar_null_moves = False; default: nulls removed as action_list(remove_null=True) */
+#define TETRIS_SIM_FINALIZE    1   /* simulate_actions(finalize=True): make_action + finish_action(ms) */
+/* replaces: tetris_environment_vector.get_actions(player) = PythonHandle.get_actions + data_types.action_list(..., remove_null)
+ * (PythonHandle.cpp:190, TestField.cpp:64-415, action_list.py:3-37): the lists tetris_get_actions gives, x-major and
+ * rotation-minor, then the null action [0] in front unless present, duplicates dropped (first occurrence kept) and, without
+ * TETRIS_LISTS_KEEP_NULL, nulls removed as long as something else remains — so count >= 1.  A game whose lists do not fit
+ * L x K (1 <= K <= 254) gets count -1 and nothing else written; TETRIS_ERR_LISTS is raised (tetris_take_errors).          */
+int tetris_action_lists_dev(tetris_batch *b, const uint8_t *d_player, int max_lists, int max_keys, int flags,
+                            int32_t *d_count, uint8_t *d_lens, uint8_t *d_keys);
+/* replaces: tetris_environment_vector.simulate_actions(lists, player, finalize) (tetris_environment.py:87-100): list k of
+ * game i (k < count[i]) run through the key interpreter on a register copy of the game, [0] for the other players, with
+ * TETRIS_SIM_FINALIZE followed by finish_action(ms).  d_cols [L][P][10][N] uint32 = every player's column bitboards
+ * (bit y = row y) afterwards; with TETRIS_SIM_FINALIZE also d_done [L][N], d_lines / d_dead [L][P][N] as tetris_step_keys
+ * reports them (each may be NULL).  Nothing is written for k >= count[i]; the batch's state is not written.               */
+int tetris_simulate_lists_dev(tetris_batch *b, const uint8_t *d_player, const int32_t *d_count, const uint8_t *d_lens,
+                              const uint8_t *d_keys, int max_lists, int max_keys, int ms, int flags,
+                              uint32_t *d_cols, uint8_t *d_done, uint8_t *d_lines, uint8_t *d_dead);
+/* replaces: perform_action(lists[choice[i]], player) (tetris_environment.py:102-116): bit-identical to tetris_step_keys with
+ * the chosen list for the acting player and [0] for the others.  choice[N] int32 is clamped into [0, count - 1]; a game
+ * with count < 1 performs [0].  flags: TETRIS_STEP_AUTO_RESET as for tetris_step_rt_dev_ex (outputs describe the step
+ * before the reset).  d_done [N], d_lines / d_dead [P][N] (each may be NULL).                                             */
+int tetris_step_lists_dev(tetris_batch *b, const uint8_t *d_player, const int32_t *d_choice, const int32_t *d_count,
+                          const uint8_t *d_lens, const uint8_t *d_keys, int max_lists, int max_keys, int ms, int flags,
+                          uint8_t *d_done, uint8_t *d_lines, uint8_t *d_dead);
 
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
