@@ -419,7 +419,7 @@ class TetrisBatch:
 
     def set_direct_dispatch(self, on, min_launches=None):
         """Long chained calls through HSA queues of the library's own (AQL packets written by the library) on / off;
-        min_launches: calls of at least that many launches (default: the library's, 128) — include/tetris_hip.h:
+        min_launches: calls of at least that many launches (default: the library's, 16) — include/tetris_hip.h:
         tetris_set_direct_dispatch."""
         self._check(self.lib.tetris_set_direct_dispatch(self._h, 0 if not on else (-1 if min_launches is None else max(1, int(min_launches)))))
 

@@ -239,11 +239,6 @@ static bool make_queues(Device* d, std::string& why) {
     for (int k = 0; k < depth; k++) {
         if (hsa_queue_create(d->gpu, QUEUE_PACKETS, HSA_QUEUE_TYPE_MULTI, nullptr, nullptr, UINT32_MAX, UINT32_MAX, &qs.q[k]) != HSA_STATUS_SUCCESS) { why = "hsa_queue_create failed"; destroy_queues(qs); return false; }
         (void)hsa_amd_profiling_set_profiler_enabled(qs.q[k], 1);
-        {   // (experiment knob TETRIS_DIRECT_PRIO=high: no effect that survives swapping the order in which the batches of a process
-            // are created — profiles/r03/direct_dispatch.txt)
-            const char* e = getenv("TETRIS_DIRECT_PRIO");
-            if (e && !strcmp(e, "high")) (void)hsa_amd_queue_set_priority(qs.q[k], HSA_AMD_QUEUE_PRIORITY_HIGH);
-        }
         if (hsa_amd_memory_pool_allocate(d->dev_pool, (size_t)SLOTS * qs.slot_bytes + 4096, 0, (void**)&qs.kernarg[k]) != HSA_STATUS_SUCCESS ||
             hsa_amd_agents_allow_access(1, &d->cpu, nullptr, qs.kernarg[k]) != HSA_STATUS_SUCCESS) { why = "no host-visible device memory for the kernel arguments"; destroy_queues(qs); return false; }
         for (int s = 0; s < 2; s++)

@@ -111,10 +111,14 @@ extern unsigned long long te_path_count[PC_NCOUNTERS];
 // global_load/store, so the ~60 state accesses of a step need no per-lane 64-bit address arithmetic.
 // Memory mode of a state access.  MEM_STREAM: non-temporal (the default: a state word is touched once per launch).
 // MEM_AGENT: agent-scope (`sc1`) — the word is handed from one launch to the next WHILE both are running (chained launches,
-// tetris_hip.hip): the store is written through to memory and the load bypasses the non-coherent per-XCD L2
-// (MI355X_MICROARCH.md, inter-workgroup visibility: every store and every load of the handed-off bytes must be `sc1`).
-// MEM_AFFINE (experiment only, -DTE_EXPERIMENT_AFFINE): `sc1` loads, PLAIN stores — the line stays in the storing XCD's L2, which
-// only the same XCD may then read; measured slower than MEM_AGENT in the chained kernel (profiles/r03/handoff_experiments.txt).
+// tetris_hip.hip): the store is written through to memory and drops the line from the storing XCD's L2, the load skips the
+// CU's L1 and is served through the L2 — the write-through hand-off, measured valid between any two XCDs (MI355X_MICROARCH.md,
+// inter-workgroup visibility: every store and every load of the handed-off bytes must be `sc1`).
+// MEM_AFFINE: `sc1` loads, PLAIN stores — the hand-off of k_chain_affine / k_duo_affine (direct dispatch, tetris_aql.h), which step
+// every block of games on the same XCD in every launch.  A plain store leaves the line dirty in the storing XCD's L2, and the form
+// depends on two things: the next launch's `sc1` load on that XCD (of the state words and of the plainly stored epoch word) is
+// served from that dirty line, one L2 being coherent for all CUs of its XCD; and no other XCD reads the line before the queue's
+// last packet releases at system scope.  A workgroup that is not on the XCD its block needs touches nothing (F_PLACE).
 enum MemMode : int { MEM_STREAM = 0, MEM_AGENT = 1, MEM_AFFINE = 2 };
 #if defined(__HIP_DEVICE_COMPILE__)
 TE_HD uint32_t ld_agent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

@@ -280,9 +280,9 @@ int tetris_rollout_launch(tetris_batch *b, int launches, int steps_per_launch, u
  * tetris_set_chained(b, 1).  On a GPU that the batch shares with other work, switch chaining off up front:
  * tetris_set_chained(b, 0) — or TETRIS_NO_CHAIN=1 — costs 5.7 us per launch instead of 4.0 and cannot starve anything.
  * The three chain streams belong to the device and are shared by all its batches (their chained calls exclude each other).
- * Side effect a host application may notice: the three streams are created with three different stream priorities (that is how
- * the HIP runtime is made to keep them on three hardware queues, where alone they overlap; TETRIS_CHAIN_PRIO=0: equal
- * priorities); the batch's own stream has the default priority.
+ * Side effect a host application may notice: where the device offers three stream priority levels, the three streams are created
+ * with three different priorities (that is how the HIP runtime is made to keep them on three hardware queues, where alone they
+ * overlap); the batch's own stream has the default priority.
  * on = 0: every launch on the batch's one stream.                                                                       */
 int tetris_set_chained(tetris_batch *b, int on);
 /* DIRECT DISPATCH of long chained calls.  A chained launch takes the GPU 4 us; hipLaunchKernel costs the calling thread 2.4-4.2 us
@@ -341,21 +341,13 @@ int tetris_debug_stall(tetris_batch *b, int which, int microseconds, int percent
  *                       that runs until the host has queued every launch of the call (it then sets a flag word in pinned memory):
  *                       the GPU-paced launch period, without the host's launch cost
  *   TETRIS_CHAIN_SPIN_LIMIT=<polls>  default of tetris_set_chain_spin_limit for batches created afterwards
- *   TETRIS_CHAIN_PRIO=0 the chain streams are created with equal priorities (they may then share a hardware queue)
  *   TETRIS_CHAIN_DEPTH=1..3  at most that many chained launches in flight; 1 = the chained kernel on one stream, i.e. dispatches
  *                       serialised by the stream (what per-dispatch PMC counters need: profiles/pmc_summary.py)
- *   TETRIS_EXT_EVENTS=0 chained calls record their timing / join events as packets of their own instead of attaching them to the
- *                       first and last kernels (hipExtLaunchKernel, the default)
- *   TETRIS_ENQUEUE_THREADS_MIN=<n>  (stream path) chained calls of at least n launches (default 256) are enqueued by one host thread per chain
- *                       stream (a launch costs the host 2.7-4.0 us, the GPU needs one every 4.0); 0 = always one thread
- *   TETRIS_GATE_GROUP=<n>  launches per run-ahead group (default 120: at most 241 in flight), 8..120
  *   TETRIS_DIRECT=0     batches are created with direct dispatch off; TETRIS_DIRECT_MIN=<n>: its default threshold
  *                       (tetris_set_direct_dispatch)
  *   TETRIS_AFFINE=0     no XCD-affine launches (tetris_set_xcd_affine)
  *   TETRIS_DIRECT_UNDER_TOOLS=1  direct dispatch also with a profiling tool library in the process (ROCP_TOOL_LIBRARIES, HSA_TOOLS_LIB or
  *                       LD_PRELOAD naming rocprof* / roctracer: by default the launches then stay on the streams)
- *   TETRIS_DIRECT_FENCE=none, TETRIS_DIRECT_EDGE=agent|system, TETRIS_DIRECT_PRIO=high  (experiments) direct dispatch: fence scope of
- *                       the packets between a queue's first and last / of its first and last packet; queue priority
  *   TETRIS_TIMING=1     tetris_rollout_launch prints its host-side costs (enqueue per launch, gate waits, until drained) to stderr */
 /* 1 if tetris_rollout_launch / tetris_rollout_random would chain launches of `steps_per_launch` steps on this batch, 0 if not
  * (switched off — by the caller or by a fall-back —, caller-owned stream, split or colour batch, or not even two launches fit
