@@ -60,48 +60,67 @@ __device__ __forceinline__ void chain_body(const KArgs& a) {
     if (a.steps < 0) { chain_census(a, lane == 0); return; }
     constexpr int CMEM = AFFINE ? MEM_AFFINE : MEM_AGENT;
     int wave = blockIdx.x;
+    uint32_t xcc = 0;
+    // AFFINE: block 0 reports where this queue starts dealing (F_XCC0 + queue: the host's expectation for the next call) on its way
+    // out, so that the store's trip to host memory never holds up the step (a wave waits for ALL its outstanding vector memory
+    // accesses at the first poll)
+    const auto report_xcc = [&]() { if (AFFINE && blockIdx.x == 0 && lane == 0) st_flag(a.status + F_XCC0 + (a.xcd_slot & 3u), 0x100u | xcc); };
     if (AFFINE) {
-        uint32_t xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         xcc &= 0xFu;
-        if (blockIdx.x == 0 && lane == 0) ((volatile uint32_t*)a.status)[F_XCC0 + (a.xcd_slot & 3u)] = 0x100u | xcc;      // where this queue starts dealing: the host's expectation for the next call
         if (xcc != ((a.xcd_base + blockIdx.x) & 7u)) {          // not where the host expects this block to run: hands off
-            if (lane == 0) ((volatile uint32_t*)a.status)[F_PLACE] = 1u;
+            if (lane == 0) st_flag(a.status + F_PLACE, 1u);
+            report_xcc();
             return;
         }
         wave = (int)((blockIdx.x & ~7u) | xcc);
-        if (wave * CHAIN_LANES >= a.n) return;                  // (padding of the last group of eight: no games, no epoch word)
+        if (wave * CHAIN_LANES >= a.n) { report_xcc(); return; }   // (padding of the last group of eight: no games, no epoch word)
     }
     const int i = wave * CHAIN_LANES + lane;
     const bool active = lane < CHAIN_LANES && i < a.n;
     LaneCounters cnt = {0, 0, 0, 0};
-    const uint32_t shape_word = d_shape_table.s[lane];
+    const uint32_t shape_word = d_shape_table.s[lane];     // (issued at the top; it has long arrived when the LDS table is written)
     Game<P> g;
-    // the policy draw of this step depends on kernel arguments only: its 40 dependent multiplies run while the wave waits.
+    // Work that does not depend on the predecessor happens before the poll: the policy draw of this step (kernel arguments only:
+    // its 40 dependent multiplies run while the wave waits), and the row stride of the state arrays (pinned into an SGPR here;
+    // the compiler would load it after the poll, with a wait for the scalar load in front of the first state load).  The LDS
+    // shape table is written after the state loads are issued: written before the poll it would need a wait for its global load
+    // in front of the first poll.
     // (Issuing the first poll of the epoch word BEFORE the draw — most waves find their predecessor done at that poll — measured
     // +0.06 us per launch, GPU-paced: profiles/r02/chain_ab_gpu_paced.txt.)
     TE_STAMP_CHAIN(a.epoch, 0); TE_STAMP_PLACE(a.epoch);
     if (active) policy_draw(a, (uint32_t)i, a.first_step, g.draw0, g.draw1);
     const uint32_t d0 = g.draw0, d1 = g.draw1;
+    int stride = a.n_stride;
+    asm volatile("" : "+s"(stride));
     TE_STAMP_CHAIN(a.epoch, 1);
-    if (!chain_wait(a, (uint32_t)wave, lane == 0)) return;      // gave up: the games stay as launch E - 1 (or an earlier one) left them
-    TE_STAMP_CHAIN(a.epoch, 2);
-    if (active) { load_game<P>(geo_of(a), (size_t)i, g, false, P > 1, true, CMEM, CHAIN_LANES == 64); g.draw0 = d0; g.draw1 = d1; }
+    const uint32_t seen = chain_poll(a, (uint32_t)wave);
+    if (seen == a.epoch - 1u) {                 // (a uniform branch: the state loads follow the poll's exit)
+        TE_STAMP_CHAIN(a.epoch, 2);
+        Geo geo = geo_of(a);
+        geo.stride = (size_t)stride;
+        if (active) { load_game<P>(geo, (size_t)i, g, false, P > 1, true, CMEM, CHAIN_LANES == 64); g.draw0 = d0; g.draw1 = d1; }
 #if defined(TE_PHASE_TRACE)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // diagnostic: when have ALL state words arrived
-    TE_STAMP_CHAIN(a.epoch, 3);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // diagnostic: when have ALL state words arrived
+        TE_STAMP_CHAIN(a.epoch, 3);
 #endif
-    s_shapes[lane] = shape_word;
-    __builtin_amdgcn_wave_barrier();
-    if (active) game_run<P, M_ROLLOUT, false, CMEM>(a, i, s_shapes, g, cnt);
-    TE_STAMP_CHAIN(a.epoch, 4);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every store (and counter atomic) of this wave has been acknowledged
-    TE_STAMP_CHAIN(a.epoch, 5);
-    if (lane == 0) {
-        if (AFFINE) *(volatile uint32_t*)(a.chain + (size_t)wave * CHAIN_STRIDE) = a.epoch;       // stays in this XCD's L2, where the next launch's wave polls it
-        else st_agent(a.chain + (size_t)wave * CHAIN_STRIDE, a.epoch);
+        s_shapes[lane] = shape_word;
+        __builtin_amdgcn_wave_barrier();
+        if (active) game_run<P, M_ROLLOUT, false, CMEM>(a, i, s_shapes, g, cnt);
+        TE_STAMP_CHAIN(a.epoch, 4);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every store (and counter atomic) of this wave has been acknowledged
+        TE_STAMP_CHAIN(a.epoch, 5);
+        if (lane == 0) {
+            // AFFINE: a plain store, the line stays in this XCD's L2 where the next launch's wave polls it; otherwise written through
+            // (`sc1`).  Neither waits for its acknowledgement: the wave ends here.
+            if (AFFINE) st_xcd(a.chain + (size_t)wave * CHAIN_STRIDE, a.epoch);
+            else st_agent(a.chain + (size_t)wave * CHAIN_STRIDE, a.epoch);
+        }
+        TE_STAMP_CHAIN(a.epoch, 6);
+    } else if (!(seen & CHAIN_ABANDONED)) {     // (with the bit set an earlier launch's wave gave up and recorded it)
+        chain_give_up(a, (uint32_t)wave, lane == 0);          // the games stay as launch E - 1 (or an earlier one) left them
     }
-    TE_STAMP_CHAIN(a.epoch, 6);
+    report_xcc();
 }
 template <int P>
 __global__ __launch_bounds__(64) void k_chain(KArgs a) { chain_body<P, false>(a); }
@@ -261,17 +280,18 @@ __device__ __forceinline__ void duo_body(const KArgs& a) {
     constexpr bool ROLL = MODE == M_ROLLOUT, AUTO = MODE == M_STEP_RT_AUTO;
     constexpr int MEM = CHAIN ? (AFFINE ? MEM_AFFINE : MEM_AGENT) : MEM_STREAM;
     if (CHAIN && a.steps < 0) { chain_census(a, lane == 0); return; }
-    if (AFFINE) {                        // (64-thread workgroups: one wave each; see chain_body)
-        uint32_t xcc;
+    uint32_t xcc = 0;
+    const auto report_xcc = [&]() { if (AFFINE && blockIdx.x == 0 && lane == 0) st_flag(a.status + F_XCC0 + (a.xcd_slot & 3u), 0x100u | xcc); };
+    if (AFFINE) {                        // (64-thread workgroups: one wave each; see chain_body, also for report_xcc)
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         xcc &= 0xFu;
-        if (blockIdx.x == 0 && lane == 0) ((volatile uint32_t*)a.status)[F_XCC0 + (a.xcd_slot & 3u)] = 0x100u | xcc;
         if (xcc != ((a.xcd_base + blockIdx.x) & 7u)) {
-            if (lane == 0) ((volatile uint32_t*)a.status)[F_PLACE] = 1u;
+            if (lane == 0) st_flag(a.status + F_PLACE, 1u);
+            report_xcc();
             return;
         }
         wave = (int)((blockIdx.x & ~7u) | xcc);
-        if (wave * 32 >= a.n) return;
+        if (wave * 32 >= a.n) { report_xcc(); return; }
     }
     const int gi = wave * 32 + (lane & 31);
     const bool active = gi < a.n;
@@ -289,7 +309,7 @@ __device__ __forceinline__ void duo_body(const KArgs& a) {
     uint32_t pd0 = 0, pd1 = 0;
     if (CHAIN) {
         if (active) policy_draw(a, (uint32_t)gi, a.first_step, pd0, pd1);        // while the wave waits for its predecessor
-        if (!chain_wait(a, (uint32_t)wave, lane == 0)) return;
+        if (!chain_wait(a, (uint32_t)wave, lane == 0)) { report_xcc(); return; }
     }
     if (active) {
         load_game_words<1>(gr, g, ROLL, MEM);
@@ -407,10 +427,11 @@ __device__ __forceinline__ void duo_body(const KArgs& a) {
     }
     if (CHAIN) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every store (and counter atomic) of this wave has been acknowledged
-        if (lane == 0) {
-            if (AFFINE) *(volatile uint32_t*)(a.chain + (size_t)wave * CHAIN_STRIDE) = a.epoch;
+        if (lane == 0) {                // (as in chain_body: no wait for the acknowledgement)
+            if (AFFINE) st_xcd(a.chain + (size_t)wave * CHAIN_STRIDE, a.epoch);
             else st_agent(a.chain + (size_t)wave * CHAIN_STRIDE, a.epoch);
         }
+        report_xcc();
     }
     if (OBS) {
         const int pitch = a.H * NCOL / 4, first = wave * 32;

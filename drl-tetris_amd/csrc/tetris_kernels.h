@@ -118,30 +118,64 @@ constexpr int CHAIN_STRIDE = TE_CHAIN_STRIDE;
 #endif
 constexpr uint32_t CHAIN_SPIN_LIMIT = 1u << 22;     // default polls before a wave gives up (each ~0.5 us: an agent-scope load + a short sleep): ~2 s
 
+// Scoped accesses of the chained kernels' hand-off (vector memory instructions on the global aperture, no wait behind them).
+// st_flag / ld_flag: a flag word of the batch (KArgs::status, pinned host memory) at system scope (`sc0 sc1`).  The host reads
+// F_XCC0 and F_PLACE, which only the XCD-affine kernels write, after the queue's last packet has released at system scope
+// (tetris_hip.hip: rollout_direct, `last_release`).  A give-up (F_CHAIN) can also happen in a direct call without the affine form,
+// whose last packet releases at agent scope only: chain_give_up drains that store itself (rare path).
+// st_xcd: the epoch word of the XCD-affine hand-off, a plain store: the line stays in this XCD's L2, where the same wave of the
+// next launch polls it with an `sc1` load (MEM_AFFINE).  A wavefront-scope relaxed atomic store is no promise of the HIP memory
+// model for a word another launch reads: this relies on gfx950's code generation for that scope (a `global_store_dword` with no
+// cache-policy bits; checked by tests/test_chain_isa.py), the same single-L2 coherence the MEM_AFFINE state stores rely on.
 #if defined(__HIP_DEVICE_COMPILE__)
+typedef __attribute__((address_space(1))) uint32_t te_gu32;
 TE_HD void or_agent(uint32_t* p, uint32_t v) { (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+TE_HD void st_flag(uint32_t* p, uint32_t v) { __hip_atomic_store((te_gu32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+TE_HD uint32_t ld_flag(const uint32_t* p) { return __hip_atomic_load((const te_gu32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+TE_HD void st_xcd(uint32_t* p, uint32_t v) { __hip_atomic_store((te_gu32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 #else
 TE_HD void or_agent(uint32_t* p, uint32_t v) { *p |= v; }
+TE_HD void st_flag(uint32_t* p, uint32_t v) { *(volatile uint32_t*)p = v; }
+TE_HD uint32_t ld_flag(const uint32_t* p) { return *(const volatile uint32_t*)p; }
+TE_HD void st_xcd(uint32_t* p, uint32_t v) { *p = v; }
 #endif
 
-// true when the state of this wave's games as launch E - 1 left it is visible (their stores were `sc1` and drained before the
-// epoch word was written, and the word is polled with an `sc1` load: MI355X_MICROARCH.md, valid forms of an inter-workgroup hand-off).
-// false: the wave must leave its games untouched and publish nothing (`marker`: the one lane that records a give-up).
-TE_HD bool chain_wait(const KArgs& a, uint32_t wave, bool marker) {
+// chain_poll: polls a wave's epoch word and returns the last value seen.  `a.epoch - 1`: the state of this wave's
+// games as launch E - 1 left it is visible (their stores were `sc1` and drained before the epoch word was written, and the word
+// is polled with an `sc1` load: MI355X_MICROARCH.md, valid forms of an inter-workgroup hand-off).  Anything else: the wave
+// leaves its games untouched and publishes nothing — with CHAIN_ABANDONED set an earlier launch's wave gave up and recorded it
+// (nothing to add); without it this wave gave up (its bound, or F_PLACE) and records that (chain_give_up).
+// Every lane polls the same word and the value is made wave-uniform: the loop is a scalar one, and a match at the first poll
+// (the common case) goes straight to the caller's state loads.  (chain_spin_limit >= 1: the host never sets 0.)
+TE_HD uint32_t chain_poll(const KArgs& a, uint32_t wave) {
     const uint32_t want = a.epoch - 1u;
-    uint32_t* word = a.chain + (size_t)wave * CHAIN_STRIDE;
-    for (uint32_t spin = 0; spin < a.chain_spin_limit; spin++) {
-        const uint32_t v = ld_agent(word);
-        if (v == want) return true;
-        if (v & CHAIN_ABANDONED) return false;              // an earlier launch's wave gave up: nothing to add
+    const uint32_t* word = a.chain + (size_t)wave * CHAIN_STRIDE;
+    uint32_t v = (uint32_t)wave_uniform(ld_agent(word));
+    for (uint32_t polls = 1; v != want && !(v & CHAIN_ABANDONED) && polls < a.chain_spin_limit; polls++) {
         // an XCD-affine launch found workgroups misplaced (they touched nothing; their games' epochs will never come): every waiting
         // wave learns it from the flag word within ~0.1 ms instead of waiting out its bound
-        if ((spin & 255u) == 255u && ((volatile uint32_t*)a.status)[F_PLACE]) break;
+        if ((polls & 255u) == 0 && wave_uniform(ld_flag(a.status + F_PLACE)) != 0) break;
 #if defined(__HIP_DEVICE_COMPILE__)
         __builtin_amdgcn_s_sleep(TE_CHAIN_SLEEP);
 #endif
+        v = (uint32_t)wave_uniform(ld_agent(word));
     }
-    if (marker) { or_agent(word, CHAIN_ABANDONED); ((volatile uint32_t*)a.status)[F_CHAIN] = 1u; }
+    return v;
+}
+// `marker`: the one lane that records a give-up
+TE_HD void chain_give_up(const KArgs& a, uint32_t wave, bool marker) {
+    if (!marker) return;
+    or_agent(a.chain + (size_t)wave * CHAIN_STRIDE, CHAIN_ABANDONED);
+    st_flag(a.status + F_CHAIN, 1u);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // (see st_flag: not every call's last packet releases at system scope)
+#endif
+}
+// true: the predecessor's state is visible; false: a give-up has been recorded (by this wave or an earlier one)
+TE_HD bool chain_wait(const KArgs& a, uint32_t wave, bool marker) {
+    const uint32_t seen = chain_poll(a, wave);
+    if (seen == a.epoch - 1u) return true;
+    if (!(seen & CHAIN_ABANDONED)) chain_give_up(a, wave, marker);
     return false;
 }
 
