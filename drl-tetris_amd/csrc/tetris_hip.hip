@@ -925,6 +925,7 @@ struct Stage {
         h = d = nullptr; cap = 0;
     }
 };
+constexpr int STAGES = 6;                // most pairs one synchronous call stages through (HostCall): step_keys, step_rt, enumerate_drops
 
 // 120: the host may be 241 launches (~1 ms of GPU work at 64k boards) ahead of what it has seen finish.  With 32 (round 2: 65
 // launches, 0.26 ms) a host thread that loses its core for a fraction of a millisecond — other tenants' jobs share the box's CPUs —
@@ -988,7 +989,9 @@ struct tetris_batch {
     uint32_t xcd_skew = 0;               // test aid (tetris_debug_xcd_skew): added to the queues' measured start XCDs
     int affine_failures = 0;             // calls in which a workgroup found itself misplaced (three: the affine form is switched off)
     bool home_async = false;             // asynchronous (_dev) work was enqueued on the batch's stream since the last drain
-    bool busy = true;                    // something was enqueued on one of the batch's streams since the last drain
+    // something was enqueued on one of the batch's streams since the last drain.  Whatever enqueues sets it (check_batch, HostCall,
+    // service_flags): on the batch's own stream finish_call skips the drain without it, also in a call's second drain (get_actions)
+    bool busy = true;
     // Run-ahead gate of the asynchronous entry points: every GATE_GROUP launches an event is recorded; before a new group is
     // enqueued the host waits for the event of the group before the previous one.  At most 2 * GATE_GROUP + 1 launches are
     // therefore in flight whose flag words the host has not seen; `margin` is sized for that many steps.
@@ -996,7 +999,8 @@ struct tetris_batch {
     int gate_count = 0;                  // launches since the last recorded event
     int gate_slot = 0;                   // event to record next
     int gate_pending[2] = {0, 0};        // event has been recorded and not waited for
-    Stage s_idx, s_in0, s_in1, s_in2, s_out0, s_out1, s_out2, s_big, s_act0, s_act1, s_act2;
+    Stage stage[STAGES];                 // the synchronous calls' staging pairs (HostCall hands them out in order)
+    Stage recover_idx;                   // chain_recover's game lists: it runs inside finish_call, while a call's outputs still wait in `stage`
     // tetris_action_lists_dev: device scratch for the slabs of one chunk of games (grown on demand), the identity index the
     // chunks' k_actions launches read their game numbers from, and the status words k_actions writes its own overflow flag to
     // (the compaction finds every overflow itself, per game, and reports it as F_LISTS instead)
@@ -1228,26 +1232,92 @@ static int check_batch(tetris_batch* b, bool enqueues = true) {
     return TETRIS_OK;
 }
 
-// copies idx to the device (or returns NULL for identity); validates range
-static int stage_idx(tetris_batch* b, const int32_t* idx, int n, const int32_t** d_idx) {
-    *d_idx = nullptr;
-    if (n < 0 || (!idx && n > b->N)) return fail(TETRIS_E_ARG, "n out of range");
-    if (!idx) return TETRIS_OK;
-    for (int i = 0; i < n; i++)
-        if (idx[i] < 0 || idx[i] >= b->N) return fail(TETRIS_E_ARG, "game index out of range");
-    int rc = b->s_idx.ensure((size_t)n * 4 + 4);
-    if (rc) return rc;
-    memcpy(b->s_idx.h, idx, (size_t)n * 4);
-    HIP_TRY(hipMemcpyAsync(b->s_idx.d, b->s_idx.h, (size_t)n * 4, hipMemcpyHostToDevice, b->stream));
-    *d_idx = (const int32_t*)b->s_idx.d;
+// The host traffic of one synchronous call (the entry points that take and return host arrays), on the batch's stream.  An input
+// goes from the caller's array to a pinned half, then to the device; an output gets a device half for the kernel, and finish()
+// copies it back to its pinned half, drains (finish_call) and only then copies it on to the caller's array.  The k-th input or
+// output of a call takes b->stage[k] (a NULL input keeps its place), so one call's buffers never alias, and every copy queued
+// here sets b->busy.
+struct HostCall {
+    tetris_batch* const b;
+    const int32_t* d_idx = nullptr;      // idx(): the call's game indices on the device (NULL: the first n games)
+    int used = 0, n_out = 0;
+    struct Out { const Stage* s; size_t bytes; void* dst; } outs[STAGES];
+
+    // the next pair, `bytes` long at least (the caller fills its pinned half, or the kernel its device half)
+    int take(size_t bytes, Stage** s) {
+        if (used >= STAGES) return fail(TETRIS_E_ARG, "internal: a call takes more than STAGES staging buffers");
+        *s = &b->stage[used++];
+        return (*s)->ensure(bytes + 16);
+    }
+    // pinned half -> device half
+    int send(const Stage* s, size_t bytes) {
+        b->busy = true;
+        HIP_TRY(hipMemcpyAsync(s->d, s->h, bytes, hipMemcpyHostToDevice, b->stream));
+        return TETRIS_OK;
+    }
+    // `count` T of the caller's -> the device (*d; src NULL: *d = NULL)
+    template <class T> int in(const T* src, size_t count, const T** d) {
+        *d = nullptr;
+        if (!src) { used++; return TETRIS_OK; }
+        Stage* s;
+        int rc = take(count * sizeof(T), &s);
+        if (rc) return rc;
+        memcpy(s->h, src, count * sizeof(T));
+        *d = (const T*)s->d;
+        return send(s, count * sizeof(T));
+    }
+    // game indices: validated, then staged (-> d_idx)
+    int idx(const int32_t* idx, int n) {
+        if (n < 0 || (!idx && n > b->N)) return fail(TETRIS_E_ARG, "n out of range");
+        for (int i = 0; idx && i < n; i++)
+            if (idx[i] < 0 || idx[i] >= b->N) return fail(TETRIS_E_ARG, "game index out of range");
+        return in(idx, (size_t)n, &d_idx);
+    }
+    // `count` T on the device for the kernel (*d); finish() copies them to `dst`, or leaves them in the pinned half for the caller
+    // to read (*h) when dst is NULL
+    template <class T> int out(void* dst, size_t count, T** d, const T** h = nullptr) {
+        Stage* s;
+        int rc = take(count * sizeof(T), &s);
+        if (rc) return rc;
+        outs[n_out++] = {s, count * sizeof(T), dst};
+        *d = (T*)s->d;
+        if (h) *h = (const T*)s->h;
+        return TETRIS_OK;
+    }
+    int finish() {
+        for (int k = 0; k < n_out; k++) {
+            b->busy = true;
+            HIP_TRY(hipMemcpyAsync(outs[k].s->h, outs[k].s->d, outs[k].bytes, hipMemcpyDeviceToHost, b->stream));
+        }
+        int rc = finish_call(b);
+        if (rc) return rc;
+        for (int k = 0; k < n_out; k++)
+            if (outs[k].dst) memcpy(outs[k].dst, outs[k].s->h, outs[k].bytes);
+        return TETRIS_OK;
+    }
+};
+
+// every player index < P (player NULL: nothing to check)
+static int check_players(const tetris_batch* b, const uint8_t* player, int n) {
+    for (int i = 0; player && i < n; i++)
+        if (player[i] >= b->P) return fail(TETRIS_E_ARG, "player index out of range");
     return TETRIS_OK;
 }
 
-static int stage_in(tetris_batch* b, Stage& s, const void* src, size_t bytes) {
-    int rc = s.ensure(bytes + 4);
-    if (rc) return rc;
-    memcpy(s.h, src, bytes);
-    HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, b->stream));
+// The rest of a synchronous step: done [n] and lines / dead [P][n] on the device, the launch, io.finish(), then lines / dead to the
+// caller as [n][P]
+template <int MODE>
+static int finish_step(HostCall& io, KArgs& a, int n, uint8_t* done, uint8_t* lines, uint8_t* dead) {
+    const int P = io.b->P;
+    const uint8_t *hl, *hd;
+    int rc = io.out(done, (size_t)n, &a.done);
+    if (rc || (rc = io.out(nullptr, (size_t)n * P, &a.lines, &hl)) || (rc = io.out(nullptr, (size_t)n * P, &a.dead, &hd))) return rc;
+    if ((rc = launch_game<MODE>(io.b, a)) || (rc = io.finish())) return rc;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < P; p++) {
+            if (lines) lines[(size_t)i * P + p] = hl[(size_t)p * n + i];
+            if (dead) dead[(size_t)i * P + p] = hd[(size_t)p * n + i];
+        }
     return TETRIS_OK;
 }
 
@@ -1307,8 +1377,8 @@ int tetris_destroy(tetris_batch* b) {
     if (b->stall_stream) { (void)hipStreamSynchronize(b->stall_stream); (void)hipStreamDestroy(b->stall_stream); }
     if (b->direct_used) { aql::Device* dev = aql::device_for(b->device); if (dev->ok) aql::quiesce(dev->qs); }      // (a test's idle kernel may still sit there)
     (void)hipFree(b->d_plan_slabs); (void)hipFree(b->d_iota); (void)hipFree(b->d_plan_status);
-    Stage* all[] = {&b->s_idx, &b->s_in0, &b->s_in1, &b->s_in2, &b->s_out0, &b->s_out1, &b->s_out2, &b->s_big, &b->s_act0, &b->s_act1, &b->s_act2};
-    for (Stage* s : all) s->release();
+    for (Stage& s : b->stage) s.release();
+    b->recover_idx.release();
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -1413,19 +1483,16 @@ static int create_impl(tetris_batch** out, int n_games, int n_players, int heigh
     CREATE_TRY(hipMemsetAsync(b->d_state, 0, state_bytes, b->stream));
     int rc = tables_acquire(&b->tab, device, piece_map, b->stream);
     if (rc) { std::string keep = g_err; tetris_destroy(b); return fail(rc, keep); }
-    const int16_t* d_seeds = nullptr;
-    if (seeds) {
-        rc = stage_in(b, b->s_in0, seeds, (size_t)n_games * 2);
-        if (rc) { std::string keep = g_err; tetris_destroy(b); return fail(rc, keep); }
-        d_seeds = (const int16_t*)b->s_in0.d;
-    }
+    HostCall io{b};
+    const int16_t* d_seeds;
+    if ((rc = io.in(seeds, (size_t)n_games, &d_seeds))) { std::string keep = g_err; tetris_destroy(b); return fail(rc, keep); }
     b->split = split; b->side = side;
     if (split && side == 1) CREATE_TRY(hipMalloc((void**)&b->d_shadow, (size_t)(UNDO_WORDS + b->nw) * (size_t)b->stride * 4));
     KArgs a = base_args(b, n_games, nullptr);
     a.seeds = d_seeds;
     a.steps = side;
     rc = split ? launch_game<M_SPLIT_INIT>(b, a) : launch_game<M_INIT>(b, a);
-    if (!rc) rc = finish_call(b);
+    if (!rc) rc = io.finish();
     if (rc) { std::string keep = g_err; tetris_destroy(b); return fail(rc, keep); }
     *out = b;
     return TETRIS_OK;
@@ -1653,27 +1720,24 @@ int tetris_sync(tetris_batch* b) {
 int tetris_reset(tetris_batch* b, const int32_t* idx, int n, const int16_t* seeds) {
     int rc = check_batch(b);
     if (rc) return rc;
-    const int32_t* d_idx;
-    if ((rc = stage_idx(b, idx, n, &d_idx))) return rc;
-    if (n == 0) return finish_call(b);          // still a synchronisation point: sticky errors surface, tables get extended
-    KArgs a = base_args(b, n, d_idx);
-    if (seeds) {
-        if ((rc = stage_in(b, b->s_in0, seeds, (size_t)n * 2))) return rc;
-        a.seeds = (const int16_t*)b->s_in0.d;
-    }
+    HostCall io{b};
+    if ((rc = io.idx(idx, n))) return rc;
+    if (n == 0) return io.finish();             // still a synchronisation point: sticky errors surface, tables get extended
+    KArgs a = base_args(b, n, io.d_idx);
+    if ((rc = io.in(seeds, (size_t)n, &a.seeds))) return rc;
     if ((rc = b->split ? launch_game<M_SPLIT_RESET>(b, a) : launch_game<M_RESET>(b, a))) return rc;
-    return finish_call(b);
+    return io.finish();
 }
 
 // host keys [n][P][K] -> device [K][P][n]; host lens [n][P] -> device [P][n]
-static int stage_keys(tetris_batch* b, int n, const uint8_t* keys, const uint8_t* lens, int max_keys, KArgs& a) {
+static int stage_keys(HostCall& io, int n, const uint8_t* keys, const uint8_t* lens, int max_keys, KArgs& a) {
     if (!keys || !lens || max_keys < 1) return fail(TETRIS_E_ARG, "keys/lens/max_keys");
-    const int P = b->P;
-    int rc = b->s_in0.ensure((size_t)n * P * max_keys + 4);
-    if (rc) return rc;
-    if ((rc = b->s_in1.ensure((size_t)n * P + 4))) return rc;
-    uint8_t* hk = (uint8_t*)b->s_in0.h;
-    uint8_t* hl = (uint8_t*)b->s_in1.h;
+    const int P = io.b->P;
+    Stage *sk, *sl;
+    int rc = io.take((size_t)n * P * max_keys, &sk);
+    if (rc || (rc = io.take((size_t)n * P, &sl))) return rc;
+    uint8_t* hk = (uint8_t*)sk->h;
+    uint8_t* hl = (uint8_t*)sl->h;
     for (int i = 0; i < n; i++)
         for (int p = 0; p < P; p++) {
             const int len = lens[(size_t)i * P + p];
@@ -1692,78 +1756,45 @@ static int stage_keys(tetris_batch* b, int n, const uint8_t* keys, const uint8_t
                 for (int i = i0; i < i1; i++) dst[i] = src[(size_t)i * P * max_keys];
             }
     }
-    HIP_TRY(hipMemcpyAsync(b->s_in0.d, hk, (size_t)n * P * max_keys, hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->s_in1.d, hl, (size_t)n * P, hipMemcpyHostToDevice, b->stream));
-    a.keys = (const uint8_t*)b->s_in0.d; a.lens = (const uint8_t*)b->s_in1.d; a.max_keys = max_keys;
-    return TETRIS_OK;
-}
-
-static int stage_outputs(tetris_batch* b, int n, KArgs& a) {
-    int rc;
-    if ((rc = b->s_out0.ensure((size_t)n + 4))) return rc;
-    if ((rc = b->s_out1.ensure((size_t)n * b->P + 4))) return rc;
-    if ((rc = b->s_out2.ensure((size_t)n * b->P + 4))) return rc;
-    a.done = (uint8_t*)b->s_out0.d; a.lines = (uint8_t*)b->s_out1.d; a.dead = (uint8_t*)b->s_out2.d;
-    return TETRIS_OK;
-}
-
-// device [P][n] -> host [n][P]
-static int fetch_outputs(tetris_batch* b, int n, uint8_t* done, uint8_t* lines, uint8_t* dead) {
-    const int P = b->P;
-    HIP_TRY(hipMemcpyAsync(b->s_out0.h, b->s_out0.d, (size_t)n, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->s_out1.h, b->s_out1.d, (size_t)n * P, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->s_out2.h, b->s_out2.d, (size_t)n * P, hipMemcpyDeviceToHost, b->stream));
-    int rc = finish_call(b);
-    if (rc) return rc;
-    if (done) memcpy(done, b->s_out0.h, (size_t)n);
-    const uint8_t* hl = (const uint8_t*)b->s_out1.h;
-    const uint8_t* hd = (const uint8_t*)b->s_out2.h;
-    for (int i = 0; i < n; i++)
-        for (int p = 0; p < P; p++) {
-            if (lines) lines[(size_t)i * P + p] = hl[(size_t)p * n + i];
-            if (dead) dead[(size_t)i * P + p] = hd[(size_t)p * n + i];
-        }
+    if ((rc = io.send(sk, (size_t)n * P * max_keys)) || (rc = io.send(sl, (size_t)n * P))) return rc;
+    a.keys = (const uint8_t*)sk->d; a.lens = (const uint8_t*)sl->d; a.max_keys = max_keys;
     return TETRIS_OK;
 }
 
 int tetris_make_actions(tetris_batch* b, const int32_t* idx, int n, const uint8_t* keys, const uint8_t* lens, int max_keys) {
     int rc = check_batch(b);
     if (rc) return rc;
-    const int32_t* d_idx;
-    if ((rc = stage_idx(b, idx, n, &d_idx))) return rc;
+    HostCall io{b};
+    if ((rc = io.idx(idx, n))) return rc;
     if (n == 0) return TETRIS_OK;
-    KArgs a = base_args(b, n, d_idx);
-    if ((rc = stage_keys(b, n, keys, lens, max_keys, a))) return rc;
+    KArgs a = base_args(b, n, io.d_idx);
+    if ((rc = stage_keys(io, n, keys, lens, max_keys, a))) return rc;
     if ((rc = launch_game<M_MAKE>(b, a))) return rc;
-    return finish_call(b);
+    return io.finish();
 }
 
 int tetris_finish_actions(tetris_batch* b, const int32_t* idx, int n, int ms, uint8_t* done, uint8_t* lines, uint8_t* dead) {
     int rc = check_batch(b);
     if (rc) return rc;
-    const int32_t* d_idx;
-    if ((rc = stage_idx(b, idx, n, &d_idx))) return rc;
+    HostCall io{b};
+    if ((rc = io.idx(idx, n))) return rc;
     if (n == 0) return TETRIS_OK;
-    KArgs a = base_args(b, n, d_idx);
+    KArgs a = base_args(b, n, io.d_idx);
     a.ms = ms;
-    if ((rc = stage_outputs(b, n, a))) return rc;
-    if ((rc = launch_game<M_FINISH>(b, a))) return rc;
-    return fetch_outputs(b, n, done, lines, dead);
+    return finish_step<M_FINISH>(io, a, n, done, lines, dead);
 }
 
 int tetris_step_keys(tetris_batch* b, const int32_t* idx, int n, const uint8_t* keys, const uint8_t* lens, int max_keys,
                      int ms, uint8_t* done, uint8_t* lines, uint8_t* dead) {
     int rc = check_batch(b);
     if (rc) return rc;
-    const int32_t* d_idx;
-    if ((rc = stage_idx(b, idx, n, &d_idx))) return rc;
+    HostCall io{b};
+    if ((rc = io.idx(idx, n))) return rc;
     if (n == 0) return TETRIS_OK;
-    KArgs a = base_args(b, n, d_idx);
+    KArgs a = base_args(b, n, io.d_idx);
     a.ms = ms;
-    if ((rc = stage_keys(b, n, keys, lens, max_keys, a))) return rc;
-    if ((rc = stage_outputs(b, n, a))) return rc;
-    if ((rc = launch_game<M_STEP_KEYS>(b, a))) return rc;
-    return fetch_outputs(b, n, done, lines, dead);
+    if ((rc = stage_keys(io, n, keys, lens, max_keys, a))) return rc;
+    return finish_step<M_STEP_KEYS>(io, a, n, done, lines, dead);
 }
 
 int tetris_step_rt_dev_ex(tetris_batch* b, const uint8_t* d_rot, const uint8_t* d_trans, const uint8_t* d_player, int ms,
@@ -1846,40 +1877,34 @@ int tetris_step_rt(tetris_batch* b, const uint8_t* rot, const uint8_t* trans, co
     if (rc) return rc;
     if (!rot || !trans) return fail(TETRIS_E_ARG, "rot/trans are NULL");
     const int n = b->N;
-    if (player)
-        for (int i = 0; i < n; i++)
-            if (player[i] >= b->P) return fail(TETRIS_E_ARG, "player index out of range");
+    if ((rc = check_players(b, player, n))) return rc;
     KArgs a = base_args(b, n, nullptr);
     a.ms = ms;
-    if ((rc = stage_in(b, b->s_in0, rot, (size_t)n))) return rc;
-    if ((rc = stage_in(b, b->s_in1, trans, (size_t)n))) return rc;
-    a.rot = (const uint8_t*)b->s_in0.d; a.trans = (const uint8_t*)b->s_in1.d;
-    if (player) {
-        if ((rc = stage_in(b, b->s_in2, player, (size_t)n))) return rc;
-        a.player = (const uint8_t*)b->s_in2.d;
-    }
-    if ((rc = stage_outputs(b, n, a))) return rc;
-    if ((rc = launch_game<M_STEP_RT>(b, a))) return rc;
-    return fetch_outputs(b, n, done, lines, dead);
+    HostCall io{b};
+    if ((rc = io.in(rot, (size_t)n, &a.rot)) || (rc = io.in(trans, (size_t)n, &a.trans)) || (rc = io.in(player, (size_t)n, &a.player))) return rc;
+    return finish_step<M_STEP_RT>(io, a, n, done, lines, dead);
 }
 
 int tetris_observe_records(tetris_batch* b, const int32_t* idx, int n, tetris_record* records, uint8_t* round_over,
                            int8_t* last_winner) {
     int rc = check_batch(b);
     if (rc) return rc;
-    const int32_t* d_idx;
-    if ((rc = stage_idx(b, idx, n, &d_idx))) return rc;
+    HostCall io{b};
+    if ((rc = io.idx(idx, n))) return rc;
     if (n == 0) return TETRIS_OK;
     const size_t rec_bytes = (size_t)n * b->P * sizeof(tetris_record);
-    if ((rc = b->s_big.ensure(rec_bytes + 16))) return rc;
-    if ((rc = b->s_out0.ensure((size_t)n + 4))) return rc;
-    if ((rc = b->s_out1.ensure((size_t)n + 4))) return rc;
+    tetris_record* d_rec;
+    uint8_t* d_round_over;
+    int8_t* d_last_winner;
+    Stage* rec;                         // (records NULL: the kernel writes them all the same, nothing copies them back)
+    if ((rc = records ? io.out(records, (size_t)n * b->P, &d_rec) : io.take(rec_bytes, &rec))) return rc;
+    if (!records) d_rec = (tetris_record*)rec->d;
+    if ((rc = io.out(round_over, (size_t)n, &d_round_over)) || (rc = io.out(last_winner, (size_t)n, &d_last_winner))) return rc;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    tetris_record* d_rec = (tetris_record*)b->s_big.d;
     HIP_TRY(hipMemsetAsync(d_rec, 0, rec_bytes, b->stream));      // struct padding stays deterministic
 #define LAUNCH_OBSERVE(PP, TT)                                                                                              \
-    hipLaunchKernelGGL((k_observe<PP, TT>), grid, block, 0, b->stream, geo_of_batch(b), n, d_idx, b->H, d_rec, \
-                       (uint8_t*)b->s_out0.d, (int8_t*)b->s_out1.d)
+    hipLaunchKernelGGL((k_observe<PP, TT>), grid, block, 0, b->stream, geo_of_batch(b), n, io.d_idx, b->H, d_rec, \
+                       d_round_over, d_last_winner)
     if (b->P == 1 && !b->tint) LAUNCH_OBSERVE(1, false);
     else if (b->P == 1) LAUNCH_OBSERVE(1, true);
     else if (b->P == 2 && !b->tint) LAUNCH_OBSERVE(2, false);
@@ -1890,14 +1915,7 @@ int tetris_observe_records(tetris_batch* b, const int32_t* idx, int n, tetris_re
     else LAUNCH_OBSERVE(4, true);
 #undef LAUNCH_OBSERVE
     HIP_TRY(hipGetLastError());
-    if (records) HIP_TRY(hipMemcpyAsync(b->s_big.h, b->s_big.d, rec_bytes, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->s_out0.h, b->s_out0.d, (size_t)n, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->s_out1.h, b->s_out1.d, (size_t)n, hipMemcpyDeviceToHost, b->stream));
-    if ((rc = finish_call(b))) return rc;
-    if (records) memcpy(records, b->s_big.h, rec_bytes);
-    if (round_over) memcpy(round_over, b->s_out0.h, (size_t)n);
-    if (last_winner) memcpy(last_winner, b->s_out1.h, (size_t)n);
-    return TETRIS_OK;
+    return io.finish();
 }
 
 int tetris_observe_packed_dev(tetris_batch* b, const int32_t* d_idx, int n, const uint8_t* d_player, uint8_t* d_visual,
@@ -1945,49 +1963,33 @@ int tetris_observe_packed(tetris_batch* b, const int32_t* idx, int n, const uint
     int rc = check_batch(b);
     if (rc) return rc;
     if (!visual || !vector || !piece) return fail(TETRIS_E_ARG, "visual/vector/piece are NULL");
-    const int32_t* d_idx;
-    if ((rc = stage_idx(b, idx, n, &d_idx))) return rc;
+    HostCall io{b};
+    if ((rc = io.idx(idx, n))) return rc;
     if (n == 0) return TETRIS_OK;
-    const uint8_t* d_player = nullptr;
-    if (player) {
-        for (int i = 0; i < n; i++)
-            if (player[i] >= b->P) return fail(TETRIS_E_ARG, "player index out of range");
-        if ((rc = stage_in(b, b->s_in0, player, (size_t)n))) return rc;
-        d_player = (const uint8_t*)b->s_in0.d;
-    }
-    const size_t vis = (size_t)b->P * n * b->H * NCOL, vec = (size_t)b->P * n * 12, pc = (size_t)b->P * n;
-    if ((rc = b->s_big.ensure(vis + 16)) || (rc = b->s_out0.ensure(vec + 4)) || (rc = b->s_out1.ensure(pc + 4))) return rc;
-    if ((rc = tetris_observe_packed_dev(b, d_idx, n, d_player, (uint8_t*)b->s_big.d, (uint8_t*)b->s_out0.d, (uint8_t*)b->s_out1.d))) return rc;
-    HIP_TRY(hipMemcpyAsync(b->s_big.h, b->s_big.d, vis, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->s_out0.h, b->s_out0.d, vec, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->s_out1.h, b->s_out1.d, pc, hipMemcpyDeviceToHost, b->stream));
-    if ((rc = finish_call(b))) return rc;
-    memcpy(visual, b->s_big.h, vis); memcpy(vector, b->s_out0.h, vec); memcpy(piece, b->s_out1.h, pc);
-    return TETRIS_OK;
+    const uint8_t* d_player;
+    if ((rc = check_players(b, player, n)) || (rc = io.in(player, (size_t)n, &d_player))) return rc;
+    const size_t pn = (size_t)b->P * n;
+    uint8_t *d_visual, *d_vector, *d_piece;
+    if ((rc = io.out(visual, pn * b->H * NCOL, &d_visual)) || (rc = io.out(vector, pn * 12, &d_vector)) || (rc = io.out(piece, pn, &d_piece))) return rc;
+    if ((rc = tetris_observe_packed_dev(b, io.d_idx, n, d_player, d_visual, d_vector, d_piece))) return rc;
+    return io.finish();
 }
 
 static int snapshot_impl(tetris_batch* b, const int32_t* idx, int n, uint32_t* blob, int restore) {
     int rc = check_batch(b);
     if (rc) return rc;
     if (!blob) return fail(TETRIS_E_ARG, "blob is NULL");
-    const int32_t* d_idx;
-    if ((rc = stage_idx(b, idx, n, &d_idx))) return rc;
+    HostCall io{b};
+    if ((rc = io.idx(idx, n))) return rc;
     if (n == 0) return TETRIS_OK;
-    const int words = NGWORDS + b->P * b->nw;
-    const size_t bytes = (size_t)n * words * 4;
-    if ((rc = b->s_big.ensure(bytes + 16))) return rc;
-    if (restore) {
-        memcpy(b->s_big.h, blob, bytes);
-        HIP_TRY(hipMemcpyAsync(b->s_big.d, b->s_big.h, bytes, hipMemcpyHostToDevice, b->stream));
-    }
-    size_t total = (size_t)n * words;
-    hipLaunchKernelGGL(k_snapshot, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, b->stream, geo_of_batch(b), n, d_idx,
-                       (uint32_t*)b->s_big.d, restore);
+    const size_t total = (size_t)n * (NGWORDS + b->P * b->nw);
+    const uint32_t* d_in;
+    uint32_t* d_out;
+    if ((rc = restore ? io.in((const uint32_t*)blob, total, &d_in) : io.out(blob, total, &d_out))) return rc;
+    hipLaunchKernelGGL(k_snapshot, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, b->stream, geo_of_batch(b), n, io.d_idx,
+                       restore ? (uint32_t*)d_in : d_out, restore);
     HIP_TRY(hipGetLastError());
-    if (!restore) HIP_TRY(hipMemcpyAsync(b->s_big.h, b->s_big.d, bytes, hipMemcpyDeviceToHost, b->stream));
-    if ((rc = finish_call(b))) return rc;
-    if (!restore) memcpy(blob, b->s_big.h, bytes);
-    return TETRIS_OK;
+    return io.finish();
 }
 
 int tetris_snapshot(tetris_batch* b, const int32_t* idx, int n, uint32_t* blob) { return snapshot_impl(b, idx, n, blob, 0); }
@@ -1999,14 +2001,14 @@ int tetris_set_dead(tetris_batch* b, const int32_t* idx, int n, const uint8_t* d
     int rc = check_batch(b);
     if (rc) return rc;
     if (!dead) return fail(TETRIS_E_ARG, "dead is NULL");
-    const int32_t* d_idx;
-    if ((rc = stage_idx(b, idx, n, &d_idx))) return rc;
+    HostCall io{b};
+    const uint8_t* d_dead;
+    if ((rc = io.idx(idx, n))) return rc;
     if (n == 0) return TETRIS_OK;
-    if ((rc = stage_in(b, b->s_in0, dead, (size_t)n * b->P))) return rc;
-    hipLaunchKernelGGL(k_set_dead, dim3((unsigned)((n * b->P + 255) / 256)), dim3(256), 0, b->stream, geo_of_batch(b), n, d_idx,
-                       (const uint8_t*)b->s_in0.d);
+    if ((rc = io.in(dead, (size_t)n * b->P, &d_dead))) return rc;
+    hipLaunchKernelGGL(k_set_dead, dim3((unsigned)((n * b->P + 255) / 256)), dim3(256), 0, b->stream, geo_of_batch(b), n, io.d_idx, d_dead);
     HIP_TRY(hipGetLastError());
-    return finish_call(b);
+    return io.finish();
 }
 
 int tetris_enumerate_drops_dev_ex(tetris_batch* b, const int32_t* d_idx, int n, const uint8_t* d_player, uint8_t* d_valid,
@@ -2017,32 +2019,19 @@ int tetris_enumerate_drops(tetris_batch* b, const int32_t* idx, int n, const uin
     int rc = check_batch(b);
     if (rc) return rc;
     if (!valid || !land_y || !cleared) return fail(TETRIS_E_ARG, "valid/land_y/cleared are NULL");
-    const int32_t* d_idx;
-    if ((rc = stage_idx(b, idx, n, &d_idx))) return rc;
+    HostCall io{b};
+    if ((rc = io.idx(idx, n))) return rc;
     if (n == 0) return TETRIS_OK;
-    const uint8_t* d_player = nullptr;
-    if (player) {
-        for (int i = 0; i < n; i++)
-            if (player[i] >= b->P) return fail(TETRIS_E_ARG, "player index out of range");
-        if ((rc = stage_in(b, b->s_in0, player, (size_t)n))) return rc;
-        d_player = (const uint8_t*)b->s_in0.d;
-    }
+    const uint8_t* d_player;
+    if ((rc = check_players(b, player, n)) || (rc = io.in(player, (size_t)n, &d_player))) return rc;
     const size_t lanes = (size_t)n * 40;
-    if ((rc = b->s_out0.ensure(lanes + 4))) return rc;
-    if ((rc = b->s_out1.ensure(lanes + 4))) return rc;
-    if ((rc = b->s_out2.ensure(lanes + 4))) return rc;
-    if (after && (rc = b->s_big.ensure(lanes * NCOL * 4 + 16))) return rc;
-    uint32_t* d_after = after ? (uint32_t*)b->s_big.d : nullptr;
-    if ((rc = tetris_enumerate_drops_dev_ex(b, d_idx, n, d_player, (uint8_t*)b->s_out0.d, (int8_t*)b->s_out1.d, (uint8_t*)b->s_out2.d,
-                                            d_after, 0))) return rc;
-    HIP_TRY(hipMemcpyAsync(b->s_out0.h, b->s_out0.d, lanes, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->s_out1.h, b->s_out1.d, lanes, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->s_out2.h, b->s_out2.d, lanes, hipMemcpyDeviceToHost, b->stream));
-    if (after) HIP_TRY(hipMemcpyAsync(b->s_big.h, b->s_big.d, lanes * NCOL * 4, hipMemcpyDeviceToHost, b->stream));
-    if ((rc = finish_call(b))) return rc;
-    memcpy(valid, b->s_out0.h, lanes); memcpy(land_y, b->s_out1.h, lanes); memcpy(cleared, b->s_out2.h, lanes);
-    if (after) memcpy(after, b->s_big.h, lanes * NCOL * 4);
-    return TETRIS_OK;
+    uint8_t *d_valid, *d_cleared;
+    int8_t* d_land_y;
+    uint32_t* d_after = nullptr;
+    if ((rc = io.out(valid, lanes, &d_valid)) || (rc = io.out(land_y, lanes, &d_land_y)) || (rc = io.out(cleared, lanes, &d_cleared)) ||
+        (after && (rc = io.out(after, lanes * NCOL, &d_after)))) return rc;
+    if ((rc = tetris_enumerate_drops_dev_ex(b, io.d_idx, n, d_player, d_valid, d_land_y, d_cleared, d_after, 0))) return rc;
+    return io.finish();
 }
 
 int tetris_enumerate_drops_dev_ex(tetris_batch* b, const int32_t* d_idx, int n, const uint8_t* d_player, uint8_t* d_valid,
@@ -2098,66 +2087,55 @@ int tetris_get_actions(tetris_batch* b, const int32_t* idx, int n, const uint8_t
     if (rc) return rc;
     if (!keys || !lens || !count || max_lists < 1 || max_keys < 1 || max_keys > 255) return fail(TETRIS_E_ARG, "keys/lens/count/max_*");
     if (n < 0 || (!idx && n > b->N)) return fail(TETRIS_E_ARG, "n out of range");
-    if (player)
-        for (int i = 0; i < n; i++)
-            if (player[i] >= b->P) return fail(TETRIS_E_ARG, "player index out of range");
-    const int LANE_LISTS = 16;                       // lists one (x, rotation) start can produce (<= H/2)
+    if ((rc = check_players(b, player, n))) return rc;
     const int CHUNK_GAMES = 1024;                    // bounds the staging buffers
-    Stage &s_cnt = b->s_act0, &s_len = b->s_act1, &s_key = b->s_act2;
-    int result = TETRIS_OK;
-    for (int g0 = 0; g0 < n && result == TETRIS_OK; g0 += CHUNK_GAMES) {
+    const size_t L = PLAN_LANE_LISTS;                // lists one (x, rotation) start can produce
+    std::vector<int32_t> ident;
+    for (int g0 = 0; g0 < n; g0 += CHUNK_GAMES) {    // (each chunk drains before its lists are read: HostCall::finish)
         const int m = (n - g0 < CHUNK_GAMES) ? n - g0 : CHUNK_GAMES;
         const size_t lanes = (size_t)m * 40;
-        const int32_t* d_idx = nullptr;
-        std::vector<int32_t> ident;
         const int32_t* h_idx = idx ? idx + g0 : nullptr;
         if (!h_idx && g0 > 0) { ident.resize(m); for (int i = 0; i < m; i++) ident[i] = g0 + i; h_idx = ident.data(); }
-        if ((rc = stage_idx(b, h_idx, m, &d_idx))) { result = rc; break; }
-        const uint8_t* d_player = nullptr;
-        if (player) {
-            if ((rc = stage_in(b, b->s_in0, player + g0, (size_t)m))) { result = rc; break; }
-            d_player = (const uint8_t*)b->s_in0.d;
-        }
-        if ((rc = s_cnt.ensure(lanes + 4)) || (rc = s_len.ensure(lanes * LANE_LISTS + 4)) ||
-            (rc = s_key.ensure(lanes * LANE_LISTS * max_keys + 4))) { result = rc; break; }
+        HostCall io{b};
+        const uint8_t *d_player, *hc, *hl, *hk;
+        uint8_t *d_cnt, *d_len, *d_key;
+        if ((rc = io.idx(h_idx, m)) || (rc = io.in(player ? player + g0 : nullptr, (size_t)m, &d_player)) ||
+            (rc = io.out(nullptr, lanes, &d_cnt, &hc)) || (rc = io.out(nullptr, lanes * L, &d_len, &hl)) ||
+            (rc = io.out(nullptr, lanes * L * max_keys, &d_key, &hk))) return rc;
         dim3 grid((unsigned)((lanes + 63) / 64)), block(64);
         if (b->P == 1)
-            hipLaunchKernelGGL(k_actions<1>, grid, block, 0, b->stream, geo_of_batch(b), m, d_idx, d_player, b->H, (uint8_t*)s_cnt.d,
-                               (uint8_t*)s_len.d, (uint8_t*)s_key.d, LANE_LISTS, max_keys, b->flags);
+            hipLaunchKernelGGL(k_actions<1>, grid, block, 0, b->stream, geo_of_batch(b), m, io.d_idx, d_player, b->H, d_cnt, d_len, d_key,
+                               PLAN_LANE_LISTS, max_keys, b->flags);
         else if (b->P == 2)
-            hipLaunchKernelGGL(k_actions<2>, grid, block, 0, b->stream, geo_of_batch(b), m, d_idx, d_player, b->H, (uint8_t*)s_cnt.d,
-                               (uint8_t*)s_len.d, (uint8_t*)s_key.d, LANE_LISTS, max_keys, b->flags);
+            hipLaunchKernelGGL(k_actions<2>, grid, block, 0, b->stream, geo_of_batch(b), m, io.d_idx, d_player, b->H, d_cnt, d_len, d_key,
+                               PLAN_LANE_LISTS, max_keys, b->flags);
         else if (b->P == 3)
-            hipLaunchKernelGGL(k_actions<3>, grid, block, 0, b->stream, geo_of_batch(b), m, d_idx, d_player, b->H, (uint8_t*)s_cnt.d,
-                               (uint8_t*)s_len.d, (uint8_t*)s_key.d, LANE_LISTS, max_keys, b->flags);
+            hipLaunchKernelGGL(k_actions<3>, grid, block, 0, b->stream, geo_of_batch(b), m, io.d_idx, d_player, b->H, d_cnt, d_len, d_key,
+                               PLAN_LANE_LISTS, max_keys, b->flags);
         else
-            hipLaunchKernelGGL(k_actions<4>, grid, block, 0, b->stream, geo_of_batch(b), m, d_idx, d_player, b->H, (uint8_t*)s_cnt.d,
-                               (uint8_t*)s_len.d, (uint8_t*)s_key.d, LANE_LISTS, max_keys, b->flags);
-        if (hipGetLastError() != hipSuccess) { result = fail(TETRIS_E_HIP, "k_actions launch failed"); break; }
-        (void)hipMemcpyAsync(s_cnt.h, s_cnt.d, lanes, hipMemcpyDeviceToHost, b->stream);
-        (void)hipMemcpyAsync(s_len.h, s_len.d, lanes * LANE_LISTS, hipMemcpyDeviceToHost, b->stream);
-        (void)hipMemcpyAsync(s_key.h, s_key.d, lanes * LANE_LISTS * max_keys, hipMemcpyDeviceToHost, b->stream);
-        if ((rc = finish_call(b))) { result = rc; break; }
-        const uint8_t* hc = (const uint8_t*)s_cnt.h;
-        const uint8_t* hl = (const uint8_t*)s_len.h;
-        const uint8_t* hk = (const uint8_t*)s_key.h;
-        for (int i = 0; i < m && result == TETRIS_OK; i++) {
+            hipLaunchKernelGGL(k_actions<4>, grid, block, 0, b->stream, geo_of_batch(b), m, io.d_idx, d_player, b->H, d_cnt, d_len, d_key,
+                               PLAN_LANE_LISTS, max_keys, b->flags);
+        if (hipGetLastError() != hipSuccess) return fail(TETRIS_E_HIP, "k_actions launch failed");
+        if ((rc = io.finish())) return rc;
+        for (int i = 0; i < m; i++) {
             int total = 0;
+            bool over = false;
             for (int xi = 0; xi < 10; xi++)               // the reference enumerates x-major, rotation-minor
                 for (int r = 0; r < 4; r++) {
                     const size_t lane = (size_t)i * 40 + r * 10 + xi;
                     for (int k = 0; k < hc[lane]; k++) {
-                        if (total >= max_lists) { result = fail(TETRIS_E_ARG, "more than max_lists key lists for one game"); break; }
-                        const int len = hl[lane * LANE_LISTS + k];
+                        if (total >= max_lists) { over = true; break; }
+                        const int len = hl[lane * L + k];
                         lens[(size_t)(g0 + i) * max_lists + total] = (uint8_t)len;
-                        memcpy(keys + ((size_t)(g0 + i) * max_lists + total) * max_keys, hk + (lane * LANE_LISTS + k) * max_keys, (size_t)len);
+                        memcpy(keys + ((size_t)(g0 + i) * max_lists + total) * max_keys, hk + (lane * L + k) * max_keys, (size_t)len);
                         total++;
                     }
                 }
             count[g0 + i] = total;
+            if (over) return fail(TETRIS_E_ARG, "more than max_lists key lists for one game");
         }
     }
-    return result;
+    return TETRIS_OK;
 }
 
 // ---------------------------------------------------------------- planning: action lists, simulated afterstates, list steps
@@ -2342,10 +2320,13 @@ static int chain_recover(tetris_batch* b) {
         unsigned long long todo = (unsigned long long)(last - c) * (unsigned long long)S;
         while (todo > 0) {
             const int steps = todo < (unsigned long long)FUSE ? (int)todo : FUSE;
-            const int32_t* d_idx = nullptr;
-            int rc = stage_idx(b, idx.data(), (int)idx.size(), &d_idx);
+            // (a pair of its own, not one of b->stage: this runs inside finish_call, before the call's outputs are copied out)
+            Stage& s = b->recover_idx;
+            int rc = s.ensure(idx.size() * 4 + 16);
             if (rc) return rc;
-            KArgs a = base_args(b, (int)idx.size(), d_idx);
+            memcpy(s.h, idx.data(), idx.size() * 4);
+            HIP_TRY(hipMemcpyAsync(s.d, s.h, idx.size() * 4, hipMemcpyHostToDevice, home));
+            KArgs a = base_args(b, (int)idx.size(), (const int32_t*)s.d);
             a.ms = call.ms; a.steps = steps; a.policy_seed = call.policy_seed; a.first_step = step;
             if ((rc = launch_game<M_ROLLOUT>(b, a))) return rc;
             HIP_TRY(hipStreamSynchronize(home));

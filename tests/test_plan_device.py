@@ -104,6 +104,22 @@ def test_action_lists_match_get_actions(kind, P, steps):
 
 
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+def test_get_actions_matches_harness_in_every_chunk(kind):
+    """tetris_get_actions works through its games 1 024 at a time (four chunks on the GPU); every game's lists must be its own,
+    those from game 1 024 on included."""
+    n = _n(kind, 48, 4096)
+    b = engines.make(kind, n, 2, seeds=orc.episode_seed(np.arange(n), 13))
+    _scramble(b, 30, 2)
+    player = np.random.default_rng(13).integers(0, 2, n)
+    h = engines.make("harness", n, 2, height=b.height, pieces=b.piece_map.tolist())
+    h.restore(b.snapshot())
+    got = b.get_actions(None, player, max_lists=128, max_keys=64)
+    want = h.get_actions(None, player, max_lists=128, max_keys=64)
+    for i in range(n):
+        assert got[i] == want[i], f"game {i}: {len(got[i])} lists, want {len(want[i])}"
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
 @pytest.mark.parametrize("P", [3, 4])
 def test_action_lists_three_and_four_players(kind, P):
     n = _n(kind, 40, 384)
