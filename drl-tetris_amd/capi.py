@@ -16,6 +16,9 @@ DEFAULT_LIB = os.path.join(HERE, "lib", "libtetris_hip.so")
 
 MAX_H, W, FIFO_CAP = 32, 10, 16
 
+# the columns of tetris_rt_features_dev / the entries of a policy weight vector (include/tetris_hip.h: TETRIS_POLICY_FEATURES)
+POLICY_FEATURE_NAMES = ("lines", "holes", "bumpiness", "aggregate_height", "max_height", "row_transitions", "column_transitions", "wells")
+
 # mirrors `struct tetris_record` (include/tetris_hip.h)
 RECORD = np.dtype(
     [
@@ -90,6 +93,12 @@ _SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_step_lists_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tetris_rt_features_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tetris_policy_rt_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tetris_step_policy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "tetris_rollout_policy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    "tetris_rollout_game_totals_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_observe_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_observe_packed_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_create_split": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -373,6 +382,34 @@ class TetrisBatch:
         """perform_action(lists[choice[i]], player) for every game: choice int32 [N]; done [N], lines / dead [P][N]."""
         self._check(self.lib.tetris_step_lists_dev(self._h, player, choice, count, lens, keys, int(max_lists), int(max_keys), int(ms),
                                                    1 if auto_reset else 0, done, lines, dead))
+
+    # -- heuristic policy on the device (include/tetris_hip.h: tetris_rt_features_dev and the four after it).  Array arguments
+    # are raw DEVICE addresses (int / c_void_p) or None; weights: int16 [8], or [N][8] with per_game.
+    def rt_features_dev(self, features, player=None):
+        """The POLICY_FEATURE_NAMES features of the 40 (r, t) candidate fields of every game: features int16 [40][8][N]."""
+        self._check(self.lib.tetris_rt_features_dev(self._h, player, features))
+
+    def policy_rt_dev(self, weights, rot, trans, score=None, player=None, per_game=False):
+        """The best-scoring (r, t) of every game (lowest 10 r + t among equals): rot / trans uint8 [N], score int32 [N] or None."""
+        self._check(self.lib.tetris_policy_rt_dev(self._h, player, weights, 1 if per_game else 0, rot, trans, score))
+
+    def step_policy_dev(self, weights, done, lines, dead, rot=None, trans=None, player=None, per_game=False, ms=400, auto_reset=False):
+        """policy_rt_dev + step_rt_dev in one call: done [N], lines / dead [P][N]; rot / trans [N] (or None) report what was played."""
+        self._check(self.lib.tetris_step_policy_dev(self._h, player, weights, 1 if per_game else 0, int(ms), 1 if auto_reset else 0,
+                                                    done, lines, dead, rot, trans))
+
+    def rollout_policy(self, weights, launches, steps_per_launch=1, per_game=False, first_step=0, ms=400):
+        """rollout_random with the heuristic policy in place of the random draw; weights: a raw DEVICE address.
+        -> (counters[4] = env_steps, episodes, lines, sent; elapsed_ms on the batch's stream)"""
+        counters = np.zeros(4, np.uint64)
+        elapsed = C.c_float(0.0)
+        self._check(self.lib.tetris_rollout_policy(self._h, int(launches), int(steps_per_launch), weights, 1 if per_game else 0,
+                                                   int(first_step), int(ms), _p(counters), C.byref(elapsed)))
+        return counters, float(elapsed.value)
+
+    def rollout_game_totals_dev(self, totals):
+        """The per-game words rollout_totals sums: totals uint32 [4][N] = env-steps, episodes, lines cleared, garbage lines sent."""
+        self._check(self.lib.tetris_rollout_game_totals_dev(self._h, totals))
 
     def rollout_random(self, launches, steps_per_launch=1, policy_seed=0xD71, first_step=0, ms=400):
         """-> (counters[4] = env_steps, episodes, lines, sent; elapsed_ms on the batch's stream)"""

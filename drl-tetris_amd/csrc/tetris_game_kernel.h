@@ -6,6 +6,7 @@
 
 #include "tetris_kernels.h"
 #include "tetris_plan.h"
+#include "tetris_policy.h"
 
 namespace te {}
 using namespace te;
@@ -69,7 +70,29 @@ static void launch_plan(int which, dim3 grid, hipStream_t st, const PlanArgs& pa
     else hipLaunchKernelGGL((k_plan_step<P, TINT, true>), grid, dim3(64), 0, st, pa);
 }
 
+// The step kernels of the heuristic policy (tetris_policy.h), one lane per game, one wave per workgroup.  ROLL: the rollout's
+// step(s) with counters; FROM_SCORES: the choice is read from the scores k_policy_eval left (spread mapping), otherwise the
+// lane evaluates its own 40 candidates (fused launches).
+template <int P, bool TINT, bool ROLL, bool AUTO, bool FROM_SCORES>
+__global__ __launch_bounds__(64) void k_policy_step(PolicyArgs pa) {
+    __shared__ uint32_t s_shapes[SHAPE_WORDS];
+    s_shapes[threadIdx.x] = d_shape_table.s[threadIdx.x];
+    __syncthreads();
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < pa.a.n) policy_step_lane<P, TINT, ROLL, AUTO, FROM_SCORES>(pa, i, s_shapes, true);
+}
+// which: 0 step, 1 step with auto-reset, 2 one rollout step from the scores, 3 fused rollout steps (lane mapping)
+template <int P, bool TINT>
+static void launch_policy_step(int which, dim3 grid, hipStream_t st, const PolicyArgs& pa) {
+    if (which == 0) hipLaunchKernelGGL((k_policy_step<P, TINT, false, false, true>), grid, dim3(64), 0, st, pa);
+    else if (which == 1) hipLaunchKernelGGL((k_policy_step<P, TINT, false, true, true>), grid, dim3(64), 0, st, pa);
+    else if (which == 2) hipLaunchKernelGGL((k_policy_step<P, TINT, true, true, true>), grid, dim3(64), 0, st, pa);
+    else hipLaunchKernelGGL((k_policy_step<P, TINT, true, true, false>), grid, dim3(64), 0, st, pa);
+}
+
 // launches k_game<P, mode, tint> for P = 3, 4 (tetris_hip_multi.hip)
 __attribute__((visibility("hidden"))) int tetris_launch_game_multi(int n_players, int tint, int mode, dim3 grid, dim3 block, hipStream_t stream, const te::KArgs& a);
 // launches the planning kernels for P = 3, 4 (tetris_hip_multi.hip); which: 0 simulate, 1 step, 2 step with auto-reset
 __attribute__((visibility("hidden"))) int tetris_launch_plan_multi(int n_players, int tint, int which, dim3 grid, hipStream_t stream, const te::PlanArgs& pa, int fin);
+// launches the policy step kernels for P = 3, 4 (tetris_hip_multi.hip); which: as launch_policy_step
+__attribute__((visibility("hidden"))) int tetris_launch_policy_multi(int n_players, int tint, int which, dim3 grid, hipStream_t stream, const te::PolicyArgs& pa);

@@ -1008,6 +1008,8 @@ struct tetris_batch {
     size_t plan_slab_cap = 0;
     int32_t* d_iota = nullptr;
     uint32_t* d_plan_status = nullptr;
+    // the heuristic policy's spread mapping: the 40 scores of every game, [40][N], from k_policy_eval to the kernel that chooses
+    int32_t* d_policy_scores = nullptr;
 };
 
 static Geo geo_of_batch(tetris_batch* b) {
@@ -1377,6 +1379,7 @@ int tetris_destroy(tetris_batch* b) {
     if (b->stall_stream) { (void)hipStreamSynchronize(b->stall_stream); (void)hipStreamDestroy(b->stall_stream); }
     if (b->direct_used) { aql::Device* dev = aql::device_for(b->device); if (dev->ok) aql::quiesce(dev->qs); }      // (a test's idle kernel may still sit there)
     (void)hipFree(b->d_plan_slabs); (void)hipFree(b->d_iota); (void)hipFree(b->d_plan_status);
+    (void)hipFree(b->d_policy_scores);
     for (Stage& s : b->stage) s.release();
     b->recover_idx.release();
     if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -2728,6 +2731,180 @@ int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, u
         if ((rc = tetris_rollout_totals(b, after))) return rc;
         // per-game words are uint32 and wrap; a single call stays far below 2^32 per game
         for (int k = 0; k < 4; k++) counters[k] += after[k] - before[k];
+    }
+    return TETRIS_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- heuristic policy: features, choice, step, rollout (tetris_policy.h)
+// k_policy_eval: grid (ceil(N / 64), 40): a wave = 64 consecutive games of one candidate c = blockIdx.y, so that the state loads
+// and the feature / score stores of a wave are coalesced rows (as k_plan_sim).  One wave per workgroup with its own LDS copy of
+// the shape table.
+template <bool FEAT>
+__global__ __launch_bounds__(64) void k_policy_eval(PolicyArgs pa) {
+    __shared__ uint32_t s_shapes[SHAPE_WORDS];
+    s_shapes[threadIdx.x] = d_shape_table.s[threadIdx.x];
+    __syncthreads();
+    const int i = blockIdx.x * 64 + threadIdx.x, c = blockIdx.y;
+    if (i < pa.a.n) policy_eval_lane<FEAT>(pa, i, c, s_shapes);
+}
+// k_policy_pick: one lane per game, the maximum of its 40 scores
+__global__ __launch_bounds__(256) void k_policy_pick(PolicyArgs pa) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < pa.a.n) policy_pick_lane(pa, i);
+}
+__global__ __launch_bounds__(256) void k_policy_totals(Geo geo, uint32_t* totals /*[4][N]*/) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (int)geo.n_games) policy_game_totals_lane(geo, i, totals);
+}
+
+static int policy_check(tetris_batch* b, const char* what) {
+    if (b->split) return fail(TETRIS_E_ARG, std::string(what) + " is not available on split batches");
+    return TETRIS_OK;
+}
+
+static PolicyArgs policy_args(tetris_batch* b, const uint8_t* d_player, const int16_t* d_weights, int per_game, int ms) {
+    PolicyArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.a = base_args(b, b->N, nullptr);
+    pa.a.ms = ms; pa.a.steps = 1;
+    pa.player = d_player; pa.weights = d_weights; pa.per_game = per_game ? 1 : 0;
+    pa.fixed_player = -1;
+    pa.scores = b->d_policy_scores;
+    return pa;
+}
+
+static int policy_scores_buffer(tetris_batch* b) {
+    if (!b->d_policy_scores) HIP_TRY(hipMalloc((void**)&b->d_policy_scores, (size_t)POLICY_CANDIDATES * b->N * sizeof(int32_t)));
+    return TETRIS_OK;
+}
+
+static dim3 policy_eval_grid(const tetris_batch* b) { return dim3((unsigned)((b->N + 63) / 64), (unsigned)POLICY_CANDIDATES); }
+
+// the 40 scores of every game -> b->d_policy_scores
+static int launch_policy_scores(tetris_batch* b, const PolicyArgs& pa) {
+    hipLaunchKernelGGL((k_policy_eval<false>), policy_eval_grid(b), dim3(64), 0, b->stream, pa);
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+// which: as launch_policy_step (tetris_game_kernel.h)
+static int launch_policy_step_kernel(tetris_batch* b, int which, const PolicyArgs& pa) {
+    const dim3 grid((unsigned)((b->N + 63) / 64));
+    if (b->P == 1) { if (b->tint) launch_policy_step<1, true>(which, grid, b->stream, pa); else launch_policy_step<1, false>(which, grid, b->stream, pa); }
+    else if (b->P == 2) { if (b->tint) launch_policy_step<2, true>(which, grid, b->stream, pa); else launch_policy_step<2, false>(which, grid, b->stream, pa); }
+    else if (tetris_launch_policy_multi(b->P, b->tint, which, grid, b->stream, pa)) return fail(TETRIS_E_ARG, "no policy kernel for this player count");
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+extern "C" {
+
+int tetris_rt_features_dev(tetris_batch* b, const uint8_t* d_player, int16_t* d_features) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = policy_check(b, "tetris_rt_features_dev"))) return rc;
+    if (!d_features) return fail(TETRIS_E_ARG, "features is NULL");
+    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
+    PolicyArgs pa = policy_args(b, d_player, nullptr, 0, 0);
+    pa.features = d_features;
+    hipLaunchKernelGGL((k_policy_eval<true>), policy_eval_grid(b), dim3(64), 0, b->stream, pa);
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+int tetris_policy_rt_dev(tetris_batch* b, const uint8_t* d_player, const int16_t* d_weights, int per_game, uint8_t* d_rot,
+                         uint8_t* d_trans, int32_t* d_score) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = policy_check(b, "tetris_policy_rt_dev"))) return rc;
+    if (!d_weights || !d_rot || !d_trans) return fail(TETRIS_E_ARG, "weights/rot/trans are NULL");
+    if ((rc = policy_scores_buffer(b))) return rc;
+    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
+    PolicyArgs pa = policy_args(b, d_player, d_weights, per_game, 0);
+    pa.rot = d_rot; pa.trans = d_trans; pa.score = d_score;
+    if ((rc = launch_policy_scores(b, pa))) return rc;
+    hipLaunchKernelGGL(k_policy_pick, dim3((unsigned)((b->N + 255) / 256)), dim3(256), 0, b->stream, pa);
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+int tetris_step_policy_dev(tetris_batch* b, const uint8_t* d_player, const int16_t* d_weights, int per_game, int ms, int flags,
+                           uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead, uint8_t* d_rot, uint8_t* d_trans) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = policy_check(b, "tetris_step_policy_dev"))) return rc;
+    if (!d_weights) return fail(TETRIS_E_ARG, "weights is NULL");
+    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((rc = policy_scores_buffer(b))) return rc;
+    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
+    PolicyArgs pa = policy_args(b, d_player, d_weights, per_game, ms);
+    pa.a.done = d_done; pa.a.lines = d_lines; pa.a.dead = d_dead;
+    pa.rot = d_rot; pa.trans = d_trans;
+    if ((rc = launch_policy_scores(b, pa))) return rc;
+    return launch_policy_step_kernel(b, (flags & TETRIS_STEP_AUTO_RESET) ? 1 : 0, pa);
+}
+
+int tetris_rollout_game_totals_dev(tetris_batch* b, uint32_t* d_totals) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = policy_check(b, "tetris_rollout_game_totals_dev"))) return rc;
+    if (!d_totals) return fail(TETRIS_E_ARG, "totals is NULL");
+    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
+    hipLaunchKernelGGL(k_policy_totals, dim3((unsigned)((b->N + 255) / 256)), dim3(256), 0, b->stream, geo_of_batch(b), d_totals);
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+// The launches of tetris_rollout_policy, un-chained on the batch's stream.  One step per launch: the spread mapping (the scores of
+// all 40 N candidates, then one lane per game that chooses and steps); more: one launch whose lanes evaluate their own candidates.
+static int rollout_policy_launches(tetris_batch* b, int launches, int steps_per_launch, const int16_t* d_weights, int per_game,
+                                   uint64_t first_step, int ms, float* elapsed_ms) {
+    // (the margin arithmetic of tetris_rollout_launch: a step may consume 2 piece draws per player, and the host sees a request
+    // to extend the tables up to 2 * group + 1 launches late)
+    struct MarginGuard {
+        tetris_batch* b; uint32_t saved;
+        ~MarginGuard() { b->margin = saved; }
+    } margin_guard{b, b->margin};
+    int group = GATE_GROUP / steps_per_launch;
+    group = group < 1 ? 1 : group;
+    const uint32_t need = (uint32_t)(2 * steps_per_launch * (2 * group + 2) + 16);
+    if (b->margin < need) b->margin = need;
+    int rc = TETRIS_OK;
+    HIP_TRY(hipEventRecord(b->ev0, b->stream));
+    for (int l = 0; l < launches; l++) {
+        if ((rc = gate_launch(b, group))) return rc;
+        PolicyArgs pa = policy_args(b, nullptr, d_weights, per_game, ms);
+        pa.a.steps = steps_per_launch;
+        pa.a.first_step = first_step + (uint64_t)l * (uint64_t)steps_per_launch;
+        if (steps_per_launch == 1) {
+            pa.fixed_player = (int)(pa.a.first_step % (uint64_t)b->P);      // the evaluation kernel's acting player: step mod P
+            if ((rc = launch_policy_scores(b, pa))) return rc;
+            if ((rc = launch_policy_step_kernel(b, 2, pa))) return rc;
+        } else if ((rc = launch_policy_step_kernel(b, 3, pa))) return rc;
+    }
+    HIP_TRY(hipEventRecord(b->ev1, b->stream));
+    HIP_TRY(poll_event(b->ev1, 200000));
+    if ((rc = finish_call(b, true))) return rc;   // the end event is behind everything this call enqueued
+    if (elapsed_ms) HIP_TRY(hipEventElapsedTime(elapsed_ms, b->ev0, b->ev1));
+    return TETRIS_OK;
+}
+
+int tetris_rollout_policy(tetris_batch* b, int launches, int steps_per_launch, const int16_t* d_weights, int per_game,
+                          uint64_t first_step, int ms, uint64_t counters[4], float* elapsed_ms) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = policy_check(b, "tetris_rollout_policy"))) return rc;
+    if (!d_weights) return fail(TETRIS_E_ARG, "weights is NULL");
+    if (launches < 1 || steps_per_launch < 1 || steps_per_launch > 256) return fail(TETRIS_E_ARG, "launches must be >= 1, 1 <= steps_per_launch <= 256");
+    if ((rc = policy_scores_buffer(b))) return rc;
+    uint64_t before[4] = {0, 0, 0, 0}, after[4] = {0, 0, 0, 0};
+    if (counters && (rc = tetris_rollout_totals(b, before))) return rc;
+    if ((rc = rollout_policy_launches(b, launches, steps_per_launch, d_weights, per_game, first_step, ms, elapsed_ms))) return rc;
+    if (counters) {
+        if ((rc = tetris_rollout_totals(b, after))) return rc;
+        for (int k = 0; k < 4; k++) counters[k] += after[k] - before[k];      // (per-game words are uint32 and wrap, as in tetris_rollout_random)
     }
     return TETRIS_OK;
 }

@@ -1,6 +1,7 @@
 // libtetris_hip.so, second translation unit: the step kernel for three and four players per game (tetris_game_kernel.h) and,
-// beside it, the planning kernels for three and four players (k_plan_sim, k_plan_step; tetris_plan.h).  Nothing else lives
-// here; the two files are compiled in parallel (__graft_entry__.build_hip).
+// beside it, the planning kernels (k_plan_sim, k_plan_step; tetris_plan.h) and the policy step kernels (k_policy_step;
+// tetris_policy.h) for three and four players.  Nothing else lives here; the two files are compiled in parallel
+// (__graft_entry__.build_hip).
 #include "tetris_game_kernel.h"
 
 template <int P, bool TINT>
@@ -23,5 +24,11 @@ __attribute__((visibility("hidden"))) int tetris_launch_game_multi(int n_players
 __attribute__((visibility("hidden"))) int tetris_launch_plan_multi(int n_players, int tint, int which, dim3 grid, hipStream_t st, const PlanArgs& pa, int fin) {
     if (n_players == 3) { if (tint) launch_plan<3, true>(which, grid, st, pa, fin); else launch_plan<3, false>(which, grid, st, pa, fin); return 0; }
     if (n_players == 4) { if (tint) launch_plan<4, true>(which, grid, st, pa, fin); else launch_plan<4, false>(which, grid, st, pa, fin); return 0; }
+    return -1;
+}
+
+__attribute__((visibility("hidden"))) int tetris_launch_policy_multi(int n_players, int tint, int which, dim3 grid, hipStream_t st, const PolicyArgs& pa) {
+    if (n_players == 3) { if (tint) launch_policy_step<3, true>(which, grid, st, pa); else launch_policy_step<3, false>(which, grid, st, pa); return 0; }
+    if (n_players == 4) { if (tint) launch_policy_step<4, true>(which, grid, st, pa); else launch_policy_step<4, false>(which, grid, st, pa); return 0; }
     return -1;
 }

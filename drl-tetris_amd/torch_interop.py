@@ -161,3 +161,56 @@ class TorchEnv:
                               self._ptr(self.done), self._ptr(self.lines), self._ptr(self.dead), max_lists=L, max_keys=K,
                               player=self._ptr(player), ms=ms, auto_reset=auto_reset)
         return self.done, self.lines, self.dead
+
+    # ---- heuristic policy on the device (include/tetris_hip.h: tetris_rt_features_dev and the four after it)
+    def _policy_buffers(self):
+        if getattr(self, "policy_rot", None) is not None:
+            return
+        torch, n = self.torch, self.b.n_games
+        self.policy_rot = torch.zeros(n, dtype=torch.uint8, device=self.dev)
+        self.policy_trans = torch.zeros(n, dtype=torch.uint8, device=self.dev)
+        self.policy_score = torch.zeros(n, dtype=torch.int32, device=self.dev)
+
+    def _check_weights(self, weights):
+        """weights: int16 device tensor [8] (one vector for the batch) or [n, 8] (one per game) -> per_game"""
+        assert weights.dtype == self.torch.int16 and weights.is_cuda and weights.is_contiguous()
+        assert tuple(weights.shape) in ((8,), (self.b.n_games, 8)), "weights must be [8] or [n, 8]"
+        return weights.dim() == 2
+
+    def rt_features(self, player=None):
+        """The eight POLICY_FEATURE_NAMES features of the 40 (r, t) candidate fields of every game (candidate c = 10 r + t):
+        -> int16 [40, 8, n] device tensor (reused).  The games are not changed."""
+        self._check_player(player)
+        if getattr(self, "policy_features", None) is None:
+            self.policy_features = self.torch.zeros(40, 8, self.b.n_games, dtype=self.torch.int16, device=self.dev)
+        self.b.rt_features_dev(self._ptr(self.policy_features), player=self._ptr(player))
+        return self.policy_features
+
+    def policy_rt(self, weights, player=None):
+        """The best-scoring candidate of every game (score = weights . features, lowest 10 r + t among equals):
+        -> (rot uint8 [n], trans uint8 [n], score int32 [n]) device tensors (reused); rot / trans feed step_rt unchanged."""
+        self._check_player(player)
+        per_game = self._check_weights(weights)
+        self._policy_buffers()
+        self.b.policy_rt_dev(self._ptr(weights), self._ptr(self.policy_rot), self._ptr(self.policy_trans), self._ptr(self.policy_score),
+                             player=self._ptr(player), per_game=per_game)
+        return self.policy_rot, self.policy_trans, self.policy_score
+
+    def step_policy(self, weights, player=None, ms=400, auto_reset=False):
+        """policy_rt + step_rt in one call (the scripted opponent's move): -> (done [n], lines [P, n], dead [P, n], rot [n],
+        trans [n]) device tensors (reused); auto_reset as for step_rt."""
+        self._check_player(player)
+        per_game = self._check_weights(weights)
+        self._policy_buffers()
+        self.b.step_policy_dev(self._ptr(weights), self._ptr(self.done), self._ptr(self.lines), self._ptr(self.dead),
+                               rot=self._ptr(self.policy_rot), trans=self._ptr(self.policy_trans), player=self._ptr(player),
+                               per_game=per_game, ms=ms, auto_reset=auto_reset)
+        return self.done, self.lines, self.dead, self.policy_rot, self.policy_trans
+
+    def game_totals(self):
+        """The built-in rollouts' per-game counters: -> int32 [4, n] device tensor (reused; the words are uint32): env-steps,
+        episodes, lines cleared, garbage lines sent of every game — a population's fitness without a host loop."""
+        if getattr(self, "policy_totals", None) is None:
+            self.policy_totals = self.torch.zeros(4, self.b.n_games, dtype=self.torch.int32, device=self.dev)
+        self.b.rollout_game_totals_dev(self._ptr(self.policy_totals))
+        return self.policy_totals

@@ -247,6 +247,61 @@ int tetris_step_lists_dev(tetris_batch *b, const uint8_t *d_player, const int32_
                           const uint8_t *d_lens, const uint8_t *d_keys, int max_lists, int max_keys, int ms, int flags,
                           uint8_t *d_done, uint8_t *d_lines, uint8_t *d_dead);
 
+/* ---- heuristic policy on the device: a one-piece look-ahead over the 40 SVENton (rotation, translation) actions -----------
+ * The scripted player the golden traces were recorded with (tests/golden/policies.py: GreedyRT), for every game of a batch at
+ * once: a fixed-strength opponent for two-player training, the inner loop of feature-based learning (one weight vector per
+ * game, per-game lines cleared), and a rollout on boards that look like play.  The reference has no such player (it trains by
+ * self-play: drl_tetris/worker.py:91-118); its action encoding is the SVENton one (sventon_utils.py:9-13).
+ * For game i, acting player p and candidate c = 10 r + t (r = 0..3, t = 0..9) the CANDIDATE FIELD is p's occupancy after
+ * make_action of [8]*r + [2] + [3]*t + [7] for p and [0] for the others, without finish_action — what
+ * tetris_simulate_lists_dev without TETRIS_SIM_FINALIZE shows for that list: the piece is stamped, full rows are still
+ * present (a dead player's or a finished round's field is the board as it stands).  Row 0 is the top, H the batch's height.
+ * A candidate field has TETRIS_POLICY_FEATURES integer features.  Feature 0 is counted on the field as it is; for features
+ * 1-7 the full rows are removed first and the rows above move down.  With h[c] = H minus the index of the topmost filled
+ * row of column c (0 for an empty column):
+ *   0 lines              number of full rows
+ *   1 holes              empty cells with a filled cell above them in the same column
+ *   2 bumpiness          sum over c = 0..8 of |h[c+1] - h[c]|
+ *   3 aggregate height   sum of h[c]
+ *   4 max height         max of h[c]
+ *   5 row transitions    per row, changes along wall, cell 0..9, wall with both walls filled (an empty row gives 2); summed
+ *   6 column transitions per column, changes along cell 0..H-1, floor with the floor filled (no ceiling); summed
+ *   7 wells              sum over c of d (d + 1) / 2, d = max(0, min(h[c-1], h[c+1]) - h[c]), h[-1] = h[10] = H
+ * Score of a candidate = sum of w[k] * f[k] with int16 weights, in int32 (it cannot overflow: the largest feature is 4 960).
+ * The CHOICE is the candidate with the highest score, among equal scores the lowest c — ties are the normal case
+ * (translations past the wall and the repeated rotations of O, I, S, Z give identical fields); all-zero weights choose
+ * (0, 0).  No floating point anywhere.  d_weights: int16 [8] for the batch, or with per_game != 0 [N][8], one vector per game.
+ * All entry points: device pointers, asynchronous on the batch's stream, run-ahead bounded and RNG-table requests serviced
+ * as for tetris_step_rt_dev_ex; d_player[N] = acting player (NULL: player 0; out-of-range entries are clamped); one to four
+ * players, every height, colour batches included (the policy reads occupancy).  Not on split batches.                     */
+#define TETRIS_POLICY_FEATURES 8
+/* the features of all 40 candidates of every game: d_features int16 [40][8][N] (candidate-major like d_cols of
+ * tetris_simulate_lists_dev: a wavefront stores whole rows).  The batch's state is not written.                          */
+int tetris_rt_features_dev(tetris_batch *b, const uint8_t *d_player, int16_t *d_features);
+/* the choice: d_rot / d_trans uint8 [N] and its score d_score int32 [N] (d_score may be NULL).  The outputs feed
+ * tetris_step_rt_dev unchanged.  The batch's state is not written.                                                       */
+int tetris_policy_rt_dev(tetris_batch *b, const uint8_t *d_player, const int16_t *d_weights, int per_game,
+                         uint8_t *d_rot, uint8_t *d_trans, int32_t *d_score);
+/* the choice and perform_action of it (tetris_environment.py:102-116) in one call: bit-identical to tetris_policy_rt_dev
+ * followed by tetris_step_rt_dev_ex.  flags: TETRIS_STEP_AUTO_RESET as there; d_done [N], d_lines / d_dead [P][N] describe
+ * the step before the reset; d_rot / d_trans [N] (each may be NULL) report what was played.  The scripted-opponent call: the
+ * learner moves player 0 with tetris_step_rt_dev, the library moves player 1.                                            */
+int tetris_step_policy_dev(tetris_batch *b, const uint8_t *d_player, const int16_t *d_weights, int per_game, int ms,
+                           int flags, uint8_t *d_done, uint8_t *d_lines, uint8_t *d_dead, uint8_t *d_rot, uint8_t *d_trans);
+/* tetris_rollout_random with this policy in place of the Philox draw: acting player = step mod P, [0] for the others,
+ * auto-reset with the built-in seed schedule keyed by global game id, the same per-game counter words, `counters` and
+ * `elapsed_ms` as there (synchronous).  1 <= steps_per_launch <= 256; more than one step per launch gives the same results
+ * as one (the state stays in registers inside a launch, and each game's lane evaluates its own 40 candidates).  Runs
+ * un-chained on the batch's stream: tetris_rollout_is_chained and the chained / direct-dispatch paths do not apply.
+ * CAPACITY: this policy clears about 0.39 lines per piece in one-player games and does not die, so an episode is not ended by
+ * the game but by the 39 936-draw limit: after about 40 000 steps it is ended with TETRIS_ERR_STREAM (see above) and reset
+ * like any finished game.                                                                                                */
+int tetris_rollout_policy(tetris_batch *b, int launches, int steps_per_launch, const int16_t *d_weights, int per_game,
+                          uint64_t first_step, int ms, uint64_t counters[4], float *elapsed_ms);
+/* the per-game words tetris_rollout_totals sums: d_totals uint32 [4][N] = {env_steps, episodes, lines_cleared, garbage_sent}
+ * of every game — a population's fitness without a host loop.  Asynchronous.                                             */
+int tetris_rollout_game_totals_dev(tetris_batch *b, uint32_t *d_totals);
+
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
  * t = w1 mod 10), acting player = step mod P, perform_action, auto-reset of finished games with

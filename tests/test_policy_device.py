@@ -1,0 +1,493 @@
+"""The heuristic policy on the device (include/tetris_hip.h: tetris_rt_features_dev, tetris_policy_rt_dev,
+tetris_step_policy_dev, tetris_rollout_policy, tetris_rollout_game_totals_dev) against a CPU model written here on top of the
+oracle, in the way tests/golden/policies.py:GreedyRT works: every game is copied 40 times into a scratch OracleBatch, the 40
+key lists [8]*r + [2] + [3]*t + [7] are made, the eight features are computed with numpy from the observed fields as the
+header's table defines them, dotted with the weights, argmax (numpy's first maximum is the lowest candidate), step_rt on the
+oracle, finished games reset with orc.episode_seed.  The model owes nothing to the code under test.  Everything is exact
+equality.  Every test runs on the CPU harness (`-m "not gpu"`) and on the MI355X (`-m gpu`); on the harness the "device" buffers
+are numpy arrays."""
+import numpy as np
+import pytest
+
+import __graft_entry__ as ge
+from oracle import oracle as orc
+from tests import engines
+
+ROT = np.repeat(np.arange(4), 10).astype(np.uint8)
+TRA = np.tile(np.arange(10), 4).astype(np.uint8)
+W_A = np.array([76, -71, -18, -51, 0, 0, 0, 0], np.int16)          # lines, holes, bumpiness, aggregate height
+W_B = np.array([34, -79, 0, -10, 0, -32, -93, -34], np.int16)      # Dellacherie-like
+W_ZERO = np.zeros(8, np.int16)
+
+
+class Buf:
+    """A buffer the entry points read or write: numpy on the harness, a torch device tensor on the GPU; .ptr, .get() -> numpy."""
+
+    def __init__(self, kind, shape, dtype, fill=0):
+        self.kind, self.dtype = kind, dtype
+        if kind == "hip":
+            import torch
+            tdt = {np.uint8: torch.uint8, np.int16: torch.int16, np.int32: torch.int32, np.uint32: torch.int32}[dtype]
+            self.t = torch.full(shape, fill, dtype=tdt, device="cuda")
+            self.ptr = self.t.data_ptr()
+            torch.cuda.synchronize()              # (the batch runs on a stream of its own)
+        else:
+            self.a = np.full(shape, fill, dtype)
+            self.ptr = self.a.ctypes.data
+
+    def get(self):
+        if self.kind == "hip":
+            import torch
+            torch.cuda.synchronize()
+            return self.t.cpu().numpy().view(self.dtype)
+        return self.a.copy()
+
+    def set(self, values):
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(values), self.get().shape)).astype(self.dtype)
+        if self.kind == "hip":
+            import torch
+            self.t.copy_(torch.from_numpy(v.view(self.t.cpu().numpy().dtype)))
+            torch.cuda.synchronize()
+        else:
+            self.a[...] = v
+        return self
+
+
+# ---------------------------------------------------------------- the model
+def features(f):
+    """f bool [M, H, W] (row 0 = top) -> int32 [M, 8], the table of include/tetris_hip.h"""
+    M, H, W = f.shape
+    full = f.all(axis=2)
+    lines = full.sum(axis=1)
+    g = np.zeros_like(f)                              # full rows removed, the rows above moved down
+    for m in range(M):
+        keep = f[m][~full[m]]
+        g[m, H - len(keep):] = keep
+    heights = np.where(g.any(axis=1), H - g.argmax(axis=1), 0)
+    below = np.cumsum(g, axis=1) > 0
+    holes = (below & ~g).sum(axis=(1, 2))
+    bump = np.abs(np.diff(heights, axis=1)).sum(axis=1)
+    agg = heights.sum(axis=1)
+    mx = heights.max(axis=1)
+    padded = np.concatenate([np.ones((M, H, 1), bool), g, np.ones((M, H, 1), bool)], axis=2)
+    rowtr = (padded[:, :, 1:] != padded[:, :, :-1]).sum(axis=(1, 2))
+    padv = np.concatenate([g, np.ones((M, 1, W), bool)], axis=1)
+    coltr = (padv[:, 1:] != padv[:, :-1]).sum(axis=(1, 2))
+    hp = np.concatenate([np.full((M, 1), H), heights, np.full((M, 1), H)], axis=1)
+    d = np.maximum(np.minimum(hp[:, :-2], hp[:, 2:]) - heights, 0)
+    wells = (d * (d + 1) // 2).sum(axis=1)
+    return np.stack([lines, holes, bump, agg, mx, rowtr, coltr, wells], axis=1).astype(np.int32)
+
+
+class Model:
+    """The policy on the oracle.  `o` is the OracleBatch it plays; weights int16 [8] or [N, 8]."""
+
+    def __init__(self, o, ids=None):
+        self.o = o
+        self.ids = np.arange(o.n_games) if ids is None else np.asarray(ids)      # global game ids (the reset-seed schedule's key)
+        self.scratch = orc.OracleBatch(40 * o.n_games, o.n_players, o.height, 10)
+        self.episode = np.zeros(o.n_games, np.int64)
+        self.totals = np.zeros((4, o.n_games), np.int64)     # env-steps, episodes, lines, sent
+        self.decisions = self.tied = 0
+
+    def candidate_fields(self, player):
+        o, N, P, H = self.o, self.o.n_games, self.o.n_players, self.o.height
+        self.scratch.copy_from(o, src_idx=np.repeat(np.arange(N), 40).astype(np.int32))
+        keys = np.zeros((40 * N, P, 16), np.uint8)
+        lens = np.ones((40 * N, P), np.uint8)              # [0] for the others
+        pl = np.broadcast_to(np.asarray(player, np.int64), (N,))
+        for c in range(40):
+            k = [8] * int(ROT[c]) + [2] + [3] * int(TRA[c]) + [7]
+            sel = np.arange(N) * 40 + c
+            keys[sel, pl, :len(k)] = k
+            lens[sel, pl] = len(k)
+        self.scratch.make_actions(keys, lens)
+        rec, _, _ = self.scratch.observe()
+        return rec["field"][np.arange(40 * N), np.repeat(pl, 40), :H, :]      # [40 N, H, W] tile values
+
+    def features(self, player):
+        """-> int32 [N, 40, 8]"""
+        return features(self.candidate_fields(player) > 0).reshape(self.o.n_games, 40, 8)
+
+    def choose(self, weights, player):
+        """-> rot, trans, score [N]"""
+        N = self.o.n_games
+        w = np.broadcast_to(np.asarray(weights, np.int64).reshape(-1, 8), (N, 8))
+        score = (self.features(player).astype(np.int64) * w[:, None, :]).sum(axis=2)        # [N, 40]
+        best = score.argmax(axis=1)                       # lowest index on ties
+        self.decisions += N
+        self.tied += int(((score == score.max(axis=1, keepdims=True)).sum(axis=1) > 1).sum())
+        return ROT[best], TRA[best], score[np.arange(N), best].astype(np.int32)
+
+    def step(self, rot, trans, player, auto_reset, count=False):
+        """step_rt + the reset of finished games by the built-in seed schedule -> done, lines [N, P], dead [N, P] before the reset"""
+        o = self.o
+        sent0 = o.observe()[0]["lines_sent"].astype(np.int64).sum(axis=1) if count else None
+        done = o.step_rt(rot, trans, player)
+        rec = o.observe()[0]
+        lines, dead = rec["reward"].copy(), rec["dead"].copy()
+        if count:
+            self.totals[0] += 1
+            self.totals[2] += (lines.astype(np.int64) * (dead == 0)).sum(axis=1)
+            self.totals[3] += (rec["lines_sent"].astype(np.int64).sum(axis=1) - sent0) & 0xFFFF
+        d = np.nonzero(done)[0].astype(np.int32)
+        if auto_reset and len(d):
+            self.episode[d] += 1
+            self.totals[1][d] += 1
+            o.reset(d, seeds=orc.episode_seed(self.ids[d], self.episode[d]))
+        return done, lines, dead
+
+    def rollout(self, weights, steps, first_step=0):
+        P = self.o.n_players
+        for s in range(first_step, first_step + steps):
+            r, t, _ = self.choose(weights, s % P)
+            self.step(r, t, s % P, True, count=True)
+
+
+def _pair(kind, n, P, height=20, colours=False):
+    """a batch of the engine under test and an oracle holding the same games (seeds of the built-in schedule, episode 0)"""
+    seeds = orc.episode_seed(np.arange(n), 0)
+    b = engines.make(kind, n, P, height=height, seeds=seeds, colours=colours)
+    o = engines.make("oracle", n, P, height=height, seeds=seeds)
+    return b, o
+
+
+def _mixed_play(b, m, steps, rng, weights=W_A):
+    """`steps` steps, the model's choice and a random (r, t) alternating per game and step, the acting player random per game:
+    tall, holey and (two players) garbage-filled stacks.  Played on the oracle `m.o` and on the engine `b` alike."""
+    N, P = m.o.n_games, m.o.n_players
+    for s in range(steps):
+        player = rng.integers(0, P, N).astype(np.uint8)
+        r, t, _ = m.choose(weights, player)
+        rnd = rng.random(N) < 0.5
+        r = np.where(rnd, rng.integers(0, 4, N), r).astype(np.uint8)
+        t = np.where(rnd, rng.integers(0, 10, N), t).astype(np.uint8)
+        done = m.o.step_rt(r, t, player)
+        assert np.array_equal(b.step_rt(r, t, player), done)
+        d = np.nonzero(done)[0].astype(np.int32)
+        if len(d):
+            sd = orc.episode_seed(d, s + 1)
+            m.o.reset(d, seeds=sd)
+            b.reset(d, seeds=sd)
+
+
+def _assert_same_records(got, want, where):
+    """engines.assert_same_state for two observe() results (batches of different sizes)"""
+    (a, ro_a, lw_a), (b, ro_b, lw_b) = got, want
+    for f in engines.ENGINE_FIELDS:
+        fa, fb = (a[f] > 0, b[f] > 0) if f == "field" else (a[f], b[f])
+        assert np.array_equal(fa, fb), f"{where}: '{f}' differs"
+    assert np.array_equal(ro_a, ro_b) and np.array_equal(lw_a, lw_b), f"{where}: round_over / last_winner"
+
+
+# ---------------------------------------------------------------- 1. features
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("P,height", [(1, 20), (2, 20), (1, 22), (2, 22)])
+def test_features_equal_the_model(kind, P, height):
+    n, steps = 32, 120
+    rng = np.random.default_rng(100 + 10 * P + height)
+    b, o = _pair(kind, n, P, height)
+    m = Model(o)
+    seen_lines = seen_holes = False
+    garbage_boards = 0
+    feat = Buf(kind, (40, 8, n), np.int16, -1)
+    pl = Buf(kind, (n,), np.uint8)
+    for chunk in range(4):
+        _mixed_play(b, m, steps // 4, rng)
+        player = rng.integers(0, P, n).astype(np.uint8)
+        pl.set(player)
+        want = m.features(player)                                   # [N, 40, 8]
+        b.rt_features_dev(feat.ptr, player=pl.ptr)
+        got = feat.get().transpose(2, 0, 1)
+        assert np.array_equal(got, want), f"features differ after {(chunk + 1) * (steps // 4)} steps: {np.argwhere(got != want)[:5]}"
+        seen_lines |= bool((want[:, :, 0] > 0).any())
+        seen_holes |= bool((want[:, :, 1] > 0).any())
+        if P == 2:
+            rec = o.observe()[0]
+            garbage_boards = max(garbage_boards, int((rec["field"] == 8).any(axis=(2, 3)).any(axis=1).sum()))
+        engines.assert_same_state(b, o, where="features must not write the state")
+    assert seen_lines and seen_holes, "the boards of this test reach no candidate with lines / holes"
+    if P == 2:
+        assert garbage_boards > 0, "no two-player board with garbage cells"
+
+
+def test_features_player_null_and_colour_batches():
+    """NULL player array = player 0; a colour batch gives the same features (the policy reads occupancy)"""
+    n = 16
+    b, o = _pair("harness", n, 2, colours=True)
+    m = Model(o)
+    _mixed_play(b, m, 40, np.random.default_rng(5))
+    feat = Buf("harness", (40, 8, n), np.int16, -1)
+    b.rt_features_dev(feat.ptr)
+    assert np.array_equal(feat.get().transpose(2, 0, 1), m.features(0))
+
+
+# ---------------------------------------------------------------- 2. choice
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("P", [1, 2])
+def test_choice_equals_the_model(kind, P):
+    n = 32
+    rng = np.random.default_rng(200 + P)
+    b, o = _pair(kind, n, P)
+    m = Model(o)
+    per_game = np.stack([W_ZERO if g % 4 == 0 else (W_A if g % 4 == 1 else (W_B if g % 4 == 2 else rng.integers(-100, 100, 8))) for g in range(n)]).astype(np.int16)
+    rot, trans, score = Buf(kind, (n,), np.uint8, 9), Buf(kind, (n,), np.uint8, 99), Buf(kind, (n,), np.int32, -5)
+    pl = Buf(kind, (n,), np.uint8)
+    w_shared, w_games = Buf(kind, (8,), np.int16), Buf(kind, (n, 8), np.int16).set(per_game)
+    m.decisions = m.tied = 0
+    for chunk in range(6):
+        _mixed_play(b, m, 10, rng)
+        d0, t0 = m.decisions, m.tied
+        player = rng.integers(0, P, n).astype(np.uint8)
+        pl.set(player)
+        for shared in (W_A, W_B):
+            w_shared.set(shared)
+            b.policy_rt_dev(w_shared.ptr, rot.ptr, trans.ptr, score.ptr, player=pl.ptr)
+            r, t, s = m.choose(shared, player)
+            assert np.array_equal(rot.get(), r) and np.array_equal(trans.get(), t) and np.array_equal(score.get(), s), f"shared weights, chunk {chunk}"
+        b.policy_rt_dev(w_games.ptr, rot.ptr, trans.ptr, score.ptr, player=pl.ptr, per_game=True)
+        r, t, s = m.choose(per_game, player)
+        assert np.array_equal(rot.get(), r) and np.array_equal(trans.get(), t) and np.array_equal(score.get(), s), f"per-game weights, chunk {chunk}"
+        assert not r[::4].any() and not t[::4].any() and not s[::4].any()          # all-zero weights choose (0, 0)
+        b.policy_rt_dev(w_games.ptr, rot.ptr, trans.ptr, None, player=pl.ptr, per_game=True)       # score may be NULL
+        assert np.array_equal(rot.get(), r) and np.array_equal(trans.get(), t)
+        engines.assert_same_state(b, o, where="the choice must not write the state")
+    # the tie rule is covered: decisions with more than one best candidate (all decisions of this test, mixed play included)
+    assert 2 * m.tied >= m.decisions, f"only {m.tied} of {m.decisions} decisions had more than one best candidate"
+
+
+# ---------------------------------------------------------------- 3. step
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("P,auto_reset", [(1, False), (1, True), (2, False), (2, True)])
+def test_step_policy_equals_choice_plus_step_and_the_model(kind, P, auto_reset):
+    n, steps = 24, 60
+    rng = np.random.default_rng(300 + 2 * P + auto_reset)
+    b, o = _pair(kind, n, P)
+    b2, _ = _pair(kind, n, P)
+    m = Model(o)
+    per_game = np.stack([W_A if g % 2 else W_B for g in range(n)]).astype(np.int16)
+    w = Buf(kind, (n, 8), np.int16).set(per_game)
+    pl = Buf(kind, (n,), np.uint8)
+    out = [dict(done=Buf(kind, (n,), np.uint8, 7), lines=Buf(kind, (P, n), np.uint8, 7), dead=Buf(kind, (P, n), np.uint8, 7),
+                rot=Buf(kind, (n,), np.uint8, 7), trans=Buf(kind, (n,), np.uint8, 77)) for _ in range(2)]
+    ended = 0
+    for s in range(steps):
+        # random (r, t) steps in between keep the boards rough, so that rounds end (without auto-reset they are reset by hand)
+        if s % 3 == 2:
+            player = rng.integers(0, P, n).astype(np.uint8)
+            r, t = rng.integers(0, 4, n).astype(np.uint8), rng.integers(0, 10, n).astype(np.uint8)
+            done = o.step_rt(r, t, player)
+            assert np.array_equal(b.step_rt(r, t, player), done) and np.array_equal(b2.step_rt(r, t, player), done)
+        else:
+            player = rng.integers(0, P, n).astype(np.uint8)
+            pl.set(player)
+            a, c = out
+            b.step_policy_dev(w.ptr, a["done"].ptr, a["lines"].ptr, a["dead"].ptr, rot=a["rot"].ptr, trans=a["trans"].ptr, player=pl.ptr,
+                              per_game=True, auto_reset=auto_reset)
+            b2.policy_rt_dev(w.ptr, c["rot"].ptr, c["trans"].ptr, None, player=pl.ptr, per_game=True)
+            b2.step_rt_dev(c["rot"].ptr, c["trans"].ptr, pl.ptr, c["done"].ptr, c["lines"].ptr, c["dead"].ptr, auto_reset=auto_reset)
+            r, t, _ = m.choose(per_game, player)
+            done, lines, dead = m.step(r, t, player, auto_reset)
+            for name, want in (("done", done), ("lines", lines.T), ("dead", dead.T), ("rot", r), ("trans", t)):
+                assert np.array_equal(a[name].get(), want), f"step {s}: step_policy_dev '{name}' differs from the model"
+                assert np.array_equal(c[name].get(), want), f"step {s}: policy_rt_dev + step_rt_dev '{name}' differs from the model"
+            ended += int(done.sum())
+        if not auto_reset or s % 3 == 2:
+            d = np.nonzero(done)[0].astype(np.int32)
+            if len(d):
+                sd = orc.episode_seed(d, 1000 + s)
+                for e in (o, b, b2):
+                    e.reset(d, seeds=sd)
+        engines.assert_same_state(b, o, where=f"step {s}: step_policy_dev against the model")
+        engines.assert_same_state(b2, o, where=f"step {s}: policy_rt_dev + step_rt_dev against the model")
+    b.step_policy_dev(w.ptr, None, None, None, per_game=True, auto_reset=auto_reset)           # every output may be NULL
+    r, t, _ = m.choose(per_game, 0)
+    m.step(r, t, 0, auto_reset)
+    engines.assert_same_state(b, o, where="step_policy_dev without outputs")
+    assert b.take_errors() == 0
+
+
+# ---------------------------------------------------------------- 4. / 5. rollout
+def _assert_rollout(kind, b, m, counters, label):
+    engines.assert_same_state(b, m.o, where=label)
+    n = m.o.n_games
+    tot = Buf(kind, (4, n), np.uint32, 0xFFFF)
+    b.rollout_game_totals_dev(tot.ptr)
+    b.sync()
+    assert np.array_equal(tot.get().astype(np.int64), m.totals), f"{label}: per-game totals"
+    assert np.array_equal(b.rollout_totals().astype(np.int64), m.totals.sum(axis=1)), f"{label}: rollout_totals"
+    assert np.array_equal(np.asarray(counters, np.int64), m.totals.sum(axis=1)), f"{label}: counters"
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+def test_rollout_long_one_player_crosses_two_table_chunks(kind):
+    """32 games x 1 400 steps: on the model no game ends and every game passes 1 248 piece draws, so the run crosses two
+    RNG-table chunk boundaries with live games."""
+    n, steps = 32, 1400
+    b, o = _pair(kind, n, 1)
+    m = Model(o)
+    w = Buf(kind, (8,), np.int16).set(W_B)
+    m.rollout(W_B, steps)
+    draws = o.observe()[0]["piece_draws"]
+    print(f"model: piece_draws min {draws.min()} max {draws.max()}, episodes ended {int(m.totals[1].sum())}, lines {int(m.totals[2].sum())}")
+    assert draws.min() > 1248 and m.totals[1].sum() == 0, "the test's inputs are wrong (the model itself does not reach the regime)"
+    counters = np.zeros(4, np.int64)
+    for launches, spl in ((200, 1), (50, 8), (800, 1)):               # one step per launch, a fused stretch in the middle
+        c, _ = b.rollout_policy(w.ptr, launches, spl, first_step=int(counters[0]) // n)
+        counters += c.astype(np.int64)
+    assert counters[0] == n * steps
+    _assert_rollout(kind, b, m, counters, "long rollout")
+    assert b.take_errors() == 0
+    assert b.table_chunks >= 3
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("weights", [W_A, W_B], ids=["lines-holes-bump-height", "dellacherie"])
+def test_rollout_two_players_equals_the_model(kind, weights):
+    n, steps = 16, 300
+    b, o = _pair(kind, n, 2)
+    b8, _ = _pair(kind, n, 2)
+    m = Model(o)
+    w = Buf(kind, (8,), np.int16).set(weights)
+    m.rollout(weights, steps)
+    print(f"model: episodes ended {int(m.totals[1].sum())}, lines {int(m.totals[2].sum())}, sent {int(m.totals[3].sum())}")
+    assert m.totals[1].sum() >= 1, "no episode ended on the model: auto-reset is not inside the comparison"
+    c1, _ = b.rollout_policy(w.ptr, steps, 1)
+    _assert_rollout(kind, b, m, c1, "one step per launch")
+    c8 = np.zeros(4, np.int64)
+    for launches, spl, first in ((30, 6, 0), (20, 1, 180), (20, 5, 200)):      # fused launches (odd and even first steps) around single ones
+        c, _ = b8.rollout_policy(w.ptr, launches, spl, first_step=first)
+        c8 += c.astype(np.int64)
+    _assert_rollout(kind, b8, m, c8, "fused launches")
+    assert b.take_errors() == 0 and b8.take_errors() == 0
+
+
+@pytest.mark.parametrize("P,colours,height", [(3, False, 20), (4, True, 16), (1, True, 24)])
+def test_rollout_other_geometries_on_the_harness(P, colours, height):
+    """three and four players, colour batches, other heights: per-game weights, game offset, fused and single launches"""
+    n, steps = 8, 36
+    seeds = orc.episode_seed(np.arange(n) + 500, 0)
+    b = engines.make("harness", n, P, height=height, seeds=seeds, colours=colours)
+    o = engines.make("oracle", n, P, height=height, seeds=seeds)
+    b.set_game_offset(500)
+    m = Model(o, ids=np.arange(n) + 500)
+    per_game = np.stack([W_A if g % 2 else W_B for g in range(n)]).astype(np.int16)
+    w = Buf("harness", (n, 8), np.int16).set(per_game)
+    m.rollout(per_game, steps)
+    c1, _ = b.rollout_policy(w.ptr, 12, 1, per_game=True)
+    c2, _ = b.rollout_policy(w.ptr, 6, 4, per_game=True, first_step=12)
+    _assert_rollout("harness", b, m, c1.astype(np.int64) + c2.astype(np.int64), f"P={P} colours={colours} H={height}")
+
+
+# ---------------------------------------------------------------- 6. arguments
+def test_arguments_are_checked():
+    pkg = ge.package()
+    h = ge.build_harness()
+    n = 4
+    b = engines.make("harness", n, 2)
+    w = np.zeros(8, np.int16)
+    rot, trans = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    feat, tot = np.zeros((40, 8, n), np.int16), np.zeros((4, n), np.uint32)
+    p = lambda a: a.ctypes.data                                                           # noqa: E731
+    with pytest.raises(pkg.TetrisError, match="NULL"):
+        b.rt_features_dev(None)
+    with pytest.raises(pkg.TetrisError, match="NULL"):
+        b.policy_rt_dev(None, p(rot), p(trans))
+    with pytest.raises(pkg.TetrisError, match="NULL"):
+        b.policy_rt_dev(p(w), None, p(trans))
+    with pytest.raises(pkg.TetrisError, match="NULL"):
+        b.policy_rt_dev(p(w), p(rot), None)
+    with pytest.raises(pkg.TetrisError, match="NULL"):
+        b.step_policy_dev(None, None, None, None)
+    with pytest.raises(pkg.TetrisError, match="NULL"):
+        b.rollout_policy(None, 1, 1)
+    with pytest.raises(pkg.TetrisError, match="NULL"):
+        b.rollout_game_totals_dev(None)
+    for launches, spl in ((0, 1), (1, 0), (1, 257)):
+        with pytest.raises(pkg.TetrisError, match="steps_per_launch"):
+            b.rollout_policy(p(w), launches, spl)
+    rc = b.lib.tetris_step_policy_dev(b._h, None, p(w), 0, 400, 2, None, None, None, None, None)
+    assert rc == -1 and b"flag" in b.lib.tetris_last_error()
+    s = pkg.TetrisBatch(n, 2, 20, 10, lib_path=h, split_side=0)
+    for call in (lambda: s.rt_features_dev(p(feat)), lambda: s.policy_rt_dev(p(w), p(rot), p(trans)),
+                 lambda: s.step_policy_dev(p(w), None, None, None), lambda: s.rollout_policy(p(w), 1, 1),
+                 lambda: s.rollout_game_totals_dev(p(tot))):
+        with pytest.raises(pkg.TetrisError, match="split"):
+            call()
+    assert len(pkg.POLICY_FEATURE_NAMES) == 8
+
+
+# ---------------------------------------------------------------- 7. full size
+@pytest.mark.gpu
+@pytest.mark.parametrize("P", [1, 2])
+def test_full_size_rollout_equals_single_steps_and_the_model(P):
+    """65 536 games x 64 steps: rollout_policy (one step per launch, then fused) equals 64 x (policy_rt_dev + step_rt_dev with
+    auto-reset) on a second batch for EVERY game, and the model for a sample of games run on their own (games are independent and
+    keyed by global id): 336 games, the first and the last wavefront and 16 games of each of 13 more workgroups."""
+    import torch
+    n, steps = 65536, 64
+    seeds = orc.episode_seed(np.arange(n), 0)
+    a = engines.make("hip", n, P, seeds=seeds)
+    c = engines.make("hip", n, P, seeds=seeds)
+    w = Buf("hip", (8,), np.int16).set(W_B)
+    ca, _ = a.rollout_policy(w.ptr, 40, 1)
+    cb, _ = a.rollout_policy(w.ptr, 3, 8, first_step=40)
+    counters = ca.astype(np.int64) + cb.astype(np.int64)
+    rot, trans = Buf("hip", (n,), np.uint8), Buf("hip", (n,), np.uint8)
+    pl = Buf("hip", (n,), np.uint8)
+    done, lines, dead = Buf("hip", (n,), np.uint8), Buf("hip", (P, n), np.uint8), Buf("hip", (P, n), np.uint8)
+    for s in range(steps):
+        pl.t.fill_(s % P)
+        torch.cuda.synchronize()
+        c.policy_rt_dev(w.ptr, rot.ptr, trans.ptr, None, player=pl.ptr)
+        c.step_rt_dev(rot.ptr, trans.ptr, pl.ptr, done.ptr, lines.ptr, dead.ptr, auto_reset=True)
+        c.sync()
+    for lo in range(0, n, 8192):                                                        # every game, batch against batch
+        idx = np.arange(lo, lo + 8192, dtype=np.int32)
+        engines.assert_same_state(a, c, idx=idx, where=f"games {lo}..{lo + 8191}: rollout_policy against single steps")
+    sample = np.unique(np.concatenate([np.arange(64), np.arange(n - 64, n)] +
+                                      [np.arange(g, g + 16) for g in range(4096 + 7 * 64, n - 4096, 4608)]))
+    assert len(sample) >= 256 and len(np.unique(sample // 64)) >= 10 and sample[0] == 0 and sample[-1] == n - 1
+    o = orc.OracleBatch(len(sample), P, 20, 10, seeds=seeds[sample])
+    m = Model(o, ids=sample)            # games run on their own: the reset seeds are keyed by the sampled games' global ids
+    m.rollout(W_B, steps)
+    _assert_same_records(a.observe(sample.astype(np.int32)), o.observe(), "sampled games against the model")
+    tot = Buf("hip", (4, n), np.uint32)
+    a.rollout_game_totals_dev(tot.ptr)
+    a.sync()
+    got = tot.get().astype(np.int64)
+    assert np.array_equal(got[:, sample], m.totals), "per-game totals of the sampled games"
+    assert np.array_equal(got.sum(axis=1), np.asarray(counters)) and counters[0] == n * steps
+    assert a.take_errors() == 0 and c.take_errors() == 0
+
+
+# ---------------------------------------------------------------- torch interface
+@pytest.mark.gpu
+def test_torch_env_policy_calls_equal_the_model():
+    """TorchEnv.rt_features / policy_rt / step_policy / game_totals on torch's stream, device tensors only"""
+    import importlib
+    import torch
+    ti = importlib.import_module("drl-tetris_amd.torch_interop")
+    n, P = 48, 2
+    b, o = _pair("hip", n, P)
+    m = Model(o)
+    te = ti.TorchEnv(b)
+    per_game = np.stack([W_A if g % 2 else W_B for g in range(n)]).astype(np.int16)
+    w_games = torch.from_numpy(per_game).cuda()
+    w_one = torch.from_numpy(W_B).cuda()
+    for s in range(24):
+        player = np.full(n, s % P, np.uint8)
+        pt = torch.from_numpy(player).cuda()
+        if s % 8 == 0:
+            assert np.array_equal(te.rt_features(pt).cpu().numpy().transpose(2, 0, 1), m.features(player))
+            r, t, sc = m.choose(W_B, player)
+            rot, trans, score = te.policy_rt(w_one, pt)
+            assert np.array_equal(rot.cpu().numpy(), r) and np.array_equal(trans.cpu().numpy(), t) and np.array_equal(score.cpu().numpy(), sc)
+        r, t, _ = m.choose(per_game, player)
+        want_done, want_lines, want_dead = m.step(r, t, player, True)
+        done, lines, dead, rot, trans = te.step_policy(w_games, pt, auto_reset=True)
+        assert np.array_equal(rot.cpu().numpy(), r) and np.array_equal(trans.cpu().numpy(), t) and np.array_equal(done.cpu().numpy(), want_done)
+        assert np.array_equal(lines.cpu().numpy(), want_lines.T) and np.array_equal(dead.cpu().numpy(), want_dead.T)
+    torch.cuda.synchronize()
+    engines.assert_same_state(b, o, where="TorchEnv.step_policy")
+    assert te.game_totals().shape == (4, n) and int(te.game_totals()[0].sum()) == 0          # single steps do not count as rollout steps
