@@ -65,10 +65,7 @@ struct Device {                        // one per HIP device of the process, mad
     std::string why;                   // why it is not ok
 };
 
-#ifndef TE_AQL_SLOTS
-#define TE_AQL_SLOTS 4096
-#endif
-constexpr int SLOTS = TE_AQL_SLOTS;    // kernel-argument slots per queue (> 2 * wgroup + 1)
+constexpr int SLOTS = 4096;    // kernel-argument slots per queue (> 2 * wgroup + 1)
 constexpr uint32_t QUEUE_PACKETS = 1024;
 
 static std::mutex g_mutex;

@@ -27,71 +27,17 @@
 namespace te {
 
 // ---------------------------------------------------------------- small helpers
-#if defined(__HIP_DEVICE_COMPILE__)
 TE_HD int ctz32(uint32_t v) { return __builtin_ctz(v); }
 TE_HD int clz32(uint32_t v) { return __builtin_clz(v); }
-#else
-TE_HD int ctz32(uint32_t v) { return __builtin_ctz(v); }
-TE_HD int clz32(uint32_t v) { return __builtin_clz(v); }
-#endif
 // State words are touched exactly once per launch and next read by another launch (possibly on another
 // XCD): stream them past the caches (`nt`), which also leaves no dirty L2 lines for the end-of-kernel
 // write-back to drain.
-#ifndef TE_LD_NT
-#define TE_LD_NT 1
-#endif
-#ifndef TE_ST_NT
-#define TE_ST_NT 1
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
-TE_HD uint32_t ld_stream(const uint32_t* p) { return TE_LD_NT ? __builtin_nontemporal_load(p) : *p; }
-TE_HD void st_stream(uint32_t* p, uint32_t v) { if (TE_ST_NT) __builtin_nontemporal_store(v, p); else *p = v; }
+TE_HD uint32_t ld_stream(const uint32_t* p) { return __builtin_nontemporal_load(p); }
+TE_HD void st_stream(uint32_t* p, uint32_t v) { __builtin_nontemporal_store(v, p); }
 #else
 TE_HD uint32_t ld_stream(const uint32_t* p) { return *p; }
 TE_HD void st_stream(uint32_t* p, uint32_t v) { *p = v; }
-#endif
-
-// Diagnostic build only (-DTE_PHASE_TRACE, profiles/phase_trace.py): the first active lane of a wave writes the shader
-// clock at phase boundaries into a device buffer.  Product builds compile TE_STAMP to nothing.
-#if defined(TE_PHASE_TRACE) && defined(__HIPCC__)
-static __device__ unsigned long long d_trace[2048 * 16];            // (one copy per translation unit; read out by tetris_hip.hip)
-static __device__ unsigned long long d_chain_trace[8 * 1024 * 8];
-#endif
-#if defined(TE_PHASE_TRACE) && defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ void te_stamp(int k, bool realtime = false) {
-    __builtin_amdgcn_sched_barrier(0);
-    const unsigned long long t = realtime ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();
-    const unsigned wv = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int first = __ffsll((unsigned long long)__ballot(1)) - 1;
-    if ((int)(threadIdx.x & 63) == first && wv < 2048) d_trace[wv * 16 + k] = t;
-    __builtin_amdgcn_sched_barrier(0);
-}
-#define TE_STAMP(k) te_stamp(k)
-#define TE_STAMP_RT(k) te_stamp(k, true)
-// chained launches (k_chain): 100 MHz real-time clock (comparable across CUs and launches), stamps of the last 8 epochs kept
-__device__ __forceinline__ void te_stamp_chain(uint32_t epoch, int k) {
-    __builtin_amdgcn_sched_barrier(0);
-    const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) d_chain_trace[(((size_t)(epoch & 7u) * 1024) + blockIdx.x) * 8 + k] = t;
-    __builtin_amdgcn_sched_barrier(0);
-}
-// slot 7: where the wave runs — HW_ID (wave[3:0] simd[5:4] cu[11:8] sh[12] se[15:13]) | XCC_ID << 32
-__device__ __forceinline__ void te_stamp_place(uint32_t epoch) {
-    uint32_t hw, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024)
-        d_chain_trace[(((size_t)(epoch & 7u) * 1024) + blockIdx.x) * 8 + 7] = ((unsigned long long)xcc << 32) | hw;
-}
-#define TE_STAMP_CHAIN(e, k) te_stamp_chain(e, k)
-#define TE_STAMP_PLACE(e) te_stamp_place(e)
-#else
-#define TE_STAMP(k) do {} while (0)
-#define TE_STAMP_RT(k) do {} while (0)
-#endif
-#if !defined(TE_STAMP_CHAIN)
-#define TE_STAMP_PLACE(e) do {} while (0)
-#define TE_STAMP_CHAIN(e, k) do {} while (0)
 #endif
 
 // Test-only path counters (tests/cpu_harness defines TE_PATH_COUNTERS): how often the rare branches of the key interpreter
@@ -141,13 +87,13 @@ constexpr int TE_AUX_NT = 2, TE_AUX_SC1 = 16;     // cache-policy bits of the bu
 TE_HD uint32_t ldw(const uint32_t* base, uint32_t o, size_t word_off, int mem = MEM_STREAM) {
     const __amdgpu_buffer_rsrc_t r = te_rsrc(base);
     if (mem == MEM_AGENT || mem == MEM_AFFINE) return __builtin_amdgcn_raw_buffer_load_b32(r, (int)o, (int)(uint32_t)(word_off * 4u), TE_AUX_SC1);
-    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)o, (int)(uint32_t)(word_off * 4u), TE_LD_NT ? TE_AUX_NT : 0);
+    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)o, (int)(uint32_t)(word_off * 4u), TE_AUX_NT);
 }
 TE_HD void stw(uint32_t* base, uint32_t o, size_t word_off, uint32_t v, int mem = MEM_STREAM) {
     const __amdgpu_buffer_rsrc_t r = te_rsrc(base);
     if (mem == MEM_AGENT) __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)o, (int)(uint32_t)(word_off * 4u), TE_AUX_SC1);
     else if (mem == MEM_AFFINE) __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)o, (int)(uint32_t)(word_off * 4u), 0);
-    else __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)o, (int)(uint32_t)(word_off * 4u), TE_ST_NT ? TE_AUX_NT : 0);
+    else __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)o, (int)(uint32_t)(word_off * 4u), TE_AUX_NT);
 }
 #else
 TE_HD uint32_t ldw(const uint32_t* base, uint32_t o, size_t word_off, int mem = MEM_STREAM) {
@@ -351,14 +297,13 @@ TE_HD void load_game_words(const Ref& gr, Game<P>& g, bool counters = false, int
 }
 
 template <int P>
-TE_HD void load_game(const Geo& geo_in, size_t slot, Game<P>& g, bool tint = false, bool queue = true, bool counters = false, int mem = MEM_STREAM,
-                     bool uniform = false) {
+TE_HD void load_game(const Geo& geo_in, size_t slot, Game<P>& g, bool tint = false, bool queue = true, bool counters = false, int mem = MEM_STREAM) {
     Geo geo = geo_in;
     geo.P = P;                           // compile-time stride factor for the hot loads
-    load_game_words<P>(game_ref(geo, slot, uniform), g, counters, mem);
+    load_game_words<P>(game_ref(geo, slot), g, counters, mem);
     TE_UNROLL
     for (int p = 0; p < P; p++) {
-        const Ref r = board_ref(geo, p, slot, uniform);
+        const Ref r = board_ref(geo, p, slot);
         load_player(r.s, r.o, r.ws, g.pl[p], tint, queue, mem);
     }
 }
@@ -408,14 +353,13 @@ TE_HD void store_game_words(const Ref& gr, const Game<P>& g, bool counters = fal
 }
 
 template <int P>
-TE_HD void store_game(const Geo& geo_in, size_t slot, const Game<P>& g, bool tint = false, bool queue = true, bool counters = false, int mem = MEM_STREAM,
-                      bool uniform = false) {
+TE_HD void store_game(const Geo& geo_in, size_t slot, const Game<P>& g, bool tint = false, bool queue = true, bool counters = false, int mem = MEM_STREAM) {
     Geo geo = geo_in;
     geo.P = P;
-    store_game_words<P>(game_ref(geo, slot, uniform), g, counters, mem);
+    store_game_words<P>(game_ref(geo, slot), g, counters, mem);
     TE_UNROLL
     for (int p = 0; p < P; p++) {
-        const Ref r = board_ref(geo, p, slot, uniform);
+        const Ref r = board_ref(geo, p, slot);
         store_player(r.s, r.o, r.ws, g.pl[p], tint, queue, mem);
     }
 }
@@ -738,9 +682,6 @@ TE_HD void lock_piece(const Ctx& cx, Player& q) {
 
 // gamePlay.cpp:54-59 hd_finish; -1 = died
 TE_HD int settle(const Ctx& cx, Player& q, uint32_t seed16, uint32_t& status) {
-#if defined(TE_ABLATE) && (TE_ABLATE & 8)
-    return 0;                                        // diagnostic build: no clear / spawn
-#endif
     int sent = score_clears(cx, q, clear_rows(cx, q));
     if (spawn_next(cx, q, seed16, status)) return -1;
     return sent;
@@ -798,9 +739,6 @@ TE_HD bool push_garbage(const Ctx& cx, Player& q, uint32_t seed16, uint32_t& sta
 // gamePlay.cpp:90-114 delayCheck
 TE_HD int tick(const Ctx& cx, Player& q, int ms, uint32_t seed16, uint32_t& status) {
     q.time_ms += ms;
-#if defined(TE_ABLATE) && (TE_ABLATE & 4)
-    return 0;                                        // diagnostic build: no timers / garbage / combo
-#endif
     if (gravity_due(q, q.time_ms)) soft_drop(cx, q);
     // Single exit on purpose: with an early `return settle(..)` the compiler kept the board in different registers on the two
     // paths and merged them with ~50 register moves that every wave executed every step.
@@ -1085,9 +1023,6 @@ TE_HD int drop_distance_rows(const Ctx& cx, const Player& q, const RowsFrom& r, 
 }
 
 TE_HD void play_rt(const Ctx& cx, Player& q, int r, int t) {
-#if defined(TE_ABLATE) && (TE_ABLATE & 2)
-    lock_piece(cx, q); return;                       // diagnostic build: no rotations / slides
-#endif
     const Shapes4 sh = shapes_of_kind(cx, q.kind);
     const Shapes4 dw = drop_words_of_kind(cx, q.kind);
     if (q.y != 0 || q.x != (NCOL - 4) / 2) TE_COUNT(PC_RT_OFF_SPAWN);
@@ -1098,7 +1033,6 @@ TE_HD void play_rt(const Ctx& cx, Player& q, int r, int t) {
     const bool fit2 = (((pick4(sh, q.rot + 2) & 0xFFFFu) << 8) & win) == 0;
     const bool fit3 = (((pick4(sh, q.rot + 3) & 0xFFFFu) << 8) & win) == 0;
     const bool easy = (r < 1 || fit1) && (r < 2 || fit2) && (r < 3 || fit3);
-    TE_STAMP(10);
     if (easy) {
         q.rot = (q.rot + r) & 3;
     } else {
@@ -1147,7 +1081,6 @@ TE_HD void play_rt(const Ctx& cx, Player& q, int r, int t) {
             }
         }
     }
-    TE_STAMP(11);
     const uint32_t shape = pick4(sh, q.rot);
     const uint32_t free = free_positions32(band, shape);
     const int xs0 = q.x + 2;
@@ -1156,10 +1089,8 @@ TE_HD void play_rt(const Ctx& cx, Player& q, int r, int t) {
     const uint32_t blocked_right = (~free >> (xs + 1)) | (1u << 13);
     xs += imin(t, ctz32(blocked_right));
     q.x = xs - 2;
-    TE_STAMP(12);
     // gamePlay.cpp:48-52 hd_make
     q.y += drop_distance_rows(cx, q, rows, shape, pick4(dw, q.rot));
-    TE_STAMP(13);
     stamp(cx, q, shape);
     q.drop_time = q.time_ms;
     q.lock_armed = 0;
@@ -1434,7 +1365,6 @@ TE_HD int finish_game(const Ctx& cx, Game<P>& g, int ms) {
             else if (sent) share_lines<P>(g, p, sent);
         }
     }
-    TE_STAMP(6);
     int alive = 0;
     TE_UNROLL
     for (int p = 0; p < P; p++) {

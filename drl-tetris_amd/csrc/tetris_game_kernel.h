@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "tetris_kernels.h"
 #include "tetris_plan.h"
 #include "tetris_policy.h"
@@ -23,24 +25,12 @@ __global__ __launch_bounds__(256) void k_game(KArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = lane_active(a, i);
     LaneCounters cnt = {0, 0, 0, 0};                   // (per-lane sums feed the CPU test harness only)
-    TE_STAMP(0); TE_STAMP_RT(1);
     const uint32_t shape_word = d_shape_table.s[threadIdx.x & 63];
     Game<P> g;
     if (active) game_load<P, MODE, TINT>(a, i, g);
-    TE_STAMP(2);
-#if defined(TE_PHASE_TRACE) && TE_PHASE_TRACE == 2
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // variant: time until ALL state words have arrived
-    TE_STAMP(3);
-#endif
     s_shapes[threadIdx.x & 63] = shape_word;
     __builtin_amdgcn_wave_barrier();
     if (active) game_run<P, MODE, TINT>(a, i, s_shapes, g, cnt);
-    TE_STAMP(9);
-#if defined(TE_PHASE_TRACE) && TE_PHASE_TRACE == 3
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // variant: time until all stores are acknowledged
-    TE_STAMP(10);
-#endif
-    TE_STAMP(14); TE_STAMP_RT(15);
 }
 
 // The planning kernels (tetris_plan.h), one wave per workgroup with its own LDS copy of the shape table.
@@ -88,6 +78,24 @@ static void launch_policy_step(int which, dim3 grid, hipStream_t st, const Polic
     else if (which == 1) hipLaunchKernelGGL((k_policy_step<P, TINT, false, true, true>), grid, dim3(64), 0, st, pa);
     else if (which == 2) hipLaunchKernelGGL((k_policy_step<P, TINT, true, true, true>), grid, dim3(64), 0, st, pa);
     else hipLaunchKernelGGL((k_policy_step<P, TINT, true, true, false>), grid, dim3(64), 0, st, pa);
+}
+
+// Runtime value -> template argument, on the host.  with_value<LO, HI>(v, f) calls f(std::integral_constant<int, v>) when
+// LO <= v <= HI and returns whether it did; with_flag(v, f) calls f(std::true_type or std::false_type); with_shape<LO, HI>(P, flag, f)
+// calls f(P, FLAG) with both.  f is a generic lambda that names its kernel with them (k_game<P(), MODE, TINT()>).  The bounds decide
+// which instantiations a translation unit holds: player counts 1..2 of k_game, k_plan_* and k_policy_step live in tetris_hip.hip,
+// 3..4 in tetris_hip_multi.hip.
+template <int LO, int HI, class F>
+static bool with_value(int v, F&& f) {
+    if constexpr (LO > HI) return false;
+    else if (v == LO) { f(std::integral_constant<int, LO>{}); return true; }
+    else return with_value<LO + 1, HI>(v, f);
+}
+template <class F>
+static void with_flag(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+template <int LO, int HI, class F>
+static bool with_shape(int P, bool flag, F&& f) {
+    return with_value<LO, HI>(P, [&](auto p) { with_flag(flag, [&](auto t) { f(p, t); }); });
 }
 
 // launches k_game<P, mode, tint> for P = 3, 4 (tetris_hip_multi.hip)

@@ -88,35 +88,25 @@ __device__ __forceinline__ void chain_body(const KArgs& a) {
     // in front of the first poll.
     // (Issuing the first poll of the epoch word BEFORE the draw — most waves find their predecessor done at that poll — measured
     // +0.06 us per launch, GPU-paced: profiles/r02/chain_ab_gpu_paced.txt.)
-    TE_STAMP_CHAIN(a.epoch, 0); TE_STAMP_PLACE(a.epoch);
     if (active) policy_draw(a, (uint32_t)i, a.first_step, g.draw0, g.draw1);
     const uint32_t d0 = g.draw0, d1 = g.draw1;
     int stride = a.n_stride;
     asm volatile("" : "+s"(stride));
-    TE_STAMP_CHAIN(a.epoch, 1);
     const uint32_t seen = chain_poll(a, (uint32_t)wave);
     if (seen == a.epoch - 1u) {                 // (a uniform branch: the state loads follow the poll's exit)
-        TE_STAMP_CHAIN(a.epoch, 2);
         Geo geo = geo_of(a);
         geo.stride = (size_t)stride;
-        if (active) { load_game<P>(geo, (size_t)i, g, false, P > 1, true, CMEM, CHAIN_LANES == 64); g.draw0 = d0; g.draw1 = d1; }
-#if defined(TE_PHASE_TRACE)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // diagnostic: when have ALL state words arrived
-        TE_STAMP_CHAIN(a.epoch, 3);
-#endif
+        if (active) { load_game<P>(geo, (size_t)i, g, false, P > 1, true, CMEM); g.draw0 = d0; g.draw1 = d1; }
         s_shapes[lane] = shape_word;
         __builtin_amdgcn_wave_barrier();
         if (active) game_run<P, M_ROLLOUT, false, CMEM>(a, i, s_shapes, g, cnt);
-        TE_STAMP_CHAIN(a.epoch, 4);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every store (and counter atomic) of this wave has been acknowledged
-        TE_STAMP_CHAIN(a.epoch, 5);
         if (lane == 0) {
             // AFFINE: a plain store, the line stays in this XCD's L2 where the next launch's wave polls it; otherwise written through
             // (`sc1`).  Neither waits for its acknowledgement: the wave ends here.
             if (AFFINE) st_xcd(a.chain + (size_t)wave * CHAIN_STRIDE, a.epoch);
             else st_agent(a.chain + (size_t)wave * CHAIN_STRIDE, a.epoch);
         }
-        TE_STAMP_CHAIN(a.epoch, 6);
     } else if (!(seen & CHAIN_ABANDONED)) {     // (with the bit set an earlier launch's wave gave up and recorded it)
         chain_give_up(a, (uint32_t)wave, lane == 0);          // the games stay as launch E - 1 (or an earlier one) left them
     }
@@ -297,13 +287,9 @@ __device__ __forceinline__ void duo_body(const KArgs& a) {
     const bool active = gi < a.n;
     Geo geo = geo_of(a);
     geo.P = 2;                           // compile-time stride factor for the hot loads
-    const Ref gr = game_ref(geo, (size_t)gi, true);
-#if TE_TILED
-    const Ref br = board_ref(geo, side, (size_t)gi);
-#else
+    const Ref gr = game_ref(geo, (size_t)gi);
     // one UNIFORM row base for both half-waves (it becomes a buffer resource): the player's offset goes into the lane offset
     const Ref br = {geo.state, (uint32_t)((size_t)side * geo.stride + (size_t)gi) * 4u, 2 * geo.stride};
-#endif
     Game<1> g;
     Player& q = g.pl[0];
     uint32_t pd0 = 0, pd1 = 0;
@@ -616,7 +602,7 @@ __global__ __launch_bounds__(ENUM_BLOCK) void k_enumerate(Geo geo, int n, const 
         }
         if (j >= 1 && j < 5) pre[PRE_STRIP + (j - 1)] = 0u;
     }
-    if (ENUM_ONE_WAVE) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); else __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     if (live) {
         int word;
         const uint32_t bits = pre_band_bits(mine, floor_bits, j, word);
@@ -626,7 +612,7 @@ __global__ __launch_bounds__(ENUM_BLOCK) void k_enumerate(Geo geo, int n, const 
         pre[PRE_SUF + j] = pre_and_from(pre + PRE_COL, j);
         if (j == 0) { pre[PRE_PRE + NCOL] = pre_and_below(pre + PRE_COL, NCOL); pre[PRE_SUF + NCOL] = ~0u; }
     }
-    if (ENUM_ONE_WAVE) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); else __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     if (!live) return;
     const ColumnCtx cc = enum_column(pre, j);
     if (PLANAR) {
@@ -1013,14 +999,14 @@ struct tetris_batch {
 };
 
 static Geo geo_of_batch(tetris_batch* b) {
-    Geo g = {b->d_state, b->d_gstate ? b->d_gstate : b->d_state, (size_t)b->N, b->P, b->nw, (size_t)b->stride};
+    Geo g = {b->d_state, b->d_gstate, (size_t)b->N, b->P, b->nw, (size_t)b->stride};
     return g;
 }
 
 static KArgs base_args(tetris_batch* b, int n, const int32_t* d_idx) {
     KArgs a;
     memset(&a, 0, sizeof a);
-    a.state = b->d_state; a.gstate = b->d_gstate ? b->d_gstate : b->d_state; a.status = b->flags;      // (tiled layout: one allocation)
+    a.state = b->d_state; a.gstate = b->d_gstate; a.status = b->flags;
     {   // tables are shared between batches: take pointer and size together (another batch may be growing them)
         std::lock_guard<std::mutex> lock(g_tab_mutex);
         a.table = b->tab->d_table;
@@ -1045,11 +1031,10 @@ static int launch_game(tetris_batch* b, const KArgs& a) {
         }
     }
     // (three and four players per game: the same kernel with all players of a game in one lane; it spills, and nothing is tuned for it)
-    if (b->P == 1 && !b->tint) hipLaunchKernelGGL((k_game<1, MODE, false>), grid, block, 0, b->stream, a);
-    else if (b->P == 1) hipLaunchKernelGGL((k_game<1, MODE, true>), grid, block, 0, b->stream, a);
-    else if (b->P == 2 && !b->tint) hipLaunchKernelGGL((k_game<2, MODE, false>), grid, block, 0, b->stream, a);
-    else if (b->P == 2) hipLaunchKernelGGL((k_game<2, MODE, true>), grid, block, 0, b->stream, a);
-    else if (tetris_launch_game_multi(b->P, b->tint, MODE, grid, block, b->stream, a)) return fail(TETRIS_E_ARG, "no kernel for this player count / mode");
+    const bool here = with_shape<1, 2>(b->P, b->tint != 0, [&](auto P, auto TINT) {
+        hipLaunchKernelGGL((k_game<P(), MODE, TINT()>), grid, block, 0, b->stream, a);
+    });
+    if (!here && tetris_launch_game_multi(b->P, b->tint, MODE, grid, block, b->stream, a)) return fail(TETRIS_E_ARG, "no kernel for this player count / mode");
     HIP_TRY(hipGetLastError());
     return TETRIS_OK;
 }
@@ -1327,18 +1312,6 @@ extern "C" {
 
 const char* tetris_last_error(void) { return g_err.c_str(); }
 
-#if defined(TE_PHASE_TRACE)
-// diagnostic build only: copies the phase stamps out (and clears them)
-extern "C" int tetris_debug_trace(unsigned long long* out, int n_words) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(d_trace), (size_t)n_words * 8) != hipSuccess) return -1;
-    static unsigned long long zero[2048 * 16];
-    return hipMemcpyToSymbol(HIP_SYMBOL(d_trace), zero, sizeof zero) == hipSuccess ? 0 : -1;
-}
-extern "C" int tetris_debug_chain_trace(unsigned long long* out /*[8][1024][8]*/) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(d_chain_trace), sizeof(unsigned long long) * 8 * 1024 * 8) == hipSuccess ? 0 : -1;
-}
-#endif
-
 int tetris_device_count(void) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -1476,13 +1449,13 @@ static int create_impl(tetris_batch** out, int n_games, int n_players, int heigh
     CREATE_TRY(hipEventCreateWithFlags(&b->gate_ev[1], hipEventDisableTiming));
     const size_t state_bytes = state_words((size_t)b->stride, n_players, b->nw) * 4, gstate_bytes = gstate_words((size_t)b->stride) * 4;
     CREATE_TRY(hipMalloc((void**)&b->d_state, state_bytes));
-    if (gstate_bytes) CREATE_TRY(hipMalloc((void**)&b->d_gstate, gstate_bytes));
+    CREATE_TRY(hipMalloc((void**)&b->d_gstate, gstate_bytes));
     CREATE_TRY(hipMalloc((void**)&b->d_counters, 8 * sizeof(unsigned long long)));
     CREATE_TRY(hipHostMalloc((void**)&b->h_counters, 8 * sizeof(unsigned long long), hipHostMallocDefault));
     // flag words: host memory the GPU can write (fine-grained, so a store is visible to the host while the kernel runs)
     CREATE_TRY(hipHostMalloc((void**)&b->flags, NFLAGS * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
     memset(b->flags, 0, NFLAGS * sizeof(uint32_t));
-    if (gstate_bytes) CREATE_TRY(hipMemsetAsync(b->d_gstate, 0, gstate_bytes, b->stream));
+    CREATE_TRY(hipMemsetAsync(b->d_gstate, 0, gstate_bytes, b->stream));
     CREATE_TRY(hipMemsetAsync(b->d_state, 0, state_bytes, b->stream));
     int rc = tables_acquire(&b->tab, device, piece_map, b->stream);
     if (rc) { std::string keep = g_err; tetris_destroy(b); return fail(rc, keep); }
@@ -1660,10 +1633,7 @@ static int split_stage_launch(tetris_batch* b, int stage, KArgs& a, const uint32
     for (int k = 0; k < 4; k++) a.xw[k] = d_words ? d_words[k] : nullptr;
     a.shadow = b->d_shadow; a.xout = d_out; a.split_side = b->side;
     dim3 grid((unsigned)((b->N + 255) / 256)), block(256);
-    if (stage == 0) hipLaunchKernelGGL((k_split<0, false>), grid, block, 0, b->stream, a);
-    else if (stage == 1) hipLaunchKernelGGL((k_split<1, false>), grid, block, 0, b->stream, a);
-    else if (stage == 2) hipLaunchKernelGGL((k_split<2, false>), grid, block, 0, b->stream, a);
-    else hipLaunchKernelGGL((k_split<3, false>), grid, block, 0, b->stream, a);
+    with_value<0, 3>(stage, [&](auto STAGE) { hipLaunchKernelGGL((k_split<STAGE(), false>), grid, block, 0, b->stream, a); });
     HIP_TRY(hipGetLastError());
     return TETRIS_OK;
 }
@@ -1838,10 +1808,7 @@ int tetris_step_rt_observe_dev(tetris_batch* b, const uint8_t* d_rot, const uint
         const size_t lds = ((size_t)SHAPE_WORDS + (size_t)64 * nw) * 4;
     const dim3 grid((unsigned)((b->N + 63) / 64)), block(64);
     const bool autoreset = (flags & TETRIS_STEP_AUTO_RESET) != 0;
-    if (b->P == 1) {
-        if (autoreset) hipLaunchKernelGGL((k_step_observe<1, M_STEP_RT_AUTO>), grid, block, lds, b->stream, a);
-        else hipLaunchKernelGGL((k_step_observe<1, M_STEP_RT>), grid, block, lds, b->stream, a);
-    } else if (b->use_duo) {
+    if (b->P == 2 && b->use_duo) {
         // two players: one player per lane (k_duo) — every lane builds the one board it holds
         const size_t lds2 = ((size_t)4 * 64 * nw + 16) * 4;
         if (lds2 > 48 * 1024) {
@@ -1852,8 +1819,9 @@ int tetris_step_rt_observe_dev(tetris_batch* b, const uint8_t* d_rot, const uint
         if (autoreset) hipLaunchKernelGGL((k_duo<M_STEP_RT_AUTO, false, true>), grid2, block2, lds2, b->stream, a);
         else hipLaunchKernelGGL((k_duo<M_STEP_RT, false, true>), grid2, block2, lds2, b->stream, a);
     } else {
-        if (autoreset) hipLaunchKernelGGL((k_step_observe<2, M_STEP_RT_AUTO>), grid, block, lds, b->stream, a);
-        else hipLaunchKernelGGL((k_step_observe<2, M_STEP_RT>), grid, block, lds, b->stream, a);
+        with_shape<1, 2>(b->P, autoreset, [&](auto P, auto AUTO) {
+            hipLaunchKernelGGL((k_step_observe<P(), AUTO() ? M_STEP_RT_AUTO : M_STEP_RT>), grid, block, lds, b->stream, a);
+        });
     }
     HIP_TRY(hipGetLastError());
     return TETRIS_OK;
@@ -1905,18 +1873,9 @@ int tetris_observe_records(tetris_batch* b, const int32_t* idx, int n, tetris_re
     if ((rc = io.out(round_over, (size_t)n, &d_round_over)) || (rc = io.out(last_winner, (size_t)n, &d_last_winner))) return rc;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
     HIP_TRY(hipMemsetAsync(d_rec, 0, rec_bytes, b->stream));      // struct padding stays deterministic
-#define LAUNCH_OBSERVE(PP, TT)                                                                                              \
-    hipLaunchKernelGGL((k_observe<PP, TT>), grid, block, 0, b->stream, geo_of_batch(b), n, io.d_idx, b->H, d_rec, \
-                       d_round_over, d_last_winner)
-    if (b->P == 1 && !b->tint) LAUNCH_OBSERVE(1, false);
-    else if (b->P == 1) LAUNCH_OBSERVE(1, true);
-    else if (b->P == 2 && !b->tint) LAUNCH_OBSERVE(2, false);
-    else if (b->P == 2) LAUNCH_OBSERVE(2, true);
-    else if (b->P == 3 && !b->tint) LAUNCH_OBSERVE(3, false);
-    else if (b->P == 3) LAUNCH_OBSERVE(3, true);
-    else if (!b->tint) LAUNCH_OBSERVE(4, false);
-    else LAUNCH_OBSERVE(4, true);
-#undef LAUNCH_OBSERVE
+    with_shape<1, 4>(b->P, b->tint != 0, [&](auto P, auto TINT) {
+        hipLaunchKernelGGL((k_observe<P(), TINT()>), grid, block, 0, b->stream, geo_of_batch(b), n, io.d_idx, b->H, d_rec, d_round_over, d_last_winner);
+    });
     HIP_TRY(hipGetLastError());
     return io.finish();
 }
@@ -1937,26 +1896,23 @@ int tetris_observe_packed_dev(tetris_batch* b, const int32_t* d_idx, int n, cons
         const int nw = b->H * NCOL / 4;
         const size_t lds = (size_t)OB * nw * 4;
         dim3 ogrid((unsigned)((n + OB - 1) / OB), (unsigned)b->P), oblock(OB);
-        if (b->P == 1)
-            hipLaunchKernelGGL((k_observe_packed<1, OB>), ogrid, oblock, lds, b->stream, geo_of_batch(b), n, d_idx, d_player, b->H,
+        with_value<1, 2>(b->P, [&](auto P) {
+            hipLaunchKernelGGL((k_observe_packed<P(), OB>), ogrid, oblock, lds, b->stream, geo_of_batch(b), n, d_idx, d_player, b->H,
                                d_visual, d_vector, d_piece);
-        else
-            hipLaunchKernelGGL((k_observe_packed<2, OB>), ogrid, oblock, lds, b->stream, geo_of_batch(b), n, d_idx, d_player, b->H,
-                               d_visual, d_vector, d_piece);
+        });
         HIP_TRY(hipGetLastError());
         return TETRIS_OK;
     }
     const size_t lds = (size_t)256 * b->H * NCOL;             // odd heights (boards are not word-aligned in `visual`): byte tile
     if (lds > 48 * 1024) {      // up to 79 KB of the CU's 160 KB for 31-row boards
-        const void* fn = b->P == 1 ? (const void*)k_observe_packed_bytes<1> : (const void*)k_observe_packed_bytes<2>;
+        const void* fn = nullptr;
+        with_value<1, 2>(b->P, [&](auto P) { fn = (const void*)k_observe_packed_bytes<P()>; });
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
-    if (b->P == 1)
-        hipLaunchKernelGGL(k_observe_packed_bytes<1>, grid, block, lds, b->stream, geo_of_batch(b), n, d_idx, d_player, b->H, d_visual,
+    with_value<1, 2>(b->P, [&](auto P) {
+        hipLaunchKernelGGL(k_observe_packed_bytes<P()>, grid, block, lds, b->stream, geo_of_batch(b), n, d_idx, d_player, b->H, d_visual,
                            d_vector, d_piece);
-    else
-        hipLaunchKernelGGL(k_observe_packed_bytes<2>, grid, block, lds, b->stream, geo_of_batch(b), n, d_idx, d_player, b->H, d_visual,
-                           d_vector, d_piece);
+    });
     HIP_TRY(hipGetLastError());
     return TETRIS_OK;
 }
@@ -2051,13 +2007,9 @@ int tetris_enumerate_drops_dev_ex(tetris_batch* b, const int32_t* d_idx, int n, 
     dim3 grid((unsigned)((n + ENUM_BOARDS - 1) / ENUM_BOARDS)), block(ENUM_BLOCK);
     const Geo geo = geo_of_batch(b);
     const bool planar = (flags & TETRIS_ENUM_PLANAR) != 0;
-#define LAUNCH_ENUM(PP, PL) hipLaunchKernelGGL((k_enumerate<PP, PL>), grid, block, 0, b->stream, geo, n, d_idx, d_player, b->H, d_valid, \
-                                               d_land_y, d_cleared, d_after)
-    if (b->P == 1) { if (planar) LAUNCH_ENUM(1, true); else LAUNCH_ENUM(1, false); }
-    else if (b->P == 2) { if (planar) LAUNCH_ENUM(2, true); else LAUNCH_ENUM(2, false); }
-    else if (b->P == 3) { if (planar) LAUNCH_ENUM(3, true); else LAUNCH_ENUM(3, false); }
-    else { if (planar) LAUNCH_ENUM(4, true); else LAUNCH_ENUM(4, false); }
-#undef LAUNCH_ENUM
+    with_shape<1, 4>(b->P, planar, [&](auto P, auto PLANAR) {
+        hipLaunchKernelGGL((k_enumerate<P(), PLANAR()>), grid, block, 0, b->stream, geo, n, d_idx, d_player, b->H, d_valid, d_land_y, d_cleared, d_after);
+    });
     HIP_TRY(hipGetLastError());
     return TETRIS_OK;
 }
@@ -2106,18 +2058,10 @@ int tetris_get_actions(tetris_batch* b, const int32_t* idx, int n, const uint8_t
             (rc = io.out(nullptr, lanes, &d_cnt, &hc)) || (rc = io.out(nullptr, lanes * L, &d_len, &hl)) ||
             (rc = io.out(nullptr, lanes * L * max_keys, &d_key, &hk))) return rc;
         dim3 grid((unsigned)((lanes + 63) / 64)), block(64);
-        if (b->P == 1)
-            hipLaunchKernelGGL(k_actions<1>, grid, block, 0, b->stream, geo_of_batch(b), m, io.d_idx, d_player, b->H, d_cnt, d_len, d_key,
+        with_value<1, 4>(b->P, [&](auto P) {
+            hipLaunchKernelGGL(k_actions<P()>, grid, block, 0, b->stream, geo_of_batch(b), m, io.d_idx, d_player, b->H, d_cnt, d_len, d_key,
                                PLAN_LANE_LISTS, max_keys, b->flags);
-        else if (b->P == 2)
-            hipLaunchKernelGGL(k_actions<2>, grid, block, 0, b->stream, geo_of_batch(b), m, io.d_idx, d_player, b->H, d_cnt, d_len, d_key,
-                               PLAN_LANE_LISTS, max_keys, b->flags);
-        else if (b->P == 3)
-            hipLaunchKernelGGL(k_actions<3>, grid, block, 0, b->stream, geo_of_batch(b), m, io.d_idx, d_player, b->H, d_cnt, d_len, d_key,
-                               PLAN_LANE_LISTS, max_keys, b->flags);
-        else
-            hipLaunchKernelGGL(k_actions<4>, grid, block, 0, b->stream, geo_of_batch(b), m, io.d_idx, d_player, b->H, d_cnt, d_len, d_key,
-                               PLAN_LANE_LISTS, max_keys, b->flags);
+        });
         if (hipGetLastError() != hipSuccess) return fail(TETRIS_E_HIP, "k_actions launch failed");
         if ((rc = io.finish())) return rc;
         for (int i = 0; i < m; i++) {
@@ -2164,9 +2108,8 @@ static PlanArgs plan_args(tetris_batch* b, const uint8_t* d_player, const int32_
 
 // which: 0 simulate, 1 step, 2 step with auto-reset
 static int launch_plan_kernel(tetris_batch* b, int which, dim3 grid, const PlanArgs& pa, int fin) {
-    if (b->P == 1) { if (b->tint) launch_plan<1, true>(which, grid, b->stream, pa, fin); else launch_plan<1, false>(which, grid, b->stream, pa, fin); }
-    else if (b->P == 2) { if (b->tint) launch_plan<2, true>(which, grid, b->stream, pa, fin); else launch_plan<2, false>(which, grid, b->stream, pa, fin); }
-    else if (tetris_launch_plan_multi(b->P, b->tint, which, grid, b->stream, pa, fin)) return fail(TETRIS_E_ARG, "no planning kernel for this player count");
+    const bool here = with_shape<1, 2>(b->P, b->tint != 0, [&](auto P, auto TINT) { launch_plan<P(), TINT()>(which, grid, b->stream, pa, fin); });
+    if (!here && tetris_launch_plan_multi(b->P, b->tint, which, grid, b->stream, pa, fin)) return fail(TETRIS_E_ARG, "no planning kernel for this player count");
     HIP_TRY(hipGetLastError());
     return TETRIS_OK;
 }
@@ -2206,13 +2149,9 @@ int tetris_action_lists_dev(tetris_batch* b, const uint8_t* d_player, int max_li
         const int32_t* d_idx = b->d_iota + g0;
         const uint8_t* pl = d_player ? d_player + g0 : nullptr;
         const dim3 grid((unsigned)(((size_t)m * 40 + 63) / 64)), block(64);
-#define LAUNCH_ACTIONS(PP) hipLaunchKernelGGL(k_actions<PP>, grid, block, 0, b->stream, geo, m, d_idx, pl, b->H, s_cnt, s_len, s_key, \
-                                              PLAN_LANE_LISTS, KS, b->d_plan_status)
-        if (b->P == 1) LAUNCH_ACTIONS(1);
-        else if (b->P == 2) LAUNCH_ACTIONS(2);
-        else if (b->P == 3) LAUNCH_ACTIONS(3);
-        else LAUNCH_ACTIONS(4);
-#undef LAUNCH_ACTIONS
+        with_value<1, 4>(b->P, [&](auto P) {
+            hipLaunchKernelGGL(k_actions<P()>, grid, block, 0, b->stream, geo, m, d_idx, pl, b->H, s_cnt, s_len, s_key, PLAN_LANE_LISTS, KS, b->d_plan_status);
+        });
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_plan_lists, dim3((unsigned)m), block, 0, b->stream, s_cnt, s_len, s_key, KS, g0, max_lists, max_keys,
                            (flags & TETRIS_LISTS_KEEP_NULL) ? 1 : 0, d_count, d_lens, d_keys, b->flags);
@@ -2792,9 +2731,8 @@ static int launch_policy_scores(tetris_batch* b, const PolicyArgs& pa) {
 // which: as launch_policy_step (tetris_game_kernel.h)
 static int launch_policy_step_kernel(tetris_batch* b, int which, const PolicyArgs& pa) {
     const dim3 grid((unsigned)((b->N + 63) / 64));
-    if (b->P == 1) { if (b->tint) launch_policy_step<1, true>(which, grid, b->stream, pa); else launch_policy_step<1, false>(which, grid, b->stream, pa); }
-    else if (b->P == 2) { if (b->tint) launch_policy_step<2, true>(which, grid, b->stream, pa); else launch_policy_step<2, false>(which, grid, b->stream, pa); }
-    else if (tetris_launch_policy_multi(b->P, b->tint, which, grid, b->stream, pa)) return fail(TETRIS_E_ARG, "no policy kernel for this player count");
+    const bool here = with_shape<1, 2>(b->P, b->tint != 0, [&](auto P, auto TINT) { launch_policy_step<P(), TINT()>(which, grid, b->stream, pa); });
+    if (!here && tetris_launch_policy_multi(b->P, b->tint, which, grid, b->stream, pa)) return fail(TETRIS_E_ARG, "no policy kernel for this player count");
     HIP_TRY(hipGetLastError());
     return TETRIS_OK;
 }

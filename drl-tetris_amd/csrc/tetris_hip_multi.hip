@@ -16,19 +16,15 @@ static int launch_mode(int mode, dim3 grid, dim3 block, hipStream_t st, const KA
 }
 
 __attribute__((visibility("hidden"))) int tetris_launch_game_multi(int n_players, int tint, int mode, dim3 grid, dim3 block, hipStream_t st, const KArgs& a) {
-    if (n_players == 3) return tint ? launch_mode<3, true>(mode, grid, block, st, a) : launch_mode<3, false>(mode, grid, block, st, a);
-    if (n_players == 4) return tint ? launch_mode<4, true>(mode, grid, block, st, a) : launch_mode<4, false>(mode, grid, block, st, a);
-    return -1;
+    int rc = -1;
+    with_shape<3, 4>(n_players, tint != 0, [&](auto P, auto TINT) { rc = launch_mode<P(), TINT()>(mode, grid, block, st, a); });
+    return rc;
 }
 
 __attribute__((visibility("hidden"))) int tetris_launch_plan_multi(int n_players, int tint, int which, dim3 grid, hipStream_t st, const PlanArgs& pa, int fin) {
-    if (n_players == 3) { if (tint) launch_plan<3, true>(which, grid, st, pa, fin); else launch_plan<3, false>(which, grid, st, pa, fin); return 0; }
-    if (n_players == 4) { if (tint) launch_plan<4, true>(which, grid, st, pa, fin); else launch_plan<4, false>(which, grid, st, pa, fin); return 0; }
-    return -1;
+    return with_shape<3, 4>(n_players, tint != 0, [&](auto P, auto TINT) { launch_plan<P(), TINT()>(which, grid, st, pa, fin); }) ? 0 : -1;
 }
 
 __attribute__((visibility("hidden"))) int tetris_launch_policy_multi(int n_players, int tint, int which, dim3 grid, hipStream_t st, const PolicyArgs& pa) {
-    if (n_players == 3) { if (tint) launch_policy_step<3, true>(which, grid, st, pa); else launch_policy_step<3, false>(which, grid, st, pa); return 0; }
-    if (n_players == 4) { if (tint) launch_policy_step<4, true>(which, grid, st, pa); else launch_policy_step<4, false>(which, grid, st, pa); return 0; }
-    return -1;
+    return with_shape<3, 4>(n_players, tint != 0, [&](auto P, auto TINT) { launch_policy_step<P(), TINT()>(which, grid, st, pa); }) ? 0 : -1;
 }

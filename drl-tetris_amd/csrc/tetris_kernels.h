@@ -109,13 +109,8 @@ constexpr uint32_t CHAIN_EPOCH_MAX = 0x7FFF0000u;    // the host restarts the ep
 // one line) every publication hit a line that 31 other waves were polling: GPU-paced 4.72 us per launch against 4.50 with one
 // line each at the same poll interval, and with the lines private a SHORT poll interval pays (s_sleep 32: 4.50, 8: 4.24,
 // 0-2: 4.13-4.15 us; packed it had been the other way round: profiles/r02/chain_sleep_ab.txt, chain_stride_ab.txt).
-#ifndef TE_CHAIN_STRIDE
-#define TE_CHAIN_STRIDE 32
-#endif
-constexpr int CHAIN_STRIDE = TE_CHAIN_STRIDE;
-#ifndef TE_CHAIN_SLEEP
-#define TE_CHAIN_SLEEP 1            // s_sleep between two polls of the epoch word (x 64 cycles)
-#endif
+constexpr int CHAIN_STRIDE = 32;
+constexpr int CHAIN_SLEEP = 1;       // s_sleep between two polls of the epoch word (x 64 cycles)
 constexpr uint32_t CHAIN_SPIN_LIMIT = 1u << 22;     // default polls before a wave gives up (each ~0.5 us: an agent-scope load + a short sleep): ~2 s
 
 // Scoped accesses of the chained kernels' hand-off (vector memory instructions on the global aperture, no wait behind them).
@@ -156,7 +151,7 @@ TE_HD uint32_t chain_poll(const KArgs& a, uint32_t wave) {
         // wave learns it from the flag word within ~0.1 ms instead of waiting out its bound
         if ((polls & 255u) == 0 && wave_uniform(ld_flag(a.status + F_PLACE)) != 0) break;
 #if defined(__HIP_DEVICE_COMPILE__)
-        __builtin_amdgcn_s_sleep(TE_CHAIN_SLEEP);
+        __builtin_amdgcn_s_sleep(CHAIN_SLEEP);
 #endif
         v = (uint32_t)wave_uniform(ld_agent(word));
     }
@@ -248,20 +243,16 @@ TE_HD void make_rt(const Ctx& cx, Game<P>& g, int player, int r, int t) {
 // kernel runs this BEFORE its table-init barrier and both memory round-trips overlap).
 // SURVEY.md §8(d) synthetic policy: words 0 and 1 of Philox4x32-10 keyed by (policy_seed, global game id, step)
 TE_HD void policy_draw(const KArgs& a, uint32_t slot, unsigned long long step, uint32_t& w0, uint32_t& w1) {
-#if defined(TE_ABLATE) && (TE_ABLATE & 1)
-    w0 = slot + (uint32_t)step; w1 = slot * 7u + (uint32_t)step;      // diagnostic build: no Philox
-#else
     uint32_t w[4];
     philox4x32_10(a.policy_seed, a.game_offset + slot, (uint32_t)step, (uint32_t)(step >> 32), w);
     w0 = w[0]; w1 = w[1];
-#endif
 }
 
 template <int P, int MODE, bool TINT = false, int MEM = MEM_STREAM>
 TE_HD void game_load(const KArgs& a, int i, Game<P>& g) {
     const size_t slot = a.idx ? (size_t)a.idx[i] : (size_t)i;
     if (MODE != M_INIT && MODE != M_SPLIT_INIT)
-        load_game<P>(geo_of(a), slot, g, TINT, P > 1 || MODE == M_SPLIT_RESET, MODE == M_ROLLOUT, MEM, !a.idx);   // split batches: 1-player layout WITH a queue
+        load_game<P>(geo_of(a), slot, g, TINT, P > 1 || MODE == M_SPLIT_RESET, MODE == M_ROLLOUT, MEM);   // split batches: 1-player layout WITH a queue
     // the first step's draw depends on kernel arguments only: its 40 dependent multiplies run while the state loads are in flight
     if (MODE == M_ROLLOUT) policy_draw(a, (uint32_t)slot, a.first_step, g.draw0, g.draw1);
     // (r, t) actions: the three action bytes are requested together with the state, not after it has arrived
@@ -320,14 +311,11 @@ TE_HD void game_run(const KArgs& a, int i, const uint32_t* shapes, Game<P>& g, L
             prefetch_reset(cx, episode_seed(a.game_offset + (uint32_t)slot, g.episode + 1), rpf);
             int r = (int)(g.draw0 & 3u), t = (int)(g.draw1 % 10u);
             int player = P > 1 ? (int)(step % (unsigned long long)P) : 0;
-            TE_STAMP(4);
             uint32_t sent_before = 0;
             TE_UNROLL
             for (int p = 0; p < P; p++) sent_before += g.pl[p].lines_sent;
             make_rt<P>(cx, g, player, r, t);
-            TE_STAMP(5);
             int done = finish_game<P>(cx, g, a.ms);
-            TE_STAMP(7);
             cnt.steps++;
             g.steps++;
             uint32_t sent_after = 0;
@@ -338,20 +326,16 @@ TE_HD void game_run(const KArgs& a, int i, const uint32_t* shapes, Game<P>& g, L
             }
             cnt.sent += (sent_after - sent_before) & 0xFFFFu;
             g.add_sent += (sent_after - sent_before) & 0xFFFFu;
-#if defined(TE_ABLATE) && (TE_ABLATE & 16)
-            done = 0;                                // diagnostic build: no auto-reset
-#endif
             if (done) {
                 cnt.episodes++;
                 g.episode++;
                 reset_game<P>(cx, g, episode_seed(a.game_offset + (uint32_t)slot, g.episode), &rpf);
             }
             if (s + 1 < a.steps) policy_draw(a, (uint32_t)slot, step + 1, g.draw0, g.draw1);
-            TE_STAMP(8);
         }
     }
     store_game<P>(geo_of(a), slot, g, TINT, P > 1 || MODE == M_SPLIT_INIT || MODE == M_SPLIT_RESET,
-                  MODE == M_ROLLOUT || MODE == M_INIT || MODE == M_SPLIT_INIT, MEM, !a.idx);   // 1-player: FIFO words stay as zeroed at creation
+                  MODE == M_ROLLOUT || MODE == M_INIT || MODE == M_SPLIT_INIT, MEM);   // 1-player: FIFO words stay as zeroed at creation
     report_status(a, g.status);
 }
 
@@ -574,14 +558,10 @@ TE_HD int observe_board(const Geo& geo, size_t slot, int p, int H, uint8_t* cell
 //             pre[x] & suf[x + 4] & (the four columns under the piece | its cells) — no pass over all ten columns
 // A placement lane then needs ~10 LDS reads and no loop over the board.
 constexpr int PRE_COL = 0, PRE_PIECE = 10, PRE_BAND = 11, PRE_STRIP = 13, PRE_PRE = 17, PRE_SUF = 28, PRE_WORDS = 40;
-#ifndef TE_ENUM_BOARDS
-#define TE_ENUM_BOARDS 6
-#endif
 // boards / threads per workgroup of k_enumerate (10 lanes per board).  6 boards = one WAVE per workgroup (60 working lanes, 4 idle):
 // the two phases of the per-board precompute are ordered within the wave and need no workgroup barrier — 7.65 -> 7.25 us on
 // C4's 16 384 boards against 32 boards (five waves, two __syncthreads) per workgroup, same box
-constexpr int ENUM_BOARDS = TE_ENUM_BOARDS, ENUM_BLOCK = ENUM_BOARDS == 6 ? 64 : ENUM_BOARDS * 10;
-constexpr bool ENUM_ONE_WAVE = ENUM_BOARDS == 6;
+constexpr int ENUM_BOARDS = 6, ENUM_BLOCK = 64;
 
 // element functions of the per-board precompute (lane j of a board calls the ones its index selects)
 TE_HD uint32_t pre_band_bits(uint32_t col, uint32_t floor_bits, int c, int& word) {      // nibble c+2 of the 64-bit band

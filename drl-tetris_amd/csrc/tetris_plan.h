@@ -152,14 +152,15 @@ TE_HD const uint8_t* plan_list(const PlanArgs& pa, int i, int k, int& len) {
 // simulate_actions(lists, player, finalize) (tetris_environment.py:87-100) of list k of game i, on a register copy of the
 // game: loads as game_load does, runs make_keys (and with `fin`, finish_game as M_STEP_KEYS does), stores the columns of
 // every player to cols[k][p][c][i] and, with `fin`, done[k][i] / lines[k][p][i] / dead[k][p][i].  Nothing of the batch's
-// state is written.  `uniform`: the 64 lanes of the calling wave hold 64 consecutive games of one k.
+// state is written.  The trailing bool of the *_lane functions (do the wave's lanes hold consecutive games?) is unused since the
+// tiles layout went; it stays because the CPU harness under tests/ passes it.
 template <int P, bool TINT>
-TE_HD void plan_sim_lane(const PlanArgs& pa, int i, int k, bool fin, const uint32_t* shapes, bool uniform) {
+TE_HD void plan_sim_lane(const PlanArgs& pa, int i, int k, bool fin, const uint32_t* shapes, bool /*consecutive*/) {
     const KArgs& a = pa.a;
     const int c = pa.count[i];
     if (k >= c) return;                                    // (count -1: nothing)
     Game<P> g;
-    load_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, false, MEM_STREAM, uniform);
+    load_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, false);
     const Ctx cx = make_ctx(a, shapes, TINT, P > 1);
     const int player = safe_player(pa.player, i, P);
     if (fin) {
@@ -190,10 +191,10 @@ TE_HD void plan_sim_lane(const PlanArgs& pa, int i, int k, bool fin, const uint3
 // include/tetris_hip.h); done / lines / dead describe the step before the reset.  choice is clamped into [0, count - 1]; a
 // game whose lists did not fit (count < 1) performs the null action.
 template <int P, bool TINT, bool AUTO>
-TE_HD void plan_step_lane(const PlanArgs& pa, int i, const uint32_t* shapes, bool uniform) {
+TE_HD void plan_step_lane(const PlanArgs& pa, int i, const uint32_t* shapes, bool /*consecutive*/) {
     const KArgs& a = pa.a;
     Game<P> g;
-    load_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, false, MEM_STREAM, uniform);
+    load_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, false);
     const Ctx cx = make_ctx(a, shapes, TINT, P > 1);
     TE_UNROLL
     for (int p = 0; p < P; p++) prefetch_next(cx, g.pl[p], g.seed16, g.status);
@@ -212,7 +213,7 @@ TE_HD void plan_step_lane(const PlanArgs& pa, int i, const uint32_t* shapes, boo
         g.episode++;
         reset_game<P>(cx, g, episode_seed(a.game_offset + (uint32_t)i, g.episode), &rpf);
     }
-    store_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, false, MEM_STREAM, uniform);
+    store_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, false);
     report_status(a, g.status);
 }
 

@@ -221,10 +221,10 @@ TE_HD void policy_pick_lane(const PolicyArgs& pa, int i) {
 // auto-reset) with the policy's choice in place of the Philox draw.  FROM_SCORES: the choice is the maximum of scores[..][i]
 // (spread mapping; one step per launch); otherwise the lane evaluates its candidates itself.
 template <int P, bool TINT, bool ROLL, bool AUTO, bool FROM_SCORES>
-TE_HD void policy_step_lane(const PolicyArgs& pa, int i, const uint32_t* shapes, bool uniform) {
+TE_HD void policy_step_lane(const PolicyArgs& pa, int i, const uint32_t* shapes, bool /*consecutive: unused, see plan_sim_lane*/) {
     const KArgs& a = pa.a;
     Game<P> g;
-    load_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, ROLL, MEM_STREAM, uniform);
+    load_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, ROLL);
     const Ctx cx = make_ctx(a, shapes, TINT, P > 1);
     int w[POLICY_FEATURES];
     if (!FROM_SCORES) policy_weights(pa, i, w);
@@ -261,7 +261,7 @@ TE_HD void policy_step_lane(const PolicyArgs& pa, int i, const uint32_t* shapes,
             reset_game<P>(cx, g, episode_seed(a.game_offset + (uint32_t)i, g.episode), &rpf);
         }
     }
-    store_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, ROLL, MEM_STREAM, uniform);
+    store_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, ROLL);
     report_status(a, g.status);
 }
 
