@@ -59,7 +59,7 @@ struct Device {                        // one per HIP device of the process, mad
     hsa_amd_memory_pool_t dev_pool{};
     uint64_t ts_freq = 0;
     std::vector<hsa_executable_t> exes;
-    Kernel chain1, chain1_affine, duo, duo_affine, blocker, xcc_probe;
+    Kernel chain1, chain1_affine, chain1_fused, chain1_fused_affine, duo, duo_affine, blocker, xcc_probe;
     std::vector<std::vector<char>> images;   // the code objects' bytes: the loader (and a profiler's code-object tracking) keep reading them
     Queues qs;
     std::string why;                   // why it is not ok
@@ -109,6 +109,8 @@ static hsa_status_t on_symbol(hsa_executable_t, hsa_agent_t, hsa_executable_symb
     Kernel* k = nullptr;
     // k_chain<1>(te::KArgs) and k_duo<M_ROLLOUT = 6, true, false>(te::KArgs), Itanium-mangled, with the descriptor suffix
     if (name.rfind("_Z7k_chainILi1EEvN2te5KArgsE", 0) == 0) k = &d->chain1;
+    else if (name.rfind("_Z13k_chain_fusedILi1EEvN2te5KArgsE", 0) == 0) k = &d->chain1_fused;
+    else if (name.rfind("_Z20k_chain_fused_affineILi1EEvN2te5KArgsE", 0) == 0) k = &d->chain1_fused_affine;
     else if (name.rfind("_Z5k_duoILi6ELb1ELb0EEvN2te5KArgsE", 0) == 0) k = &d->duo;
     else if (name.rfind("_Z9k_blockerPKjy", 0) == 0) k = &d->blocker;            // (test aid: tetris_debug_stall)
     else if (name.rfind("_Z14k_chain_affineILi1EEvN2te5KArgsE", 0) == 0) k = &d->chain1_affine;
@@ -205,10 +207,11 @@ static Device* device_for(int hip_device) {
         SymCtx sc{d};
         (void)hsa_executable_iterate_agent_symbols(exe, d->gpu, on_symbol, &sc);
     }
-    if (!d->chain1.ok || !d->duo.ok) return bad("the chained kernels were not found in the loaded code objects");
-    if (d->chain1.priv || d->duo.priv) return bad("the chained kernels use scratch memory");
+    if (!d->chain1.ok || !d->chain1_fused.ok || !d->duo.ok) return bad("the chained kernels were not found in the loaded code objects");
+    if (d->chain1.priv || d->chain1_fused.priv || d->duo.priv) return bad("the chained kernels use scratch memory");
     const uint32_t explicit_bytes = (uint32_t)((sizeof(KArgs) + 7) & ~(size_t)7);
-    if (d->chain1.kernarg < explicit_bytes || d->duo.kernarg < explicit_bytes || d->chain1.kernarg > 1024 || d->duo.kernarg > 1024)
+    if (d->chain1.kernarg < explicit_bytes || d->duo.kernarg < explicit_bytes || d->chain1.kernarg > 1024 || d->duo.kernarg > 1024 ||
+        d->chain1_fused.kernarg != d->chain1.kernarg)
         return bad("unexpected kernel-argument segment size");
     d->ok = true;
     return d;

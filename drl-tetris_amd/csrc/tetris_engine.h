@@ -84,27 +84,40 @@ TE_HD __amdgpu_buffer_rsrc_t te_rsrc(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, -1, 0x00020000);
 }
 constexpr int TE_AUX_NT = 2, TE_AUX_SC1 = 16;     // cache-policy bits of the buffer instructions on gfx940+
-TE_HD uint32_t ldw(const uint32_t* base, uint32_t o, size_t word_off, int mem = MEM_STREAM) {
+// (ldw_b / stw_b: the row offset in BYTES, as the instruction takes it)
+TE_HD uint32_t ldw_b(const uint32_t* base, uint32_t o, size_t row_bytes, int mem = MEM_STREAM) {
     const __amdgpu_buffer_rsrc_t r = te_rsrc(base);
-    if (mem == MEM_AGENT || mem == MEM_AFFINE) return __builtin_amdgcn_raw_buffer_load_b32(r, (int)o, (int)(uint32_t)(word_off * 4u), TE_AUX_SC1);
-    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)o, (int)(uint32_t)(word_off * 4u), TE_AUX_NT);
+    if (mem == MEM_AGENT || mem == MEM_AFFINE) return __builtin_amdgcn_raw_buffer_load_b32(r, (int)o, (int)(uint32_t)row_bytes, TE_AUX_SC1);
+    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)o, (int)(uint32_t)row_bytes, TE_AUX_NT);
 }
-TE_HD void stw(uint32_t* base, uint32_t o, size_t word_off, uint32_t v, int mem = MEM_STREAM) {
+TE_HD void stw_b(uint32_t* base, uint32_t o, size_t row_bytes, uint32_t v, int mem = MEM_STREAM) {
     const __amdgpu_buffer_rsrc_t r = te_rsrc(base);
-    if (mem == MEM_AGENT) __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)o, (int)(uint32_t)(word_off * 4u), TE_AUX_SC1);
-    else if (mem == MEM_AFFINE) __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)o, (int)(uint32_t)(word_off * 4u), 0);
-    else __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)o, (int)(uint32_t)(word_off * 4u), TE_AUX_NT);
+    if (mem == MEM_AGENT) __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)o, (int)(uint32_t)row_bytes, TE_AUX_SC1);
+    else if (mem == MEM_AFFINE) __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)o, (int)(uint32_t)row_bytes, 0);
+    else __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)o, (int)(uint32_t)row_bytes, TE_AUX_NT);
 }
 #else
-TE_HD uint32_t ldw(const uint32_t* base, uint32_t o, size_t word_off, int mem = MEM_STREAM) {
-    const uint32_t* p = (const uint32_t*)((const char*)(base + word_off) + o);
+TE_HD uint32_t ldw_b(const uint32_t* base, uint32_t o, size_t row_bytes, int mem = MEM_STREAM) {
+    const uint32_t* p = (const uint32_t*)((const char*)base + row_bytes + o);
     return mem != MEM_STREAM ? ld_agent(p) : ld_stream(p);
 }
-TE_HD void stw(uint32_t* base, uint32_t o, size_t word_off, uint32_t v, int mem = MEM_STREAM) {
-    uint32_t* p = (uint32_t*)((char*)(base + word_off) + o);
+TE_HD void stw_b(uint32_t* base, uint32_t o, size_t row_bytes, uint32_t v, int mem = MEM_STREAM) {
+    uint32_t* p = (uint32_t*)((char*)base + row_bytes + o);
     if (mem != MEM_STREAM) st_agent(p, v); else st_stream(p, v);
 }
 #endif
+TE_HD uint32_t ldw(const uint32_t* base, uint32_t o, size_t word_off, int mem = MEM_STREAM) { return ldw_b(base, o, word_off * 4u, mem); }
+TE_HD void stw(uint32_t* base, uint32_t o, size_t word_off, uint32_t v, int mem = MEM_STREAM) { stw_b(base, o, word_off * 4u, v, mem); }
+// Where word w of a board (or of the game words) lies, as a byte offset from the board's base: the load / store functions below
+// take it from a ROWS object.  RowStride multiplies it out at the access, one scalar multiply each (the default, what
+// load_player(s, o, ws, ...) and its like do).  RowTable holds offsets that were computed beforehand: the single-step chained kernels
+// (tetris_hip.hip: chain_body) fill one before they poll, so that neither the loads nor the stores of the step wait for a multiply.
+struct RowStride { size_t ws; };
+template <int N>
+struct RowTable { uint32_t bytes[N]; };
+TE_HD size_t row_bytes(const RowStride& r, int w) { return (size_t)w * r.ws * 4u; }
+template <int N>
+TE_HD size_t row_bytes(const RowTable<N>& r, int w) { return r.bytes[w]; }
 #if defined(__HIP_DEVICE_COMPILE__)
 TE_HD void add_word(uint32_t* p, uint32_t v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #else
@@ -238,130 +251,161 @@ struct Game {
 // ---------------------------------------------------------------- load / store (SoA, coalesced)
 // state[(w * P + p) * n + slot]; game words at gstate[w * n + slot]
 // one player-board: word w of this board lives at s[w * ws]
-TE_HD void load_player(const uint32_t* s, uint32_t o, size_t ws, Player& q, bool tint, bool queue = true, int mem = MEM_STREAM) {
-    for (int c = 0; c < NCOL; c++) q.col[c] = ldw(s, o, (size_t)(W_COL0 + c) * ws, mem);
+template <class ROWS>
+TE_HD void load_player_rows(const uint32_t* s, uint32_t o, const ROWS& rows, Player& q, bool tint, bool queue = true, int mem = MEM_STREAM) {
+    for (int c = 0; c < NCOL; c++) q.col[c] = ldw_b(s, o, row_bytes(rows, W_COL0 + c), mem);
     if (tint)
         for (int k = 0; k < 3; k++)
-            for (int c = 0; c < NCOL; c++) q.tint[k][c] = ldw(s, o, (size_t)(W_TINT0 + 10 * k + c) * ws, mem);
-    uint32_t w = ldw(s, o, (size_t)W_PIECE * ws, mem);
+            for (int c = 0; c < NCOL; c++) q.tint[k][c] = ldw_b(s, o, row_bytes(rows, W_TINT0 + 10 * k + c), mem);
+    uint32_t w = ldw_b(s, o, row_bytes(rows, W_PIECE), mem);
     q.kind = w & 7; q.rot = (w >> 3) & 3; q.x = (int)((w >> 5) & 15) - 4; q.y = (w >> 9) & 31;
     q.next = (w >> 14) & 7; q.dead = (w >> 17) & 1; q.lock_armed = (w >> 18) & 1; q.reward = (w >> 19) & 255;
-    w = ldw(s, o, (size_t)W_MISC * ws, mem);
+    w = ldw_b(s, o, row_bytes(rows, W_MISC), mem);
     q.inc_count = w & 255; q.combo_count = (w >> 8) & 255; q.line_count = (w >> 16) & 255;
     q.qlen = (w >> 24) & 15; q.q_overflow = (w >> 28) & 3;
     if (!queue) { q.inc_count = 0; q.qlen = 0; q.q_overflow = 0; }      // invariants of a game without opponents
-    q.time_ms = (int32_t)ldw(s, o, (size_t)W_TIME * ws, mem);
-    w = ldw(s, o, (size_t)W_DROPCOMBO * ws, mem);
+    q.time_ms = (int32_t)ldw_b(s, o, row_bytes(rows, W_TIME), mem);
+    w = ldw_b(s, o, row_bytes(rows, W_DROPCOMBO), mem);
     q.drop_delay = w & 0xFFFF; q.combo_remaining = w >> 16;
-    q.drop_time = (int32_t)ldw(s, o, (size_t)W_DROP_TIME * ws, mem);
-    q.speedup_time = (int32_t)ldw(s, o, (size_t)W_SPEEDUP_TIME * ws, mem);
-    q.lock_time = (int32_t)ldw(s, o, (size_t)W_LOCK_TIME * ws, mem);
-    q.combo_start = (int32_t)ldw(s, o, (size_t)W_COMBO_START * ws, mem);
-    q.combo_time = (int32_t)ldw(s, o, (size_t)W_COMBO_TIME * ws, mem);
+    q.drop_time = (int32_t)ldw_b(s, o, row_bytes(rows, W_DROP_TIME), mem);
+    q.speedup_time = (int32_t)ldw_b(s, o, row_bytes(rows, W_SPEEDUP_TIME), mem);
+    q.lock_time = (int32_t)ldw_b(s, o, row_bytes(rows, W_LOCK_TIME), mem);
+    q.combo_start = (int32_t)ldw_b(s, o, row_bytes(rows, W_COMBO_START), mem);
+    q.combo_time = (int32_t)ldw_b(s, o, row_bytes(rows, W_COMBO_TIME), mem);
     // nobody can send garbage to a single player: incoming lines, hole draws and the queue timer never leave their
     // reset values (0, 0, 1000), so 1-player kernels neither load nor (for the two zeros) store these words
-    q.incoming = queue ? u2f(ldw(s, o, (size_t)W_INCOMING * ws, mem)) : 0.0f;
-    q.min_remaining = queue ? (int32_t)ldw(s, o, (size_t)W_MIN_REMAINING * ws, mem) : 1000;
-    q.piece_draws = ldw(s, o, (size_t)W_PIECE_DRAWS * ws, mem);
-    q.hole_draws = queue ? ldw(s, o, (size_t)W_HOLE_DRAWS * ws, mem) : 0u;
-    q.pgroup = ldw(s, o, (size_t)W_PIECE_GROUP * ws, mem);
-    w = ldw(s, o, (size_t)W_STATS0 * ws, mem); q.lines_sent = w & 0xFFFF; q.lines_cleared = w >> 16;
-    w = ldw(s, o, (size_t)W_STATS1 * ws, mem); q.lines_blocked = w & 0xFFFF; q.max_combo = w >> 16;
-    w = ldw(s, o, (size_t)W_STATS2 * ws, mem); q.lines_seen = w & 0xFFFF; q.garbage_cleared = w >> 16;
+    q.incoming = queue ? u2f(ldw_b(s, o, row_bytes(rows, W_INCOMING), mem)) : 0.0f;
+    q.min_remaining = queue ? (int32_t)ldw_b(s, o, row_bytes(rows, W_MIN_REMAINING), mem) : 1000;
+    q.piece_draws = ldw_b(s, o, row_bytes(rows, W_PIECE_DRAWS), mem);
+    q.hole_draws = queue ? ldw_b(s, o, row_bytes(rows, W_HOLE_DRAWS), mem) : 0u;
+    q.pgroup = ldw_b(s, o, row_bytes(rows, W_PIECE_GROUP), mem);
+    w = ldw_b(s, o, row_bytes(rows, W_STATS0), mem); q.lines_sent = w & 0xFFFF; q.lines_cleared = w >> 16;
+    w = ldw_b(s, o, row_bytes(rows, W_STATS1), mem); q.lines_blocked = w & 0xFFFF; q.max_combo = w >> 16;
+    w = ldw_b(s, o, row_bytes(rows, W_STATS2), mem); q.lines_seen = w & 0xFFFF; q.garbage_cleared = w >> 16;
     q.q_loaded = queue && q.qlen > 0;
     q.pf_ok = 0; q.pf_raw.lo = 0; q.pf_raw.hi = 0;
     if (queue)
         for (int i = 0; i < FIFO_CAP; i++) { q.qcount[i] = 0; q.qdelay[i] = 0; }
     if (q.q_loaded) {
         for (int i = 0; i < FIFO_CAP / 2; i++) {
-            uint32_t cw = ldw(s, o, (size_t)(W_FIFO_COUNT0 + i) * ws, mem);
+            uint32_t cw = ldw_b(s, o, row_bytes(rows, W_FIFO_COUNT0 + i), mem);
             q.qcount[2 * i] = (int16_t)(cw & 0xFFFF);
             q.qcount[2 * i + 1] = (int16_t)(cw >> 16);
         }
-        for (int i = 0; i < FIFO_CAP; i++) q.qdelay[i] = (int32_t)ldw(s, o, (size_t)(W_FIFO_DELAY0 + i) * ws, mem);
+        for (int i = 0; i < FIFO_CAP; i++) q.qdelay[i] = (int32_t)ldw_b(s, o, row_bytes(rows, W_FIFO_DELAY0 + i), mem);
     }
 }
 
+TE_HD void load_player(const uint32_t* s, uint32_t o, size_t ws, Player& q, bool tint, bool queue = true, int mem = MEM_STREAM) {
+    load_player_rows(s, o, RowStride{ws}, q, tint, queue, mem);
+}
+
 // the per-game words; `counters`: also G_STEPS (the built-in rollout)
-template <int P>
-TE_HD void load_game_words(const Ref& gr, Game<P>& g, bool counters = false, int mem = MEM_STREAM) {
-    uint32_t meta = ldw(gr.s, gr.o, (size_t)G_META * gr.ws, mem);
+template <int P, class ROWS>
+TE_HD void load_game_words_rows(const Ref& gr, const ROWS& rows, Game<P>& g, bool counters = false, int mem = MEM_STREAM) {
+    uint32_t meta = ldw_b(gr.s, gr.o, row_bytes(rows, G_META), mem);
     g.seed16 = meta & 0xFFFFu;
     g.round_over = (meta >> 16) & 1;
     g.last_winner = (int)((meta >> 17) & 0xF) - 1;
     g.flags = (meta >> 21) & 7u;
-    g.episode = ldw(gr.s, gr.o, (size_t)G_EPISODE * gr.ws, mem);
-    g.steps = counters ? ldw(gr.s, gr.o, (size_t)G_STEPS * gr.ws, mem) : 0u;
+    g.episode = ldw_b(gr.s, gr.o, row_bytes(rows, G_EPISODE), mem);
+    g.steps = counters ? ldw_b(gr.s, gr.o, row_bytes(rows, G_STEPS), mem) : 0u;
     g.add_lines = 0; g.add_sent = 0;
     g.status = 0;
 }
 
 template <int P>
-TE_HD void load_game(const Geo& geo_in, size_t slot, Game<P>& g, bool tint = false, bool queue = true, bool counters = false, int mem = MEM_STREAM) {
+TE_HD void load_game_words(const Ref& gr, Game<P>& g, bool counters = false, int mem = MEM_STREAM) {
+    load_game_words_rows<P>(gr, RowStride{gr.ws}, g, counters, mem);
+}
+
+// (`rows`, `grows`: where the words of a board / the game words lie — see RowStride)
+template <int P, class ROWS, class GROWS>
+TE_HD void load_game_rows(const Geo& geo_in, size_t slot, const ROWS& rows, const GROWS& grows, Game<P>& g, bool tint = false, bool queue = true,
+                          bool counters = false, int mem = MEM_STREAM) {
     Geo geo = geo_in;
     geo.P = P;                           // compile-time stride factor for the hot loads
-    load_game_words<P>(game_ref(geo, slot), g, counters, mem);
+    load_game_words_rows<P>(game_ref(geo, slot), grows, g, counters, mem);
     TE_UNROLL
     for (int p = 0; p < P; p++) {
         const Ref r = board_ref(geo, p, slot);
-        load_player(r.s, r.o, r.ws, g.pl[p], tint, queue, mem);
+        load_player_rows(r.s, r.o, rows, g.pl[p], tint, queue, mem);
+    }
+}
+template <int P>
+TE_HD void load_game(const Geo& geo_in, size_t slot, Game<P>& g, bool tint = false, bool queue = true, bool counters = false, int mem = MEM_STREAM) {
+    load_game_rows<P>(geo_in, slot, RowStride{(size_t)P * geo_in.stride}, RowStride{geo_in.stride}, g, tint, queue, counters, mem);
+}
+
+template <class ROWS>
+TE_HD void store_player_rows(uint32_t* s, uint32_t o, const ROWS& rows, const Player& q, bool tint, bool queue = true, int mem = MEM_STREAM) {
+    for (int c = 0; c < NCOL; c++) stw_b(s, o, row_bytes(rows, W_COL0 + c), q.col[c], mem);
+    if (tint)
+        for (int k = 0; k < 3; k++)
+            for (int c = 0; c < NCOL; c++) stw_b(s, o, row_bytes(rows, W_TINT0 + 10 * k + c), q.tint[k][c], mem);
+    stw_b(s, o, row_bytes(rows, W_PIECE), (uint32_t)q.kind | ((uint32_t)q.rot << 3) | ((uint32_t)(q.x + 4) << 5) | ((uint32_t)q.y << 9) |
+                              ((uint32_t)q.next << 14) | ((uint32_t)q.dead << 17) | ((uint32_t)q.lock_armed << 18) |
+                              ((uint32_t)(q.reward & 255) << 19), mem);
+    stw_b(s, o, row_bytes(rows, W_MISC), (uint32_t)(q.inc_count & 255) | ((uint32_t)(q.combo_count & 255) << 8) |
+                             ((uint32_t)(q.line_count & 255) << 16) | ((uint32_t)q.qlen << 24) | ((uint32_t)q.q_overflow << 28), mem);
+    stw_b(s, o, row_bytes(rows, W_TIME), (uint32_t)q.time_ms, mem);
+    stw_b(s, o, row_bytes(rows, W_DROPCOMBO), ((uint32_t)q.drop_delay & 0xFFFF) | (q.combo_remaining << 16), mem);
+    stw_b(s, o, row_bytes(rows, W_DROP_TIME), (uint32_t)q.drop_time, mem);
+    stw_b(s, o, row_bytes(rows, W_SPEEDUP_TIME), (uint32_t)q.speedup_time, mem);
+    stw_b(s, o, row_bytes(rows, W_LOCK_TIME), (uint32_t)q.lock_time, mem);
+    stw_b(s, o, row_bytes(rows, W_COMBO_START), (uint32_t)q.combo_start, mem);
+    stw_b(s, o, row_bytes(rows, W_COMBO_TIME), (uint32_t)q.combo_time, mem);
+    if (queue) stw_b(s, o, row_bytes(rows, W_INCOMING), f2u(q.incoming), mem);
+    stw_b(s, o, row_bytes(rows, W_MIN_REMAINING), (uint32_t)q.min_remaining, mem);
+    stw_b(s, o, row_bytes(rows, W_PIECE_DRAWS), q.piece_draws, mem);
+    if (queue) stw_b(s, o, row_bytes(rows, W_HOLE_DRAWS), q.hole_draws, mem);
+    stw_b(s, o, row_bytes(rows, W_PIECE_GROUP), q.pgroup, mem);
+    stw_b(s, o, row_bytes(rows, W_STATS0), (q.lines_sent & 0xFFFF) | (q.lines_cleared << 16), mem);
+    stw_b(s, o, row_bytes(rows, W_STATS1), (q.lines_blocked & 0xFFFF) | (q.max_combo << 16), mem);
+    stw_b(s, o, row_bytes(rows, W_STATS2), (q.lines_seen & 0xFFFF) | (q.garbage_cleared << 16), mem);
+    if (queue && (q.q_loaded || q.qlen > 0)) {
+        for (int i = 0; i < FIFO_CAP / 2; i++)
+            stw_b(s, o, row_bytes(rows, W_FIFO_COUNT0 + i), ((uint32_t)q.qcount[2 * i] & 0xFFFF) | ((uint32_t)q.qcount[2 * i + 1] << 16), mem);
+        for (int i = 0; i < FIFO_CAP; i++) stw_b(s, o, row_bytes(rows, W_FIFO_DELAY0 + i), (uint32_t)q.qdelay[i], mem);
     }
 }
 
 TE_HD void store_player(uint32_t* s, uint32_t o, size_t ws, const Player& q, bool tint, bool queue = true, int mem = MEM_STREAM) {
-    for (int c = 0; c < NCOL; c++) stw(s, o, (size_t)(W_COL0 + c) * ws, q.col[c], mem);
-    if (tint)
-        for (int k = 0; k < 3; k++)
-            for (int c = 0; c < NCOL; c++) stw(s, o, (size_t)(W_TINT0 + 10 * k + c) * ws, q.tint[k][c], mem);
-    stw(s, o, (size_t)W_PIECE * ws, (uint32_t)q.kind | ((uint32_t)q.rot << 3) | ((uint32_t)(q.x + 4) << 5) | ((uint32_t)q.y << 9) |
-                              ((uint32_t)q.next << 14) | ((uint32_t)q.dead << 17) | ((uint32_t)q.lock_armed << 18) |
-                              ((uint32_t)(q.reward & 255) << 19), mem);
-    stw(s, o, (size_t)W_MISC * ws, (uint32_t)(q.inc_count & 255) | ((uint32_t)(q.combo_count & 255) << 8) |
-                             ((uint32_t)(q.line_count & 255) << 16) | ((uint32_t)q.qlen << 24) | ((uint32_t)q.q_overflow << 28), mem);
-    stw(s, o, (size_t)W_TIME * ws, (uint32_t)q.time_ms, mem);
-    stw(s, o, (size_t)W_DROPCOMBO * ws, ((uint32_t)q.drop_delay & 0xFFFF) | (q.combo_remaining << 16), mem);
-    stw(s, o, (size_t)W_DROP_TIME * ws, (uint32_t)q.drop_time, mem);
-    stw(s, o, (size_t)W_SPEEDUP_TIME * ws, (uint32_t)q.speedup_time, mem);
-    stw(s, o, (size_t)W_LOCK_TIME * ws, (uint32_t)q.lock_time, mem);
-    stw(s, o, (size_t)W_COMBO_START * ws, (uint32_t)q.combo_start, mem);
-    stw(s, o, (size_t)W_COMBO_TIME * ws, (uint32_t)q.combo_time, mem);
-    if (queue) stw(s, o, (size_t)W_INCOMING * ws, f2u(q.incoming), mem);
-    stw(s, o, (size_t)W_MIN_REMAINING * ws, (uint32_t)q.min_remaining, mem);
-    stw(s, o, (size_t)W_PIECE_DRAWS * ws, q.piece_draws, mem);
-    if (queue) stw(s, o, (size_t)W_HOLE_DRAWS * ws, q.hole_draws, mem);
-    stw(s, o, (size_t)W_PIECE_GROUP * ws, q.pgroup, mem);
-    stw(s, o, (size_t)W_STATS0 * ws, (q.lines_sent & 0xFFFF) | (q.lines_cleared << 16), mem);
-    stw(s, o, (size_t)W_STATS1 * ws, (q.lines_blocked & 0xFFFF) | (q.max_combo << 16), mem);
-    stw(s, o, (size_t)W_STATS2 * ws, (q.lines_seen & 0xFFFF) | (q.garbage_cleared << 16), mem);
-    if (queue && (q.q_loaded || q.qlen > 0)) {
-        for (int i = 0; i < FIFO_CAP / 2; i++)
-            stw(s, o, (size_t)(W_FIFO_COUNT0 + i) * ws, ((uint32_t)q.qcount[2 * i] & 0xFFFF) | ((uint32_t)q.qcount[2 * i + 1] << 16), mem);
-        for (int i = 0; i < FIFO_CAP; i++) stw(s, o, (size_t)(W_FIFO_DELAY0 + i) * ws, (uint32_t)q.qdelay[i], mem);
-    }
+    store_player_rows(s, o, RowStride{ws}, q, tint, queue, mem);
+}
+
+template <int P, class ROWS>
+TE_HD void store_game_words_rows(const Ref& gr, const ROWS& rows, const Game<P>& g, bool counters = false, int mem = MEM_STREAM) {
+    stw_b(gr.s, gr.o, row_bytes(rows, G_META), g.seed16 | ((uint32_t)g.round_over << 16) | ((uint32_t)(g.last_winner + 1) << 17) | (g.flags << 21), mem);
+    stw_b(gr.s, gr.o, row_bytes(rows, G_EPISODE), g.episode, mem);
+    if (counters) stw_b(gr.s, gr.o, row_bytes(rows, G_STEPS), g.steps, mem);
+    // lines are cleared / sent in a few steps per thousand under a random policy: these two words are updated only then, by
+    // a fire-and-forget atomic add (no return value: the wave does not wait for the memory round trip at the end of its
+    // step — a dependent load + store there made the slowest wave, and with it every launch, ~0.8 us longer)
+    if (g.add_lines) add_word((uint32_t*)((char*)gr.s + row_bytes(rows, G_LINES) + gr.o), g.add_lines);
+    if (g.add_sent) add_word((uint32_t*)((char*)gr.s + row_bytes(rows, G_SENT) + gr.o), g.add_sent);
 }
 
 template <int P>
 TE_HD void store_game_words(const Ref& gr, const Game<P>& g, bool counters = false, int mem = MEM_STREAM) {
-    stw(gr.s, gr.o, (size_t)G_META * gr.ws, g.seed16 | ((uint32_t)g.round_over << 16) | ((uint32_t)(g.last_winner + 1) << 17) | (g.flags << 21), mem);
-    stw(gr.s, gr.o, (size_t)G_EPISODE * gr.ws, g.episode, mem);
-    if (counters) stw(gr.s, gr.o, (size_t)G_STEPS * gr.ws, g.steps, mem);
-    // lines are cleared / sent in a few steps per thousand under a random policy: these two words are updated only then, by
-    // a fire-and-forget atomic add (no return value: the wave does not wait for the memory round trip at the end of its
-    // step — a dependent load + store there made the slowest wave, and with it every launch, ~0.8 us longer)
-    if (g.add_lines) add_word(&word_at(gr, G_LINES), g.add_lines);
-    if (g.add_sent) add_word(&word_at(gr, G_SENT), g.add_sent);
+    store_game_words_rows<P>(gr, RowStride{gr.ws}, g, counters, mem);
 }
 
-template <int P>
-TE_HD void store_game(const Geo& geo_in, size_t slot, const Game<P>& g, bool tint = false, bool queue = true, bool counters = false, int mem = MEM_STREAM) {
+template <int P, class ROWS, class GROWS>
+TE_HD void store_game_rows(const Geo& geo_in, size_t slot, const ROWS& rows, const GROWS& grows, const Game<P>& g, bool tint = false, bool queue = true,
+                           bool counters = false, int mem = MEM_STREAM) {
     Geo geo = geo_in;
     geo.P = P;
-    store_game_words<P>(game_ref(geo, slot), g, counters, mem);
+    store_game_words_rows<P>(game_ref(geo, slot), grows, g, counters, mem);
     TE_UNROLL
     for (int p = 0; p < P; p++) {
         const Ref r = board_ref(geo, p, slot);
-        store_player(r.s, r.o, r.ws, g.pl[p], tint, queue, mem);
+        store_player_rows(r.s, r.o, rows, g.pl[p], tint, queue, mem);
     }
+}
+template <int P>
+TE_HD void store_game(const Geo& geo_in, size_t slot, const Game<P>& g, bool tint = false, bool queue = true, bool counters = false, int mem = MEM_STREAM) {
+    store_game_rows<P>(geo_in, slot, RowStride{(size_t)P * geo_in.stride}, RowStride{geo_in.stride}, g, tint, queue, counters, mem);
 }
 
 // ---------------------------------------------------------------- board primitives

@@ -53,7 +53,12 @@ constexpr int CHAIN_STREAMS = 3;     // streams the chained launches rotate over
 // What makes this FASTER only with direct dispatch: the packets between a queue's first and last carry no cache maintenance
 // (a kernel boundary's L2 write-back + invalidate, three times per 12 us, cost more than the fabric: +0.1 us per launch through
 // streams); the queue's last packet releases, so memory is current when the call returns.
-template <int P, bool AFFINE>
+// FUSED says which launches a kernel serves.  false: one env-step per launch, the case that is timed (k_chain, k_chain_affine) —
+// rollout_step once, straight-line.  With game_run's loop over a.steps around the step the compiler hoists the loop's constants
+// and the next step's policy draw into a preheader BEHIND the state loads, where every instruction is on the wave's dependent
+// chain, and keeps a second copy of Philox in the body; a one-step launch uses none of it.  true: any other step count (k_chain_fused,
+// k_chain_fused_affine: S > 1, and S = 0 of the counter calibration), game_run with its loop.
+template <int P, bool AFFINE, bool FUSED>
 __device__ __forceinline__ void chain_body(const KArgs& a) {
     __shared__ __attribute__((aligned(16))) uint32_t s_shapes[SHAPE_WORDS];
     const int lane = threadIdx.x;
@@ -92,14 +97,45 @@ __device__ __forceinline__ void chain_body(const KArgs& a) {
     const uint32_t d0 = g.draw0, d1 = g.draw1;
     int stride = a.n_stride;
     asm volatile("" : "+s"(stride));
+    // The single-step kernels also multiply out, here, the byte offsets of the state rows the step touches (tetris_engine.h: RowTable)
+    // and pin them into SGPRs: the loads behind the poll and the stores behind the step then find their offsets ready.  Left to itself
+    // the compiler multiplies them out where they are used, twice, between the loads and among the stores: on the chain.
+    RowTable<NWORDS> rows = {};
+    RowTable<NGWORDS> grows = {};
+    if (!FUSED) {
+        TE_UNROLL
+        for (int w = 0; w < NWORDS; w++)
+            if (P > 1 || (w < NWORDS_HOT && w != W_INCOMING && w != W_HOLE_DRAWS)) {      // (one player: no queue, these are never touched)
+                uint32_t bytes = (uint32_t)(w * P) * (uint32_t)stride * 4u;
+                asm volatile("" : "+s"(bytes));
+                rows.bytes[w] = bytes;
+            }
+        TE_UNROLL
+        for (int w = 0; w < NGWORDS; w++) {            // (G_LINES, G_SENT: the rare counter atomics)
+            uint32_t bytes = (uint32_t)w * (uint32_t)stride * 4u;
+            asm volatile("" : "+s"(bytes));
+            grows.bytes[w] = bytes;
+        }
+    }
     const uint32_t seen = chain_poll(a, (uint32_t)wave);
     if (seen == a.epoch - 1u) {                 // (a uniform branch: the state loads follow the poll's exit)
         Geo geo = geo_of(a);
         geo.stride = (size_t)stride;
-        if (active) { load_game<P>(geo, (size_t)i, g, false, P > 1, true, CMEM); g.draw0 = d0; g.draw1 = d1; }
+        if (active) {
+            if (FUSED) load_game<P>(geo, (size_t)i, g, false, P > 1, true, CMEM);
+            else load_game_rows<P>(geo, (size_t)i, rows, grows, g, false, P > 1, true, CMEM);
+            g.draw0 = d0; g.draw1 = d1;
+        }
         s_shapes[lane] = shape_word;
         __builtin_amdgcn_wave_barrier();
-        if (active) game_run<P, M_ROLLOUT, false, CMEM>(a, i, s_shapes, g, cnt);
+        if (FUSED) {
+            if (active) game_run<P, M_ROLLOUT, false, CMEM>(a, i, s_shapes, g, cnt);
+        } else if (active) {
+            const Ctx cx = make_ctx(a, s_shapes, false, P > 1);
+            rollout_step<P>(cx, a, (size_t)i, a.first_step, g, cnt);
+            store_game_rows<P>(geo, (size_t)i, rows, grows, g, false, P > 1, true, CMEM);
+            report_status(a, g.status);
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every store (and counter atomic) of this wave has been acknowledged
         if (lane == 0) {
             // AFFINE: a plain store, the line stays in this XCD's L2 where the next launch's wave polls it; otherwise written through
@@ -113,10 +149,15 @@ __device__ __forceinline__ void chain_body(const KArgs& a) {
     report_xcc();
 }
 template <int P>
-__global__ __launch_bounds__(64) void k_chain(KArgs a) { chain_body<P, false>(a); }
+__global__ __launch_bounds__(64) void k_chain(KArgs a) { chain_body<P, false, false>(a); }
 template <int P>
-__global__ __launch_bounds__(64) void k_chain_affine(KArgs a) { chain_body<P, true>(a); }
+__global__ __launch_bounds__(64) void k_chain_affine(KArgs a) { chain_body<P, true, false>(a); }
+template <int P>
+__global__ __launch_bounds__(64) void k_chain_fused(KArgs a) { chain_body<P, false, true>(a); }
+template <int P>
+__global__ __launch_bounds__(64) void k_chain_fused_affine(KArgs a) { chain_body<P, true, true>(a); }
 template __global__ void k_chain_affine<1>(KArgs);
+template __global__ void k_chain_fused_affine<1>(KArgs);
 // the XCD every workgroup of a launch lands on (calibration of the affine form: aql::make_queues)
 extern "C" __global__ void tetris_k_xcc_probe(uint32_t* out) {
     if (threadIdx.x == 0) {
@@ -958,7 +999,7 @@ struct tetris_batch {
     uint32_t chain_epoch = 0;
     int use_chain = 1;                   // TETRIS_NO_CHAIN=1 in the environment: every rollout launch on the batch's one stream
     int use_graph = 0;                   // TETRIS_GRAPH=1: un-chained rollout launches replayed from HIP graphs (profiling aid)
-    long long chain_capacity = -1;       // wave slots of the device for the chained kernel (computed on first use)
+    long long chain_capacity[2] = {-1, -1};   // wave slots of the device for the chained kernel, [fused] (computed on first use)
     int chain_depth = 0;                 // launches in flight = streams rotated over (3, or 2 where only two launches fit; 0: not chained)
     bool chain_pending = false;          // chained launches were enqueued since the last drain
     uint32_t chain_spin_limit = CHAIN_SPIN_LIMIT;     // polls before a waiting wave gives up (tetris_set_chain_spin_limit)
@@ -1052,19 +1093,23 @@ static uint32_t chain_waves(const tetris_batch* b) { return (uint32_t)((b->N + c
 // one workgroup per CU too high for kernels of this SGPR count (MI355X_MICROARCH.md, correctness boundaries): one is
 // subtracted.  64k single-player boards: 1 024 waves per launch, 15 x 256 slots.  64k two-player boards (k_duo, 220
 // VGPRs: 8 waves per CU): 2 048 waves per launch, 7 x 256 slots — does not fit, those launches stay on one stream.
-static const void* chain_kernel(tetris_batch* b, long long* waves) {
+// `fused`: the call's launches make another number of steps than one (one player only: rollout_chained) — k_chain_fused, which has
+// a footprint of its own: what fits and the census are asked of the kernel that will be launched.
+static bool chain_is_fused(const tetris_batch* b, int steps_per_launch) { return b->P == 1 && steps_per_launch != 1; }
+static const void* chain_kernel(tetris_batch* b, bool fused, long long* waves) {
     *waves = chain_waves(b);
-    return b->P == 1 ? (const void*)k_chain<1> : (const void*)k_duo<M_ROLLOUT, true>;
+    return b->P == 1 ? (fused ? (const void*)k_chain_fused<1> : (const void*)k_chain<1>) : (const void*)k_duo<M_ROLLOUT, true>;
 }
 // `blocks` workgroups of the chained kernel on stream `st`; `start` / `stop` (may be NULL): events attached to the kernel itself
-static hipError_t launch_chain_kernel(tetris_batch* b, uint32_t blocks, hipStream_t st, const KArgs& a, hipEvent_t start = nullptr,
+static hipError_t launch_chain_kernel(tetris_batch* b, bool fused, uint32_t blocks, hipStream_t st, const KArgs& a, hipEvent_t start = nullptr,
                                       hipEvent_t stop = nullptr) {
-    if (b->P == 1) hipExtLaunchKernelGGL((k_chain<1>), dim3(blocks), dim3(64), 0, st, start, stop, 0, a);
+    if (b->P == 1 && fused) hipExtLaunchKernelGGL((k_chain_fused<1>), dim3(blocks), dim3(64), 0, st, start, stop, 0, a);
+    else if (b->P == 1) hipExtLaunchKernelGGL((k_chain<1>), dim3(blocks), dim3(64), 0, st, start, stop, 0, a);
     else hipExtLaunchKernelGGL((k_duo<M_ROLLOUT, true>), dim3(blocks), dim3(64), 0, st, start, stop, 0, a);
     return hipGetLastError();
 }
 // `waves` workgroups of the chained kernel resident at once?  Asked of the device itself: one census launch (chain_census).
-static bool chain_census_ok(tetris_batch* b, long long waves) {
+static bool chain_census_ok(tetris_batch* b, bool fused, long long waves) {
     uint32_t* d = nullptr;
     if (hipMalloc((void**)&d, 2 * CHAIN_STRIDE * sizeof(uint32_t)) != hipSuccess) return false;
     bool ok = false;
@@ -1073,7 +1118,7 @@ static bool chain_census_ok(tetris_batch* b, long long waves) {
     memset(&a, 0, sizeof a);
     a.steps = -1; a.chain = d; a.epoch = (uint32_t)waves; a.chain_spin_limit = 4000;       // a few ms at most, and only where the answer is no
     if (hipMemsetAsync(d, 0, 2 * CHAIN_STRIDE * sizeof(uint32_t), b->own_stream) == hipSuccess) {
-        if (launch_chain_kernel(b, (uint32_t)waves, b->own_stream, a) == hipSuccess && hipMemcpyAsync(&h[0], d, 4, hipMemcpyDeviceToHost, b->own_stream) == hipSuccess &&
+        if (launch_chain_kernel(b, fused, (uint32_t)waves, b->own_stream, a) == hipSuccess && hipMemcpyAsync(&h[0], d, 4, hipMemcpyDeviceToHost, b->own_stream) == hipSuccess &&
             hipMemcpyAsync(&h[1], d + CHAIN_STRIDE, 4, hipMemcpyDeviceToHost, b->own_stream) == hipSuccess &&
             hipStreamSynchronize(b->own_stream) == hipSuccess)
             ok = h[0] == (uint32_t)waves && h[1] == 0;
@@ -1082,13 +1127,14 @@ static bool chain_census_ok(tetris_batch* b, long long waves) {
     return ok;
 }
 
-static bool chain_fits(tetris_batch* b) {
+static bool chain_fits(tetris_batch* b, bool fused) {
     long long waves = 0;
-    const void* fn = chain_kernel(b, &waves);
+    const void* fn = chain_kernel(b, fused, &waves);
+    long long& capacity = b->chain_capacity[fused ? 1 : 0];
     // TETRIS_CHAIN_DEPTH=1..3 (measurement aid): at most that many launches in flight.  1 = the chained kernel on ONE stream: its
     // dispatches are then serialised by the stream — the reference point for per-dispatch PMC counters (profiles/pmc_summary.py).
     static const int cap = [] { const char* e = getenv("TETRIS_CHAIN_DEPTH"); const int v = e ? atoi(e) : CHAIN_STREAMS; return v < 1 ? 1 : (v > CHAIN_STREAMS ? CHAIN_STREAMS : v); }();
-    if (b->chain_capacity < 0) {
+    if (capacity < 0) {
         int per_cu = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0) != hipSuccess) per_cu = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device) != hipSuccess) cus = 0;
@@ -1096,16 +1142,16 @@ static bool chain_fits(tetris_batch* b) {
         // boundaries).  A batch that would chain only WITH that last workgroup per CU — 64k two-player boards: two launches of
         // 2 048 waves are exactly the 16 x 256 slots a 116-register kernel has — asks the device: a census launch of that many
         // waves of the very kernel, once per batch.
-        b->chain_capacity = per_cu > 1 ? (long long)(per_cu - 1) * cus : 0;
+        capacity = per_cu > 1 ? (long long)(per_cu - 1) * cus : 0;
         const long long full = (long long)per_cu * cus;
         int want = 0;
         for (int d = cap; d >= 2 && !want; d--)
             if (d * waves <= full) want = d;
-        if (want && want * waves > b->chain_capacity && b->stream == b->own_stream && chain_census_ok(b, want * waves)) b->chain_capacity = want * waves;
+        if (want && want * waves > capacity && b->stream == b->own_stream && chain_census_ok(b, fused, want * waves)) capacity = want * waves;
     }
     b->chain_depth = 0;
     for (int d = cap; d >= 1 && !b->chain_depth; d--)
-        if (d * waves <= b->chain_capacity) b->chain_depth = d;
+        if (d * waves <= capacity) b->chain_depth = d;
     return b->chain_depth >= (cap == 1 ? 1 : 2);
 }
 
@@ -2212,7 +2258,7 @@ static void chain_release(tetris_batch* b) {
 
 static bool rollout_chained(tetris_batch* b, int steps_per_launch) {
     return b->use_chain && !b->tint && !b->split && b->stream == b->own_stream &&
-           (b->P == 1 || (b->P == 2 && steps_per_launch == 1 && b->use_duo)) && chain_fits(b);
+           (b->P == 1 || (b->P == 2 && steps_per_launch == 1 && b->use_duo)) && chain_fits(b, chain_is_fused(b, steps_per_launch));
 }
 
 int tetris_rollout_is_chained(tetris_batch* b, int steps_per_launch) {
@@ -2375,7 +2421,7 @@ static int rollout_plain(tetris_batch* b, const RolloutCall& call, int group, Cl
 static hipError_t launch_chained(tetris_batch* b, const RolloutCall& call, int l, hipStream_t st) {
     const int depth = b->chain_depth;
     hipEvent_t const stop = l < call.launches - depth ? nullptr : (l == call.launches - 1 ? b->ev1 : b->chain_ev[l % depth]);
-    return launch_chain_kernel(b, chain_waves(b), st, rollout_args(b, call, l), l == 0 ? b->ev0 : nullptr, stop);
+    return launch_chain_kernel(b, chain_is_fused(b, call.steps_per_launch), chain_waves(b), st, rollout_args(b, call, l), l == 0 ? b->ev0 : nullptr, stop);
 }
 
 // Long chained calls are enqueued by one host thread PER CHAIN STREAM.  A launch costs the host 2.7-4.0 us depending on the process
@@ -2501,9 +2547,11 @@ static int rollout_direct(tetris_batch* b, aql::Device* dev, const RolloutCall& 
     const int launches = call.launches, depth = b->chain_depth;
     // one-player batches on queues that deal their blocks round-robin over the XCDs: the XCD-affine kernel (k_chain_affine), whole groups
     // of eight workgroups, no cache maintenance between a queue's launches
-    const bool affine = b->use_affine && qs.affine_ok && (b->P == 1 ? dev->chain1_affine.ok : dev->duo_affine.ok);
+    const bool fused = chain_is_fused(b, call.steps_per_launch);
+    const aql::Kernel& one = fused ? dev->chain1_fused : dev->chain1, & one_affine = fused ? dev->chain1_fused_affine : dev->chain1_affine;
+    const bool affine = b->use_affine && qs.affine_ok && (b->P == 1 ? one_affine.ok && !one_affine.priv : dev->duo_affine.ok);
     b->last_affine = affine;
-    const aql::Kernel& kern = affine ? (b->P == 1 ? dev->chain1_affine : dev->duo_affine) : (b->P == 1 ? dev->chain1 : dev->duo);
+    const aql::Kernel& kern = affine ? (b->P == 1 ? one_affine : dev->duo_affine) : (b->P == 1 ? one : dev->duo);
     uint32_t blocks = chain_waves(b);
     if (affine) blocks = (blocks + 7u) & ~7u;
     const int wgroup = std::min(aql::SLOTS / 2 - 2, std::max(8, group / depth));

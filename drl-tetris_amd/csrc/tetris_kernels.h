@@ -259,6 +259,39 @@ TE_HD void game_load(const KArgs& a, int i, Game<P>& g) {
     if (MODE == M_STEP_RT || MODE == M_STEP_RT_AUTO) { g.draw0 = a.rot[i]; g.draw1 = (uint32_t)a.trans[i] | ((a.player ? (uint32_t)a.player[i] : 0u) << 8); }
 }
 
+// One env-step of the built-in rollout (SURVEY.md §8(d) synthetic workload: worker.py:91-118 with a counter-based random
+// policy): the action from g.draw0 / g.draw1, the step, the counters, the auto-reset.  game_run calls it in its loop over
+// a.steps; the single-step chained kernels (tetris_hip.hip: k_chain, k_chain_affine) call it once, with no loop around it.
+template <int P>
+TE_HD void rollout_step(const Ctx& cx, const KArgs& a, size_t slot, unsigned long long step, Game<P>& g, LaneCounters& cnt) {
+    TE_UNROLL
+    for (int p = 0; p < P; p++) prefetch_next(cx, g.pl[p], g.seed16, g.status);
+    ResetPrefetch rpf;
+    prefetch_reset(cx, episode_seed(a.game_offset + (uint32_t)slot, g.episode + 1), rpf);
+    int r = (int)(g.draw0 & 3u), t = (int)(g.draw1 % 10u);
+    int player = P > 1 ? (int)(step % (unsigned long long)P) : 0;
+    uint32_t sent_before = 0;
+    TE_UNROLL
+    for (int p = 0; p < P; p++) sent_before += g.pl[p].lines_sent;
+    make_rt<P>(cx, g, player, r, t);
+    int done = finish_game<P>(cx, g, a.ms);
+    cnt.steps++;
+    g.steps++;
+    uint32_t sent_after = 0;
+    TE_UNROLL
+    for (int p = 0; p < P; p++) {
+        sent_after += g.pl[p].lines_sent;
+        if (!g.pl[p].dead) { cnt.lines += (unsigned)g.pl[p].reward; g.add_lines += (unsigned)g.pl[p].reward; }
+    }
+    cnt.sent += (sent_after - sent_before) & 0xFFFFu;
+    g.add_sent += (sent_after - sent_before) & 0xFFFFu;
+    if (done) {
+        cnt.episodes++;
+        g.episode++;
+        reset_game<P>(cx, g, episode_seed(a.game_offset + (uint32_t)slot, g.episode), &rpf);
+    }
+}
+
 // Phase 2: step and store.
 template <int P, int MODE, bool TINT = false, int MEM = MEM_STREAM>
 TE_HD void game_run(const KArgs& a, int i, const uint32_t* shapes, Game<P>& g, LaneCounters& cnt) {
@@ -302,35 +335,9 @@ TE_HD void game_run(const KArgs& a, int i, const uint32_t* shapes, Game<P>& g, L
             reset_game<P>(cx, g, episode_seed(a.game_offset + (uint32_t)slot, g.episode), &rpf);
         }
     } else if (MODE == M_ROLLOUT) {
-        // SURVEY.md §8(d) synthetic workload: worker.py:91-118 with a counter-based random policy
         for (int s = 0; s < a.steps; s++) {
             unsigned long long step = a.first_step + (unsigned long long)s;
-            TE_UNROLL
-            for (int p = 0; p < P; p++) prefetch_next(cx, g.pl[p], g.seed16, g.status);
-            ResetPrefetch rpf;
-            prefetch_reset(cx, episode_seed(a.game_offset + (uint32_t)slot, g.episode + 1), rpf);
-            int r = (int)(g.draw0 & 3u), t = (int)(g.draw1 % 10u);
-            int player = P > 1 ? (int)(step % (unsigned long long)P) : 0;
-            uint32_t sent_before = 0;
-            TE_UNROLL
-            for (int p = 0; p < P; p++) sent_before += g.pl[p].lines_sent;
-            make_rt<P>(cx, g, player, r, t);
-            int done = finish_game<P>(cx, g, a.ms);
-            cnt.steps++;
-            g.steps++;
-            uint32_t sent_after = 0;
-            TE_UNROLL
-            for (int p = 0; p < P; p++) {
-                sent_after += g.pl[p].lines_sent;
-                if (!g.pl[p].dead) { cnt.lines += (unsigned)g.pl[p].reward; g.add_lines += (unsigned)g.pl[p].reward; }
-            }
-            cnt.sent += (sent_after - sent_before) & 0xFFFFu;
-            g.add_sent += (sent_after - sent_before) & 0xFFFFu;
-            if (done) {
-                cnt.episodes++;
-                g.episode++;
-                reset_game<P>(cx, g, episode_seed(a.game_offset + (uint32_t)slot, g.episode), &rpf);
-            }
+            rollout_step<P>(cx, a, slot, step, g, cnt);
             if (s + 1 < a.steps) policy_draw(a, (uint32_t)slot, step + 1, g.draw0, g.draw1);
         }
     }
