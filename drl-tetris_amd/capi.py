@@ -93,6 +93,8 @@ _SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_step_lists_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tetris_plan_deltas_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "tetris_rt_features_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_policy_rt_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_step_policy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -365,7 +367,7 @@ class TetrisBatch:
             return (out[0], masks[0]) if single else (out, masks)
         return out[0] if single else out
 
-    # -- planning on the device (include/tetris_hip.h: tetris_action_lists_dev and the two after it).  Every array argument is
+    # -- planning on the device (include/tetris_hip.h: tetris_action_lists_dev and the three after it).  Every array argument is
     # a raw DEVICE address (int / c_void_p) or None; these only enqueue.  Lists: count int32 [N], lens uint8 [N][L],
     # keys uint8 [N][L][K].
     def action_lists_dev(self, count, lens, keys, max_lists=64, max_keys=48, player=None, keep_null=False):
@@ -382,6 +384,14 @@ class TetrisBatch:
         """perform_action(lists[choice[i]], player) for every game: choice int32 [N]; done [N], lines / dead [P][N]."""
         self._check(self.lib.tetris_step_lists_dev(self._h, player, choice, count, lens, keys, int(max_lists), int(max_keys), int(ms),
                                                    1 if auto_reset else 0, done, lines, dead))
+
+    def plan_deltas_dev(self, count, cols, deltas, sums=None, small=None, max_lists=64, player=None, small_fill=1e-3, f16=False,
+                        list_major=False):
+        """sherlock_utils.generate_deltas from the columns simulate_lists_dev(finalize=False) wrote: deltas float32 [N][H][10][L]
+        (list_major: [N][L][H][10]; f16: binary16), sums N x H x 10 (or None), small uint8 [N][L] (or None); deltas / sums
+        16-byte aligned, max_lists <= 256."""
+        self._check(self.lib.tetris_plan_deltas_dev(self._h, player, count, cols, int(max_lists), float(small_fill),
+                                                    (1 if f16 else 0) | (2 if list_major else 0), deltas, sums, small))
 
     # -- heuristic policy on the device (include/tetris_hip.h: tetris_rt_features_dev and the four after it).  Array arguments
     # are raw DEVICE addresses (int / c_void_p) or None; weights: int16 [8], or [N][8] with per_game.

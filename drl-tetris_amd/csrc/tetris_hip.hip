@@ -809,6 +809,135 @@ __global__ __launch_bounds__(64) void k_plan_lists(const uint8_t* cnt, const uin
     }
 }
 
+// tetris_plan_deltas_dev: one workgroup per game, list k = thread k (L <= 256 = PD_BLOCK).  The output of a game is one contiguous
+// run of H * 10 * L elements in either layout and is what the kernel costs (64 lists of a 20-row board: 51 KB of float32 against
+// 2.5 KB of column words), so everything is arranged around its stores:
+//   1. thread k gathers its list's ten column words (a stride of P * 10 * N words between threads: every word its own cache line,
+//      shared with the 15 neighbouring games), applies the small rule on popcounts and leaves the words (zero unless the list is
+//      normal) and the list's kind in LDS; the field before is the same for all threads (uniform loads);
+//   2. the deltas: a thread builds 16 bytes of consecutive output elements from LDS and streams them out, so a wave instruction
+//      stores 1 KB contiguous — lists-last: 4 (binary16: 8) lists of one cell from one 16-byte LDS read; list-major: consecutive
+//      cells of one list.  Shapes whose inner extent is no multiple of that take one element per thread, still consecutive;
+//   3. the sums: thread = cell, the integer count of set bits over the LDS rows, then plan_sums_value.
+// Games are dealt to workgroups so that the 16 games sharing the cache lines of d_cols run on one XCD (workgroups go round-robin
+// over the 8 XCDs, each with an L2 of its own): workgroup 8 m + x takes game ((m / 16) * 8 + x) * 16 + m % 16.  Only speed
+// depends on that placement.
+constexpr int PD_BLOCK = 256;
+constexpr int PD_LS = PD_BLOCK + 4;     // words per LDS row: the ten rows start in ten different 16-byte slots
+
+__device__ __forceinline__ uint32_t pd_pack(const float* v, int w) { return f2u(v[w]); }
+__device__ __forceinline__ uint32_t pd_pack(const uint16_t* v, int w) { return (uint32_t)v[2 * w] | ((uint32_t)v[2 * w + 1] << 16); }
+
+// the element of (list kind, column word, before bit b, row y): plan_delta_value over its four possible values, encoded once
+// (passed by value: selecting between members of a struct in memory becomes a load from a selected address, i.e. scratch)
+template <typename T>
+__device__ __forceinline__ T pd_element(T v_fill, T v_zero, T v_one, T v_mone, int kind, uint32_t after, uint32_t b, int y) {
+    const uint32_t a = (after >> y) & 1u;
+    const T dv = a > b ? v_one : a < b ? v_mone : v_zero;
+    return kind == PLAN_LIST_NORMAL ? dv : kind == PLAN_LIST_SMALL ? v_fill : v_zero;
+}
+
+template <typename T, bool LIST_MAJOR>
+__global__ __launch_bounds__(PD_BLOCK) void k_plan_deltas(PlanDeltaArgs da) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    constexpr int EPL = 16 / (int)sizeof(T);                  // elements of one 16-byte store
+    __shared__ __attribute__((aligned(16))) uint32_t s_after[NCOL * PD_LS];
+    __shared__ __attribute__((aligned(16))) uint8_t s_kind[PD_BLOCK];
+    __shared__ uint32_t s_before[NCOL];
+    const uint32_t m = blockIdx.x >> 3;
+    const int i = (int)((((m >> 4) * 8u + (blockIdx.x & 7u)) << 4) + (m & 15u));
+    if (i >= da.n) return;
+    const int tid = (int)threadIdx.x, L = da.max_lists, H = da.H, HW = H * NCOL, P = da.geo.P;
+    const int p = safe_player(da.player, i, P);
+    const int count = plan_clamp_count(da.count[i], L);
+    const uint32_t mask = plan_row_mask(H);
+    const Ref br = board_ref(da.geo, p, (size_t)i);
+    {
+        uint32_t before[NCOL], after[NCOL];
+        TE_UNROLL
+        for (int c = 0; c < NCOL; c++) {
+            before[c] = word_at(br, W_COL0 + c) & mask;
+            after[c] = 0;
+        }
+        if (tid < count) {
+            const uint32_t* src = da.cols + ((size_t)tid * P + p) * NCOL * (size_t)da.n + i;
+            TE_UNROLL
+            for (int c = 0; c < NCOL; c++) after[c] = src[(size_t)c * da.n] & mask;
+        }
+        const int kind = plan_list_kind(tid, count, plan_list_sum(after, before));
+        TE_UNROLL
+        for (int c = 0; c < NCOL; c++) s_after[c * PD_LS + tid] = kind == PLAN_LIST_NORMAL ? after[c] : 0u;
+        s_kind[tid] = (uint8_t)kind;
+        if (tid < NCOL) s_before[tid] = word_at(br, W_COL0 + tid) & mask;
+        if (da.small && tid < L) da.small[(size_t)i * L + tid] = (uint8_t)(kind == PLAN_LIST_SMALL);
+    }
+    const int n_small = __syncthreads_count(s_kind[tid] == PLAN_LIST_SMALL);
+    const int n_normal = __syncthreads_count(s_kind[tid] == PLAN_LIST_NORMAL);
+
+    const float fill = da.small_fill;
+    const T v_fill = plan_encode<T>(plan_delta_value(PLAN_LIST_SMALL, 0, fill));
+    const T v_zero = plan_encode<T>(plan_delta_value(PLAN_LIST_NORMAL, 0, fill));
+    const T v_one = plan_encode<T>(plan_delta_value(PLAN_LIST_NORMAL, 1, fill));
+    const T v_mone = plan_encode<T>(plan_delta_value(PLAN_LIST_NORMAL, -1, fill));
+    T* out = (T*)da.deltas + (size_t)i * HW * L;
+    const int inner = LIST_MAJOR ? HW : L, outer_n = LIST_MAJOR ? L : HW;
+    if (inner % EPL == 0) {
+        // unit u = 16 bytes: (outer, in) = (u / LG, u % LG), stepped without a division
+        const uint32_t LG = (uint32_t)(inner / EPL), units = (uint32_t)outer_n * LG;
+        const uint32_t d_outer = PD_BLOCK / LG, d_in = PD_BLOCK % LG;
+        uint32_t outer = (uint32_t)tid / LG, in = (uint32_t)tid % LG;
+        for (uint32_t u = (uint32_t)tid; u < units; u += PD_BLOCK) {
+            T v[EPL];
+            if (!LIST_MAJOR) {
+                const int y = (int)outer / NCOL, c = (int)outer - y * NCOL, k0 = (int)in * EPL;
+                const uint32_t b = (s_before[c] >> y) & 1u;
+                TE_UNROLL
+                for (int q = 0; q < EPL / 4; q++) {
+                    const u32x4 a4 = *reinterpret_cast<const u32x4*>(&s_after[c * PD_LS + k0 + 4 * q]);
+                    const uint32_t k4 = *reinterpret_cast<const uint32_t*>(&s_kind[k0 + 4 * q]);
+                    v[4 * q + 0] = pd_element(v_fill, v_zero, v_one, v_mone, (int)(k4 & 255u), a4.x, b, y);
+                    v[4 * q + 1] = pd_element(v_fill, v_zero, v_one, v_mone, (int)((k4 >> 8) & 255u), a4.y, b, y);
+                    v[4 * q + 2] = pd_element(v_fill, v_zero, v_one, v_mone, (int)((k4 >> 16) & 255u), a4.z, b, y);
+                    v[4 * q + 3] = pd_element(v_fill, v_zero, v_one, v_mone, (int)(k4 >> 24), a4.w, b, y);
+                }
+            } else {
+                const int k = (int)outer, kind = s_kind[k], cell0 = (int)in * EPL;
+                TE_UNROLL
+                for (int j = 0; j < EPL; j++) {
+                    const int y = (cell0 + j) / NCOL, c = (cell0 + j) - y * NCOL;
+                    v[j] = pd_element(v_fill, v_zero, v_one, v_mone, kind, s_after[c * PD_LS + k], (s_before[c] >> y) & 1u, y);
+                }
+            }
+            u32x4 w;
+            w.x = pd_pack(v, 0); w.y = pd_pack(v, 1); w.z = pd_pack(v, 2); w.w = pd_pack(v, 3);
+            __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(out) + u);
+            in += d_in; outer += d_outer;
+            if (in >= LG) { in -= LG; outer++; }
+        }
+    } else {
+        const uint32_t total = (uint32_t)HW * (uint32_t)L;
+        for (uint32_t e = (uint32_t)tid; e < total; e += PD_BLOCK) {
+            const int o = (int)(e / (uint32_t)inner), r = (int)(e - (uint32_t)o * (uint32_t)inner);
+            const int k = LIST_MAJOR ? o : r, cell = LIST_MAJOR ? r : o;
+            const int y = cell / NCOL, c = cell - y * NCOL;
+            __builtin_nontemporal_store(pd_element(v_fill, v_zero, v_one, v_mone, s_kind[k], s_after[c * PD_LS + k], (s_before[c] >> y) & 1u, y), &out[e]);
+        }
+    }
+    if (da.sums) {
+        T* sums = (T*)da.sums + (size_t)i * HW;
+        for (int t = tid; t < HW; t += PD_BLOCK) {
+            const int y = t / NCOL, c = t - y * NCOL;
+            uint32_t cnt = 0;
+            for (int k = 0; k < L; k += 4) {                 // (the rows are zero from L on)
+                const u32x4 a4 = *reinterpret_cast<const u32x4*>(&s_after[c * PD_LS + k]);
+                cnt += ((a4.x >> y) & 1u) + ((a4.y >> y) & 1u) + ((a4.z >> y) & 1u) + ((a4.w >> y) & 1u);
+            }
+            const int b = (int)((s_before[c] >> y) & 1u);
+            __builtin_nontemporal_store(plan_encode<T>(plan_sums_value((int)cnt - n_normal * b, n_small, fill)), &sums[t]);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_snapshot(Geo geo, int n, const int32_t* idx, uint32_t* blob, int restore) {
     size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < (size_t)n * (NGWORDS + geo.P * geo.nw)) snapshot_body(geo, t, idx, blob, restore);
@@ -2237,6 +2366,37 @@ int tetris_step_lists_dev(tetris_batch* b, const uint8_t* d_player, const int32_
     pa.choice = d_choice;
     pa.a.done = d_done; pa.a.lines = d_lines; pa.a.dead = d_dead;
     return launch_plan_kernel(b, (flags & TETRIS_STEP_AUTO_RESET) ? 2 : 1, dim3((unsigned)((b->N + 63) / 64)), pa, 0);
+}
+
+int tetris_plan_deltas_dev(tetris_batch* b, const uint8_t* d_player, const int32_t* d_count, const uint32_t* d_cols, int max_lists,
+                           float small_fill, int flags, void* d_deltas, void* d_sums, uint8_t* d_small) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = plan_check(b, "tetris_plan_deltas_dev"))) return rc;
+    if (!d_count || !d_cols || !d_deltas) return fail(TETRIS_E_ARG, "count/cols/deltas are NULL");
+    if (max_lists < 1 || max_lists > PD_BLOCK) return fail(TETRIS_E_ARG, "1 <= max_lists <= 256");
+    if (flags & ~(TETRIS_DELTAS_F16 | TETRIS_DELTAS_LIST_MAJOR)) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((((uintptr_t)d_deltas) | ((uintptr_t)d_sums)) & 15u) return fail(TETRIS_E_ARG, "deltas / sums must be 16-byte aligned");
+    if (((uintptr_t)d_cols) & 3u) return fail(TETRIS_E_ARG, "cols must be 4-byte aligned");
+    b->home_async = true;
+    PlanDeltaArgs da;
+    memset(&da, 0, sizeof da);
+    da.geo = geo_of_batch(b);
+    da.H = b->H; da.n = b->N;
+    da.player = d_player; da.count = d_count; da.cols = d_cols;
+    da.max_lists = max_lists; da.small_fill = small_fill;
+    da.deltas = d_deltas; da.sums = d_sums; da.small = d_small;
+    const dim3 grid((unsigned)((b->N + 127) / 128) * 128u), block(PD_BLOCK);     // whole groups of 8 XCDs x 16 games
+    const bool major = (flags & TETRIS_DELTAS_LIST_MAJOR) != 0;
+    if (flags & TETRIS_DELTAS_F16) {
+        if (major) hipLaunchKernelGGL((k_plan_deltas<uint16_t, true>), grid, block, 0, b->stream, da);
+        else hipLaunchKernelGGL((k_plan_deltas<uint16_t, false>), grid, block, 0, b->stream, da);
+    } else {
+        if (major) hipLaunchKernelGGL((k_plan_deltas<float, true>), grid, block, 0, b->stream, da);
+        else hipLaunchKernelGGL((k_plan_deltas<float, false>), grid, block, 0, b->stream, da);
+    }
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
 }
 
 // Chained launches of two batches at once would need room for four launches; only one batch per device chains at a time

@@ -1,11 +1,11 @@
 // Kernel bodies of the planning entry points (include/tetris_hip.h: tetris_action_lists_dev, tetris_simulate_lists_dev,
-// tetris_step_lists_dev): the afterstate loop of a planning agent on the device.  The reference's sherlock agent asks the
+// tetris_step_lists_dev, tetris_plan_deltas_dev): the afterstate loop of a planning agent on the device.  The reference's sherlock agent asks the
 // environment, per decision and game, for the ordered key lists of the current piece (get_actions), for the afterstate of
 // every list (simulate_all_actions) and then performs the one it picked (perform_action)
 // (agents/sherlock_agent/sherlock_agent.py:94-120, sherlock_utils.py:9-20).
 //
 // `__host__ __device__` like tetris_kernels.h: tetris_hip.hip / tetris_hip_multi.hip wrap these in gfx950 kernels,
-// tests/cpu_harness/harness_plan.cpp in plain host loops.
+// tests/cpu_harness/harness_plan.cpp (the deltas: harness_deltas.cpp) in plain host loops.
 //
 // Lists of one game live at lens[i][L] and keys[i][L][K] (L = max_lists, K = max_keys), count[i] of them (-1: the game's
 // lists did not fit).  The per-(game, x, rotation) search is actions_body (k_actions), which writes "slabs": for lane
@@ -215,6 +215,113 @@ TE_HD void plan_step_lane(const PlanArgs& pa, int i, const uint32_t* shapes, boo
     }
     store_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, false);
     report_status(a, g.status);
+}
+
+// ---------------------------------------------------------------- deltas: simulated columns -> the network input of a planning agent
+// sherlock_utils.deltas / generate_deltas (agents/sherlock_agent/sherlock_utils.py:9-20), per game and list: the acting player's
+// field after the list minus the field before; a list whose difference adds up to less than 4 is `small_fill` everywhere; lists
+// past count are zero; sums = the sum over the lists.  The element logic below is shared by k_plan_deltas (tetris_hip.hip) and
+// the host loop of tests/cpu_harness/harness_deltas.cpp, so that both give the same bits.
+struct PlanDeltaArgs {
+    Geo geo;
+    int H, n;                   // rows of a board, games
+    const uint8_t* player;      // [N] acting player (NULL: player 0; clamped)
+    const int32_t* count;       // [N] lists per game (clamped into [0, L])
+    const uint32_t* cols;       // [L][P][10][N] (as plan_sim_lane wrote them)
+    int max_lists;              // L
+    float small_fill;
+    void* deltas;               // [N][H][W][L], list-major [N][L][H][W]; float32 or binary16
+    void* sums;                 // [N][H][W] (NULL: no sums)
+    uint8_t* small;             // [N][L] (NULL: not wanted)
+};
+
+enum PlanListKind : int { PLAN_LIST_NORMAL = 0, PLAN_LIST_SMALL = 1, PLAN_LIST_PAST = 2 };
+
+TE_HD uint32_t plan_row_mask(int H) { return H >= 32 ? ~0u : (1u << H) - 1u; }                 // rows 0..H-1 of a column word
+// the delta of cell (y, column): bit y of the column after minus bit y of the column before, in {-1, 0, 1}
+TE_HD int plan_cell_delta(uint32_t after, uint32_t before, int y) { return (int)((after >> y) & 1u) - (int)((before >> y) & 1u); }
+// the integer sum of a list's deltas, from its (masked) columns
+TE_HD int plan_list_sum(const uint32_t* after, const uint32_t* before) {
+    int s = 0;
+    TE_UNROLL
+    for (int c = 0; c < NCOL; c++) s += __builtin_popcount(after[c]) - __builtin_popcount(before[c]);
+    return s;
+}
+// the "fewer than 4 cells" rule (sherlock_utils.py:12-14: the piece did not land whole, or the player could not move)
+TE_HD int plan_list_kind(int k, int count, int sum) { return k >= count ? PLAN_LIST_PAST : sum < 4 ? PLAN_LIST_SMALL : PLAN_LIST_NORMAL; }
+TE_HD int plan_clamp_count(int count, int L) { return imax(0, imin(count, L)); }
+// one cell of list `kind`
+TE_HD float plan_delta_value(int kind, int delta, float small_fill) {
+    return kind == PLAN_LIST_NORMAL ? (float)delta : kind == PLAN_LIST_SMALL ? small_fill : 0.0f;
+}
+// one cell of the sums: `normal_sum` = the integer sum of the cell's deltas over the normal lists, n_small = the small lists.
+// One float32 multiply and one float32 add (the builds use -ffp-contract=off), so no reduction order enters.
+TE_HD float plan_sums_value(int normal_sum, int n_small, float small_fill) {
+    const float fill = small_fill * (float)n_small;
+    return (float)normal_sum + fill;
+}
+// float32 -> IEEE binary16 bits, round to nearest even, in integer arithmetic (the host compiler of the CPU harness has no
+// half type; the kernel uses the same function so that both give the same bits)
+TE_HD uint16_t plan_f32_to_f16(float f) {
+    uint32_t x = f2u(f);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7FFFFFFFu;
+    if (x > 0x7F800000u) return (uint16_t)(sign | 0x7E00u);                  // NaN
+    if (x >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);                 // >= 65520 rounds to infinity
+    if (x >= 0x38800000u) {                                                  // a normal half: rebias, round the 13 dropped bits
+        const uint32_t m = x - 0x38000000u;
+        return (uint16_t)(sign | ((m + 0xFFFu + ((m >> 13) & 1u)) >> 13));
+    }
+    const uint32_t shift = 126u - (x >> 23);                                 // a subnormal half: units of 2^-24
+    if (shift > 24u) return (uint16_t)sign;                                  // below 2^-25: zero
+    const uint32_t mant = (x & 0x7FFFFFu) | 0x800000u;
+    uint32_t q = mant >> shift;
+    const uint32_t rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+    if (rem > half || (rem == half && (q & 1u))) q++;
+    return (uint16_t)(sign | q);
+}
+// an output element of type T (float, or uint16_t = binary16 bits) from the float32 value
+TE_HD void plan_encode_to(float v, float& out) { out = v; }
+TE_HD void plan_encode_to(float v, uint16_t& out) { out = plan_f32_to_f16(v); }
+template <typename T>
+TE_HD T plan_encode(float v) {
+    T out;
+    plan_encode_to(v, out);
+    return out;
+}
+
+// Serial form of game i (CPU harness; k_plan_deltas spreads the same steps over a workgroup).
+template <typename T>
+TE_HD void plan_deltas_game(const PlanDeltaArgs& da, int i, bool list_major) {
+    const int H = da.H, L = da.max_lists, P = da.geo.P, HW = H * NCOL;
+    const size_t n = (size_t)da.n;
+    const int p = safe_player(da.player, i, P);
+    const int count = plan_clamp_count(da.count[i], L);
+    const uint32_t mask = plan_row_mask(H);
+    const Ref br = board_ref(da.geo, p, (size_t)i);
+    uint32_t before[NCOL], after[NCOL];
+    for (int c = 0; c < NCOL; c++) before[c] = word_at(br, W_COL0 + c) & mask;
+    T* out = (T*)da.deltas + (size_t)i * HW * L;
+    int n_small = 0;
+    int acc[MAX_H * NCOL];
+    for (int t = 0; t < HW; t++) acc[t] = 0;
+    for (int k = 0; k < L; k++) {
+        int sum = 0;
+        if (k < count) {
+            for (int c = 0; c < NCOL; c++) after[c] = da.cols[(((size_t)k * P + p) * NCOL + c) * n + i] & mask;
+            sum = plan_list_sum(after, before);
+        }
+        const int kind = plan_list_kind(k, count, sum);
+        n_small += kind == PLAN_LIST_SMALL;
+        if (da.small) da.small[(size_t)i * L + k] = (uint8_t)(kind == PLAN_LIST_SMALL);
+        for (int t = 0; t < HW; t++) {
+            const int d = kind == PLAN_LIST_NORMAL ? plan_cell_delta(after[t % NCOL], before[t % NCOL], t / NCOL) : 0;
+            acc[t] += d;
+            out[list_major ? (size_t)k * HW + t : (size_t)t * L + k] = plan_encode<T>(plan_delta_value(kind, d, da.small_fill));
+        }
+    }
+    if (da.sums)
+        for (int t = 0; t < HW; t++) ((T*)da.sums)[(size_t)i * HW + t] = plan_encode<T>(plan_sums_value(acc[t], n_small, da.small_fill));
 }
 
 }  // namespace te

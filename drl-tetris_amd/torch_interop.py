@@ -105,10 +105,8 @@ class TorchEnv:
         self.sim_done = torch.zeros(max_lists, n, **u8)
         self.sim_lines = torch.zeros(max_lists, P, n, **u8)
         self.sim_dead = torch.zeros(max_lists, P, n, **u8)
-        self.plan_deltas = torch.zeros(n, self.b.height, 10, max_lists, dtype=torch.float32, device=self.dev)
-        self._plan_visual = torch.zeros(P, n, self.b.height, 10, **u8)
-        self._plan_vector = torch.zeros(P, n, 12, **u8)
-        self._plan_piece = torch.zeros(P, n, **u8)
+        self._plan_delta_bufs = {}            # deltas(): (L, dtype, list_major) -> (deltas, sums), allocated on first use
+        self.plan_small = torch.zeros(n, max_lists, **u8)
 
     def _check_player(self, player):
         if player is not None:
@@ -139,16 +137,28 @@ class TorchEnv:
                                   lines=self._ptr(self.sim_lines), dead=self._ptr(self.sim_dead))
         return self.sim_cols, self.sim_done, self.sim_lines, self.sim_dead
 
-    def deltas(self, player=None, small_fill=1e-3):
-        """sherlock_utils.generate_deltas for every game (lists of the last action_lists(player) call): -> (deltas float32
-        [n, H, W, L], sums float32 [n, H, W, 1]) device tensors; see columns_to_deltas.  One or two players (the field before is
-        read through the packed observation)."""
+    def deltas(self, player=None, small_fill=1e-3, dtype=None, list_major=False):
+        """sherlock_utils.generate_deltas for every game (lists of the last action_lists(player) call), simulate(finalize=False)
+        and one kernel (tetris_plan_deltas_dev): -> (deltas [n, H, W, L], sums [n, H, W, 1]) device tensors, reused per
+        (dtype, layout); list_major: deltas [n, L, H, W], sums [n, 1, H, W].  dtype: torch.float32 (default) or torch.float16.
+        self.plan_small uint8 [n, L] = 1 where a list fell under the "fewer than 4 cells" rule.  One to four players; values as
+        columns_to_deltas, sums by the formula of include/tetris_hip.h."""
+        torch = self.torch
+        dtype = torch.float32 if dtype is None else dtype
+        assert dtype in (torch.float32, torch.float16), "deltas are float32 or float16"
         self._check_player(player)
         cols = self.simulate(player, finalize=False)[0]
-        self.b._check(self.b.lib.tetris_observe_packed_dev(self.b._h, None, self.b.n_games, self._ptr(player), self._ptr(self._plan_visual),
-                                                          self._ptr(self._plan_vector), self._ptr(self._plan_piece)))
-        who = player if player is not None else self.torch.zeros(self.b.n_games, dtype=self.torch.uint8, device=self.dev)
-        return columns_to_deltas(cols, who, self._plan_visual[0], self.list_count, self.b.height, out=self.plan_deltas, small_fill=small_fill)
+        L, _ = self._lists()
+        n, H = self.b.n_games, self.b.height
+        key = (dtype, bool(list_major))
+        bufs = self._plan_delta_bufs
+        if key not in bufs:
+            shape, sshape = ((n, L, H, 10), (n, 1, H, 10)) if list_major else ((n, H, 10, L), (n, H, 10, 1))
+            bufs[key] = (torch.zeros(shape, dtype=dtype, device=self.dev), torch.zeros(sshape, dtype=dtype, device=self.dev))
+        d, s = bufs[key]
+        self.b.plan_deltas_dev(self._ptr(self.list_count), self._ptr(cols), self._ptr(d), sums=self._ptr(s), small=self._ptr(self.plan_small),
+                               max_lists=L, player=self._ptr(player), small_fill=small_fill, f16=dtype == torch.float16, list_major=list_major)
+        return d, s
 
     def step_lists(self, choice, player=None, ms=400, auto_reset=False):
         """perform_action(lists[choice[i]], player) for every game (lists of the last action_lists(player) call); choice: int32

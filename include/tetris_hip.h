@@ -246,6 +246,31 @@ int tetris_simulate_lists_dev(tetris_batch *b, const uint8_t *d_player, const in
 int tetris_step_lists_dev(tetris_batch *b, const uint8_t *d_player, const int32_t *d_choice, const int32_t *d_count,
                           const uint8_t *d_lens, const uint8_t *d_keys, int max_lists, int max_keys, int ms, int flags,
                           uint8_t *d_done, uint8_t *d_lines, uint8_t *d_dead);
+/* replaces: sherlock_utils.deltas / generate_deltas (agents/sherlock_agent/sherlock_utils.py:9-20) for games 0..N-1: the
+ * network input of the planning agent from the columns tetris_simulate_lists_dev wrote, in one kernel.  Device pointers,
+ * asynchronous on the batch's stream like tetris_observe_packed_dev; one to four players, every height, colour batches
+ * included (it reads occupancy); not on split batches.  The batch's state is read, not written, and the RNG tables are not
+ * touched.  d_cols uint32 [L][P][10][N] as tetris_simulate_lists_dev without TETRIS_SIM_FINALIZE wrote it (L = max_lists,
+ * 1 <= L <= 256); d_count [N] as tetris_action_lists_dev wrote it (below 0 counts as 0, above L as L); d_player as above.
+ * For game i, acting player p and list k: `before` = p's ten column words in the batch's state now, `after` =
+ * d_cols[k][p][c][i], both masked to rows 0..H-1; delta(y, x) = bit y of after[x] - bit y of before[x], in {-1, 0, 1};
+ * s = the integer sum of the deltas of list k.  For k < count: if s < 4 the list is SMALL (the piece did not land whole, or
+ * the player could not move: sherlock_utils.py:12-14) and every cell of it is small_fill, otherwise the cells are the
+ * deltas; for k >= count every cell is 0 (the reference's zero padding to the longest list).  (The reference's own fields
+ * are uint8, and np.full_like on them turns its 1e-3 into 0: small_fill = 0 gives those numbers.)
+ *   d_deltas  [N][H][10][L] float32, the reference's layout; with TETRIS_DELTAS_LIST_MAJOR [N][L][H][10]
+ *   d_sums    N x H x 10 elements ([N][H][10][1], list-major [N][1][H][10]: the same memory): the sum over the lists, defined
+ *             without a reduction order as (float)(integer sum of the deltas of the lists k < count that are not small) +
+ *             small_fill * (float)(number of small lists), one float32 multiply and one float32 add.  NULL: no sums.
+ *   d_small   uint8 [N][L]: 1 where the small rule fired, else 0 (also for k >= count).  May be NULL.
+ * With TETRIS_DELTAS_F16 d_deltas and d_sums hold IEEE binary16: the float32 value above rounded to nearest even.
+ * d_deltas and d_sums must be 16-byte aligned, d_cols 4-byte aligned; TETRIS_E_ARG for that, for a max_lists out of range
+ * and for a NULL d_count, d_cols or d_deltas.                                                                            */
+#define TETRIS_DELTAS_F16        1   /* d_deltas / d_sums are IEEE binary16 instead of float32 */
+#define TETRIS_DELTAS_LIST_MAJOR 2   /* d_deltas [N][L][H][W] instead of [N][H][W][L] */
+int tetris_plan_deltas_dev(tetris_batch *b, const uint8_t *d_player, const int32_t *d_count, const uint32_t *d_cols,
+                           int max_lists, float small_fill, int flags,
+                           void *d_deltas, void *d_sums, uint8_t *d_small);
 
 /* ---- heuristic policy on the device: a one-piece look-ahead over the 40 SVENton (rotation, translation) actions -----------
  * The scripted player the golden traces were recorded with (tests/golden/policies.py: GreedyRT), for every game of a batch at

@@ -1,0 +1,260 @@
+"""The deltas of a planning agent in one kernel (include/tetris_hip.h: tetris_plan_deltas_dev) against a numpy restatement of
+its semantics on columns the tests craft themselves, against the Python path it replaces (sherlock_utils.deltas /
+generate_deltas over simulate_all_actions) and, on the MI355X, against torch_interop.columns_to_deltas at full size.  The
+tests parametrised over engines.ENGINE_PARAMS run on the CPU harness (`-m "not gpu"`) and on the GPU (`-m gpu`)."""
+import importlib
+
+import numpy as np
+import pytest
+
+import __graft_entry__ as ge
+from oracle import oracle as orc
+from tests import engines
+from tests.test_plan_device import Buf, _bits, _device_lists, _numpy_deltas, _plan_env, _simulate
+
+PAD = 64          # guard bytes behind every output buffer
+GUARD = 0xCD
+
+
+class Out:
+    """An output buffer of `count` elements of `dtype` with PAD guard bytes behind it (Buf holds the bytes)."""
+
+    def __init__(self, kind, count, dtype):
+        self.dtype, self.nbytes = np.dtype(dtype), count * np.dtype(dtype).itemsize
+        self.buf = Buf(kind, (self.nbytes + PAD,), np.uint8, GUARD)
+        self.ptr = self.buf.ptr
+        assert self.ptr % 16 == 0
+
+    def get(self, shape):
+        raw = self.buf.get()
+        assert (raw[self.nbytes:] == GUARD).all(), "wrote past the buffer"
+        return raw[: self.nbytes].view(self.dtype).reshape(shape)
+
+
+def _want(before, after, count, fill):
+    """The semantics of tetris_plan_deltas_dev in numpy.  before bool [N, H, 10], after bool [N, L, H, 10] (the acting player's
+    fields, rows 0..H-1), count int [N] -> deltas float32 [N, H, 10, L], sums float32 [N, H, 10], small uint8 [N, L]."""
+    N, L = after.shape[:2]
+    delta = after.astype(np.int32) - before[:, None].astype(np.int32)
+    s = delta.sum(axis=(2, 3))
+    valid = np.arange(L)[None, :] < np.clip(count, 0, L)[:, None]
+    small = valid & (s < 4)
+    normal = valid & ~small
+    d = np.where(normal[:, :, None, None], delta, 0).astype(np.float32)
+    d[small] = np.float32(fill)
+    isum = np.where(normal[:, :, None, None], delta, 0).sum(axis=1)                   # [N, H, 10] integers
+    fills = np.float32(fill) * small.sum(axis=1).astype(np.float32)                   # one float32 multiply
+    sums = isum.astype(np.float32) + fills[:, None, None]                             # one float32 add
+    return d.transpose(0, 2, 3, 1), sums, small.astype(np.uint8), normal
+
+
+def _words(field):
+    """bool [..., H, 10] -> uint32 column words [..., 10] (bit y = row y)"""
+    H = field.shape[-2]
+    return (field.astype(np.uint32) << np.arange(H, dtype=np.uint32)[:, None]).sum(axis=-2).astype(np.uint32)
+
+
+def _crafted(kind, N, P, H, L, seed):
+    """A scrambled batch and a d_cols buffer the test fills: per (game, list) one of five cases on the acting player's plane,
+    garbage in the other players' planes; mixed d_player (out-of-range entries included) and counts from {-1, 0, .., L, L + 5}."""
+    rng = np.random.default_rng(seed)
+    b = engines.make(kind, N, P, height=H, seeds=orc.episode_seed(np.arange(N), 7))
+    b.rollout_random(1, 18)
+    player = rng.integers(0, P + 3, N).astype(np.uint8)
+    before_all = (b.observe()[0]["field"][:, :, :H] > 0)
+    count = rng.integers(-1, L + 2, N).astype(np.int32)
+    count[count == L + 1] = L + 5
+    count[:4] = (-1, 0, L + 5, L)                                                     # every edge, whatever was drawn
+    player[4:6] = (P, P + 2)
+    who = np.minimum(player, P - 1)
+    before = before_all[np.arange(N), who]                                            # [N, H, 10]
+    cols = rng.integers(0, 2 ** 32, (L, P, 10, N), dtype=np.uint64).astype(np.uint32)
+    high = np.uint32((0xFFFFFFFF << H) & 0xFFFFFFFF)
+    for i in range(N):
+        free, used = np.argwhere(~before[i]), np.argwhere(before[i])
+        for k in range(L):
+            f = before[i].copy()
+            case = (i + k) % 5
+            if case in (1, 2):                                                        # exactly 3 / exactly 4 more cells
+                for y, x in free[rng.permutation(len(free))[: 2 + case]]:
+                    f[y, x] = True
+            elif case == 3:                                                           # two cells leave, six arrive
+                for y, x in used[rng.permutation(len(used))[:2]]:
+                    f[y, x] = False
+                for y, x in free[rng.permutation(len(free))[:6]]:
+                    f[y, x] = True
+            w = _words(f)
+            if case == 4:                                                             # random words on top, bits >= H set
+                w = w | rng.integers(0, 2 ** 32, 10, dtype=np.uint64).astype(np.uint32) | high
+            cols[k, who[i], :, i] = w
+    after = _bits(cols[:, who, :, np.arange(N)], H)                                   # [N, L, H, 10]
+    return b, player, count, cols, before, after
+
+
+def _run(kind, b, player, count, cols, L, fill, f16=False, list_major=False, with_small=True, with_sums=True):
+    N, H = b.n_games, b.height
+    dt = np.float16 if f16 else np.float32
+    pl, cnt = Buf(kind, (N,), np.uint8), Buf(kind, (N,), np.int32)
+    pl.set(player)
+    cnt.set(count)
+    dc = Buf(kind, cols.shape, np.uint32)
+    dc.set(cols)
+    d, s, sm = Out(kind, N * H * 10 * L, dt), Out(kind, N * H * 10, dt), Out(kind, N * L, np.uint8)
+    b.plan_deltas_dev(cnt.ptr, dc.ptr, d.ptr, sums=s.ptr if with_sums else None, small=sm.ptr if with_small else None, max_lists=L,
+                      player=pl.ptr, small_fill=fill, f16=f16, list_major=list_major)
+    return d.get((N, L, H, 10) if list_major else (N, H, 10, L)), s.get((N, H, 10)), sm.get((N, L))
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("L", [1, 7, 64, 130])
+@pytest.mark.parametrize("P,H", [(1, 20), (2, 20), (2, 7), (4, 31)])
+def test_crafted_columns_match_numpy(kind, P, H, L):
+    N, fill = 67, 1e-3
+    b, player, count, cols, before, after = _crafted(kind, N, P, H, L, seed=100 * P + H + L)
+    blob = b.snapshot()
+    d, s, sm = _run(kind, b, player, count, cols, L, fill)
+    assert np.array_equal(b.snapshot(), blob), "the batch's state was written"
+    want_d, want_s, want_small, normal = _want(before, after, count, fill)
+    # the inputs hold every kind of list
+    past = np.arange(L)[None, :] >= np.clip(count, 0, L)[:, None]
+    assert want_small.sum() > 0 and normal.sum() > 0 and past.sum() > 0 and (want_d < 0).sum() > 0
+    assert (count < 0).sum() > 0 and (count > L).sum() > 0 and (player >= P).sum() > 0
+    assert np.array_equal(sm, want_small)
+    assert np.array_equal(d, want_d)
+    assert np.array_equal(s, want_s)
+    assert b.take_errors() == 0
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("fill", [1e-3, 0.0, -2.5])
+@pytest.mark.parametrize("P,H,L", [(2, 20, 64), (1, 7, 7), (3, 31, 12)])
+def test_four_output_forms(kind, P, H, L, fill):
+    """(2, 20, 64) takes the 16-byte stores in every form; (1, 7, 7) no form; (3, 31, 12) float32 lists-last only."""
+    N = 33
+    b, player, count, cols, before, after = _crafted(kind, N, P, H, L, seed=L)
+    d, s, sm = _run(kind, b, player, count, cols, L, fill)
+    want_d, want_s, want_small, _ = _want(before, after, count, fill)
+    assert np.array_equal(d, want_d) and np.array_equal(s, want_s) and np.array_equal(sm, want_small)
+    dm, s_m, _ = _run(kind, b, player, count, cols, L, fill, list_major=True, with_small=False)
+    assert np.array_equal(dm, d.transpose(0, 3, 1, 2)) and np.array_equal(s_m, s)
+    h, sh, smh = _run(kind, b, player, count, cols, L, fill, f16=True)
+    assert np.array_equal(h.view(np.uint16), d.astype(np.float16).view(np.uint16))
+    assert np.array_equal(sh.view(np.uint16), s.astype(np.float16).view(np.uint16))
+    assert np.array_equal(smh, sm)
+    hm, shm, _ = _run(kind, b, player, count, cols, L, fill, f16=True, list_major=True, with_sums=False)
+    assert np.array_equal(hm.view(np.uint16), d.transpose(0, 3, 1, 2).astype(np.float16).view(np.uint16))
+    assert (shm.view(np.uint8) == GUARD).all(), "sums were written although none were asked for"
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+def test_binary16_rounding_edges(kind):
+    """small_fill values on both sides of every binary16 rounding boundary: ties to even, the subnormal range, underflow to
+    zero, overflow to infinity, infinity itself; the sums carry fill * (number of small lists) + integer through the same
+    conversion."""
+    N, L = 5, 8
+    b = engines.make(kind, N, 1, seeds=orc.episode_seed(np.arange(N), 1))
+    cols = np.zeros((L, 1, 10, N), np.uint32)                                         # empty afterstates: every list is small
+    count = np.full(N, L, np.int32)
+    fills = [1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11, 1.0 + 2.0 ** -11 + 2.0 ** -20, 65504.0, 65519.99, 65520.0, 1e5, np.inf, -np.inf,
+             2.0 ** -14, 2.0 ** -14 - 2.0 ** -26, 2.0 ** -24, 2.0 ** -25, 2.0 ** -25 + 2.0 ** -40, 3 * 2.0 ** -25, 2.0 ** -26, 1e-8, 6e-8,
+             -1e-3, -0.0, 0.1, 1 / 3, 2049.0, 2051.0, 1e-5, 6.1e-5]
+    for fill in fills:
+        d, s, _ = _run(kind, b, np.zeros(N, np.uint8), count, cols, L, fill)
+        h, sh, _ = _run(kind, b, np.zeros(N, np.uint8), count, cols, L, fill, f16=True)
+        assert (d == np.float32(fill)).all()
+        with np.errstate(over="ignore"):
+            assert np.array_equal(h.view(np.uint16), d.astype(np.float16).view(np.uint16)), fill
+            assert np.array_equal(sh.view(np.uint16), s.astype(np.float16).view(np.uint16)), fill
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+def test_end_to_end_matches_python_path(kind):
+    n, L = 64, 64
+    env = _plan_env(kind, n)
+    b = env.backend
+    player = np.arange(n) % 2
+    cnt, lens, keys, pl = _device_lists(kind, b, player, False, L=L)
+    cols = _simulate(kind, b, cnt, lens, keys, pl, False, L=L)[0]
+    d, s, sm = _run(kind, b, player.astype(np.uint8), cnt.get(), cols, L, 1e-3)
+    want_d, want_s = _numpy_deltas(env.get_state(), env.simulate_all_actions(player=player.tolist(), finalize=False), player, L)
+    assert np.array_equal(d, want_d.astype(np.float32))
+    assert np.allclose(s[..., None], want_s, rtol=1e-6, atol=1e-6)
+    assert np.array_equal(sm != 0, (d == np.float32(1e-3)).all(axis=(1, 2)))
+    assert (cnt.get() >= 1).all() and b.take_errors() == 0
+
+
+def test_argument_errors():
+    pkg = ge.package()
+    N, L = 4, 8
+    b = engines.make("harness", N, 2)
+    cnt, cols = np.zeros(N, np.int32), np.zeros((L, 2, 10, N), np.uint32)
+    out = np.zeros(N * 200 * L + 8, np.float32)
+    base = out.ctypes.data + (-out.ctypes.data) % 16
+    b.plan_deltas_dev(cnt.ctypes.data, cols.ctypes.data, base, max_lists=L)
+    for kw in (dict(max_lists=0), dict(max_lists=257)):
+        with pytest.raises(pkg.TetrisError):
+            b.plan_deltas_dev(cnt.ctypes.data, cols.ctypes.data, base, **kw)
+    with pytest.raises(pkg.TetrisError):
+        b.plan_deltas_dev(cnt.ctypes.data, cols.ctypes.data, base + 4, max_lists=L)
+    with pytest.raises(pkg.TetrisError):
+        b.plan_deltas_dev(cnt.ctypes.data, cols.ctypes.data, base, sums=base + 8, max_lists=L)
+    with pytest.raises(pkg.TetrisError):
+        b.plan_deltas_dev(cnt.ctypes.data, None, base, max_lists=L)
+    with pytest.raises(pkg.TetrisError):
+        b.plan_deltas_dev(None, cols.ctypes.data, base, max_lists=L)
+    with pytest.raises(pkg.TetrisError):
+        b.plan_deltas_dev(cnt.ctypes.data, cols.ctypes.data, None, max_lists=L)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P", [3, 4])
+def test_torch_env_deltas_three_and_four_players(P):
+    torch = pytest.importorskip("torch")
+    ti = importlib.import_module("drl-tetris_amd.torch_interop")
+    n, L, H = 64, 64, 20
+    b = engines.make("hip", n, P, seeds=orc.episode_seed(np.arange(n), 3))
+    b.rollout_random(1, 18)
+    te = ti.TorchEnv(b)
+    player = (np.arange(n) * 7 + 1) % P
+    pt = torch.from_numpy(player.astype(np.uint8)).cuda()
+    count, _, _ = te.action_lists(player=pt, max_lists=L)
+    d, s = te.deltas(player=pt)
+    dm, s_m = te.deltas(player=pt, dtype=torch.float16, list_major=True)
+    torch.cuda.synchronize()
+    before = (b.observe()[0]["field"][:, :, :H] > 0)[np.arange(n), player]
+    cnt = count.cpu().numpy()
+    cols = te.sim_cols.cpu().numpy().view(np.uint32)
+    after = _bits(cols[:, player, :, np.arange(n)], H)
+    after[np.arange(L)[None, :] >= cnt[:, None]] = False                               # (simulate leaves those entries alone)
+    want_d, want_s, want_small, normal = _want(before, after, cnt, 1e-3)
+    assert normal.sum() > 0 and (cnt >= 1).all()
+    assert d.shape == (n, H, 10, L) and s.shape == (n, H, 10, 1) and dm.shape == (n, L, H, 10) and s_m.shape == (n, 1, H, 10)
+    assert np.array_equal(d.cpu().numpy(), want_d)
+    assert np.array_equal(s.cpu().numpy()[..., 0], want_s)
+    assert np.array_equal(te.plan_small.cpu().numpy(), want_small)
+    assert np.array_equal(dm.cpu().numpy().view(np.uint16), want_d.transpose(0, 3, 1, 2).astype(np.float16).view(np.uint16))
+    assert np.array_equal(s_m.cpu().numpy()[:, 0].view(np.uint16), want_s.astype(np.float16).view(np.uint16))
+    assert b.take_errors() == 0
+    b.set_stream(None, external=False)
+
+
+@pytest.mark.gpu
+def test_full_size_matches_columns_to_deltas():
+    """4 096 two-player games after 18 steps, 64 lists: the kernel against the torch arithmetic it replaces, on the device."""
+    torch = pytest.importorskip("torch")
+    ti = importlib.import_module("drl-tetris_amd.torch_interop")
+    n, L = 4096, 64
+    b = engines.make("hip", n, 2, seeds=orc.episode_seed(np.arange(n), 2))
+    b.rollout_random(1, 18)
+    te = ti.TorchEnv(b)
+    pt = (torch.arange(n, device="cuda") % 2).to(torch.uint8)
+    count, _, _ = te.action_lists(player=pt, max_lists=L)
+    d, s = te.deltas(player=pt)
+    visual = te.observe(player=pt)[0]
+    want_d, want_s = ti.columns_to_deltas(te.sim_cols, pt, visual[0], count, b.height)
+    assert torch.equal(d, want_d)
+    assert torch.allclose(s, want_s, rtol=1e-6, atol=1e-6)
+    assert torch.equal(te.plan_small != 0, (want_d == torch.tensor(1e-3, dtype=torch.float32, device="cuda")).all(dim=1).all(dim=1))
+    torch.cuda.synchronize()
+    assert b.take_errors() == 0
+    b.set_stream(None, external=False)
