@@ -5,6 +5,6 @@ Only what the hot path needs lives here: ``csrc/`` (HIP kernels + C ABI, built i
 the reference's ``tetris_environment_vector`` API).  The directory name contains a hyphen; import
 it with ``importlib.import_module("drl-tetris_amd")`` or through ``__graft_entry__.package()``.
 """
-from .capi import POLICY_FEATURE_NAMES, RECORD, TetrisBatch, TetrisError, load_library  # noqa: F401
+from .capi import ACT_MODES, POLICY_FEATURE_NAMES, RECORD, TetrisBatch, TetrisError, load_library  # noqa: F401
 
-__all__ = ["POLICY_FEATURE_NAMES", "RECORD", "TetrisBatch", "TetrisError", "load_library"]
+__all__ = ["ACT_MODES", "POLICY_FEATURE_NAMES", "RECORD", "TetrisBatch", "TetrisError", "load_library"]

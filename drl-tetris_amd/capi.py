@@ -38,6 +38,41 @@ RECORD = np.dtype(
 )
 
 
+# the modes of tetris_select_eval_dev (include/tetris_hip.h: TETRIS_ACT_*)
+ACT_MODES = {"argmax": 0, "pi": 1, "rank": 2, "epsilon": 3}
+
+
+class ActEval(C.Structure):
+    """mirrors `struct tetris_act_eval` (include/tetris_hip.h)"""
+    _fields_ = [("d_action_eval", C.c_void_p), ("d_state_eval", C.c_void_p), ("n_pieces", C.c_int), ("n_values", C.c_int),
+                ("mode", C.c_int), ("flags", C.c_int), ("sample_seed", C.c_uint32), ("reserved", C.c_uint32), ("draw", C.c_uint64),
+                ("epsilon", C.c_float), ("table", C.c_void_p), ("d_player", C.c_void_p), ("d_rot", C.c_void_p), ("d_trans", C.c_void_p),
+                ("d_piece", C.c_void_p), ("d_eval", C.c_void_p), ("d_value", C.c_void_p), ("d_entropy", C.c_void_p)]
+
+
+def pareto_table(theta):
+    """The RANK table of the reference's pareto (tools/utils.py:88-91): (k + 1) ** -theta for rank k + 1, float32 [40]."""
+    return (np.arange(1, 41, dtype=np.float64) ** -float(theta)).astype(np.float32)
+
+
+def act_entropy(mode, epsilon=0.0, table=None):
+    """The entropy the reference reports for the modes whose entropy does not depend on the evaluation (sventon_utils.py:21-45,
+    tools/utils.py:93-94): argmax 0; epsilon: of e / 40 everywhere plus 1 - e on one entry, e = min(1, epsilon); rank: of the
+    normalised table.  (PI's depends on the map: tetris_select_eval_dev writes it per game.)"""
+    entropy = lambda p: float(-np.sum(p * np.log(p + 1e-8)))                  # noqa: E731
+    if mode == "argmax":
+        return 0.0
+    if mode == "epsilon":
+        e = min(1.0, float(epsilon))
+        p = e * np.full(40, 1.0 / 40)
+        p[0] += 1.0 - e
+        return entropy(p)
+    if mode == "rank":
+        t = np.asarray(table, np.float64)
+        return entropy(t / t.sum())
+    raise ValueError(f"the entropy of mode {mode!r} is a per-game output")
+
+
 class TetrisError(RuntimeError):
     pass
 
@@ -101,6 +136,10 @@ _SIGNATURES = {
                                          C.c_void_p, C.c_void_p]),
     "tetris_rollout_policy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
     "tetris_rollout_game_totals_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_select_eval_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_step_eval_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tetris_step_eval_observe_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_observe_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_observe_packed_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_create_split": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -416,6 +455,42 @@ class TetrisBatch:
         self._check(self.lib.tetris_rollout_policy(self._h, int(launches), int(steps_per_launch), weights, 1 if per_game else 0,
                                                    int(first_step), int(ms), _p(counters), C.byref(elapsed)))
         return counters, float(elapsed.value)
+
+    # -- acting on a network's (r, t, piece) evaluation (include/tetris_hip.h: tetris_select_eval_dev and the two after it)
+    def act_eval(self, action_eval, rot, trans, n_pieces=7, f16=False, state_eval=None, n_values=1, value_f16=False, mode="argmax",
+                 player=None, seed=0, draw=0, epsilon=0.0, table=None, piece=None, eval=None, value=None, entropy=None, flags=0):
+        """The argument struct of the three calls below.  Array arguments are raw DEVICE addresses (int / c_void_p) or None, but
+        `table`: a host float32 [40] array (RANK; pareto_table(theta) gives the reference's).  mode: a key of ACT_MODES or a number.
+        action_eval [N][4][10][n_pieces] float32 (f16: binary16), state_eval [N][n_values]; rot / trans / piece uint8 [N], eval
+        float32 [N], value float32 [2][N], entropy float32 [N] (PI)."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        e = ActEval()
+        e.d_action_eval, e.d_state_eval, e.n_pieces, e.n_values = val(action_eval), val(state_eval), int(n_pieces), int(n_values)
+        e.mode = ACT_MODES[mode] if isinstance(mode, str) else int(mode)
+        e.flags = (1 if f16 else 0) | (2 if value_f16 else 0) | int(flags)
+        e.sample_seed, e.draw, e.epsilon = int(seed) & 0xFFFFFFFF, int(draw), float(epsilon)
+        if table is not None:
+            e._table = np.ascontiguousarray(table, dtype=np.float32)             # kept alive with the struct
+            if e._table.shape != (40,):
+                raise ValueError("table must hold 40 float32")
+            e.table = e._table.ctypes.data
+        e.d_player, e.d_rot, e.d_trans, e.d_piece = val(player), val(rot), val(trans), val(piece)
+        e.d_eval, e.d_value, e.d_entropy = val(eval), val(value), val(entropy)
+        return e
+
+    def select_eval_dev(self, e):
+        """The choice of every game from the network's evaluation (e = act_eval(...)); the games are not changed."""
+        self._check(self.lib.tetris_select_eval_dev(self._h, C.byref(e) if e is not None else None))
+
+    def step_eval_dev(self, e, done, lines, dead, ms=400, auto_reset=False):
+        """select_eval_dev + step_rt_dev in one call: done [N], lines / dead [P][N] (each may be None)."""
+        self._check(self.lib.tetris_step_eval_dev(self._h, C.byref(e) if e is not None else None, int(ms), 1 if auto_reset else 0,
+                                                  done, lines, dead))
+
+    def step_eval_observe_dev(self, e, done, lines, dead, next_player, visual, vector, piece, ms=400, auto_reset=False):
+        """step_eval_dev and the packed observation of the stepped state (perspective of next_player), as step_rt_observe_dev."""
+        self._check(self.lib.tetris_step_eval_observe_dev(self._h, C.byref(e) if e is not None else None, int(ms), 1 if auto_reset else 0,
+                                                          done, lines, dead, next_player, visual, vector, piece))
 
     def rollout_game_totals_dev(self, totals):
         """The per-game words rollout_totals sums: totals uint32 [4][N] = env-steps, episodes, lines cleared, garbage lines sent."""

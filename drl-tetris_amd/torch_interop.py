@@ -224,3 +224,64 @@ class TorchEnv:
             self.policy_totals = self.torch.zeros(4, self.b.n_games, dtype=self.torch.int32, device=self.dev)
         self.b.rollout_game_totals_dev(self._ptr(self.policy_totals))
         return self.policy_totals
+
+    # ---- acting on a network's (r, t, piece) evaluation (include/tetris_hip.h: tetris_select_eval_dev and the two after it):
+    # the part of sventon_agent.get_action between the network and perform_action
+    def _act_eval(self, action_eval, state_eval, mode, player, seed, draw, epsilon, theta, table):
+        """-> (the argument struct, value or None, entropy): the checks and the reused output tensors of the three calls"""
+        from . import capi
+        torch, n = self.torch, self.b.n_games
+        for t in (action_eval,) + (() if state_eval is None else (state_eval,)):
+            assert t.dtype in (torch.float32, torch.float16) and t.is_cuda and t.is_contiguous(), "evaluations are contiguous float32 or float16 device tensors"
+        assert action_eval.dim() == 4 and tuple(action_eval.shape[:3]) == (n, 4, 10) and action_eval.shape[3] in (1, 7), "action_eval must be [n, 4, 10, 7 or 1]"
+        if state_eval is not None:
+            assert state_eval.dim() == 2 and state_eval.shape[0] == n and state_eval.shape[1] in (1, 7, 8), "state_eval must be [n, 1, 7 or 8]"
+        self._check_player(player)
+        if getattr(self, "act_rot", None) is None:
+            u8, f32 = dict(dtype=torch.uint8, device=self.dev), dict(dtype=torch.float32, device=self.dev)
+            self.act_rot, self.act_trans, self.act_piece = torch.zeros(n, **u8), torch.zeros(n, **u8), torch.zeros(n, **u8)
+            self.act_chosen, self.act_value, self.act_entropy = torch.zeros(n, **f32), torch.zeros(2, n, **f32), torch.zeros(n, **f32)
+        if mode == "rank":
+            assert (theta is None) != (table is None), "the rank mode takes theta or a table"
+            table = capi.pareto_table(theta) if table is None else np.ascontiguousarray(table, dtype=np.float32)
+        else:
+            table = None
+        e = self.b.act_eval(self._ptr(action_eval), self._ptr(self.act_rot), self._ptr(self.act_trans), n_pieces=action_eval.shape[3],
+                            f16=action_eval.dtype == torch.float16, state_eval=self._ptr(state_eval),
+                            n_values=1 if state_eval is None else state_eval.shape[1],
+                            value_f16=state_eval is not None and state_eval.dtype == torch.float16, mode=mode, player=self._ptr(player),
+                            seed=seed, draw=draw, epsilon=epsilon, table=table, piece=self._ptr(self.act_piece), eval=self._ptr(self.act_chosen),
+                            value=None if state_eval is None else self._ptr(self.act_value), entropy=self._ptr(self.act_entropy) if mode == "pi" else None)
+        entropy = self.act_entropy if mode == "pi" else capi.act_entropy(mode, epsilon, table)
+        return e, (None if state_eval is None else self.act_value), entropy
+
+    def select_eval(self, action_eval, state_eval=None, mode="argmax", player=None, seed=0, draw=0, epsilon=0.0, theta=None, table=None):
+        """The (r, t) of every game from the network's action_eval [n, 4, 10, K] (K = 7, or 1 with the piece in the state vector;
+        float32 or float16): the map of the piece the game holds, then mode "argmax", "pi" (the map as a distribution), "rank" (the
+        reference's pareto: theta, or a table of 40 weights by rank) or "epsilon".  The draw is keyed by (seed, global game id,
+        draw): pass the agent's step as `draw`.  state_eval [n, V] (V = 1, 7, 8) gives value = (v(s | piece), mean v(s)).
+        -> (rot [n], trans [n], piece [n] uint8, eval float32 [n] = the chosen entry, value float32 [2, n] or None, entropy:
+        float32 [n] for "pi", else the reference's number as a Python float) — device tensors, reused; rot / trans feed step_rt
+        unchanged.  The games are not changed; nothing waits for the GPU."""
+        e, value, entropy = self._act_eval(action_eval, state_eval, mode, player, seed, draw, epsilon, theta, table)
+        self.b.select_eval_dev(e)
+        return self.act_rot, self.act_trans, self.act_piece, self.act_chosen, value, entropy
+
+    def step_eval(self, action_eval, state_eval=None, mode="argmax", player=None, seed=0, draw=0, epsilon=0.0, theta=None, table=None,
+                  ms=400, auto_reset=False):
+        """select_eval + step_rt in one call: -> (done [n], lines [P, n], dead [P, n]) + select_eval's outputs; auto_reset as for
+        step_rt."""
+        e, value, entropy = self._act_eval(action_eval, state_eval, mode, player, seed, draw, epsilon, theta, table)
+        self.b.step_eval_dev(e, self._ptr(self.done), self._ptr(self.lines), self._ptr(self.dead), ms=ms, auto_reset=auto_reset)
+        return self.done, self.lines, self.dead, self.act_rot, self.act_trans, self.act_piece, self.act_chosen, value, entropy
+
+    def step_eval_observe(self, action_eval, state_eval=None, mode="argmax", player=None, next_player=None, seed=0, draw=0, epsilon=0.0,
+                          theta=None, table=None, ms=400, auto_reset=False):
+        """step_eval and observe(next_player) of the stepped state (one or two players): -> (done, lines, dead, visual, vector,
+        piece [S, n] of the observation) + select_eval's outputs.  The agent loop is network forward, this call, network forward."""
+        self._check_player(next_player)
+        e, value, entropy = self._act_eval(action_eval, state_eval, mode, player, seed, draw, epsilon, theta, table)
+        self.b.step_eval_observe_dev(e, self._ptr(self.done), self._ptr(self.lines), self._ptr(self.dead), self._ptr(next_player),
+                                     self._ptr(self.visual), self._ptr(self.vector), self._ptr(self.piece), ms=ms, auto_reset=auto_reset)
+        return (self.done, self.lines, self.dead, self.visual, self.vector, self.piece, self.act_rot, self.act_trans, self.act_piece,
+                self.act_chosen, value, entropy)

@@ -327,6 +327,81 @@ int tetris_rollout_policy(tetris_batch *b, int launches, int steps_per_launch, c
  * of every game — a population's fitness without a host loop.  Asynchronous.                                             */
 int tetris_rollout_game_totals_dev(tetris_batch *b, uint32_t *d_totals);
 
+/* ---- acting on a network's (r, t, piece) evaluation on the device ---------------------------------------------------------
+ * replaces: the part of sventon_agent.get_action between the network and perform_action (agents/sventon_agent/sventon_agent.py:
+ * 56-98 with sventon_utils.py:15-76: action_argmax / action_distribution / action_pareto / action_epsilongreedy, value_piece,
+ * value_mean) for every game of a batch at once: with the network in torch on the same GPU the agent loop is network forward,
+ * one call, network forward.
+ * For game i the acting player is p = d_player[i] (NULL: player 0; out-of-range entries are clamped).  PIECE is the kind held in
+ * p's board now — the index tetris_observe_packed writes to `piece` (state_dict "piece_idx") — limited to K - 1.  K = n_pieces
+ * is the last dimension of the evaluation: 7, or 1 when the network takes the piece in its state vector (the piece is then 0).
+ * d_action_eval is a contiguous [N][4][10][K] array of float32, or of IEEE binary16 with TETRIS_ACT_F16.  Candidate c = 10 r + t
+ * (r = 0..3, t = 0..9) has the value x[c] = d_action_eval[i][r][t][piece], taken to float32 exactly.
+ * The CHOICE, by mode:
+ *   TETRIS_ACT_ARGMAX   (action_argmax)  the highest x[c] among the candidates that are not NaN, among equals the lowest c
+ *                       (values are compared with `>`, so a NaN never wins); if all 40 are NaN the choice is 0.
+ *   TETRIS_ACT_PI       (action_distribution)  the inverse-CDF draw below with the weights m[c] = x[c] > 0 ? x[c] : 0.
+ *   TETRIS_ACT_RANK     (action_pareto / tools.utils.pareto)  rank[c] = 1 + the number of c' with x[c'] > x[c], or x[c'] == x[c]
+ *                       and c' < c (scipy.stats.rankdata(n - x, 'ordinal')); the draw below with m[c] = table[rank[c] - 1].
+ *                       `table` is a HOST array of 40 float32, read during the call; the reference's pareto with temperature
+ *                       theta is table[k] = (k + 1) ** -theta.  It comes from the host so that no powf runs on the device.
+ *   TETRIS_ACT_EPSILON  (action_epsilongreedy)  with e = (w1 >> 8) * 2^-24: if e < epsilon then r = w2 & 3, t = w3 mod 10,
+ *                       otherwise ARGMAX's choice.
+ * The DRAW: w[0..3] = Philox4x32-10 with key (sample_seed, 0) and counter (global game id, low word of `draw`, high word of
+ * `draw`, 0) — the function and key layout of the built-in synthetic rollout, global game id = tetris_set_game_offset + i: the
+ * stream is reproducible and does not depend on how games are spread over batches.  u = (w0 >> 8) * 2^-24; total = the float32
+ * sum of m[0..39] in index order; target = u * total; the choice is the first c whose running sum (the same partial sums) is
+ * > target, if there is none the last c with m[c] > 0, and if total is not a positive finite number ARGMAX's choice.  No fused
+ * multiply-adds.  Every path ends with 0 <= c < 40 whatever the input bits are.
+ * OUTPUTS per game, all optional except d_rot and d_trans:
+ *   d_rot, d_trans uint8 [N]   c / 10 and c mod 10; they feed tetris_step_rt_dev unchanged
+ *   d_piece  uint8 [N]         the piece index used
+ *   d_eval   float32 [N]       x[c] (the reference's a_internal[0])
+ *   d_value  float32 [2][N]    from d_state_eval [N][V], V = n_values in {1, 7, 8}, float32 or binary16 (TETRIS_ACT_VALUE_F16):
+ *                              [0] = V > 1 ? state_eval[i][min(piece, V - 1)] : state_eval[i][0] (value_piece),
+ *                              [1] = the float32 sum of state_eval[i][0..V-1] in index order divided by (float)V (value_mean)
+ *   d_entropy float32 [N]      PI only: -sum over c of q log(q + 1e-8), q = x[c] + 1e-6, in float32 with the accurate logf,
+ *                              summed in index order.  (The other modes' entropies depend on epsilon or the table alone.)
+ * One to four players, every height, colour batches included; not on split batches.  Device pointers (but `table`),
+ * asynchronous on the batch's stream, run-ahead bounded and RNG-table requests serviced as for tetris_step_rt_dev_ex.
+ * TETRIS_E_ARG: a NULL argument struct, d_action_eval, d_rot or d_trans; n_pieces not 1 or 7; d_state_eval with n_values not
+ * 1, 7 or 8, or d_value without d_state_eval; an unknown mode or flag; RANK without a table; d_entropy in another mode than PI;
+ * a d_action_eval that is not 16-byte aligned; a split batch.                                                              */
+#define TETRIS_ACT_ARGMAX  0
+#define TETRIS_ACT_PI      1
+#define TETRIS_ACT_RANK    2
+#define TETRIS_ACT_EPSILON 3
+#define TETRIS_ACT_F16       1   /* d_action_eval is IEEE binary16 instead of float32 */
+#define TETRIS_ACT_VALUE_F16 2   /* d_state_eval is IEEE binary16 instead of float32 */
+typedef struct tetris_act_eval {
+    const void    *d_action_eval;   /* [N][4][10][n_pieces] */
+    const void    *d_state_eval;    /* [N][n_values], or NULL */
+    int            n_pieces;        /* K */
+    int            n_values;        /* V */
+    int            mode;            /* TETRIS_ACT_ARGMAX .. TETRIS_ACT_EPSILON */
+    int            flags;           /* TETRIS_ACT_F16 | TETRIS_ACT_VALUE_F16 */
+    uint32_t       sample_seed;
+    uint32_t       reserved;        /* 0 */
+    uint64_t       draw;            /* the number of this draw, e.g. the agent's step */
+    float          epsilon;
+    const float   *table;           /* HOST float32 [40] (RANK), else NULL */
+    const uint8_t *d_player;        /* [N] or NULL */
+    uint8_t       *d_rot, *d_trans, *d_piece;
+    float         *d_eval, *d_value, *d_entropy;
+} tetris_act_eval;
+/* the choice and its outputs.  The batch's state is not written.                                                          */
+int tetris_select_eval_dev(tetris_batch *b, const tetris_act_eval *e);
+/* the choice and perform_action of it (tetris_environment.py:102-116) in one call: tetris_select_eval_dev followed by
+ * tetris_step_rt_dev_ex, bit for bit.  flags: TETRIS_STEP_AUTO_RESET as there; d_done [N], d_lines / d_dead [P][N] describe the
+ * step before the reset (each may be NULL).                                                                               */
+int tetris_step_eval_dev(tetris_batch *b, const tetris_act_eval *e, int ms, int flags, uint8_t *d_done, uint8_t *d_lines,
+                         uint8_t *d_dead);
+/* the same plus the packed observation of the stepped state for d_next_player, as tetris_step_rt_observe_dev gives it (one or
+ * two players): the selection kernel followed by that call's launch.  d_obs_piece [P][N] is the observation's piece output. */
+int tetris_step_eval_observe_dev(tetris_batch *b, const tetris_act_eval *e, int ms, int flags, uint8_t *d_done,
+                                 uint8_t *d_lines, uint8_t *d_dead, const uint8_t *d_next_player, uint8_t *d_visual,
+                                 uint8_t *d_vector, uint8_t *d_obs_piece);
+
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
  * t = w1 mod 10), acting player = step mod P, perform_action, auto-reset of finished games with
