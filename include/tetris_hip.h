@@ -25,6 +25,14 @@
  *    run through the general one-lane-per-game kernel (all of a game's players in one lane); the packed observation
  *    (own / opponent planes), the one-launch step + observation, split batches and chained launches are one- and
  *    two-player features.
+ *  - `ms` (every stepping entry point) = the game time that passes per action: the reference's
+ *    settings["time_elapsed_each_action"] (400 in its presets), which tetris_environment.py:110 hands to finish_action(ms).  Any
+ *    non-negative int; 0 (time stands still) to 60 000 is tested against the compiled reference and the oracle.
+ *    The episode clock is an int32 as in the reference (gamePlay.h:64) and starts at 0 with every reset: one episode
+ *    may last 2^31 ms of game time, 35 791 actions at 60 000 ms.  A small `ms` makes one capacity limit easier to hit: garbage
+ *    packets wait 1000 ms of game time in the queue, so the fewer milliseconds pass per action the more packets are pending at
+ *    once — 8 per board at most (TETRIS_ERR_FIFO below; strong two-player play reaches 8 at 0..1 ms, 7 at 50 ms, 4 at 100 ms
+ *    and above).
  */
 #ifndef TETRIS_HIP_H
 #define TETRIS_HIP_H

@@ -24,9 +24,14 @@ from tests.golden.ref_driver import RefGame  # noqa: E402
 MAXK = 32
 
 
-def record_trace(name, P, H, pieces, seed0, steps, policy, sloppiness=0.0, early_reset_every=0, record_actions=False, solo=None):
-    """One game driven for `steps` env-steps; reset with seed0 + 17*episode on done.
-    solo = p: only player p ever acts (the others get [0] every step, tetris_environment.py:102-107)."""
+MAX_PENDING = 6      # the engine queues 8 garbage packets per board; a trace stays clear of that (tests/test_edge_cases.py has the rule)
+
+
+def record_trace(name, P, H, pieces, seed0, steps, policy, sloppiness=0.0, early_reset_every=0, record_actions=False, solo=None, ms=400):
+    """One game driven for `steps` env-steps of `ms` milliseconds (settings["time_elapsed_each_action"], tetris_environment.py:110);
+    reset with seed0 + 17*episode on done.
+    solo = p: only player p ever acts (the others get [0] every step, tetris_environment.py:102-107).
+    Nothing is written if the reference ever shows more than MAX_PENDING garbage packets pending on a board."""
     rng = np.random.default_rng(abs(hash((name, seed0))) % (2**32))
     ref = RefGame(P, H, 10, pieces=pieces, seed=seed0)
     shadow = orc.OracleBatch(1, P, H, 10, pieces=pieces, seeds=seed0)   # only feeds the greedy policy
@@ -84,10 +89,10 @@ def record_trace(name, P, H, pieces, seed0, steps, policy, sloppiness=0.0, early
         else:
             raise ValueError(policy)
         keys = [int(k) for k in keys][:MAXK]
-        done = ref.step(keys, player)
+        done = ref.step(keys, player, ms)
         K = np.zeros((1, P, MAXK), np.uint8); L = np.ones((1, P), np.uint8)
         K[0, player, : len(keys)] = keys; L[0, player] = len(keys)
-        shadow.make_actions(K, L); shadow.finish_actions(400)
+        shadow.make_actions(K, L); shadow.finish_actions(ms)
         kk = np.zeros(MAXK, np.uint8); kk[: len(keys)] = keys
         ev_kind.append(1); ev_seed.append(0); ev_player.append(player)
         ev_keys.append(kk); ev_len.append(len(keys)); ev_done.append(int(done))
@@ -96,7 +101,7 @@ def record_trace(name, P, H, pieces, seed0, steps, policy, sloppiness=0.0, early
             episode += 1
             do_reset(seed0 + 17 * episode)
     out = dict(
-        n_players=P, height=H, width=10, pieces=np.array((list(pieces) * 7)[:7], np.uint8), ms=400,
+        n_players=P, height=H, width=10, pieces=np.array((list(pieces) * 7)[:7], np.uint8), ms=ms,
         ev_kind=np.array(ev_kind, np.uint8),          # 2 = constructed, 0 = reset(seed), 1 = step
         ev_seed=np.array(ev_seed, np.int64), ev_player=np.array(ev_player, np.uint8),
         ev_keys=np.stack(ev_keys), ev_len=np.array(ev_len, np.uint8), ev_done=np.array(ev_done, np.uint8),
@@ -105,10 +110,15 @@ def record_trace(name, P, H, pieces, seed0, steps, policy, sloppiness=0.0, early
     if record_actions:
         out.update(act_keys=np.stack(act_keys), act_lens=np.stack(act_lens), act_n=np.array(act_n, np.int32),
                    act_player=np.array(act_player, np.uint8))
+    pending = int(out["records"]["fifo_len"].max())
+    if pending > MAX_PENDING:
+        raise ValueError(f"{name}: the reference had {pending} garbage packets pending on one board (at most {MAX_PENDING} in a fixture)")
     path = os.path.join(HERE, f"trace_{name}.npz")
     np.savez_compressed(path, **out)
     cleared = int(out["records"]["reward"][out["ev_kind"] == 1].sum())
-    print(f"{name}: {len(ev_kind)} events, {episode} resets, {cleared} lines, {os.path.getsize(path) / 1024:.0f} KiB")
+    r = out["records"]
+    print(f"{name}: ms {ms}, {len(ev_kind)} events, {episode} resets, {cleared} lines, pending <= {pending}, combo <= {int(r['combo_count'].max())}, "
+          f"drop_delay >= {int(r['drop_delay'][2:].min())}, time_ms <= {int(r['time_ms'].max())}, {os.path.getsize(path)} bytes")
 
 
 def rotation_table():
@@ -183,13 +193,33 @@ TRACES = {
     "keys_4p": dict(P=4, H=20, pieces="all", seed0=12, steps=2000, policy="keys"),
     "greedy_3p_io": dict(P=3, H=20, pieces=[6, 4], seed0=5, steps=2400, policy="greedy", sloppiness=0.03),
     "greedy_4p_o": dict(P=4, H=20, pieces=[6], seed0=19, steps=2400, policy="greedy", sloppiness=0.03),
+    # elapsed times per action other than 400 ms (settings["time_elapsed_each_action"]): the timers of dropDelay.cpp, garbage.cpp and
+    # combo.cpp in other regimes.  50: combos far longer than at 400.  100: packets wait in the queue for many steps and get blocked.
+    # 170: timers cross at non-multiples of the tick, lock-down by the timer.  401: lock-down fires on the first tick.  3001: a speed-up
+    # every tick, drop delay down to its floor of 10.  1500: a packet is released on the tick after it arrived (three players: half
+    # lines).  0: time stands still.  60000: many lines per clear (Combo.cpp:40 multiplies by 1 + t / 60000 * 0.1), which ends every
+    # two-player round long before the clock reaches 2^24; the one-player trace at 60001 passes it after 280 steps with odd clock
+    # values, which the int -> float conversion there rounds.
+    "greedy_1p_ms50": dict(P=1, H=20, pieces="all", seed0=1050, steps=1200, policy="greedy", ms=50),
+    "greedy_2p_ms100": dict(P=2, H=20, pieces="all", seed0=1100, steps=1400, policy="greedy", sloppiness=0.05, ms=100),
+    # (seed 172: of the seeds 170..199 one in six has a piece locked by the timer within 1400 steps — at 170 ms that takes three ticks
+    # without a hard drop or a row of gravity on a board stacked up to the spawn rows; 172 is the first)
+    "keys_2p_ms170": dict(P=2, H=20, pieces="all", seed0=172, steps=1400, policy="keys", ms=170),
+    "keys_2p_ms401": dict(P=2, H=20, pieces="all", seed0=401, steps=1400, policy="keys", ms=401),
+    "greedy_1p_ms3001": dict(P=1, H=20, pieces="all", seed0=3001, steps=1200, policy="greedy", ms=3001),
+    "greedy_3p_io_ms1500": dict(P=3, H=20, pieces=[6, 4], seed0=1500, steps=1400, policy="greedy", ms=1500),
+    "rt_2p_ms0": dict(P=2, H=20, pieces="all", seed0=2000, steps=1200, policy="rt", ms=0),
+    "greedy_2p_ms60000": dict(P=2, H=20, pieces="all", seed0=6000, steps=1200, policy="greedy", ms=60000),
+    "greedy_1p_ms60001": dict(P=1, H=20, pieces="all", seed0=6001, steps=700, policy="greedy", ms=60001),
 }
 
 
 def main():
     """no arguments: every trace + the tables (NOTE: the random policies are seeded from hash((name, seed)), which
     differs between Python processes unless PYTHONHASHSEED is fixed — regenerate single traces by name instead:
-        python tests/golden/make_golden.py garbage_flood_2p ...)"""
+        python tests/golden/make_golden.py garbage_flood_2p ...
+    The greedy and drop traces do not draw from that generator and come out the same in every process, apart from combo_remaining
+    before the first step, which the reference leaves uninitialised.  The *_ms* traces were recorded with PYTHONHASHSEED=0.)"""
     orc.build()
     if not orc.ref_available():
         sys.exit("oracle/_ref is not built and /root/reference is absent: cannot generate fixtures here")

@@ -18,8 +18,8 @@ pytestmark = pytest.mark.gpu
 FELL_BACK = 4
 
 
-def _check(eng, ref, n, total, steps):
-    _, want = ref.rollout_random(steps, threads=min(32, len(os.sched_getaffinity(0))))
+def _check(eng, ref, n, total, steps, ms=400):
+    _, want = ref.rollout_random(steps, ms=ms, threads=min(32, len(os.sched_getaffinity(0))))
     assert total.tolist() == want.tolist()
     for lo in range(0, n, 8192):
         idx = np.arange(lo, min(n, lo + 8192), dtype=np.int32)
@@ -30,33 +30,43 @@ def _check(eng, ref, n, total, steps):
 def test_a_late_predecessor_makes_the_call_fall_back_and_the_results_stay_exact(P, n, direct):
     """Chain stream 1 is held by an idle kernel for 30 ms while the bound of a waiting wave is ~1 ms: the launches on the other
     streams give up, the call completes un-chained — OK, every board and the counters equal the oracle, fell-back bit reported."""
+    _late_predecessor(P, n, direct, 400)
+
+
+def test_the_recovery_of_a_fallen_back_call_steps_at_the_calls_elapsed_time():
+    """the same at 170 ms per step (two players, the HIP streams): the un-chained kernel that finishes the games the waves left
+    untouched must step them at the call's `ms`, not at the default"""
+    _late_predecessor(2, 8192, False, 170)
+
+
+def _late_predecessor(P, n, direct, ms):
     seeds = orc.episode_seed(np.arange(n), 0)
     eng, ref = engines.make("hip", n, P, seeds=seeds), engines.make("oracle", n, P, seeds=seeds)
     assert eng.rollout_is_chained(1)
     eng.set_direct_dispatch(direct)                        # the library's own queues (calls of >= 16 launches) / the HIP streams
     total = np.zeros(4, np.uint64)
-    c, _ = eng.rollout_random(40, 1)                       # chained, undisturbed
+    c, _ = eng.rollout_random(40, 1, ms=ms)                # chained, undisturbed
     total += c
     assert eng.take_errors() == 0 and eng.rollout_is_chained(1)
     eng.set_chain_spin_limit(2000)                         # ~1 ms
     before = eng.rollout_totals()                          # (synchronises: nothing may drain the streams between the stall and the launches)
     eng.debug_stall(1, 30000)                              # the second launch of the next call (and every third after it) starts 30 ms late
     stalled = 50 if P == 2 else 300                        # (300 on the streams: the call that is enqueued by one host thread per stream)
-    eng.rollout_launch(stalled, 1, first_step=40)
+    eng.rollout_launch(stalled, 1, first_step=40, ms=ms)
     assert eng.rollout_was_direct() == direct
     total += eng.rollout_totals() - before
     assert eng.take_errors() == FELL_BACK
     assert eng.take_errors() == 0                          # reported once
     assert not eng.rollout_is_chained(1)                   # off until switched on again
-    c, _ = eng.rollout_random(10, 1, first_step=40 + stalled)        # un-chained
+    c, _ = eng.rollout_random(10, 1, first_step=40 + stalled, ms=ms)        # un-chained
     total += c
     eng.set_chained(True)
     eng.set_chain_spin_limit(0)
     assert eng.rollout_is_chained(1)
-    c, _ = eng.rollout_random(28, 1, first_step=50 + stalled)        # chained again, from the epoch words the recovery left
+    c, _ = eng.rollout_random(28, 1, first_step=50 + stalled, ms=ms)        # chained again, from the epoch words the recovery left
     total += c
     assert eng.take_errors() == 0
-    _check(eng, ref, n, total, 78 + stalled)
+    _check(eng, ref, n, total, 78 + stalled, ms)
 
 
 def test_a_co_tenant_that_holds_most_wave_slots_costs_time_not_results():

@@ -37,18 +37,19 @@ def _pool_seeds(pool):
 
 # ---------------------------------------------------------------- 1. seeding
 @functools.lru_cache(maxsize=None)
-def _model_pool(P, H):
-    """-> the oracle pool after the model's play, the actions [(rot, trans, player, done)], the pool games that did not end"""
-    pool = engines.make("oracle", POOL, P, height=H, seeds=_pool_seeds(POOL))
+def _model_pool(P, H, ms=400, prep=None, pool_size=POOL, survivors=0.75):
+    """-> the oracle pool after the model's play (`prep` steps of `ms` milliseconds; PREP[P] if None), the actions
+    [(rot, trans, player, done)], the pool games that did not end"""
+    pool = engines.make("oracle", pool_size, P, height=H, seeds=_pool_seeds(pool_size))
     m = Model(pool)
-    ended, actions = np.zeros(POOL, bool), []
-    for s in range(PREP[P]):                        # (no auto-reset)
+    ended, actions = np.zeros(pool_size, bool), []
+    for s in range(PREP[P] if prep is None else prep):                        # (no auto-reset)
         r, t, _ = m.choose(W_A, s % P)
-        done = pool.step_rt(r, t, s % P)
+        done = pool.step_rt(r, t, s % P, ms=ms)
         ended |= done > 0
         actions.append((r.copy(), t.copy(), s % P, done.copy()))
     keep = np.nonzero(~ended)[0].astype(np.int32)
-    assert 4 * len(keep) >= 3 * POOL, f"only {len(keep)} of {POOL} pool games survive the preparation"
+    assert len(keep) >= survivors * pool_size, f"only {len(keep)} of {pool_size} pool games survive the preparation"
     return pool, tuple(actions), keep
 
 
@@ -67,12 +68,12 @@ def _o_pool(boundary):
     return pool, tuple(actions), np.arange(8, dtype=np.int32)
 
 
-def _seeded(kind, n, P, H, prepared, pieces=(0, 1, 2, 3, 4, 5, 6)):
-    """-> engine batch and oracle batch of n games tiled from the prepared pool, equal before any rollout"""
+def _seeded(kind, n, P, H, prepared, pieces=(0, 1, 2, 3, 4, 5, 6), ms=400):
+    """-> engine batch and oracle batch of n games tiled from the prepared pool (played at `ms` per step), equal before any rollout"""
     pool_ref, actions, keep = prepared
     pool_eng = engines.make(kind, pool_ref.n_games, P, height=H, pieces=pieces, seeds=_pool_seeds(pool_ref.n_games))
     for s, (r, t, player, done) in enumerate(actions):
-        assert np.array_equal(pool_eng.step_rt(r, t, player), done), f"preparation step {s}: done flags"
+        assert np.array_equal(pool_eng.step_rt(r, t, player, ms=ms), done), f"preparation step {s}: done flags"
     engines.assert_same_state(pool_eng, pool_ref, where="the pool after the preparation")
     src = keep[np.arange(n) % len(keep)]
     eng = engines.make(kind, n, P, height=H, pieces=pieces, seeds=_pool_seeds(n))
@@ -88,8 +89,8 @@ def _seeded(kind, n, P, H, prepared, pieces=(0, 1, 2, 3, 4, 5, 6)):
 class Census:
     """Steps an oracle batch one step per rollout_random call (carrying its episode array) and keeps what was seen."""
 
-    def __init__(self, ref):
-        self.ref, self.episode, self.step = ref, None, 0
+    def __init__(self, ref, ms=400):
+        self.ref, self.ms, self.episode, self.step = ref, ms, None, 0
         self.total = np.zeros(4, np.uint64)
         self.seen = dict(reward=0, combo=0, fifo=0, blocked=0, holes=0, draws=0,
                          multi_clears=0, combo2=0, combo3=0, fifo2=0, blocked_steps=0, hole_steps=0)     # these: board-steps
@@ -109,12 +110,13 @@ class Census:
         s["hole_steps"] += int((rec["hole_draws"] > prev["hole_draws"]).sum())
         return rec
 
-    def roll(self, steps):
-        """-> the oracle's counters of these steps"""
+    def roll(self, steps, ms=None):
+        """-> the oracle's counters of these steps (of `ms` milliseconds; the census's own if None)"""
+        ms = self.ms if ms is None else ms
         c = np.zeros(4, np.uint64)
         rec = self.ref.observe()[0]
         for _ in range(steps):
-            self.episode, one = self.ref.rollout_random(1, first_step=self.step, episode=self.episode)
+            self.episode, one = self.ref.rollout_random(1, first_step=self.step, ms=ms, episode=self.episode)
             c += one
             self.step += 1
             rec = self._look(rec)
@@ -134,10 +136,10 @@ class Census:
             assert s["blocked_steps"] >= 1 and s["hole_steps"] >= 1, "no rollout step blocked a line / drew a hole itself"
 
 
-def _call(eng, cen, launches, S, where):
+def _call(eng, cen, launches, S, where, ms=400):
     """one rollout call of the engine against the same steps of the oracle: counters and state"""
-    c, _ = eng.rollout_random(launches, S, first_step=cen.step)
-    want = cen.roll(launches * S)
+    c, _ = eng.rollout_random(launches, S, first_step=cen.step, ms=ms)
+    want = cen.roll(launches * S, ms=ms)
     assert c.tolist() == want.tolist(), f"{where}: counters {c.tolist()}, the oracle's {want.tolist()}"
     assert int(c[0]) == eng.n_games * launches * S
     engines.assert_same_state(eng, cen.ref, where=where)
@@ -187,15 +189,15 @@ def _assert_path(eng, path):
         assert not eng.rollout_was_affine()
 
 
-def _interleaved_step(eng, ref, rng, k):
+def _interleaved_step(eng, ref, rng, k, ms=400):
     """One step_rt of random (r, t) on the batch's stream between two chained calls, finished games reset with explicit seeds
     (tetris_reset leaves G_EPISODE alone, so the oracle's carried episode array still holds), then an observe: a stream kernel must
     meet current memory after a queue's last release, and the next chained call's first acquire must see the step."""
     n, P = eng.n_games, eng.n_players
     player = rng.integers(0, P, n).astype(np.uint8)
     r, t = rng.integers(0, 4, n).astype(np.uint8), rng.integers(0, 10, n).astype(np.uint8)
-    done = ref.step_rt(r, t, player)
-    assert np.array_equal(eng.step_rt(r, t, player), done), f"interleaved step {k}: done flags"
+    done = ref.step_rt(r, t, player, ms=ms)
+    assert np.array_equal(eng.step_rt(r, t, player, ms=ms), done), f"interleaved step {k}: done flags"
     d = np.nonzero(done)[0].astype(np.int32)
     if len(d):
         sd = orc.episode_seed(d, 1000 + k)

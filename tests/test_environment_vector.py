@@ -82,6 +82,81 @@ def test_worker_loop_matches_oracle(kind):
 
 
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+def test_time_elapsed_each_action_reaches_every_step(kind):
+    """settings["time_elapsed_each_action"] = 170 (tetris_environment.py:110 hands it to finish_action): perform_action,
+    simulate_actions and simulate_all_actions of the vector (their scratch batch steps at the setting too) and the single-env
+    wrapper's simulated step, against the oracle stepped with finish_actions(170) — the complete state, timers included."""
+    n, P, H, ms = 24, 2, 20, 170
+    clock = _Clock()
+    settings = {"n_players": P, "game_size": [H, 10], "seed_source": clock, "time_elapsed_each_action": ms}
+    pkg, env_mod, env = _make_env(kind, n, settings)
+    edt = __import__("importlib").import_module("drl-tetris_amd.data_types")
+    lib = ge.build_harness() if kind == "harness" else None
+    assert env.settings["time_elapsed_each_action"] == ms
+    ref = orc.OracleBatch(n, P, H, 10, seeds=1001)           # construction at seed 1001, then the always-once reset at 1002
+    ref.reset(seeds=1002)
+    rng = np.random.default_rng(170)
+
+    def oracle_afterstates(lists, p):
+        """one oracle game per (env, list): copy, make_actions, finish_actions(ms)"""
+        counts = [len(l) for l in lists]
+        T = sum(counts)
+        one = orc.OracleBatch(T, P, H, 10)
+        one.copy_from(ref, dst_idx=np.arange(T, dtype=np.int32), src_idx=np.repeat(np.arange(n), counts).astype(np.int32))
+        keys, lens = np.zeros((T, P, 48), np.uint8), np.ones((T, P), np.uint8)
+        for j, a in enumerate(a for l in lists for a in l):
+            keys[j, p, : len(a)] = a
+            lens[j, p] = len(a)
+        one.make_actions(keys, lens)
+        one.finish_actions(ms)
+        return one
+
+    def assert_states(states, one, where):
+        got = engines.make(kind, len(states), P, H)
+        got.restore(np.stack([st.backend_state.blob for st in states]))
+        engines.assert_same_state(got, one, where=where)
+        got.close()
+
+    simulated = 0
+    for it in range(60):
+        p = it % 2
+        if it % 12 == 5:
+            al = env.get_actions(player=p)
+            sims = env.simulate_all_actions(player=p, finalize=True)
+            assert_states([st for per_env in sims for st in per_env], oracle_afterstates(al, p), f"step {it}: simulate_all_actions")
+            some = [edt.action_list([[2, 7], [4, 7], [8, 6, 6], [5]]) for _ in range(n)]          # (the null action is put first)
+            sims = env.simulate_actions(some, player=p)
+            assert_states([st for per_env in sims for st in per_env], oracle_afterstates(some, p), f"step {it}: simulate_actions")
+            simulated += 1
+            engines.assert_same_state(env.backend, ref, where=f"step {it}: simulating must not move the env")
+            # the single-env wrapper: a simulated, finalized step of game 0's state
+            one_env = env_mod.tetris_environment(settings=settings, _lib_path=lib)
+            one_env.set(env.get_state()[0])
+            one_env.perform_action(edt.action([4, 7]), player=p, simulate=True, finalize=True)
+            want = oracle_afterstates([[[4, 7]]] + [[] for _ in range(n - 1)], p)
+            engines.assert_same_state(one_env.backend, want, where=f"step {it}: tetris_environment.perform_action(simulate=True)")
+            r1, d1 = one_env.perform_action(edt.action([7]), player=1 - p)
+            keys, lens = np.zeros((1, P, 4), np.uint8), np.ones((1, P), np.uint8)
+            keys[0, 1 - p, 0] = 7
+            want.make_actions(keys, lens)
+            assert bool(want.finish_actions(ms)[0]) == d1
+            engines.assert_same_state(one_env.backend, want, where=f"step {it}: tetris_environment.perform_action")
+        rs, ts = rng.integers(0, 4, n), rng.integers(0, 10, n)
+        actions = [edt.action([8] * int(r) + [2] + [3] * int(t) + [7]) for r, t in zip(rs, ts)]
+        _, done = env.perform_action(actions, player=p)
+        d_ref = ref.step_rt(rs.astype(np.uint8), ts.astype(np.uint8), np.full(n, p, np.uint8), ms=ms)
+        assert [bool(x) for x in done] == [bool(x) for x in d_ref], it
+        engines.assert_same_state(env.backend, ref, where=f"step {it}: perform_action")
+        reset_list = [i for i, d in enumerate(done) if d]
+        env.reset(env=reset_list)
+        if reset_list:
+            ref.reset(np.array(reset_list, np.int32), seeds=clock.t)
+    assert simulated == 5
+    t = ref.observe()[0]["time_ms"]
+    assert (t % ms == 0).all() and t.max() > 20 * ms
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
 def test_set_copy_simulate_and_winner(kind):
     n, P = 6, 2
     pkg, env_mod, env = _make_env(kind, n, {"n_players": P, "game_size": [20, 10], "seed_source": _Clock(50)})

@@ -80,10 +80,10 @@ def features(f):
 
 
 class Model:
-    """The policy on the oracle.  `o` is the OracleBatch it plays; weights int16 [8] or [N, 8]."""
+    """The policy on the oracle.  `o` is the OracleBatch it plays; weights int16 [8] or [N, 8]; ms = game time per step."""
 
-    def __init__(self, o, ids=None):
-        self.o = o
+    def __init__(self, o, ids=None, ms=400):
+        self.o, self.ms = o, ms
         self.ids = np.arange(o.n_games) if ids is None else np.asarray(ids)      # global game ids (the reset-seed schedule's key)
         self.scratch = orc.OracleBatch(40 * o.n_games, o.n_players, o.height, 10)
         self.episode = np.zeros(o.n_games, np.int64)
@@ -123,7 +123,7 @@ class Model:
         """step_rt + the reset of finished games by the built-in seed schedule -> done, lines [N, P], dead [N, P] before the reset"""
         o = self.o
         sent0 = o.observe()[0]["lines_sent"].astype(np.int64).sum(axis=1) if count else None
-        done = o.step_rt(rot, trans, player)
+        done = o.step_rt(rot, trans, player, ms=self.ms)
         rec = o.observe()[0]
         lines, dead = rec["reward"].copy(), rec["dead"].copy()
         if count:

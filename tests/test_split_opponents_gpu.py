@@ -45,6 +45,16 @@ class ThreadGather:
 
 @pytest.mark.parametrize("scenario,pieces", [("random", (0, 1, 2, 3, 4, 5, 6)), ("o_only", (6,))])
 def test_split_kernels_on_gpu_match_colocated_oracle(scenario, pieces):
+    _split_kernels_match_colocated_oracle(scenario, pieces, 400)
+
+
+def test_split_kernels_at_1500_ms_per_step():
+    """the three stages of tetris_split_stage_dev carry `ms`: at 1500 a garbage packet is released on the tick after it arrived,
+    so the exchanged words hold rows pushed and lines blocked in the same steps that send new ones"""
+    _split_kernels_match_colocated_oracle("o_only", (6,), 1500)
+
+
+def _split_kernels_match_colocated_oracle(scenario, pieces, ms):
     import importlib
 
     import tests.test_split_opponents_gloo as base
@@ -60,7 +70,7 @@ def test_split_kernels_on_gpu_match_colocated_oracle(scenario, pieces):
             dones, episode = [], np.zeros(N, np.int64)
             for s in range(STEPS):
                 rot, trans, acting = _actions(s, scenario)
-                done, _, _ = so.step_rt(rot, trans, acting)
+                done, _, _ = so.step_rt(rot, trans, acting, ms=ms)
                 dones.append(done)
                 idx = np.nonzero(done)[0].astype(np.int32)
                 if len(idx):
@@ -82,7 +92,7 @@ def test_split_kernels_on_gpu_match_colocated_oracle(scenario, pieces):
     episode, want = np.zeros(N, np.int64), []
     for s in range(STEPS):
         rot, trans, acting = _actions(s, scenario)
-        d = ref.step_rt(rot, trans, acting)
+        d = ref.step_rt(rot, trans, acting, ms=ms)
         want.append(d.copy())
         idx = np.nonzero(d)[0].astype(np.int32)
         if len(idx):
@@ -100,6 +110,9 @@ def test_split_kernels_on_gpu_match_colocated_oracle(scenario, pieces):
             assert np.array_equal(got[f][:, 0], rec[f][:, side]), (side, f)
         assert np.array_equal(got["field"][:, 0] > 0, rec["field"][:, side] > 0)
         assert np.array_equal(gro, ro) and np.array_equal(glw, lw)
+    if ms != 400:
+        print(f"split step_rt at {ms} ms: hole draws {int(rec['hole_draws'].sum())}, lines blocked {int(rec['lines_blocked'].sum())}")
+        assert rec["hole_draws"].sum() > 0, "no garbage row was pushed: the scenario does not reach the queue's timers"
 
 
 @pytest.mark.parametrize("N,STEPS", [(4096, 160), (65536, 96)], ids=["4096x160", "c5_per_gpu_size_65536x96"])
@@ -107,6 +120,15 @@ def test_split_rollout_kernels_on_gpu_match_oracle_rollout(N, STEPS):
     """Device-driven split rollout (policy + auto-reset inside the split kernels) on the GPU, both sides in one process.
     The second case is BASELINE config 5's per-GPU size: 65 536 games per side (each side = what one GPU of the 8 holds),
     96 steps, counters and EVERY board of both sides against the oracle's co-located two-player rollout on all host cores."""
+    _split_rollout_matches_oracle_rollout(N, STEPS, 400)
+
+
+def test_split_rollout_kernels_at_1500_ms_per_step():
+    """tetris_split_rollout_stage_dev carries `ms` through its four stages"""
+    _split_rollout_matches_oracle_rollout(4096, 160, 1500)
+
+
+def _split_rollout_matches_oracle_rollout(N, STEPS, ms):
     import importlib
     import os
 
@@ -119,7 +141,7 @@ def test_split_rollout_kernels_on_gpu_match_oracle_rollout(N, STEPS):
         try:
             tg.bind(side)
             so = mod.SplitOpponents(N, side=side, peer=1 - side, dist=tg, seeds=orc.episode_seed(np.arange(N), 0))
-            so.rollout(STEPS)
+            so.rollout(STEPS, ms=ms)
             results[side] = (so.batch.observe(), so.batch.rollout_totals())
             so.close()
         except Exception as e:
@@ -133,7 +155,7 @@ def test_split_rollout_kernels_on_gpu_match_oracle_rollout(N, STEPS):
         t.join()
     assert not errors, errors
     ref = orc.OracleBatch(N, 2, 20, 10, seeds=orc.episode_seed(np.arange(N), 0))
-    _, want = ref.rollout_random(STEPS, threads=min(32, len(os.sched_getaffinity(0))))
+    _, want = ref.rollout_random(STEPS, ms=ms, threads=min(32, len(os.sched_getaffinity(0))))
     rec, ro, lw = ref.observe()
     t0, t1 = results[0][1], results[1][1]
     assert int(t0[0]) == int(want[0]) == int(t1[0]) == N * STEPS          # env-steps, counted on the device
