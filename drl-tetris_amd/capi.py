@@ -50,6 +50,12 @@ class ActEval(C.Structure):
                 ("d_piece", C.c_void_p), ("d_eval", C.c_void_p), ("d_value", C.c_void_p), ("d_entropy", C.c_void_p)]
 
 
+class Traj(C.Structure):
+    """mirrors `struct tetris_traj` (include/tetris_hip.h)"""
+    _fields_ = [("capacity", C.c_int), ("reserved", C.c_int), ("d_action", C.c_void_p), ("d_prob", C.c_void_p), ("d_value", C.c_void_p),
+                ("d_reward", C.c_void_p), ("d_done", C.c_void_p)]
+
+
 def pareto_table(theta):
     """The RANK table of the reference's pareto (tools/utils.py:88-91): (k + 1) ** -theta for rank k + 1, float32 [40]."""
     return (np.arange(1, 41, dtype=np.float64) ** -float(theta)).astype(np.float32)
@@ -140,6 +146,9 @@ _SIGNATURES = {
     "tetris_step_eval_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_step_eval_observe_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tetris_traj_record_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tetris_traj_advantages_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
     "tetris_observe_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_observe_packed_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_create_split": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -491,6 +500,27 @@ class TetrisBatch:
         """step_eval_dev and the packed observation of the stepped state (perspective of next_player), as step_rt_observe_dev."""
         self._check(self.lib.tetris_step_eval_observe_dev(self._h, C.byref(e) if e is not None else None, int(ms), 1 if auto_reset else 0,
                                                           done, lines, dead, next_player, visual, vector, piece))
+
+    # -- trajectory windows (include/tetris_hip.h: tetris_traj_record_dev, tetris_traj_advantages_dev)
+    def traj(self, capacity, action, prob, value, reward, done):
+        """The window struct of the two calls below over raw DEVICE addresses (int / c_void_p): action uint8 [T][N][4], prob
+        float32 [T][N], value float32 [2][T][N], reward float32 [T][N], done uint8 [T][N], T = capacity."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        t = Traj()
+        t.capacity, t.reserved = int(capacity), 0
+        t.d_action, t.d_prob, t.d_value, t.d_reward, t.d_done = val(action), val(prob), val(value), val(reward), val(done)
+        return t
+
+    def traj_record_dev(self, traj, row, e, done, dead):
+        """Row `row` of the window from the outputs of the acting call e = act_eval(...) and the step's done [N], dead [P][N]."""
+        self._check(self.lib.tetris_traj_record_dev(self._h, C.byref(traj) if traj is not None else None, int(row),
+                                                    C.byref(e) if e is not None else None, done, dead))
+
+    def traj_advantages_dev(self, traj, rows, gamma, lambda_adv, lambda_value, boot, adv, target, closed=None):
+        """Advantages and value targets of rows 0 .. rows-1: adv, target float32 [rows][N], closed uint8 [rows][N] or None, boot
+        float32 [N] or None."""
+        self._check(self.lib.tetris_traj_advantages_dev(self._h, C.byref(traj) if traj is not None else None, int(rows), float(gamma),
+                                                        float(lambda_adv), float(lambda_value), boot, adv, target, closed))
 
     def rollout_game_totals_dev(self, totals):
         """The per-game words rollout_totals sums: totals uint32 [4][N] = env-steps, episodes, lines cleared, garbage lines sent."""

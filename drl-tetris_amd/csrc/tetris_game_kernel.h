@@ -10,6 +10,7 @@
 #include "tetris_plan.h"
 #include "tetris_policy.h"
 #include "tetris_act.h"
+#include "tetris_traj.h"
 
 namespace te {}
 using namespace te;
@@ -162,6 +163,79 @@ __global__ __launch_bounds__(NT) void k_act_select(ActArgs aa) {
     __shared__ ActShared sh;
     const int g0 = blockIdx.x * ACT_BLOCK, ng = imin(ACT_BLOCK, aa.a.n - g0);
     act_block_choose<NT>(aa, g0, ng, sh);
+}
+
+// ---- trajectory windows (tetris_traj.h).  Recording is one lane per game.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_traj_record(TrajRecordArgs ra) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i < ra.n) traj_record_game(ra, i);
+}
+
+// The backward recurrence is sequential in t per game, so a lane that read its rows from memory as it went would pay a memory
+// round trip per row with 64-1 024 waves on the whole GPU.  A workgroup of five waves takes TRAJ_BLOCK consecutive games:
+// waves 1-4 stream tiles of TRAJ_TILE rows x 64 games — wave 1 the rewards, 2 value[0], 3 value[1], 4 the dones, each lane 16
+// independent loads of its game's column, every load of a wave one contiguous 256 bytes (64 for the dones) — last tile first
+// into one half of a double-buffered LDS image while wave 0, one lane per game, walks the other half backward and stores
+// adv / target / closed, a contiguous row segment per store.  LDS rows are 64 words: lane l reads and writes bank l mod 32 of
+// its half-wave, no conflicts.  Any N (lanes past N load nothing and store nothing), any rows (the last tile is the short one).
+constexpr int TRAJ_THREADS = 5 * 64;
+struct TrajShared {
+    uint32_t w[2][4][TRAJ_TILE][TRAJ_BLOCK];      // [buffer][reward, value 0, value 1, done][row][game]
+};
+
+// rows t0 .. t0 + nr - 1 of array `which`, game g, into one buffer's column `lane` (all 16 loads issued before the first store;
+// constant indices after unrolling: registers, no scratch)
+__device__ __forceinline__ void traj_load_tile(const TrajAdvArgs& aa, int which, int g, bool live, int t0, int nr, int lane,
+                                               uint32_t (*dst)[TRAJ_TILE][TRAJ_BLOCK]) {
+    uint32_t v[TRAJ_TILE];
+    const size_t at = (size_t)t0 * aa.n + g;
+    if (which == 3) {
+        const uint8_t* src = aa.done + at;
+#pragma unroll
+        for (int j = 0; j < TRAJ_TILE; j++) v[j] = (live && j < nr) ? (uint32_t)src[(size_t)j * aa.n] : 0u;
+    } else {
+        const float* src = (which == 0 ? aa.reward : which == 1 ? aa.value : aa.value + aa.plane) + at;
+#pragma unroll
+        for (int j = 0; j < TRAJ_TILE; j++) v[j] = (live && j < nr) ? f2u(src[(size_t)j * aa.n]) : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < TRAJ_TILE; j++) dst[which][j][lane] = v[j];
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_traj_advantages(TrajAdvArgs aa) {
+    static_assert(NT == TRAJ_THREADS, "one scanning wave and one loading wave per array");
+    __shared__ TrajShared sh;
+    const int lane = threadIdx.x & (TRAJ_BLOCK - 1), wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / TRAJ_BLOCK);
+    const int g = blockIdx.x * TRAJ_BLOCK + lane;
+    const bool live = g < aa.n;
+    const int ntiles = (aa.rows + TRAJ_TILE - 1) / TRAJ_TILE;
+    TrajScan s;
+    traj_scan_begin(s, (wave == 0 && live && aa.boot) ? aa.boot[g] : 0.0f);
+    if (wave != 0) traj_load_tile(aa, wave - 1, g, live, (ntiles - 1) * TRAJ_TILE, aa.rows - (ntiles - 1) * TRAJ_TILE, lane, sh.w[0]);
+    __syncthreads();
+    int cur = 0;
+    for (int k = ntiles - 1; k >= 0; k--, cur ^= 1) {
+        const int t0 = k * TRAJ_TILE, nr = imin(TRAJ_TILE, aa.rows - t0);
+        if (wave == 0) {
+#pragma unroll 4
+            for (int j = nr - 1; j >= 0; j--) {
+                float adv, target;
+                traj_scan_row(s, aa, u2f(sh.w[cur][0][j][lane]), u2f(sh.w[cur][1][j][lane]), u2f(sh.w[cur][2][j][lane]),
+                              sh.w[cur][3][j][lane] != 0u, adv, target);
+                if (live) {
+                    const size_t at = (size_t)(t0 + j) * aa.n + g;
+                    aa.adv[at] = adv;
+                    aa.target[at] = target;
+                    if (aa.closed) aa.closed[at] = (uint8_t)s.seen;
+                }
+            }
+        } else if (k > 0) {
+            traj_load_tile(aa, wave - 1, g, live, t0 - TRAJ_TILE, TRAJ_TILE, lane, sh.w[cur ^ 1]);
+        }
+        __syncthreads();
+    }
 }
 
 // Runtime value -> template argument, on the host.  with_value<LO, HI>(v, f) calls f(std::integral_constant<int, v>) when

@@ -253,6 +253,7 @@ class TorchEnv:
                             seed=seed, draw=draw, epsilon=epsilon, table=table, piece=self._ptr(self.act_piece), eval=self._ptr(self.act_chosen),
                             value=None if state_eval is None else self._ptr(self.act_value), entropy=self._ptr(self.act_entropy) if mode == "pi" else None)
         entropy = self.act_entropy if mode == "pi" else capi.act_entropy(mode, epsilon, table)
+        self._act_last = (e, player, state_eval)         # what Trajectory.record reads (the tensors are kept alive with the struct)
         return e, (None if state_eval is None else self.act_value), entropy
 
     def select_eval(self, action_eval, state_eval=None, mode="argmax", player=None, seed=0, draw=0, epsilon=0.0, theta=None, table=None):
@@ -285,3 +286,52 @@ class TorchEnv:
                                      self._ptr(self.visual), self._ptr(self.vector), self._ptr(self.piece), ms=ms, auto_reset=auto_reset)
         return (self.done, self.lines, self.dead, self.visual, self.vector, self.piece, self.act_rot, self.act_trans, self.act_piece,
                 self.act_chosen, value, entropy)
+
+    # ---- trajectory windows (include/tetris_hip.h: tetris_traj_record_dev, tetris_traj_advantages_dev): the worker-side arithmetic
+    # between perform_action and the data packet (drl_tetris/worker.py:103-112)
+    def trajectory(self, capacity):
+        """A window of `capacity` rows of this batch's games: -> Trajectory (device tensors, allocated once)."""
+        return Trajectory(self, capacity)
+
+
+class Trajectory:
+    """A trajectory window of a TorchEnv: T = capacity rows of n games, time-major device tensors
+        action uint8 [T, n, 4] (r, t, piece, acting player), prob float32 [T, n] (the chosen entry), value float32 [2, T, n]
+        (v(s | piece), mean v(s)), reward float32 [T, n], done uint8 [T, n].
+    record(row) replaces store_experience, advantages(...) sventon_trajectory.process_trajectory(compute_advantages=True)
+    (agents/datatypes/trajectory.py:56-86, 111-141).  The actor loop is network forward, step_eval_observe, record, and every T
+    steps one advantages call; everything is reused device tensors and nothing waits for the GPU.  A caller with rewards of
+    their own (dual-policy re-pairing, extra rewards) fills `reward` / `done` themselves and calls advantages."""
+
+    def __init__(self, env, capacity):
+        torch, n = env.torch, env.b.n_games
+        assert int(capacity) >= 1, "a window has at least one row"
+        self.env, self.capacity = env, int(capacity)
+        u8, f32 = dict(dtype=torch.uint8, device=env.dev), dict(dtype=torch.float32, device=env.dev)
+        T = self.capacity
+        self.action, self.prob, self.value = torch.zeros(T, n, 4, **u8), torch.zeros(T, n, **f32), torch.zeros(2, T, n, **f32)
+        self.reward, self.done = torch.zeros(T, n, **f32), torch.zeros(T, n, **u8)
+        self.adv, self.target, self.closed = torch.zeros(T, n, **f32), torch.zeros(T, n, **f32), torch.zeros(T, n, **u8)
+        p = env._ptr
+        self._traj = env.b.traj(T, p(self.action), p(self.prob), p(self.value), p(self.reward), p(self.done))
+
+    def record(self, row):
+        """Row `row` from the last step_eval / step_eval_observe call of the TorchEnv: its (r, t, piece), chosen entry, values
+        (zeros without a state_eval) and player, the step's done, and the reference's reward (tetris_environment.reward_fcn
+        without extra_rewards) from done / dead.  One and two players."""
+        env = self.env
+        last = getattr(env, "_act_last", None)
+        assert last is not None, "call step_eval or step_eval_observe first"
+        env.b.traj_record_dev(self._traj, row, last[0], env._ptr(env.done), env._ptr(env.dead))
+
+    def advantages(self, rows, gamma, gae_lambda, gve_lambda=0.95, bootstrap=None):
+        """adv_and_targets over rows 0 .. rows-1, every episode of every game separately: -> (adv float32 [rows, n], target float32
+        [rows, n], closed uint8 [rows, n]) views of reused device tensors.  closed = 1: the entry's episode ended inside the
+        window and adv / target are the reference's numbers; the open tail is cut off with bootstrap float32 [n] = the value[0]
+        the next row would have (None: zero).  gamma may be negative (single-policy self-play)."""
+        env, torch = self.env, self.env.torch
+        if bootstrap is not None:
+            assert bootstrap.dtype == torch.float32 and bootstrap.is_cuda and bootstrap.is_contiguous() and bootstrap.numel() == env.b.n_games
+        p = env._ptr
+        env.b.traj_advantages_dev(self._traj, rows, gamma, gae_lambda, gve_lambda, p(bootstrap), p(self.adv), p(self.target), p(self.closed))
+        return self.adv[:rows], self.target[:rows], self.closed[:rows]

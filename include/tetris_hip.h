@@ -410,6 +410,62 @@ int tetris_step_eval_observe_dev(tetris_batch *b, const tetris_act_eval *e, int 
                                  uint8_t *d_lines, uint8_t *d_dead, const uint8_t *d_next_player, uint8_t *d_visual,
                                  uint8_t *d_vector, uint8_t *d_obs_piece);
 
+/* ---- trajectory windows: recording what an acting call wrote, advantages and value targets on the device ----------------
+ * replaces: the worker-side arithmetic between perform_action and the data packet (drl_tetris/worker.py:103-112):
+ * store_experience's append to a per-env trajectory, and sventon_trajectory.process_trajectory(compute_advantages=True) with
+ * its adv_and_targets (agents/datatypes/trajectory.py:56-86, 111-141) for every game of a batch at once.  With it the actor
+ * loop is network forward, tetris_step_eval_observe_dev, tetris_traj_record_dev, and every T steps one
+ * tetris_traj_advantages_dev; nothing in it waits for the host.
+ * A WINDOW holds T = capacity rows of N games, time-major, in caller-owned device memory (struct tetris_traj below).
+ * RECORD writes row `row` of every array from the outputs of a tetris_act_eval `e` that has just been used and from the
+ * step's d_done [N] and d_dead [P][N].  With p = e->d_player[i] (NULL: 0; clamped as in the acting calls):
+ *   d_action[row][i] = (e->d_rot[i], e->d_trans[i], e->d_piece[i], p)      (the reference's a_environment, and the player)
+ *   d_prob[row][i]   = e->d_eval[i]                                         (a_internal[0])
+ *   d_value[0][row][i], d_value[1][row][i] = e->d_value[0][i], e->d_value[1][i]; zeros when e->d_value is NULL
+ *   d_done[row][i]   = d_done[i]
+ *   d_reward[row][i] = tetris_environment.reward_fcn without extra_rewards (tetris_environment.py:135-144): 0 unless
+ *                      d_done[i]; else with me = d_dead[p][i] != 0, you = d_dead[1 - p][i] != 0 (one player: you = 0):
+ *                      -1 when both, otherwise (float)(you - me).
+ * One and two players.  TETRIS_E_ARG: three or four players; a split batch; a row outside [0, T); a NULL e, traj, array of
+ * the window, e->d_rot, e->d_trans, e->d_piece, e->d_eval, d_done or d_dead.
+ * ADVANTAGES works on rows 0 .. rows-1.  Per game n it walks backward through t, all in float32, in exactly this order of
+ * operations, with no fused multiply-adds and with the correctly rounded division:
+ *     A1 = A2 = W1 = W2 = 0;  seen_done = 0;  vnext = d_boot ? d_boot[n] : 0
+ *     for t = rows-1 .. 0:
+ *         if done[t][n]: A1 = A2 = W1 = W2 = 0; seen_done = 1
+ *         v0 = value[0][t][n]; v1 = value[1][t][n]
+ *         td = (reward[t][n] + (gamma * vnext) * (done[t][n] ? 0 : 1)) - v0
+ *         for (A, W, lam) in ((A1, W1, lambda_adv), (A2, W2, lambda_value)):
+ *             A = A * (gamma * lam) + td;   W = W * lam + 1;   est = ((A + v0) - v1) / W
+ *         adv[t][n] = est1;  target[t][n] = v1 + est2;  closed[t][n] = seen_done
+ *         vnext = v0
+ * This is adv_and_targets as sventon_trajectory.process_trajectory calls it: the call (trajectory.py:72-80) passes (v_piece,
+ * v_mean) into parameters named (v_mean, v_piece) (trajectory.py:111), so the TD errors (trajectory.py:124-126) are built on
+ * v(s | piece) = value[0], the estimate (trajectory.py:116-121) is (A + value[0] - value[1]) / W and the target
+ * (trajectory.py:138) is mean v + adjustment = value[1] + est2.  The reference runs it once per episode; here the accumulators
+ * reset at a done, which applies it to every episode of a column separately.  gamma may be negative (single-policy self-play:
+ * sventon_agent_base.py:76); lambda_value is the reference's gve_lambda (default 0.95).  closed[t][n] = 1: the entry's
+ * episode ended inside the window, so adv / target are the reference's numbers for it.  For the open tail d_boot [N] is the
+ * value the next row's value[0] would have (the usual truncated estimate); with d_boot NULL the tail is what the reference
+ * computes for a trajectory that does not end in done.  d_adv, d_target float32 [rows][N] (row stride N), d_closed uint8
+ * [rows][N] or NULL.  Any N, any number of players, split batches too: the batch gives N and the stream.
+ * TETRIS_E_ARG: a NULL traj, d_value, d_reward or d_done of the window, d_adv or d_target; rows outside [1, T].
+ * Both calls: device pointers, asynchronous on the batch's stream; the batch's games are neither read (but the status of
+ * being split) nor written.                                                                                                */
+typedef struct tetris_traj {
+    int      capacity;     /* T */
+    int      reserved;     /* 0 */
+    uint8_t *d_action;     /* [T][N][4]  r, t, piece, acting player   (a_environment + p) */
+    float   *d_prob;       /* [T][N]     the chosen entry x[c]        (a_internal[0])     */
+    float   *d_value;      /* [2][T][N]  [0] v(s | piece), [1] mean v(s)  (a_internal[1], [2]) */
+    float   *d_reward;     /* [T][N] */
+    uint8_t *d_done;       /* [T][N] */
+} tetris_traj;
+int tetris_traj_record_dev(tetris_batch *b, const tetris_traj *traj, int row, const tetris_act_eval *e, const uint8_t *d_done,
+                           const uint8_t *d_dead);
+int tetris_traj_advantages_dev(tetris_batch *b, const tetris_traj *traj, int rows, float gamma, float lambda_adv,
+                               float lambda_value, const float *d_boot, float *d_adv, float *d_target, uint8_t *d_closed);
+
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
  * t = w1 mod 10), acting player = step mod P, perform_action, auto-reset of finished games with

@@ -1,0 +1,371 @@
+"""Trajectory windows on the device (include/tetris_hip.h: tetris_traj_record_dev, tetris_traj_advantages_dev) against a model
+written here from the header's definition: numpy float32, an explicit sequential loop over the rows, every operation rounded to
+float32 in the header's order.  The model owes nothing to drl-tetris_amd/csrc/tetris_traj.h.  The kernel is compared with the
+model by exact bit equality; the model is compared with the reference's own float64 numbers (tests/golden/traj_gae.npz, written
+by tests/golden/make_traj_golden.py from agents/datatypes/trajectory.py) at 4e-6 absolute — by transitivity this pins the kernel
+to the reference.  Every test runs on the CPU harness (`-m "not gpu"`) and on the MI355X (`-m gpu`); on the harness the "device"
+buffers are numpy arrays."""
+import importlib
+import os
+import types
+
+import numpy as np
+import pytest
+
+import __graft_entry__ as ge
+from tests import engines
+
+F32 = np.float32
+TILE = 16                      # rows per LDS tile of k_traj_advantages (tetris_traj.h: TRAJ_TILE)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "traj_gae.npz")
+
+
+class Buf:
+    """A buffer the entry points read or write: numpy on the harness, a torch device tensor on the GPU; .ptr, .get() -> numpy."""
+
+    def __init__(self, kind, values):
+        values = np.ascontiguousarray(values)
+        self.kind, self.dtype, self.shape = kind, values.dtype, values.shape
+        if kind == "hip":
+            import torch
+            self.t = torch.from_numpy(values.copy()).cuda()
+            self.ptr = self.t.data_ptr()
+            torch.cuda.synchronize()              # (the batch runs on a stream of its own)
+        else:
+            self.a = values.copy()
+            self.ptr = self.a.ctypes.data
+
+    def get(self):
+        if self.kind == "hip":
+            import torch
+            torch.cuda.synchronize()
+            return self.t.cpu().numpy().view(self.dtype)
+        return self.a.copy()
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=F32).view(np.uint32)
+
+
+# ---------------------------------------------------------------- the model
+def model(value, reward, done, rows, gamma, lambda_adv, lambda_value, boot=None):
+    """value float32 [2, T, n], reward float32 [T, n], done [T, n] -> adv, target float32 [rows, n], closed uint8 [rows, n]: the
+    header's recurrence, one row at a time, all games of a row side by side (elementwise float32 operations round as the
+    scalar ones do)."""
+    n = reward.shape[1]
+    g, la, lv = F32(gamma), F32(lambda_adv), F32(lambda_value)
+    gla, glv = F32(g * la), F32(g * lv)
+    zero, one = F32(0.0), F32(1.0)
+    A1, A2, W1, W2 = (np.zeros(n, F32) for _ in range(4))
+    vnext = np.zeros(n, F32) if boot is None else boot.astype(F32).copy()
+    seen = np.zeros(n, np.uint8)
+    adv, target, closed = np.zeros((rows, n), F32), np.zeros((rows, n), F32), np.zeros((rows, n), np.uint8)
+    with np.errstate(all="ignore"):
+        for t in range(rows - 1, -1, -1):
+            d = done[t] != 0
+            A1, A2, W1, W2 = (np.where(d, zero, x).astype(F32) for x in (A1, A2, W1, W2))
+            seen = np.where(d, 1, seen).astype(np.uint8)
+            v0, v1 = value[0, t].astype(F32), value[1, t].astype(F32)
+            boot_term = ((g * vnext).astype(F32) * np.where(d, zero, one).astype(F32)).astype(F32)
+            td = ((reward[t].astype(F32) + boot_term).astype(F32) - v0).astype(F32)
+            A1 = ((A1 * gla).astype(F32) + td).astype(F32)
+            W1 = ((W1 * la).astype(F32) + one).astype(F32)
+            A2 = ((A2 * glv).astype(F32) + td).astype(F32)
+            W2 = ((W2 * lv).astype(F32) + one).astype(F32)
+            adv[t] = (((A1 + v0).astype(F32) - v1).astype(F32) / W1).astype(F32)
+            target[t] = (v1 + (((A2 + v0).astype(F32) - v1).astype(F32) / W2).astype(F32)).astype(F32)
+            closed[t] = seen
+            vnext = v0
+    return adv, target, closed
+
+
+class Window:
+    """A window of T rows of the batch's games in buffers of the engine's kind, and the struct over them"""
+
+    def __init__(self, kind, b, T, value=None, reward=None, done=None, fill=0):
+        n = b.n_games
+        self.T, self.n = T, n
+        self.action = Buf(kind, np.full((T, n, 4), fill, np.uint8))
+        self.prob = Buf(kind, np.full((T, n), fill, F32))
+        self.value = Buf(kind, np.full((2, T, n), fill, F32) if value is None else value.astype(F32))
+        self.reward = Buf(kind, np.full((T, n), fill, F32) if reward is None else reward.astype(F32))
+        self.done = Buf(kind, np.full((T, n), fill, np.uint8) if done is None else done.astype(np.uint8))
+        self.traj = b.traj(T, self.action.ptr, self.prob.ptr, self.value.ptr, self.reward.ptr, self.done.ptr)
+
+
+def done_columns(rng, T, n, rows, shift):
+    """dones of a window: game i follows pattern (i + shift) mod 7 — none; every row; the last row of the call only; the first
+    row only; three consecutive rows; the last row and the one before; random with one row in six"""
+    done = np.zeros((T, n), np.uint8)
+    for i in range(n):
+        k = (i + shift) % 7
+        if k == 1:
+            done[:, i] = 1
+        elif k == 2:
+            done[rows - 1, i] = 1
+        elif k == 3:
+            done[0, i] = 1
+        elif k == 4:
+            start = int(rng.integers(0, max(1, rows - 2)))
+            done[start:start + 3, i] = 1
+        elif k == 5:
+            done[max(0, rows - 2):rows, i] = 1
+        elif k == 6:
+            done[:, i] = rng.random(T) < 1.0 / 6.0
+    return done
+
+
+# gamma, lambda_adv, lambda_value: the reference's defaults, single-policy self-play (negative gamma), lambda 0 and 1 on either side
+COEFFICIENTS = [(0.98, 0.96, 0.95), (-0.98, 0.7, 0.95), (0.5, 0.0, 1.0), (0.98, 1.0, 0.0), (-0.98, 0.96, 0.95), (1.0, 1.0, 1.0), (0.0, 0.5, 0.5)]
+ROWS = (1, 2, TILE - 1, TILE, TILE + 1, 2 * TILE + 3)
+CAPACITY = 2 * TILE + 5
+
+
+# ---------------------------------------------------------------- 1. the kernel against the model
+# N: a single game, a partial wave, a whole block of 64, a block and one game, several blocks with a partial last one
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("n", [1, 33, 64, 65, 257])
+def test_advantages_equal_the_model_bit_for_bit(kind, n):
+    rng = np.random.default_rng(3000 + n)
+    b = engines.make(kind, n, 1)
+    T = CAPACITY
+    patterns = set()
+    for case, rows in enumerate(ROWS + (CAPACITY,)):
+        for k, (gamma, la, lv) in enumerate(COEFFICIENTS):
+            shift = case + k
+            value = (2.0 * rng.standard_normal((2, T, n))).astype(F32)
+            done = done_columns(rng, T, n, rows, shift)
+            reward = np.where(done != 0, rng.choice(np.array([-1.0, 1.0], F32), (T, n)), F32(0.0)).astype(F32)
+            if k % 3 == 2:                                  # rewards on every row, as a caller with shaped rewards would have
+                reward = rng.standard_normal((T, n)).astype(F32)
+            boot = (2.0 * rng.standard_normal(n)).astype(F32) if (case + k) % 2 else None
+            w = Window(kind, b, T, value, reward, done)
+            adv, target, closed = (Buf(kind, np.full((T, n), -7.0, F32)), Buf(kind, np.full((T, n), -7.0, F32)), Buf(kind, np.full((T, n), 9, np.uint8)))
+            bb = None if boot is None else Buf(kind, boot)
+            b.traj_advantages_dev(w.traj, rows, gamma, la, lv, None if bb is None else bb.ptr, adv.ptr, target.ptr, closed.ptr)
+            want = model(value, reward, done, rows, gamma, la, lv, boot)
+            where = f"rows {rows}, gamma {gamma}, lambdas {la} / {lv}, boot {'given' if boot is not None else 'NULL'}"
+            for name, got, exp in zip(("adv", "target"), (adv.get(), target.get()), want[:2]):
+                assert np.isfinite(exp).all(), where
+                assert np.array_equal(bits(got[:rows]), bits(exp)), f"{where}: '{name}' differs at (row, game) {np.argwhere(bits(got[:rows]) != bits(exp))[:6].tolist()}"
+                assert np.all(got[rows:] == F32(-7.0)), f"{where}: '{name}' was written past the rows of the call"
+            got = closed.get()
+            assert np.array_equal(got[:rows], want[2]) and np.all(got[rows:] == 9), f"{where}: 'closed'"
+            for buf, src in ((w.value, value), (w.reward, reward), (w.done, done)):
+                assert np.array_equal(buf.get(), src), f"{where}: the window was written"
+            patterns |= {(i + shift) % 7 for i in range(n)}
+    assert patterns == set(range(7)), "a pattern of dones did not occur"
+    # closed is optional
+    adv, target = Buf(kind, np.zeros((T, n), F32)), Buf(kind, np.zeros((T, n), F32))
+    b.traj_advantages_dev(w.traj, T, 0.98, 0.96, 0.95, None, adv.ptr, target.ptr, None)
+    want = model(value, reward, done, T, 0.98, 0.96, 0.95)
+    assert np.array_equal(bits(adv.get()), bits(want[0])) and np.array_equal(bits(target.get()), bits(want[1]))
+
+
+def test_the_model_restates_the_recurrence_by_hand():
+    """three rows of one game, worked out operation by operation: a done in the middle, a bootstrap behind the open tail"""
+    value = np.array([[[0.5], [1.5], [-0.25]], [[0.25], [1.0], [0.75]]], F32)
+    reward = np.array([[0.0], [1.0], [0.0]], F32)
+    done = np.array([[0], [1], [0]], np.uint8)
+    g, la, lv, boot = F32(0.5), F32(0.5), F32(0.25), F32(2.0)
+    adv, target, closed = model(value, reward, done, 3, g, la, lv, np.array([boot], F32))
+    td2 = F32(F32(0.0) + F32(g * boot)) - F32(-0.25)                          # 1.25
+    assert adv[2, 0] == F32(F32(F32(td2 + F32(-0.25)) - F32(0.75)) / F32(1.0)) and target[2, 0] == F32(F32(0.75) + F32(0.25))
+    td1 = F32(1.0) - F32(1.5)                                                 # the done cuts the bootstrap and the sums
+    assert adv[1, 0] == F32(F32(td1 + F32(1.5)) - F32(1.0)) and target[1, 0] == F32(1.0)
+    td0 = F32(F32(0.0) + F32(g * F32(1.5))) - F32(0.5)                        # 0.25
+    A1, W1 = F32(F32(td1 * F32(g * la)) + td0), F32(F32(1.0) * la + F32(1.0))
+    A2, W2 = F32(F32(td1 * F32(g * lv)) + td0), F32(F32(1.0) * lv + F32(1.0))
+    assert adv[0, 0] == F32(F32(F32(A1 + F32(0.5)) - F32(0.25)) / W1)
+    assert target[0, 0] == F32(F32(0.25) + F32(F32(F32(A2 + F32(0.5)) - F32(0.25)) / W2))
+    assert closed[:, 0].tolist() == [1, 1, 0]
+
+
+# ---------------------------------------------------------------- 2. the model against the reference
+def test_the_model_is_within_4e_6_of_the_reference_on_every_fixture_entry():
+    """Every episode of the fixture is one game column of one window, at the window's end, with another finished episode in
+    front of it (so the resets at a done are inside the comparison); the column's case decides gamma and gae_lambda.  Closed
+    entries against the reference's float64 numbers: 4e-6 absolute, eight times the worst difference (4.8e-7) measured for the
+    definition on values drawn from 2 N(0, 1).  Measured here: 3.93e-7 (adv) and 5.42e-7 (target)."""
+    z = np.load(GOLDEN)
+    E = len(z["case"])
+    T = int(z["length"].max()) + 19
+    rng = np.random.default_rng(8)
+    value = (2.0 * rng.standard_normal((2, T, E))).astype(F32)
+    reward, done = np.zeros((T, E), F32), np.zeros((T, E), np.uint8)
+    for e in range(E):
+        s, length = int(z["start"][e]), int(z["length"][e])
+        first = T - length
+        done[first - 1, e], reward[first - 1, e] = 1, -1.0                    # the episode in front ends here
+        value[0, first:, e], value[1, first:, e] = z["v_piece"][s:s + length], z["v_mean"][s:s + length]
+        reward[first:, e], done[first:, e] = z["reward"][s:s + length], z["done"][s:s + length]
+    compared, worst = 0, [0.0, 0.0]
+    for case in range(len(z["gamma"])):
+        adv, target, closed = model(value, reward, done, T, z["gamma"][case], z["gae_lambda"][case], float(z["gve_lambda"]))
+        for e in np.nonzero(z["case"] == case)[0]:
+            s, length = int(z["start"][e]), int(z["length"][e])
+            first = T - length
+            assert closed[first:, e].all()
+            for k, (got, ref) in enumerate(((adv, z["adv"]), (target, z["target"]))):
+                err = np.abs(got[first:, e].astype(np.float64) - ref[s:s + length])
+                worst[k] = max(worst[k], float(err.max()))
+            compared += length
+    print(f"largest difference from the reference: adv {worst[0]:.3g}, target {worst[1]:.3g} over {compared} entries")
+    assert compared == len(z["adv"]) == 2 * (1 + 2 + 3 + 17 + 64 + 257 + 1581), "every entry of the fixture is compared"
+    assert worst[0] <= 4e-6 and worst[1] <= 4e-6
+
+
+# ---------------------------------------------------------------- 3. record
+class _Played:
+    """A batch played for T steps with step_eval (random evaluations, auto-reset) and recorded row by row; the call's own outputs
+    are copied every step.  On the harness through the C-level calls, on the GPU through TorchEnv.trajectory."""
+
+    def __init__(self, kind, n, P, height, T, with_value, seed):
+        rng = np.random.default_rng(seed)
+        self.b = b = engines.make(kind, n, P, height=height)
+        self.steps = []
+        if kind == "hip":
+            import torch
+            ti = importlib.import_module("drl-tetris_amd.torch_interop")
+            te = ti.TorchEnv(b)
+            self.tr = tr = te.trajectory(T)
+        else:
+            self.w = w = Window(kind, b, T, fill=7)
+            outs = dict(rot=Buf(kind, np.zeros(n, np.uint8)), trans=Buf(kind, np.zeros(n, np.uint8)), piece=Buf(kind, np.zeros(n, np.uint8)),
+                        eval=Buf(kind, np.zeros(n, F32)), value=Buf(kind, np.zeros((2, n), F32)), done=Buf(kind, np.zeros(n, np.uint8)),
+                        lines=Buf(kind, np.zeros((P, n), np.uint8)), dead=Buf(kind, np.zeros((P, n), np.uint8)))
+        for s in range(T):
+            ae = rng.random((n, 4, 10, 7)).astype(F32)
+            se = rng.standard_normal((n, 7)).astype(F32) if with_value else None
+            player = rng.integers(0, P, n).astype(np.uint8)
+            mode = ("pi", "argmax")[s % 2]
+            if kind == "hip":
+                pt = torch.from_numpy(player).cuda()
+                out = te.step_eval(torch.from_numpy(ae).cuda(), None if se is None else torch.from_numpy(se).cuda(), mode=mode, player=pt,
+                                   seed=5, draw=s, auto_reset=True)
+                tr.record(s)
+                got = dict(done=out[0], dead=out[2], rot=out[3], trans=out[4], piece=out[5], eval=out[6])
+                if with_value:
+                    got["value"] = out[7]
+                got = {k: v.cpu().numpy().copy() for k, v in got.items()}
+            else:
+                aeb, seb, plb = Buf(kind, ae), (None if se is None else Buf(kind, se)), Buf(kind, player)
+                e = b.act_eval(aeb.ptr, outs["rot"].ptr, outs["trans"].ptr, n_pieces=7, state_eval=None if seb is None else seb.ptr, n_values=7,
+                               mode=mode, player=plb.ptr, seed=5, draw=s, piece=outs["piece"].ptr, eval=outs["eval"].ptr,
+                               value=outs["value"].ptr if with_value else None)
+                b.step_eval_dev(e, outs["done"].ptr, outs["lines"].ptr, outs["dead"].ptr, auto_reset=True)
+                b.traj_record_dev(w.traj, s, e, outs["done"].ptr, outs["dead"].ptr)
+                got = {k: outs[k].get() for k in ("done", "dead", "rot", "trans", "piece", "eval") + (("value",) if with_value else ())}
+            got["player"] = player
+            self.steps.append(got)
+        if kind == "hip":
+            import torch
+            torch.cuda.synchronize()
+            self.window = {k: getattr(tr, k).cpu().numpy() for k in ("action", "prob", "value", "reward", "done")}
+        else:
+            self.window = {k: getattr(w, k).get() for k in ("action", "prob", "value", "reward", "done")}
+
+    def advantages(self, kind, rows, gamma, la, lv, boot):
+        if kind == "hip":
+            import torch
+            adv, target, closed = self.tr.advantages(rows, gamma, la, gve_lambda=lv, bootstrap=None if boot is None else torch.from_numpy(boot).cuda())
+            assert tuple(adv.shape) == tuple(target.shape) == tuple(closed.shape) == (rows, self.b.n_games)
+            return adv.cpu().numpy(), target.cpu().numpy(), closed.cpu().numpy()
+        T, n = self.w.T, self.w.n
+        adv, target, closed = Buf(kind, np.zeros((T, n), F32)), Buf(kind, np.zeros((T, n), F32)), Buf(kind, np.zeros((T, n), np.uint8))
+        bb = None if boot is None else Buf(kind, boot)
+        self.b.traj_advantages_dev(self.w.traj, rows, gamma, la, lv, None if bb is None else bb.ptr, adv.ptr, target.ptr, closed.ptr)
+        return adv.get()[:rows], target.get()[:rows], closed.get()[:rows]
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("P,with_value", [(2, True), (1, True), (1, False)], ids=["two-players", "one-player", "one-player-no-values"])
+def test_record_writes_the_calls_outputs_and_the_reference_reward(kind, P, with_value):
+    """257 games of height 12 for 14 steps with auto-reset: some games end inside the window and some do not.  Every row of every
+    window array equals the call's own outputs, the reward equals environment.py's _reward on the copied done / dead / player,
+    and the advantages of the recorded window equal the model's."""
+    n, T, height = 257, 14, 12
+    env = importlib.import_module("drl-tetris_amd.environment")
+    reward_of = lambda done, dead, player: env.tetris_environment_vector._reward(types.SimpleNamespace(n_players=P), done, dead, player)    # noqa: E731
+    run = _Played(kind, n, P, height, T, with_value, seed=900 + P)
+    win = run.window
+    for s, got in enumerate(run.steps):
+        where = f"row {s}"
+        assert np.array_equal(win["action"][s], np.stack([got["rot"], got["trans"], got["piece"], got["player"]], axis=1)), f"{where}: 'action'"
+        assert np.array_equal(bits(win["prob"][s]), bits(got["eval"])), f"{where}: 'prob'"
+        want_value = got["value"] if with_value else np.zeros((2, n), F32)
+        assert np.array_equal(bits(win["value"][:, s]), bits(want_value)), f"{where}: 'value'"
+        assert np.array_equal(win["done"][s], got["done"]), f"{where}: 'done'"
+        want = np.array([reward_of(bool(got["done"][i]), got["dead"][:, i], int(got["player"][i])) for i in range(n)], F32)
+        assert np.array_equal(win["reward"][s], want), f"{where}: 'reward' differs in games {np.nonzero(win['reward'][s] != want)[0][:8]}"
+    ended = win["done"].any(axis=0)
+    assert ended.any() and not ended.all(), f"{int(ended.sum())} of {n} games ended: both kinds of game must occur"
+    if P == 2:
+        assert (win["reward"] == 1.0).any() and (win["reward"] == -1.0).any(), "both rewards must occur"
+    else:
+        assert (win["reward"] == -1.0).any() and not (win["reward"] > 0).any()
+    assert np.all((win["reward"] != 0) <= (win["done"] != 0))
+    rng = np.random.default_rng(1)
+    for rows, (gamma, la, lv), boot in ((T, (0.98, 0.96, 0.95), None), (T - 3, (-0.98, 0.7, 0.95), (2.0 * rng.standard_normal(n)).astype(F32))):
+        adv, target, closed = run.advantages(kind, rows, gamma, la, lv, boot)
+        want = model(win["value"], win["reward"], win["done"], rows, gamma, la, lv, boot)
+        assert np.array_equal(bits(adv), bits(want[0])) and np.array_equal(bits(target), bits(want[1])) and np.array_equal(closed, want[2])
+    assert run.b.take_errors() == 0
+
+
+# ---------------------------------------------------------------- 4. arguments
+def test_arguments_are_checked():
+    pkg = ge.package()
+    n, T = 4, 6
+    b = engines.make("harness", n, 2)
+    w = Window("harness", b, T, fill=7)
+    p = lambda arr: arr.ctypes.data                                                           # noqa: E731
+    rot, trans, piece, ev, value = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, F32), np.zeros((2, n), F32)
+    done, dead = np.zeros(n, np.uint8), np.zeros((2, n), np.uint8)
+    ae = np.zeros((n, 4, 10, 7), F32)
+    e = b.act_eval(p(ae), p(rot), p(trans), piece=p(piece), eval=p(ev), value=p(value))
+    arrays = dict(action=w.action.ptr, prob=w.prob.ptr, value=w.value.ptr, reward=w.reward.ptr, done=w.done.ptr)
+    # record
+    for row in (-1, T, T + 100):
+        with pytest.raises(pkg.TetrisError, match="row"):
+            b.traj_record_dev(w.traj, row, e, p(done), p(dead))
+    for name in arrays:
+        with pytest.raises(pkg.TetrisError, match="NULL"):
+            b.traj_record_dev(b.traj(T, **dict(arrays, **{name: None})), 0, e, p(done), p(dead))
+    for kw in (dict(rot=None), dict(trans=None), dict(piece=None), dict(eval=None)):
+        args = dict(rot=p(rot), trans=p(trans), piece=p(piece), eval=p(ev))
+        args.update(kw)
+        with pytest.raises(pkg.TetrisError, match="NULL"):
+            b.traj_record_dev(w.traj, 0, b.act_eval(p(ae), args.pop("rot"), args.pop("trans"), **args), p(done), p(dead))
+    for call in (lambda: b.traj_record_dev(None, 0, e, p(done), p(dead)), lambda: b.traj_record_dev(w.traj, 0, None, p(done), p(dead)),
+                 lambda: b.traj_record_dev(w.traj, 0, e, None, p(dead)), lambda: b.traj_record_dev(w.traj, 0, e, p(done), None)):
+        with pytest.raises(pkg.TetrisError, match="NULL"):
+            call()
+    for players in (3, 4):
+        many = engines.make("harness", n, players)
+        with pytest.raises(pkg.TetrisError, match="one or two players"):
+            many.traj_record_dev(w.traj, 0, e, p(done), p(np.zeros((players, n), np.uint8)))
+    split = pkg.TetrisBatch(n, 2, 20, 10, lib_path=ge.build_harness(), split_side=0)
+    with pytest.raises(pkg.TetrisError, match="split"):
+        split.traj_record_dev(w.traj, 0, e, p(done), p(dead))
+    for name in ("action", "prob", "value", "reward", "done"):
+        assert np.all(getattr(w, name).get() == 7), "a rejected call must not run"
+    # advantages
+    adv, target = np.full((T, n), -7.0, F32), np.full((T, n), -7.0, F32)
+    for rows in (0, -1, T + 1):
+        with pytest.raises(pkg.TetrisError, match="rows"):
+            b.traj_advantages_dev(w.traj, rows, 0.98, 0.96, 0.95, None, p(adv), p(target))
+    for a, t in ((None, p(target)), (p(adv), None)):
+        with pytest.raises(pkg.TetrisError, match="NULL"):
+            b.traj_advantages_dev(w.traj, T, 0.98, 0.96, 0.95, None, a, t)
+    for name in ("value", "reward", "done"):
+        with pytest.raises(pkg.TetrisError, match="NULL"):
+            b.traj_advantages_dev(b.traj(T, **dict(arrays, **{name: None})), T, 0.98, 0.96, 0.95, None, p(adv), p(target))
+    with pytest.raises(pkg.TetrisError, match="NULL"):
+        b.traj_advantages_dev(None, T, 0.98, 0.96, 0.95, None, p(adv), p(target))
+    assert np.all(adv == F32(-7.0)) and np.all(target == F32(-7.0)), "a rejected call must not run"
+    # what is accepted: a value-less acting call, a window without action / prob for advantages, three players and rows = T
+    b.traj_record_dev(w.traj, T - 1, b.act_eval(p(ae), p(rot), p(trans), piece=p(piece), eval=p(ev)), p(done), p(dead))
+    assert np.all(w.value.get()[:, T - 1] == 0) and np.all(w.value.get()[:, :T - 1] == 7)
+    engines.make("harness", n, 3).traj_advantages_dev(b.traj(T, None, None, w.value.ptr, w.reward.ptr, w.done.ptr), T, 0.98, 0.96, 0.95, None, p(adv), p(target))
+    assert np.all(adv != F32(-7.0))
