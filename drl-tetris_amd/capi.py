@@ -56,6 +56,21 @@ class Traj(C.Structure):
                 ("d_reward", C.c_void_p), ("d_done", C.c_void_p)]
 
 
+class TrajObs(C.Structure):
+    """mirrors `struct tetris_traj_obs` (include/tetris_hip.h)"""
+    _fields_ = [("capacity", C.c_int), ("reserved", C.c_int), ("d_obs", C.c_void_p)]
+
+
+class TrajBatch(C.Structure):
+    """mirrors `struct tetris_traj_batch` (include/tetris_hip.h)"""
+    _fields_ = [("d_visual", C.c_void_p), ("d_vector", C.c_void_p), ("d_piece", C.c_void_p), ("d_action", C.c_void_p), ("d_prob", C.c_void_p),
+                ("d_adv", C.c_void_p), ("d_target", C.c_void_p), ("d_reward", C.c_void_p), ("d_done", C.c_void_p), ("d_valid", C.c_void_p)]
+
+
+SELECT_AUGMENT = 1            # TETRIS_SELECT_AUGMENT
+MIRROR_BIT = 1 << 31          # bit 31 of an index of tetris_traj_batch_dev: the mirrored sample
+
+
 def pareto_table(theta):
     """The RANK table of the reference's pareto (tools/utils.py:88-91): (k + 1) ** -theta for rank k + 1, float32 [40]."""
     return (np.arange(1, 41, dtype=np.float64) ** -float(theta)).astype(np.float32)
@@ -149,6 +164,9 @@ _SIGNATURES = {
     "tetris_traj_record_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_traj_advantages_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
+    "tetris_traj_observe_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "tetris_traj_select_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "tetris_traj_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tetris_observe_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_observe_packed_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_create_split": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -521,6 +539,40 @@ class TetrisBatch:
         float32 [N] or None."""
         self._check(self.lib.tetris_traj_advantages_dev(self._h, C.byref(traj) if traj is not None else None, int(rows), float(gamma),
                                                         float(lambda_adv), float(lambda_value), boot, adv, target, closed))
+
+    # -- a window's states and sample sets (include/tetris_hip.h: tetris_traj_observe_dev, tetris_traj_select_dev, tetris_traj_batch_dev)
+    def traj_obs(self, capacity, obs):
+        """The record struct of the calls below over a raw DEVICE address: obs uint32 [T][N][S][12], 16-byte aligned."""
+        o = TrajObs()
+        o.capacity, o.reserved, o.d_obs = int(capacity), 0, (obs.value if isinstance(obs, C.c_void_p) else obs)
+        return o
+
+    def traj_batch(self, visual=None, vector=None, piece=None, action=None, prob=None, adv=None, target=None, reward=None, done=None,
+                   valid=None):
+        """The output struct of traj_batch_dev over raw DEVICE addresses (None: that output is skipped): visual uint8 [S][M][H][10],
+        vector uint8 [S][M][12], piece uint8 [S][M], action uint8 [M][3], prob / adv / target / reward float32 [M], done / valid
+        uint8 [M]."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        o = TrajBatch()
+        o.d_visual, o.d_vector, o.d_piece, o.d_action, o.d_prob = val(visual), val(vector), val(piece), val(action), val(prob)
+        o.d_adv, o.d_target, o.d_reward, o.d_done, o.d_valid = val(adv), val(target), val(reward), val(done), val(valid)
+        return o
+
+    def traj_observe_dev(self, obs, row, player=None):
+        """Row `row` of the records from the games' current state, perspective of player [N] (None: player 0)."""
+        self._check(self.lib.tetris_traj_observe_dev(self._h, C.byref(obs) if obs is not None else None, int(row), player))
+
+    def traj_select_dev(self, mask, rows, index, cap, count, augment=False):
+        """The flat indices of the non-zero bytes of mask uint8 [rows][N], ascending, into index int32 [cap] (-1 past the list;
+        augment: the list once more with bit 31 set); count int32 [1] = the length of the full list."""
+        self._check(self.lib.tetris_traj_select_dev(self._h, mask, int(rows), SELECT_AUGMENT if augment else 0, index, int(cap), count))
+
+    def traj_batch_dev(self, traj, obs, index, m, out, adv=None, target=None):
+        """The samples index int32 [m] names (bit 31: mirrored; -1 or out of range: zeros, valid 0) into out = traj_batch(...);
+        adv / target float32 [T][N] or None."""
+        self._check(self.lib.tetris_traj_batch_dev(self._h, C.byref(traj) if traj is not None else None,
+                                                   C.byref(obs) if obs is not None else None, adv, target, index, int(m),
+                                                   C.byref(out) if out is not None else None))
 
     def rollout_game_totals_dev(self, totals):
         """The per-game words rollout_totals sums: totals uint32 [4][N] = env-steps, episodes, lines cleared, garbage lines sent."""

@@ -11,6 +11,7 @@
 #include "tetris_policy.h"
 #include "tetris_act.h"
 #include "tetris_traj.h"
+#include "tetris_batch.h"
 
 namespace te {}
 using namespace te;
@@ -236,6 +237,146 @@ __global__ __launch_bounds__(NT) void k_traj_advantages(TrajAdvArgs aa) {
         }
         __syncthreads();
     }
+}
+
+// ---- a window's states and sample sets (tetris_batch.h)
+// One board's ten column words -> its row of a workgroup's LDS tile, for even heights: the byte planes are built as words in
+// registers — two rows = 20 cells = 5 words per loop trip, columns indexed statically — and go to LDS as dwords.  Shared by
+// k_observe_packed (tetris_hip.hip) and k_traj_batch.  `col` is used up.
+__device__ __forceinline__ void obs_row_words(uint32_t (&col)[NCOL], int H, uint32_t* row) {
+    for (int yp = 0; yp < H / 2; yp++) {
+        uint32_t lo[NCOL], hi[NCOL];                 // cells of rows 2 yp and 2 yp + 1
+        for (int c = 0; c < NCOL; c++) { lo[c] = col[c] & 1u; hi[c] = (col[c] >> 1) & 1u; col[c] >>= 2; }
+        row[5 * yp + 0] = lo[0] | (lo[1] << 8) | (lo[2] << 16) | (lo[3] << 24);
+        row[5 * yp + 1] = lo[4] | (lo[5] << 8) | (lo[6] << 16) | (lo[7] << 24);
+        row[5 * yp + 2] = lo[8] | (lo[9] << 8) | (hi[0] << 16) | (hi[1] << 24);
+        row[5 * yp + 3] = hi[2] | (hi[3] << 8) | (hi[4] << 16) | (hi[5] << 24);
+        row[5 * yp + 4] = hi[6] | (hi[7] << 8) | (hi[8] << 16) | (hi[9] << 24);
+    }
+}
+// the same for odd heights, where a board's H * 10 bytes start on an even byte that need not be a word: one row = 5 halfwords
+__device__ __forceinline__ void obs_row_halves(uint32_t (&col)[NCOL], int H, uint16_t* row) {
+    for (int y = 0; y < H; y++) {
+#pragma unroll
+        for (int k = 0; k < NCOL / 2; k++) row[5 * y + k] = (uint16_t)((col[2 * k] & 1u) | ((col[2 * k + 1] & 1u) << 8));
+#pragma unroll
+        for (int c = 0; c < NCOL; c++) col[c] >>= 1;
+    }
+}
+
+// tetris_traj_observe_dev: one lane per (game, slot) record
+template <int NT>
+__global__ __launch_bounds__(NT) void k_traj_observe(TrajObserveArgs oa) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i < oa.n) traj_observe_slot(oa, i, (int)blockIdx.y);
+}
+
+// tetris_traj_select_dev in three launches, none of which waits for another workgroup: the non-zero bytes of every workgroup's
+// SELECT_ELEMS mask bytes (16 per lane, one 16-byte load); the exclusive scan of those counts by ONE workgroup, SELECT_THREADS
+// counts per trip with a carry; the scatter, in which every workgroup repeats its count, scans its lanes' counts and writes
+// its entries from its offset on — in ascending order whatever the order the workgroups run in.
+template <int NT>
+__device__ __forceinline__ uint32_t select_block_scan(uint32_t v, uint32_t* s, uint32_t& sum) {      // -> exclusive prefix of v
+    const int t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (int off = 1; off < NT; off <<= 1) {
+        const uint32_t add = t >= off ? s[t - off] : 0u;
+        __syncthreads();
+        s[t] += add;
+        __syncthreads();
+    }
+    const uint32_t incl = s[t];
+    sum = s[NT - 1];
+    __syncthreads();
+    return incl - v;
+}
+template <int NT>
+__global__ __launch_bounds__(NT) void k_select_count(TrajSelectArgs sa) {
+    __shared__ uint32_t s[NT];
+    const uint32_t base = (uint32_t)blockIdx.x * (uint32_t)SELECT_ELEMS + (uint32_t)threadIdx.x * 16u;
+    uint32_t sum;
+    select_block_scan<NT>((uint32_t)__builtin_popcount(select_bits(sa, base)), s, sum);
+    if (threadIdx.x == 0) sa.blocks[blockIdx.x] = (int32_t)sum;
+}
+template <int NT>
+__global__ __launch_bounds__(NT) void k_select_scan(TrajSelectArgs sa) {
+    __shared__ uint32_t s[NT];
+    uint32_t carry = 0u;
+    for (int first = 0; first < sa.nblocks; first += NT) {
+        const int k = first + (int)threadIdx.x;
+        uint32_t sum;
+        const uint32_t excl = select_block_scan<NT>(k < sa.nblocks ? (uint32_t)sa.blocks[k] : 0u, s, sum);
+        if (k < sa.nblocks) sa.blocks[k] = (int32_t)(carry + excl);
+        carry += sum;
+    }
+    if (threadIdx.x == 0) {
+        sa.blocks[sa.nblocks] = (int32_t)carry;
+        *sa.count = (int32_t)(sa.augment ? 2u * carry : carry);
+    }
+}
+template <int NT>
+__global__ __launch_bounds__(NT) void k_select_scatter(TrajSelectArgs sa) {
+    __shared__ uint32_t s[NT];
+    const uint32_t base = (uint32_t)blockIdx.x * (uint32_t)SELECT_ELEMS + (uint32_t)threadIdx.x * 16u;
+    const uint32_t bits = select_bits(sa, base);
+    uint32_t sum;
+    const uint32_t excl = select_block_scan<NT>((uint32_t)__builtin_popcount(bits), s, sum);
+    const long long k = (long long)(uint32_t)sa.blocks[sa.nblocks];
+    select_emit(sa, base, bits, (long long)(uint32_t)sa.blocks[blockIdx.x] + excl, k);
+    // the rest of d_index, up to cap: -1
+    const long long step = (long long)gridDim.x * NT;
+    for (long long p = (sa.augment ? 2 * k : k) + (long long)blockIdx.x * NT + threadIdx.x; p < sa.cap; p += step) sa.index[p] = -1;
+}
+
+// tetris_traj_batch_dev.  A workgroup of one wave takes BATCH_BLOCK consecutive samples of one slot (blockIdx.y): a lane reads
+// its sample's record with three 16-byte loads — 48 contiguous bytes, one or two cache lines, wherever the index points — and
+// expands the ten column words into its row of an LDS tile that is laid out as the workgroup's slice of `visual` itself (row
+// pitch H * 10 bytes, not padded: rows start 50 / 55 words apart, at most two lanes per LDS bank while they are written, as in
+// k_observe_packed).  The mirror image is the choice of the source column of every tile column — selects between registers,
+// no second pass.  The tile leaves as 16-byte LDS reads -> 16-byte streaming stores, one contiguous run of 64 * H * 10 bytes
+// (a multiple of 16 for every H); a slice of `visual` that does not start on 16 bytes leaves as dwords or bytes.  The slot-0
+// workgroup also writes the samples' row entries.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_traj_batch(TrajBatchArgs ba) {
+    static_assert(NT == BATCH_BLOCK, "one lane per sample");
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_tile[];      // BATCH_BLOCK * H * 10 bytes
+    const int lane = threadIdx.x, sl = blockIdx.y, first = blockIdx.x * NT, j = first + lane;
+    const int nb = imin(NT, ba.m - first), cells = ba.H * NCOL;
+    if (j < ba.m) {
+        const BatchEntry en = batch_entry(ba, j);
+        const Quad* rec = reinterpret_cast<const Quad*>(ba.obs + ((size_t)en.at * ba.n_slots + sl) * OBS_WORDS);
+        const Quad zero = {0u, 0u, 0u, 0u};
+        const Quad a = en.valid ? rec[0] : zero, b = en.valid ? rec[1] : zero, c = en.valid ? rec[2] : zero;
+        if (ba.visual) {
+            const bool mi = en.mirror;
+            uint32_t col[NCOL] = {mi ? c.y : a.x, mi ? c.x : a.y, mi ? b.w : a.z, mi ? b.z : a.w, mi ? b.y : b.x,
+                                  mi ? b.x : b.y, mi ? a.w : b.z, mi ? a.z : b.w, mi ? a.y : c.x, mi ? a.x : c.y};
+            if (ba.H % 2 == 0) obs_row_words(col, ba.H, s_tile + (size_t)lane * (cells / 4));
+            else obs_row_halves(col, ba.H, reinterpret_cast<uint16_t*>(s_tile) + (size_t)lane * (cells / 2));
+        }
+        uint32_t v0, v1, v2, piece;
+        batch_scalars(en, c.z, c.w, v0, v1, v2, piece);
+        batch_store_vector(ba, sl, j, v0, v1, v2, piece);
+        if (sl == 0) batch_store_entry(ba, j, en);
+    }
+    if (!ba.visual) return;
+    __syncthreads();
+    uint8_t* out = ba.visual + ((size_t)sl * ba.m + first) * (size_t)cells;
+    const uint32_t bytes = (uint32_t)nb * (uint32_t)cells;
+    const uint8_t* tile = reinterpret_cast<const uint8_t*>(s_tile);
+    uint32_t done = 0u;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    if ((((uintptr_t)out) & 15u) == 0) {
+        done = bytes & ~15u;
+        for (uint32_t k = 16u * (uint32_t)lane; k < done; k += 16u * NT)
+            __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(tile + k), reinterpret_cast<u32x4*>(out + k));
+    } else if ((((uintptr_t)out) & 3u) == 0) {
+        done = bytes & ~3u;
+        for (uint32_t k = 4u * (uint32_t)lane; k < done; k += 4u * NT)
+            *reinterpret_cast<uint32_t*>(out + k) = *reinterpret_cast<const uint32_t*>(tile + k);
+    }
+    for (uint32_t k = done + (uint32_t)lane; k < bytes; k += NT) out[k] = tile[k];
 }
 
 // Runtime value -> template argument, on the host.  with_value<LO, HI>(v, f) calls f(std::integral_constant<int, v>) when

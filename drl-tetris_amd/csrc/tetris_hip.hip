@@ -576,26 +576,12 @@ __global__ __launch_bounds__(BLOCK) void k_observe_packed(Geo geo, int n, const 
             uint32_t col[NCOL];
             for (int c = 0; c < NCOL; c++) col[c] = word_at(br, W_COL0 + c);
             const uint32_t w = word_at(br, W_PIECE), m = word_at(br, W_MISC), dc = word_at(br, W_DROPCOMBO);
-            uint32_t* row = s_words + (size_t)threadIdx.x * nw;
-            for (int yp = 0; yp < H / 2; yp++) {
-                uint32_t lo[NCOL], hi[NCOL];                 // cells of rows 2 yp and 2 yp + 1
-                for (int c = 0; c < NCOL; c++) { lo[c] = col[c] & 1u; hi[c] = (col[c] >> 1) & 1u; col[c] >>= 2; }
-                row[5 * yp + 0] = lo[0] | (lo[1] << 8) | (lo[2] << 16) | (lo[3] << 24);
-                row[5 * yp + 1] = lo[4] | (lo[5] << 8) | (lo[6] << 16) | (lo[7] << 24);
-                row[5 * yp + 2] = lo[8] | (lo[9] << 8) | (hi[0] << 16) | (hi[1] << 24);
-                row[5 * yp + 3] = hi[2] | (hi[3] << 8) | (hi[4] << 16) | (hi[5] << 24);
-                row[5 * yp + 4] = hi[6] | (hi[7] << 8) | (hi[8] << 16) | (hi[9] << 24);
-            }
+            obs_row_words(col, H, s_words + (size_t)threadIdx.x * nw);
             // state_processors.py:23-54 vector: x, y, incoming, combo time, combo count, one-hot next piece
-            const uint32_t x = (uint32_t)((int)((w >> 5) & 15) - 4) & 0xFFu, y = (w >> 9) & 31u, next = (w >> 14) & 7u;
-            uint32_t t = ((dc >> 16) + 50u) & 0xFFFFu;     // uint16 + 50 wraps like numpy (state_processors.py:38)
-            if (t > 25000u) t = 25000u;
+            const ObsScalars s = obs_scalars(w, m, dc);
             uint32_t* v = (uint32_t*)(vector + ((size_t)sl * n + i) * 12);
-            const uint64_t hot = next < 7u ? (1ull << (8 * next)) : 0ull;          // bytes 5..11
-            v[0] = x | (y << 8) | ((m & 255u) << 16) | ((t / 100u) << 24);
-            v[1] = ((m >> 8) & 255u) | ((uint32_t)(hot & 0xFFFFFFu) << 8);
-            v[2] = (uint32_t)(hot >> 24);
-            piece[(size_t)sl * n + i] = (uint8_t)(w & 7u);
+            obs_vector_words(s, false, v[0], v[1], v[2]);
+            piece[(size_t)sl * n + i] = (uint8_t)s.kind;
         }
         __syncthreads();
         // the tile is not padded (rows nw words apart: at most two lanes per LDS bank while it is written), so it IS the output
@@ -1166,6 +1152,9 @@ struct tetris_batch {
     uint32_t* d_plan_status = nullptr;
     // the heuristic policy's spread mapping: the 40 scores of every game, [40][N], from k_policy_eval to the kernel that chooses
     int32_t* d_policy_scores = nullptr;
+    // tetris_traj_select_dev: the counts per workgroup and their scan (grown on demand)
+    int32_t* d_select_blocks = nullptr;
+    size_t select_blocks_cap = 0;
 };
 
 static Geo geo_of_batch(tetris_batch* b) {
@@ -1528,6 +1517,7 @@ int tetris_destroy(tetris_batch* b) {
     if (b->direct_used) { aql::Device* dev = aql::device_for(b->device); if (dev->ok) aql::quiesce(dev->qs); }      // (a test's idle kernel may still sit there)
     (void)hipFree(b->d_plan_slabs); (void)hipFree(b->d_iota); (void)hipFree(b->d_plan_status);
     (void)hipFree(b->d_policy_scores);
+    (void)hipFree(b->d_select_blocks);
     for (Stage& s : b->stage) s.release();
     b->recover_idx.release();
     if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -3186,6 +3176,111 @@ int tetris_traj_advantages_dev(tetris_batch* b, const tetris_traj* traj, int row
     if ((rc = traj_adv_args(b, traj, rows, gamma, lambda_adv, lambda_value, d_boot, d_adv, d_target, d_closed, aa))) return rc;
     hipLaunchKernelGGL((k_traj_advantages<TRAJ_THREADS>), dim3((unsigned)((b->N + TRAJ_BLOCK - 1) / TRAJ_BLOCK)), dim3(TRAJ_THREADS), 0,
                        b->stream, aa);
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- a window's states and sample sets (tetris_batch.h)
+// the checks the three calls share: the rules of tetris_traj_record_dev
+static int traj_batch_rules(tetris_batch* b, const char* what) {
+    if (b->split) return fail(TETRIS_E_ARG, (std::string(what) + " is not available on split batches").c_str());
+    if (b->P > 2) return fail(TETRIS_E_ARG, "the packed observation is defined for one or two players (own / opponent's board: state_unpack.py:88-137)");
+    return TETRIS_OK;
+}
+
+static int traj_obs_check(tetris_batch* b, const tetris_traj_obs* obs) {
+    if (!obs || !obs->d_obs) return fail(TETRIS_E_ARG, "the observation records are NULL");
+    if (((uintptr_t)obs->d_obs) & 15u) return fail(TETRIS_E_ARG, "d_obs must be 16-byte aligned");
+    if (obs->capacity < 1 || (unsigned long long)obs->capacity * (unsigned long long)b->N >= (1ull << 31)) return fail(TETRIS_E_ARG, "the window must hold between 1 and 2^31 - 1 entries");
+    return TETRIS_OK;
+}
+
+static int traj_select_args(tetris_batch* b, const uint8_t* d_mask, int rows, int flags, int32_t* d_index, long long cap, int32_t* d_count,
+                            TrajSelectArgs& sa) {
+    int rc = traj_batch_rules(b, "tetris_traj_select_dev");
+    if (rc) return rc;
+    if (!d_mask || !d_index || !d_count) return fail(TETRIS_E_ARG, "mask/index/count are NULL");
+    if (flags & ~TETRIS_SELECT_AUGMENT) return fail(TETRIS_E_ARG, "unknown flag");
+    if (rows < 1 || cap < 0) return fail(TETRIS_E_ARG, "rows < 1 or cap < 0");
+    if ((unsigned long long)rows * (unsigned long long)b->N >= (1ull << 31)) return fail(TETRIS_E_ARG, "rows * N must be below 2^31");
+    sa.mask = d_mask; sa.total = (uint32_t)rows * (uint32_t)b->N; sa.augment = flags & TETRIS_SELECT_AUGMENT;
+    sa.index = d_index; sa.cap = cap; sa.count = d_count;
+    sa.nblocks = (int)((sa.total + SELECT_ELEMS - 1) / SELECT_ELEMS);
+    sa.blocks = nullptr;
+    return TETRIS_OK;
+}
+
+static int traj_batch_args(tetris_batch* b, const tetris_traj* traj, const tetris_traj_obs* obs, const float* d_adv_in, const float* d_target_in,
+                           const int32_t* d_index, int M, const tetris_traj_batch* out, TrajBatchArgs& ba) {
+    int rc = traj_batch_rules(b, "tetris_traj_batch_dev");
+    if (rc) return rc;
+    if (!traj || !out || !d_index) return fail(TETRIS_E_ARG, "the window, the outputs or the index list are NULL");
+    if ((rc = traj_obs_check(b, obs))) return rc;
+    if (!traj->d_action || !traj->d_prob || !traj->d_reward || !traj->d_done) return fail(TETRIS_E_ARG, "an array of the window is NULL");
+    if (traj->capacity != obs->capacity) return fail(TETRIS_E_ARG, "the window and its observation records differ in capacity");
+    if (M < 0) return fail(TETRIS_E_ARG, "M < 0");
+    ba.m = M; ba.n_slots = b->P; ba.H = b->H;
+    ba.total = (uint32_t)traj->capacity * (uint32_t)b->N;
+    ba.index = d_index; ba.obs = obs->d_obs;
+    ba.action = traj->d_action; ba.prob = traj->d_prob; ba.reward = traj->d_reward; ba.done = traj->d_done;
+    ba.adv = d_adv_in; ba.target = d_target_in;
+    ba.visual = out->d_visual; ba.vector = out->d_vector; ba.piece = out->d_piece; ba.action_out = out->d_action;
+    ba.prob_out = out->d_prob; ba.adv_out = out->d_adv; ba.target_out = out->d_target; ba.reward_out = out->d_reward;
+    ba.done_out = out->d_done; ba.valid = out->d_valid;
+    return TETRIS_OK;
+}
+
+extern "C" {
+
+int tetris_traj_observe_dev(tetris_batch* b, const tetris_traj_obs* obs, int row, const uint8_t* d_player) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = traj_batch_rules(b, "tetris_traj_observe_dev")) || (rc = traj_obs_check(b, obs))) return rc;
+    if (row < 0 || row >= obs->capacity) return fail(TETRIS_E_ARG, "row outside the window");
+    TrajObserveArgs oa;
+    oa.geo = geo_of_batch(b); oa.n = b->N; oa.n_players = b->P; oa.player = d_player;
+    oa.obs = obs->d_obs + (size_t)row * (size_t)b->N * (size_t)b->P * OBS_WORDS;
+    b->home_async = true;
+    hipLaunchKernelGGL((k_traj_observe<256>), dim3((unsigned)((b->N + 255) / 256), (unsigned)b->P), dim3(256), 0, b->stream, oa);
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+int tetris_traj_select_dev(tetris_batch* b, const uint8_t* d_mask, int rows, int flags, int32_t* d_index, long long cap,
+                           int32_t* d_count) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    TrajSelectArgs sa;
+    if ((rc = traj_select_args(b, d_mask, rows, flags, d_index, cap, d_count, sa))) return rc;
+    if ((size_t)sa.nblocks + 1 > b->select_blocks_cap) {
+        if (b->d_select_blocks) { HIP_TRY(hipStreamSynchronize(b->stream)); (void)hipFree(b->d_select_blocks); }
+        b->d_select_blocks = nullptr; b->select_blocks_cap = 0;
+        HIP_TRY(hipMalloc((void**)&b->d_select_blocks, ((size_t)sa.nblocks + 1) * sizeof(int32_t)));
+        b->select_blocks_cap = (size_t)sa.nblocks + 1;
+    }
+    sa.blocks = b->d_select_blocks;
+    b->home_async = true;
+    const dim3 grid((unsigned)sa.nblocks), block(SELECT_THREADS);
+    hipLaunchKernelGGL((k_select_count<SELECT_THREADS>), grid, block, 0, b->stream, sa);
+    hipLaunchKernelGGL((k_select_scan<SELECT_THREADS>), dim3(1), block, 0, b->stream, sa);
+    hipLaunchKernelGGL((k_select_scatter<SELECT_THREADS>), grid, block, 0, b->stream, sa);
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+int tetris_traj_batch_dev(tetris_batch* b, const tetris_traj* traj, const tetris_traj_obs* obs, const float* d_adv_in,
+                          const float* d_target_in, const int32_t* d_index, int M, const tetris_traj_batch* out) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    TrajBatchArgs ba;
+    if ((rc = traj_batch_args(b, traj, obs, d_adv_in, d_target_in, d_index, M, out, ba))) return rc;
+    if (M == 0) return TETRIS_OK;
+    b->home_async = true;
+    const size_t lds = ba.visual ? (size_t)BATCH_BLOCK * b->H * NCOL : 0;          // at most 19 840 bytes (31 rows)
+    hipLaunchKernelGGL((k_traj_batch<BATCH_BLOCK>), dim3((unsigned)((M + BATCH_BLOCK - 1) / BATCH_BLOCK), (unsigned)b->P), dim3(BATCH_BLOCK), lds,
+                       b->stream, ba);
     HIP_TRY(hipGetLastError());
     return TETRIS_OK;
 }

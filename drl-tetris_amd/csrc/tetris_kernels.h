@@ -536,6 +536,31 @@ TE_HD void observe_body(const Geo& geo, int i, const int32_t* idx, int H,
     }
 }
 
+// The scalar bytes of state_dict's vector and piece (state_processors.py:23-54) from a board's W_PIECE, W_MISC and W_DROPCOMBO
+// words: what observe_board, k_observe_packed and the packed observation record of a trajectory window (tetris_batch.h) share.
+struct ObsScalars {
+    uint32_t x, y, inc, time, combo;      // vector bytes 0..4
+    uint32_t next;                        // index of the one-hot in vector bytes 5..11 (7: none)
+    uint32_t kind;                        // the piece byte (state_dict "piece_idx")
+};
+TE_HD ObsScalars obs_scalars(uint32_t w, uint32_t m, uint32_t dc) {
+    ObsScalars s;
+    s.x = (uint32_t)((int)((w >> 5) & 15) - 4) & 0xFFu; s.y = (w >> 9) & 31u; s.next = (w >> 14) & 7u;
+    uint32_t t = ((dc >> 16) + 50u) & 0xFFFFu;            // uint16 array + 50 wraps like numpy (state_processors.py:38)
+    if (t > 25000u) t = 25000u;
+    s.inc = m & 255u; s.time = t / 100u; s.combo = (m >> 8) & 255u;
+    s.kind = w & 7u;
+    return s;
+}
+// vector bytes 0..3, 4..7 and 8..11 as three little-endian words; `flip`: the seven one-hot bytes as 1 - one-hot
+TE_HD void obs_vector_words(const ObsScalars& s, bool flip, uint32_t& v0, uint32_t& v1, uint32_t& v2) {
+    uint64_t hot = s.next < 7u ? (1ull << (8 * s.next)) : 0ull;          // bytes 5..11
+    if (flip) hot ^= 0x01010101010101ull;
+    v0 = s.x | (s.y << 8) | (s.inc << 16) | (s.time << 24);
+    v1 = s.combo | ((uint32_t)(hot & 0xFFFFFFu) << 8);
+    v2 = (uint32_t)(hot >> 24);
+}
+
 // state_dict + unpacker for one player-board (state_processors.py:23-54, state_unpack.py:88-137):
 // `cells` receives H*10 bytes (field > 0, row-major), `vec` 12 bytes, returns the piece index
 TE_HD int observe_board(const Geo& geo, size_t slot, int p, int H, uint8_t* cells, uint8_t* vec) {
@@ -544,15 +569,10 @@ TE_HD int observe_board(const Geo& geo, size_t slot, int p, int H, uint8_t* cell
     for (int c = 0; c < NCOL; c++) col[c] = word_at(br, W_COL0 + c);
     for (int y = 0; y < H; y++)
         for (int c = 0; c < NCOL; c++) cells[y * NCOL + c] = (uint8_t)((col[c] >> y) & 1u);
-    const uint32_t w = word_at(br, W_PIECE);
-    const uint32_t m = word_at(br, W_MISC);
-    const uint32_t dc = word_at(br, W_DROPCOMBO);
-    const int x = (int)((w >> 5) & 15) - 4, y = (w >> 9) & 31, next = (w >> 14) & 7;
-    uint32_t t = ((dc >> 16) + 50u) & 0xFFFFu;            // uint16 array + 50 wraps like numpy (state_processors.py:38)
-    if (t > 25000u) t = 25000u;
-    vec[0] = (uint8_t)x; vec[1] = (uint8_t)y; vec[2] = (uint8_t)(m & 255); vec[3] = (uint8_t)(t / 100u); vec[4] = (uint8_t)((m >> 8) & 255);
-    for (int k = 0; k < 7; k++) vec[5 + k] = (uint8_t)(next == k);
-    return (int)(w & 7);
+    const ObsScalars s = obs_scalars(word_at(br, W_PIECE), word_at(br, W_MISC), word_at(br, W_DROPCOMBO));
+    vec[0] = (uint8_t)s.x; vec[1] = (uint8_t)s.y; vec[2] = (uint8_t)s.inc; vec[3] = (uint8_t)s.time; vec[4] = (uint8_t)s.combo;
+    for (int k = 0; k < 7; k++) vec[5 + k] = (uint8_t)(s.next == (uint32_t)k);
+    return (int)s.kind;
 }
 
 // ---------------------------------------------------------------- drop enumeration (BASELINE config 4)

@@ -289,9 +289,10 @@ class TorchEnv:
 
     # ---- trajectory windows (include/tetris_hip.h: tetris_traj_record_dev, tetris_traj_advantages_dev): the worker-side arithmetic
     # between perform_action and the data packet (drl_tetris/worker.py:103-112)
-    def trajectory(self, capacity):
-        """A window of `capacity` rows of this batch's games: -> Trajectory (device tensors, allocated once)."""
-        return Trajectory(self, capacity)
+    def trajectory(self, capacity, states=False):
+        """A window of `capacity` rows of this batch's games: -> Trajectory (device tensors, allocated once).  states: the window
+        also holds the packed observation records (observe / select / batch)."""
+        return Trajectory(self, capacity, states)
 
 
 class Trajectory:
@@ -301,9 +302,12 @@ class Trajectory:
     record(row) replaces store_experience, advantages(...) sventon_trajectory.process_trajectory(compute_advantages=True)
     (agents/datatypes/trajectory.py:56-86, 111-141).  The actor loop is network forward, step_eval_observe, record, and every T
     steps one advantages call; everything is reused device tensors and nothing waits for the GPU.  A caller with rewards of
-    their own (dual-policy re-pairing, extra rewards) fills `reward` / `done` themselves and calls advantages."""
+    their own (dual-policy re-pairing, extra rewards) fills `reward` / `done` themselves and calls advantages.
+    With states=True the window also holds obs int32 [T, n, S, 12] (the words are uint32), the packed observation record of
+    include/tetris_hip.h: observe(row) before the acting call of the row, then after advantages select(...) lists the finished
+    entries and batch(index) expands a minibatch of them, mirrored or not, into the trainer's arrays."""
 
-    def __init__(self, env, capacity):
+    def __init__(self, env, capacity, states=False):
         torch, n = env.torch, env.b.n_games
         assert int(capacity) >= 1, "a window has at least one row"
         self.env, self.capacity = env, int(capacity)
@@ -314,6 +318,12 @@ class Trajectory:
         self.adv, self.target, self.closed = torch.zeros(T, n, **f32), torch.zeros(T, n, **f32), torch.zeros(T, n, **u8)
         p = env._ptr
         self._traj = env.b.traj(T, p(self.action), p(self.prob), p(self.value), p(self.reward), p(self.done))
+        if states:
+            assert env.b.n_players <= 2, "the packed observation is defined for one or two players"
+            self.obs = torch.zeros(T, n, env.b.n_players, 12, dtype=torch.int32, device=env.dev)
+            self._obs = env.b.traj_obs(T, p(self.obs))
+            self.count = torch.zeros(1, dtype=torch.int32, device=env.dev)
+            self._index, self._batches, self._rows = {}, {}, 0
 
     def record(self, row):
         """Row `row` from the last step_eval / step_eval_observe call of the TorchEnv: its (r, t, piece), chosen entry, values
@@ -334,4 +344,53 @@ class Trajectory:
             assert bootstrap.dtype == torch.float32 and bootstrap.is_cuda and bootstrap.is_contiguous() and bootstrap.numel() == env.b.n_games
         p = env._ptr
         env.b.traj_advantages_dev(self._traj, rows, gamma, gae_lambda, gve_lambda, p(bootstrap), p(self.adv), p(self.target), p(self.closed))
+        if hasattr(self, "obs"):
+            self._rows = rows
         return self.adv[:rows], self.target[:rows], self.closed[:rows]
+
+    # ---- states and sample sets (include/tetris_hip.h: tetris_traj_observe_dev, tetris_traj_select_dev, tetris_traj_batch_dev)
+    def observe(self, row, player=None):
+        """Row `row` of obs from the games' current state, perspective of player (uint8 [n] or None: player 0): call it before the
+        acting call of the row — observe(row), step_eval_observe, record(row)."""
+        assert hasattr(self, "obs"), "the window was made without states=True"
+        self.env._check_player(player)
+        self.env.b.traj_observe_dev(self._obs, row, self.env._ptr(player))
+
+    def select(self, rows, mask=None, augment=False, capacity=None):
+        """The flat indices t n + i of the non-zero entries of mask uint8 [rows, n] (None: closed of the last advantages call) in
+        ascending order, with augment followed by the same list with bit 31 set (augment_data's concatenation): -> (index int32
+        [capacity], count int32 [1]) device tensors, reused; -1 past the list; count is the full length even when it exceeds
+        capacity (default: rows n, twice that with augment)."""
+        env, torch = self.env, self.env.torch
+        assert hasattr(self, "obs"), "the window was made without states=True"
+        n = env.b.n_games
+        if mask is None:
+            assert 1 <= rows <= self._rows, "no advantages call covers these rows"
+            mask = self.closed
+        assert mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.numel() >= rows * n
+        cap = rows * n * (2 if augment else 1) if capacity is None else int(capacity)
+        if cap not in self._index:
+            self._index[cap] = torch.zeros(max(cap, 1), dtype=torch.int32, device=env.dev)
+        index = self._index[cap]
+        env.b.traj_select_dev(env._ptr(mask), rows, env._ptr(index), cap, env._ptr(self.count), augment=augment)
+        return index[:cap], self.count
+
+    def batch(self, index):
+        """The samples index (int32 device tensor [M]: a slice of select's list, permuted at will; bit 31 = mirrored, -1 = none)
+        names -> TrajectoryBatch(visual [S, M, H, 10], vector [S, M, 12], piece [S, M], action [M, 3], prob, adv, target, reward
+        [M], done, valid [M]) device tensors, reused per M.  adv / target are those of the last advantages call."""
+        from collections import namedtuple
+        env, torch = self.env, self.env.torch
+        assert hasattr(self, "obs"), "the window was made without states=True"
+        assert index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.dim() == 1
+        M, S, H = index.numel(), env.b.n_players, env.b.height
+        if M not in self._batches:
+            u8, f32 = dict(dtype=torch.uint8, device=env.dev), dict(dtype=torch.float32, device=env.dev)
+            kind = namedtuple("TrajectoryBatch", "visual vector piece action prob adv target reward done valid")
+            t = kind(torch.zeros(S, M, H, 10, **u8), torch.zeros(S, M, 12, **u8), torch.zeros(S, M, **u8), torch.zeros(M, 3, **u8),
+                     torch.zeros(M, **f32), torch.zeros(M, **f32), torch.zeros(M, **f32), torch.zeros(M, **f32), torch.zeros(M, **u8),
+                     torch.zeros(M, **u8))
+            self._batches[M] = (t, env.b.traj_batch(*[env._ptr(x) for x in t]))
+        t, out = self._batches[M]
+        env.b.traj_batch_dev(self._traj, self._obs, env._ptr(index), M, out, adv=env._ptr(self.adv), target=env._ptr(self.target))
+        return t

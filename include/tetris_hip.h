@@ -466,6 +466,76 @@ int tetris_traj_record_dev(tetris_batch *b, const tetris_traj *traj, int row, co
 int tetris_traj_advantages_dev(tetris_batch *b, const tetris_traj *traj, int rows, float gamma, float lambda_adv,
                                float lambda_value, const float *d_boot, float *d_adv, float *d_target, uint8_t *d_closed);
 
+/* ---- trajectory windows: the states, the finished entries, a minibatch in the trainer's form ----------------------------
+ * replaces: what lies between a processed trajectory and the trainer's model.train(...) arguments —
+ * sventon_trajectory.process_trajectory(..., augment=...) with augment_data (agents/datatypes/trajectory.py:56-109),
+ * experience_replay.add_samples / retrieve_all (agents/agent_utils/experience_replay.py:96-150) and the permuted minibatch
+ * slices of sventon_agent_ppo_trainer.do_training (sventon_agent_ppo_trainer.py:34-62) — for the window's own sample set
+ * (no priorities, no k-step views).  Three calls; device pointers, asynchronous on the batch's stream; one and two players.
+ * TETRIS_E_ARG for three or four players, split batches and NULLs as for tetris_traj_record_dev.
+ *
+ * THE PACKED OBSERVATION RECORD (struct tetris_traj_obs): d_obs is uint32 [T][N][S][12], S = number of players, 16-byte
+ * aligned: SAMPLE-major, the record of entry (t, n) is 48 S contiguous bytes, slot 0 = the board of d_player[n] at the time,
+ * slot 1 = the opponent's (the perspective order of tetris_observe_packed).  Per slot:
+ *   words 0..9   occupancy of columns 0..9, bit y = row y (state words 0..9; bits at and above H carry no meaning)
+ *   word 10      x | y << 8 | inc_lines << 16 | combo_time << 24       the bytes tetris_observe_packed writes to vector[0..3]
+ *   word 11      combo_count | next << 8 | piece << 16                 vector[4]; the index of the one-hot of vector[5..11]
+ *                                                                      (7: none); the byte tetris_observe_packed writes to `piece`
+ * 48 bytes per player-board against the 213 of the byte planes.  (Sample-major so that a gather touches one or two cache
+ * lines per sample; a word-major layout has not been measured against it.)
+ * OBSERVE (replaces: keeping trajectory.s, the states state_fcn later unpacks — trajectory.py:24-31, 62) writes row `row`
+ * from the batch's current state, which it only reads; d_player [N] or NULL as for tetris_observe_packed_dev.  Colour
+ * batches give the same records (occupancy).  In the actor loop: observe(row), tetris_step_eval_observe_dev, record(row).
+ * TETRIS_E_ARG: a NULL obs or d_obs, d_obs not 16-byte aligned, row outside [0, T).
+ *
+ * SELECT (replaces: the choice of the entries that reach the replay, experience_replay.py:96-150, in the order of
+ * augment_data's np.concatenate([x, x2]), trajectory.py:102-106): d_mask uint8 [rows][N] (typically d_closed of
+ * tetris_traj_advantages_dev; any non-zero byte counts).  d_index int32 [cap] receives the flat indices t N + n of the
+ * non-zero entries in ascending order; with TETRIS_SELECT_AUGMENT the same list follows once more with bit 31 set.  d_count
+ * int32 [1] receives the length of the full list (k or 2 k) even when it exceeds cap; then the first cap entries are written.
+ * Entries past the list, up to cap, are set to -1.  Stable and deterministic; three launches, no workgroup waits for another.
+ * TETRIS_E_ARG: NULL d_mask, d_index or d_count; rows < 1; cap < 0; rows N >= 2^31; an unknown flag.
+ *
+ * BATCH (replaces: state_fcn(self.s, player=self.p[, mirrored=True]) of the chosen entries — state_dict's `aug`,
+ * environment/env_utils/state_processors.py:44-53, through unpacker(..., mirrored=True), agents/agent_utils/
+ * state_unpack.py:88-105 — augment_data's mirrored action, trajectory.py:88-99, and the trainer's slices): d_index int32 [M],
+ * any order, repeats allowed.  Outputs, each NULL to skip it:
+ *   d_visual uint8 [S][M][H][10], d_vector uint8 [S][M][12], d_piece uint8 [S][M]     as tetris_observe_packed
+ *   d_action uint8 [M][3] (r, t, piece); d_prob, d_adv, d_target, d_reward float32 [M]; d_done, d_valid uint8 [M]
+ * (struct tetris_traj_batch).  d_adv_in / d_target_in: float32 [T][N] like the window (row stride N; rows no index names
+ * are not read), either may be NULL: zeros.  With e = d_index[j] & 0x7FFFFFFF = t N + n:
+ *   bit 31 clear: the bytes tetris_observe_packed gave for that state, the row entry of the window; floats bit for bit.
+ *   bit 31 set: the reference's mirrored sample, both slots: field column c is column 9 - c; piece is piece_swap[piece],
+ *     piece_swap = (1, 0, 3, 2, 4, 5, 6), 7 stays 7; the seven nextpiece bytes are piece_swap[int(p == next)], that is
+ *     1 - one-hot — THE REFERENCE'S QUIRK (state_processors.py:50 indexes piece_swap with the one-hot's values), kept;
+ *     x, y, inc_lines, combo_time, combo_count unchanged; action r unchanged, t -> 9 - t, piece -> piece_swap[piece].
+ *   e outside [0, T N) — -1 among them: zeros everywhere and d_valid = 0 (else 1).
+ * TETRIS_E_ARG: NULL traj, obs, out, d_index, d_obs or d_action / d_prob / d_reward / d_done of the window; capacities of
+ * traj and obs that differ; d_obs not 16-byte aligned; M < 0; T N >= 2^31.                                                  */
+#define TETRIS_SELECT_AUGMENT 1
+typedef struct tetris_traj_obs {
+    int       capacity;    /* T */
+    int       reserved;    /* 0 */
+    uint32_t *d_obs;       /* [T][N][S][12], 16-byte aligned */
+} tetris_traj_obs;
+typedef struct tetris_traj_batch {
+    uint8_t *d_visual;     /* [S][M][H][10] */
+    uint8_t *d_vector;     /* [S][M][12] */
+    uint8_t *d_piece;      /* [S][M] */
+    uint8_t *d_action;     /* [M][3] */
+    float   *d_prob;       /* [M] */
+    float   *d_adv;        /* [M] */
+    float   *d_target;     /* [M] */
+    float   *d_reward;     /* [M] */
+    uint8_t *d_done;       /* [M] */
+    uint8_t *d_valid;      /* [M] */
+} tetris_traj_batch;
+int tetris_traj_observe_dev(tetris_batch *b, const tetris_traj_obs *obs, int row, const uint8_t *d_player);
+int tetris_traj_select_dev(tetris_batch *b, const uint8_t *d_mask, int rows, int flags, int32_t *d_index, long long cap,
+                           int32_t *d_count);
+int tetris_traj_batch_dev(tetris_batch *b, const tetris_traj *traj, const tetris_traj_obs *obs, const float *d_adv_in,
+                          const float *d_target_in, const int32_t *d_index, int M, const tetris_traj_batch *out);
+
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
  * t = w1 mod 10), acting player = step mod P, perform_action, auto-reset of finished games with
