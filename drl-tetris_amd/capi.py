@@ -120,6 +120,7 @@ _SIGNATURES = {
     "tetris_rollout_was_direct": (C.c_int, [C.c_void_p]),
     "tetris_set_xcd_affine": (C.c_int, [C.c_void_p, C.c_int]),
     "tetris_debug_xcd_skew": (C.c_int, [C.c_void_p, C.c_int]),
+    "tetris_debug_table_limit": (C.c_int, [C.c_void_p, C.c_int]),
     "tetris_debug_code_objects": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     "tetris_set_chain_spin_limit": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tetris_debug_stall": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -646,6 +647,11 @@ class TetrisBatch:
     def debug_xcd_skew(self, skew):
         """Test aid: the kernels are told start XCDs that are off by `skew` (every workgroup then finds itself misplaced)."""
         self._check(self.lib.tetris_debug_xcd_skew(self._h, int(skew)))
+
+    def debug_table_limit(self, chunks):
+        """Test aid (include/tetris_hip.h: tetris_debug_table_limit): this batch's episodes end with TETRIS_ERR_STREAM after
+        624 * chunks piece draws (1..64; 0 = the real limit, 64)."""
+        self._check(self.lib.tetris_debug_table_limit(self._h, int(chunks)))
 
     def set_chain_spin_limit(self, polls):
         """Polls of the predecessor's epoch word after which a waiting wave of a chained launch gives up (0 = default, ~2 s)."""

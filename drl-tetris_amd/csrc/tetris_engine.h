@@ -252,7 +252,8 @@ struct Game {
 // state[(w * P + p) * n + slot]; game words at gstate[w * n + slot]
 // one player-board: word w of this board lives at s[w * ws]
 template <class ROWS>
-TE_HD void load_player_rows(const uint32_t* s, uint32_t o, const ROWS& rows, Player& q, bool tint, bool queue = true, int mem = MEM_STREAM) {
+TE_HD void load_player_rows(const uint32_t* s, uint32_t o, const ROWS& rows, Player& q, bool tint, bool queue = true, int mem = MEM_STREAM,
+                            bool errs = true) {
     for (int c = 0; c < NCOL; c++) q.col[c] = ldw_b(s, o, row_bytes(rows, W_COL0 + c), mem);
     if (tint)
         for (int k = 0; k < 3; k++)
@@ -263,7 +264,10 @@ TE_HD void load_player_rows(const uint32_t* s, uint32_t o, const ROWS& rows, Pla
     w = ldw_b(s, o, row_bytes(rows, W_MISC), mem);
     q.inc_count = w & 255; q.combo_count = (w >> 8) & 255; q.line_count = (w >> 16) & 255;
     q.qlen = (w >> 24) & 15; q.q_overflow = (w >> 28) & 3;
-    if (!queue) { q.inc_count = 0; q.qlen = 0; q.q_overflow = 0; }      // invariants of a game without opponents
+    if (!queue) { q.inc_count = 0; q.qlen = 0; }                        // invariants of a game without opponents
+    // ERR_STREAM ends one-player games too, and the board carries it until the reset.  `errs` = false (the built-in rollouts, which
+    // reset a game in the step that ends it and so never load the bit set): known zero, nothing is extracted
+    if (!queue && !errs) q.q_overflow = 0;
     q.time_ms = (int32_t)ldw_b(s, o, row_bytes(rows, W_TIME), mem);
     w = ldw_b(s, o, row_bytes(rows, W_DROPCOMBO), mem);
     q.drop_delay = w & 0xFFFF; q.combo_remaining = w >> 16;
@@ -329,7 +333,7 @@ TE_HD void load_game_rows(const Geo& geo_in, size_t slot, const ROWS& rows, cons
     TE_UNROLL
     for (int p = 0; p < P; p++) {
         const Ref r = board_ref(geo, p, slot);
-        load_player_rows(r.s, r.o, rows, g.pl[p], tint, queue, mem);
+        load_player_rows(r.s, r.o, rows, g.pl[p], tint, queue, mem, !counters);
     }
 }
 template <int P>
@@ -1451,6 +1455,9 @@ TE_HD uint32_t split_settle(const Ctx& cx, Game<1>& g) {
     Player& q = g.pl[0];
     if (g.round_over || q.dead) return 0u;
     int sent = settle(cx, q, g.seed16, g.status);
+    // the piece settle deals is the one that can run past the tables.  g.status does not outlive this stage's kernel: the bit goes
+    // onto the board now, and stage B tells the other side (XW_ERR)
+    if (g.status & ST_STREAM_EXHAUSTED) q.q_overflow |= ERR_STREAM;
     if (sent == -1) { q.dead = 1; return XW_RAN | XW_DIED; }
     return XW_RAN | (uint32_t)(sent & 0xFFFF);
 }

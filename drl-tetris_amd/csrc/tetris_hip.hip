@@ -1129,6 +1129,7 @@ struct tetris_batch {
     int use_affine = 1;                  // XCD-affine launches (k_chain_affine) where the device's queues allow them; TETRIS_AFFINE=0 / tetris_set_xcd_affine
     bool last_affine = false;            // the last rollout call ran them
     uint32_t xcd_skew = 0;               // test aid (tetris_debug_xcd_skew): added to the queues' measured start XCDs
+    int table_limit = MAX_CHUNKS;        // test aid (tetris_debug_table_limit): this batch's kernels see at most that many chunks of the tables
     int affine_failures = 0;             // calls in which a workgroup found itself misplaced (three: the affine form is switched off)
     bool home_async = false;             // asynchronous (_dev) work was enqueued on the batch's stream since the last drain
     // something was enqueued on one of the batch's streams since the last drain.  Whatever enqueues sets it (check_batch, HostCall,
@@ -1169,7 +1170,7 @@ static KArgs base_args(tetris_batch* b, int n, const int32_t* d_idx) {
     {   // tables are shared between batches: take pointer and size together (another batch may be growing them)
         std::lock_guard<std::mutex> lock(g_tab_mutex);
         a.table = b->tab->d_table;
-        a.n_draws = (uint32_t)b->tab->n_chunks * CHUNK;
+        a.n_draws = (uint32_t)(b->tab->n_chunks < b->table_limit ? b->tab->n_chunks : b->table_limit) * CHUNK;
     }
     a.start = b->tab->d_start; a.combo_pow = b->tab->d_pow; a.margin = b->margin;
     a.H = b->H; a.n_games = b->N; a.n_stride = b->stride; a.n_players = b->P; a.nw = b->nw; a.n = n; a.idx = d_idx; a.game_offset = b->game_offset;
@@ -1280,9 +1281,9 @@ static int service_flags(tetris_batch* b) {
     const uint32_t want = f[F_EXTEND];
     if (want) {
         std::lock_guard<std::mutex> lock(g_tab_mutex);
-        // not yet answered (requests carry the size their kernel saw); at MAX_CHUNKS the tables stay as they are and a game
-        // that outruns them is ended with ERR_STREAM
-        if (want >= (uint32_t)b->tab->n_chunks * CHUNK && b->tab->n_chunks < MAX_CHUNKS) {
+        // not yet answered (requests carry the size their kernel saw); at MAX_CHUNKS (the batch's table_limit) the tables stay as
+        // they are and a game that outruns them is ended with ERR_STREAM
+        if (want >= (uint32_t)b->tab->n_chunks * CHUNK && b->tab->n_chunks < b->table_limit) {
             int rc = tables_extend(b->tab, b->stream);
             if (rc) return rc;
             b->busy = true;
@@ -1676,6 +1677,15 @@ int tetris_debug_xcd_skew(tetris_batch* b, int skew) {
     if (rc) return rc;
     if ((rc = finish_call(b))) return rc;
     b->xcd_skew = (uint32_t)skew & 7u;
+    return TETRIS_OK;
+}
+
+int tetris_debug_table_limit(tetris_batch* b, int chunks) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if (chunks < 0 || chunks > MAX_CHUNKS) return fail(TETRIS_E_ARG, "chunks must be 0..64");
+    if ((rc = finish_call(b))) return rc;
+    b->table_limit = chunks ? chunks : MAX_CHUNKS;
     return TETRIS_OK;
 }
 

@@ -335,11 +335,18 @@ TE_HD void game_run(const KArgs& a, int i, const uint32_t* shapes, Game<P>& g, L
             reset_game<P>(cx, g, episode_seed(a.game_offset + (uint32_t)slot, g.episode), &rpf);
         }
     } else if (MODE == M_ROLLOUT) {
+        // g.status is one STEP's: confine_errors reads it, and a game that a capacity error ended in one step of this launch has
+        // been reset when the next begins — left standing, ST_STREAM_EXHAUSTED would end the new game in every further step
+        uint32_t earlier = 0;
         for (int s = 0; s < a.steps; s++) {
             unsigned long long step = a.first_step + (unsigned long long)s;
             rollout_step<P>(cx, a, slot, step, g, cnt);
-            if (s + 1 < a.steps) policy_draw(a, (uint32_t)slot, step + 1, g.draw0, g.draw1);
+            if (s + 1 < a.steps) {
+                policy_draw(a, (uint32_t)slot, step + 1, g.draw0, g.draw1);
+                earlier |= g.status; g.status = 0;
+            }
         }
+        g.status |= earlier;
     }
     store_game<P>(geo_of(a), slot, g, TINT, P > 1 || MODE == M_SPLIT_INIT || MODE == M_SPLIT_RESET,
                   MODE == M_ROLLOUT || MODE == M_INIT || MODE == M_SPLIT_INIT, MEM);   // 1-player: FIFO words stay as zeroed at creation
@@ -369,6 +376,7 @@ TE_HD void undo_simple_settle(Player& q, uint32_t pose, uint32_t group, uint32_t
     q.kind = (int)(pose & 7u); q.rot = (int)((pose >> 3) & 3u); q.x = (int)((pose >> 5) & 15u) - 4;
     q.y = (int)((pose >> 9) & 31u); q.next = (int)((pose >> 14) & 7u);
     q.pgroup = group; q.piece_draws = draws; q.pf_ok = 0;
+    q.q_overflow &= ~ERR_STREAM;         // (raised, if at all, by the piece this pass dealt: a board that had it before did not run)
     q.combo_time += 200;
 }
 

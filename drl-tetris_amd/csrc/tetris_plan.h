@@ -183,7 +183,9 @@ TE_HD void plan_sim_lane(const PlanArgs& pa, int i, int k, bool fin, const uint3
     TE_UNROLL
     for (int p = 0; p < P; p++)
         for (int col = 0; col < NCOL; col++) pa.cols[(((size_t)k * P + p) * NCOL + col) * n + i] = g.pl[p].col[col];
-    report_status(a, g.status);
+    // a simulated afterstate that runs over a capacity limit says so in its `done`; no game of the batch was ended (nothing is
+    // stored), so tetris_take_errors has nothing to report.  The request to extend the tables stands.
+    report_status(a, g.status & ~(uint32_t)(ST_STREAM_EXHAUSTED | ST_FIFO_OVERFLOW));
 }
 
 // perform_action(lists[choice[i]], player) (tetris_environment.py:102-116): the step of M_STEP_KEYS with the chosen list for

@@ -229,7 +229,9 @@ TE_HD void policy_step_lane(const PolicyArgs& pa, int i, const uint32_t* shapes,
     int w[POLICY_FEATURES];
     if (!FROM_SCORES) policy_weights(pa, i, w);
     const int steps = ROLL ? a.steps : 1;
+    uint32_t earlier = 0;            // the status bits of the launch's earlier steps (g.status is one step's: see game_run)
     for (int s = 0; s < steps; s++) {
+        if (ROLL) { earlier |= g.status; g.status = 0; }
         const unsigned long long step = a.first_step + (unsigned long long)s;
         const int player = ROLL ? (P > 1 ? (int)(step % (unsigned long long)P) : 0) : safe_player(pa.player, i, P);
         int32_t best;
@@ -262,7 +264,7 @@ TE_HD void policy_step_lane(const PolicyArgs& pa, int i, const uint32_t* shapes,
         }
     }
     store_game<P>(geo_of(a), (size_t)i, g, TINT, P > 1, ROLL);
-    report_status(a, g.status);
+    report_status(a, g.status | earlier);
 }
 
 // tetris_rollout_game_totals_dev: totals[k][i] = the per-game word tetris_rollout_totals sums

@@ -53,7 +53,24 @@ extern "C" {
  * (Garbage.h:27) and its generators never run out (randomizer.h:44-50); here a board holds at most 8 pending garbage
  * packets and an episode at most 39 936 piece draws.  A game that exceeds either ends its round in that step (`done`), its
  * boards carry the bits below in tetris_record.fifo_overflow until the game is reset, and every other game of the batch
- * goes on untouched.  tetris_take_errors tells whether any game of the batch was ended this way since the last call.   */
+ * goes on untouched.  tetris_take_errors tells whether any game of the batch was ended this way since the last call.
+ * THE RULE.  Draws: the step in which a board's piece_draws REACHES the limit (tetris_record.piece_draws: two at the reset, one
+ * more with every piece dealt; every live board is dealt one per step) — the piece that appears in that step is still right,
+ * the `next` behind it is the first that is not.  TETRIS_ERR_STREAM is set on EVERY board of the game: the seed, and with it the
+ * tables, is the game's.  Queue: the step in which a packet arrives at a board that has 8 pending; TETRIS_ERR_FIFO is set on that
+ * board and on no other, the packet is dropped, the eight stay.
+ * WHAT THE STEP SHOWS.  done = 1; `lines` and `dead`, the boards' lines_cleared / lines_sent and the per-game counters of the
+ * built-in rollouts (lines cleared, lines sent, one episode) are what the step did before it was cut short — the reference's
+ * numbers for that step.  Nobody need be dead: a game ended this way has done = 1 with all its `dead` flags 0 (a player who dies
+ * in that very step is dead as usual), so tetris_traj_record_dev's reward for it is 0, and the reset that follows leaves
+ * last_winner as for any round that is reset with more than one player alive: -1 (one-player games: 0).
+ * AFTERWARDS.  Without auto-reset the game is round-over: stepping calls leave it exactly as it is (done = 1 every time) until
+ * tetris_reset / tetris_reset_dev, after which it is an ordinary game again.  With TETRIS_STEP_AUTO_RESET and in the built-in
+ * rollouts it is reset inside the same launch like any finished game, so the bits are gone from its boards when the call
+ * returns, and tetris_take_errors is the only witness.  (State.inc_count of a board is refreshed by a step, not by a reset —
+ * here as in the reference: until its next step a board reset after TETRIS_ERR_FIFO shows the total of the eight packets it held.)
+ * A SIMULATION ENDS NO GAME: a list of tetris_simulate_lists_dev whose afterstate runs over either limit has done = 1 in the
+ * simulation's own output; the batch's state is not written and tetris_take_errors is not told.                            */
 #define TETRIS_ERR_FIFO 1u       /* a 9th garbage packet arrived while 8 were pending: it was dropped */
 #define TETRIS_ERR_STREAM 2u     /* the episode ran past the RNG tables: the pieces dealt in that step are wrong */
 /* Not a capacity error and nothing is wrong with any game: reported once by tetris_take_errors after a chained rollout call had
@@ -607,6 +624,12 @@ int tetris_rollout_was_direct(tetris_batch *b);
 int tetris_set_xcd_affine(tetris_batch *b, int on);
 /* TEST AID for the check above: `skew` (0..7) is added to the start XCDs the kernels are told                              */
 int tetris_debug_xcd_skew(tetris_batch *b, int skew);
+/* TEST AID for the draw limit (TETRIS_ERR_STREAM; nothing in the product calls it): the real limit needs all 64 chunks of the RNG
+ * tables, 2.6 GB.  From this call on the kernels of THIS batch are told min(resident chunks, chunks) * 624 draws per episode, and a
+ * request to extend the tables is answered only while they have fewer than `chunks` chunks — what happens at 64 without it.
+ * chunks = 1..64; 0 restores 64.  The tables themselves (shared by the batches of a device with the same piece map) and
+ * tetris_table_chunks are not affected; other batches see all of them.  Synchronises.                                       */
+int tetris_debug_table_limit(tetris_batch *b, int chunks);
 /* TEST AID (needs no GPU): the gfx950 code objects direct dispatch would load — found in this library's own fat binary —: their
  * number and total size in bytes.  0 objects = direct dispatch cannot work with this build (e.g. a compressed offload bundle).  */
 int tetris_debug_code_objects(int *count, uint64_t *bytes);
@@ -665,7 +688,8 @@ int tetris_set_game_offset(tetris_batch *b, uint64_t first_game_id);
  * player 1's B words (entries a stage does not read may be NULL): the words a stage wrote (d_out) and the rows an
  * all-gather delivered are read where they lie, nothing is copied in between.  d_out [n]: this stage's words (stages 0, 1, 3).
  * All data pointers are device pointers; everything is enqueued on the batch's stream.  tetris_reset() on a split
- * batch applies the two-player winner rule.
+ * batch applies the two-player winner rule.  A capacity error (TETRIS_ERR_*) on one side ends the round on BOTH sides in the
+ * same step (a bit of the B words); the bit is on the board that has it, and tetris_take_errors of that side's batch reports it.
  * Why three exchanges and not two: within one step the reference's order makes player 0's tick depend on player 1's loop-1
  * words (A), player 1's tick on player 0's tick words (B0), and `done` on player 1's tick words (B1) — three messages that
  * depend on each other.  Folding B1 into the next step's A exchange would need a second speculative shadow state on side 0

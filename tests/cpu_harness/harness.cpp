@@ -77,6 +77,7 @@ struct tetris_batch {
     uint32_t game_offset = 0;
     int split = 0, side = 0;
     int tint = 0, nw = NWORDS;
+    int table_limit = MAX_CHUNKS;    // tetris_debug_table_limit
     std::vector<uint32_t> shadow;
     Tables* tab;
 };
@@ -86,7 +87,7 @@ static KArgs base_args(tetris_batch* b, int n, const int32_t* idx) {
     memset(&a, 0, sizeof a);
     a.state = b->state.data(); a.gstate = b->gstate.empty() ? b->state.data() : b->gstate.data(); a.status = b->flags;
     a.table = b->tab->table.data(); a.start = b->tab->start.data(); a.combo_pow = b->tab->powtab;
-    a.n_draws = (uint32_t)b->tab->n_chunks * CHUNK; a.margin = b->margin;
+    a.n_draws = (uint32_t)(b->tab->n_chunks < b->table_limit ? b->tab->n_chunks : b->table_limit) * CHUNK; a.margin = b->margin;
     a.H = b->H; a.n_games = b->N; a.n_stride = b->N; a.n_players = b->P; a.nw = b->nw; a.n = n; a.idx = idx; a.game_offset = b->game_offset;
     return a;
 }
@@ -116,7 +117,7 @@ static void run(tetris_batch* b, const KArgs& a, LaneCounters* total = nullptr) 
 
 static int finish_call(tetris_batch* b) {
     if (b->flags[F_EXTEND]) {
-        if (b->flags[F_EXTEND] >= (uint32_t)b->tab->n_chunks * CHUNK && b->tab->n_chunks < MAX_CHUNKS) b->tab->extend();
+        if (b->flags[F_EXTEND] >= (uint32_t)b->tab->n_chunks * CHUNK && b->tab->n_chunks < b->table_limit) b->tab->extend();
         b->flags[F_EXTEND] = 0;
     }
     if (b->flags[F_BADARG]) { b->flags[F_BADARG] = 0; return fail(TETRIS_E_ARG, "output capacity exceeded"); }
@@ -254,6 +255,11 @@ int tetris_set_direct_dispatch(tetris_batch*, int) { return TETRIS_OK; }
 int tetris_rollout_was_direct(tetris_batch*) { return 0; }
 int tetris_set_xcd_affine(tetris_batch*, int) { return TETRIS_OK; }
 int tetris_debug_xcd_skew(tetris_batch*, int) { return TETRIS_OK; }
+int tetris_debug_table_limit(tetris_batch* b, int chunks) {
+    if (!b || chunks < 0 || chunks > MAX_CHUNKS) return fail(TETRIS_E_ARG, "chunks must be 0..64");
+    b->table_limit = chunks ? chunks : MAX_CHUNKS;
+    return TETRIS_OK;
+}
 int tetris_debug_code_objects(int* count, uint64_t* bytes) { if (count) *count = 0; if (bytes) *bytes = 0; return TETRIS_OK; }
 int tetris_debug_stall(tetris_batch*, int, int, int) { return TETRIS_OK; }
 int tetris_debug_clock_khz(tetris_batch*, int* khz) { if (khz) *khz = 0; return TETRIS_OK; }

@@ -166,3 +166,32 @@ def _split_rollout_matches_oracle_rollout(N, STEPS, ms):
         for f in base.FIELDS:
             assert np.array_equal(got[f][:, 0], rec[f][:, side]), (side, f)
         assert np.array_equal(gro, ro) and np.array_equal(glw, lw)
+
+
+@pytest.mark.parametrize("case", ["draws", "queue"])
+def test_split_capacity_error_ends_the_round_on_both_sides(case):
+    """tests/test_split_opponents_gloo.py's capacity cases through the GPU's split kernels (k_split stages, XW_ERR)."""
+    import importlib
+
+    import tests.test_split_opponents_gloo as base
+    mod = importlib.import_module("drl-tetris_amd.distributed")
+    tg = ThreadGather(2)
+    results, errors = {}, []
+
+    def side_main(side):
+        try:
+            tg.bind(side)
+            so = mod.SplitOpponents(base.CAP_N, side=side, peer=1 - side, dist=tg, seeds=orc.episode_seed(np.arange(base.CAP_N), 0), pieces=(6,))
+            results[side] = base.capacity_side(so, case)
+            so.close()
+        except Exception as e:          # let the other thread out of its barrier
+            errors.append(e)
+            tg.barrier.abort()
+
+    threads = [threading.Thread(target=side_main, args=(s,)) for s in (0, 1)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    base.capacity_check(case, results)
