@@ -124,6 +124,7 @@ _SIGNATURES = {
     "tetris_debug_code_objects": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     "tetris_set_chain_spin_limit": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tetris_debug_stall": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "tetris_debug_chain_epoch": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p]),
     "tetris_debug_clock_khz": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tetris_make_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
@@ -661,6 +662,13 @@ class TetrisBatch:
         """Test aid (include/tetris_hip.h: tetris_debug_stall): idle kernel on chain stream 0..2, on the batch's stream (3) or,
         which = -1, holding `percent` % of the device's wave slots on a stream of its own."""
         self._check(self.lib.tetris_debug_stall(self._h, int(which), int(microseconds), int(percent)))
+
+    def debug_chain_epoch(self, epoch=None):
+        """Test aid (include/tetris_hip.h: tetris_debug_chain_epoch): with `epoch`, the batch looks as if that many chained launches
+        had already run (every wave's epoch word and the batch's count); -> the batch's count of chained launches afterwards."""
+        out = C.c_uint32(0)
+        self._check(self.lib.tetris_debug_chain_epoch(self._h, -1 if epoch is None else int(epoch), C.byref(out)))
+        return int(out.value)
 
     def clock_mhz(self):
         """Measurement aid: the GPU's shader clock of the moment (tetris_debug_clock_khz)."""

@@ -206,6 +206,27 @@ __global__ __launch_bounds__(256) void k_totals(Geo geo, unsigned long long* out
     }
 }
 
+// The per-game words as they stand, totals[k][i] (tetris_rollout_game_totals_dev; kept by a rollout call that reports counters), and
+// what the games counted since such a copy: (now - before) mod 2^32 per game, summed in 64 bits.  The words are cumulative modulo
+// 2^32, so the difference of two k_totals sums is off by 2^32 for every word that wrapped in between; this one is exact as long as
+// no single game counts 2^32 between the two readings.
+__global__ __launch_bounds__(256) void k_policy_totals(Geo geo, uint32_t* totals /*[4][N]*/) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (int)geo.n_games) policy_game_totals_lane(geo, i, totals);
+}
+__global__ __launch_bounds__(256) void k_totals_since(Geo geo, const uint32_t* before /*[4][N]*/, unsigned long long* out /*[4]*/) {
+    unsigned long long v[4] = {0, 0, 0, 0};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < (int)geo.n_games; i += gridDim.x * blockDim.x) {
+        unsigned long long t[4];
+        totals_of_game(geo, i, t);
+        for (int k = 0; k < 4; k++) v[k] += (uint32_t)((uint32_t)t[k] - before[(size_t)k * geo.n_games + i]);
+    }
+    for (int k = 0; k < 4; k++) {
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off);
+        if ((threadIdx.x & 63) == 0 && v[k]) atomicAdd(&out[k], v[k]);
+    }
+}
+
 // ---- step + observation in one launch (tetris_step_rt_observe_dev) ------------------------------------------------------------
 // One agent-loop iteration in ONE launch (worker.py:91-118: perform_action, then get_state + unpack for the next decision): the
 // (r, t) step and, straight from the registers the step leaves behind, the packed observation k_observe_packed would rebuild
@@ -1111,6 +1132,7 @@ struct tetris_batch {
     hipEvent_t chain_ev[CHAIN_STREAMS + 1] = {};      // [k]: end of chain stream k's last launch (join); [CHAIN_STREAMS]: fork from the batch's stream
     hipEvent_t worker_gate_ev[CHAIN_STREAMS][2] = {}; // run-ahead gates of the per-stream enqueue threads (tetris_rollout_launch)
     uint32_t* d_chain = nullptr;
+    uint32_t* d_words_before = nullptr;  // the per-game counter words [4][N] as a rollout call found them (rollout_counters_begin)
     uint32_t chain_epoch = 0;
     int use_chain = 1;                   // TETRIS_NO_CHAIN=1 in the environment: every rollout launch on the batch's one stream
     int use_graph = 0;                   // TETRIS_GRAPH=1: un-chained rollout launches replayed from HIP graphs (profiling aid)
@@ -1518,6 +1540,7 @@ int tetris_destroy(tetris_batch* b) {
     if (b->direct_used) { aql::Device* dev = aql::device_for(b->device); if (dev->ok) aql::quiesce(dev->qs); }      // (a test's idle kernel may still sit there)
     (void)hipFree(b->d_plan_slabs); (void)hipFree(b->d_iota); (void)hipFree(b->d_plan_status);
     (void)hipFree(b->d_policy_scores);
+    (void)hipFree(b->d_words_before);
     (void)hipFree(b->d_select_blocks);
     for (Stage& s : b->stage) s.release();
     b->recover_idx.release();
@@ -1747,6 +1770,26 @@ int tetris_debug_stall(tetris_batch* b, int which, int microseconds, int percent
         if (blocks > 0) hipLaunchKernelGGL(k_blocker, dim3((unsigned)blocks), dim3(1024), 0, b->stall_stream, (const uint32_t*)nullptr, ticks);
     }
     HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+// Test aid (tests of the restart of the epoch numbering, tetris_rollout_launch; nothing in the product calls it): at a drained point
+// every wave's epoch word and the batch's count of chained launches become `set_epoch`, the way chain_recover leaves them.
+int tetris_debug_chain_epoch(tetris_batch* b, long long set_epoch, uint32_t* epoch) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if (set_epoch >= (long long)CHAIN_EPOCH_MAX) return fail(TETRIS_E_ARG, "set_epoch must be below 0x7FFF0000");
+    if ((rc = finish_call(b))) return rc;
+    if (set_epoch >= 0) {
+        hipStream_t const home = b->own_stream;
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        for (int k = 0; k < CHAIN_STREAMS; k++) HIP_TRY(hipStreamSynchronize(b->chain_stream[k]));
+        HIP_TRY(hipStreamSynchronize(home));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b->d_chain, (int)set_epoch, (((size_t)b->N + 15) / 16) * CHAIN_STRIDE, home));
+        HIP_TRY(hipStreamSynchronize(home));
+        b->chain_epoch = (uint32_t)set_epoch;
+    }
+    if (epoch) *epoch = b->chain_epoch;
     return TETRIS_OK;
 }
 
@@ -2844,6 +2887,8 @@ int tetris_rollout_launch(tetris_batch* b, int launches, int steps_per_launch, u
     } chain_guard{b, chained, b->stream};
     RolloutCall call{0, first_step, steps_per_launch, policy_seed, ms, launches, chained};
     if (!chained) return rollout_plain(b, call, group, t_entry, elapsed_ms);
+    // (a call that long could not be numbered below the CHAIN_ABANDONED bit even from 0; nothing has been enqueued yet)
+    if ((uint32_t)launches >= CHAIN_EPOCH_MAX) return fail(TETRIS_E_ARG, "a chained call takes fewer than 0x7FFF0000 launches");
     if (b->chain_epoch + (uint32_t)launches >= CHAIN_EPOCH_MAX || b->chain_epoch + (uint32_t)launches < b->chain_epoch) {
         // epoch numbers stay below the CHAIN_ABANDONED bit: restart the numbering (every chain stream is idle between calls)
         HIP_TRY(hipMemsetAsync(b->d_chain, 0, (((size_t)b->N + 15) / 16) * sizeof(uint32_t) * CHAIN_STRIDE, b->stream));
@@ -2868,17 +2913,42 @@ int tetris_rollout_launch(tetris_batch* b, int launches, int steps_per_launch, u
     return rollout_streams(b, call, group, prequeue, t_entry, elapsed_ms);
 }
 
+}  // extern "C"
+
+// The counters of ONE rollout call (tetris_rollout_random, tetris_rollout_policy).  The per-game words are cumulative and wrap at
+// 2^32 — a game passes 2^32 env-steps after a few hours —, so the difference of two tetris_rollout_totals sums is wrong by 2^32 for
+// every word that wraps during the call.  begin: a device copy of the words [4][N]; end: (now - then) mod 2^32 per game, summed
+// in 64 bits (k_totals_since) — exact while no single game counts 2^32 within the call.  Both are synchronous, on the batch's
+// stream, outside the event-timed region and outside tetris_rollout_launch.
+static int rollout_counters_begin(tetris_batch* b) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if (!b->d_words_before) HIP_TRY(hipMalloc((void**)&b->d_words_before, (size_t)4 * b->N * sizeof(uint32_t)));
+    hipLaunchKernelGGL(k_policy_totals, dim3((unsigned)((b->N + 255) / 256)), dim3(256), 0, b->stream, geo_of_batch(b), b->d_words_before);
+    HIP_TRY(hipGetLastError());
+    return finish_call(b);
+}
+static int rollout_counters_end(tetris_batch* b, uint64_t counters[4]) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(b->d_counters, 0, 8 * sizeof(unsigned long long), b->stream));
+    const int tot_blocks = b->N >= 65536 ? 64 : (b->N + 1023) / 1024;
+    hipLaunchKernelGGL(k_totals_since, dim3(tot_blocks), dim3(256), 0, b->stream, geo_of_batch(b), (const uint32_t*)b->d_words_before, b->d_counters);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_counters, b->d_counters, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
+    if ((rc = finish_call(b))) return rc;
+    for (int k = 0; k < 4; k++) counters[k] += b->h_counters[k];
+    return TETRIS_OK;
+}
+
+extern "C" {
+
 int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,
                           int ms, uint64_t counters[4], float* elapsed_ms) {
-    uint64_t before[4] = {0, 0, 0, 0}, after[4] = {0, 0, 0, 0};
     int rc;
-    if (counters && (rc = tetris_rollout_totals(b, before))) return rc;
+    if (counters && (rc = rollout_counters_begin(b))) return rc;
     if ((rc = tetris_rollout_launch(b, launches, steps_per_launch, policy_seed, first_step, ms, elapsed_ms))) return rc;
-    if (counters) {
-        if ((rc = tetris_rollout_totals(b, after))) return rc;
-        // per-game words are uint32 and wrap; a single call stays far below 2^32 per game
-        for (int k = 0; k < 4; k++) counters[k] += after[k] - before[k];
-    }
+    if (counters && (rc = rollout_counters_end(b, counters))) return rc;
     return TETRIS_OK;
 }
 
@@ -2901,10 +2971,7 @@ __global__ __launch_bounds__(256) void k_policy_pick(PolicyArgs pa) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < pa.a.n) policy_pick_lane(pa, i);
 }
-__global__ __launch_bounds__(256) void k_policy_totals(Geo geo, uint32_t* totals /*[4][N]*/) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (int)geo.n_games) policy_game_totals_lane(geo, i, totals);
-}
+// (k_policy_totals: beside k_totals)
 
 static int policy_check(tetris_batch* b, const char* what) {
     if (b->split) return fail(TETRIS_E_ARG, std::string(what) + " is not available on split batches");
@@ -3045,13 +3112,9 @@ int tetris_rollout_policy(tetris_batch* b, int launches, int steps_per_launch, c
     if (!d_weights) return fail(TETRIS_E_ARG, "weights is NULL");
     if (launches < 1 || steps_per_launch < 1 || steps_per_launch > 256) return fail(TETRIS_E_ARG, "launches must be >= 1, 1 <= steps_per_launch <= 256");
     if ((rc = policy_scores_buffer(b))) return rc;
-    uint64_t before[4] = {0, 0, 0, 0}, after[4] = {0, 0, 0, 0};
-    if (counters && (rc = tetris_rollout_totals(b, before))) return rc;
+    if (counters && (rc = rollout_counters_begin(b))) return rc;
     if ((rc = rollout_policy_launches(b, launches, steps_per_launch, d_weights, per_game, first_step, ms, elapsed_ms))) return rc;
-    if (counters) {
-        if ((rc = tetris_rollout_totals(b, after))) return rc;
-        for (int k = 0; k < 4; k++) counters[k] += after[k] - before[k];      // (per-game words are uint32 and wrap, as in tetris_rollout_random)
-    }
+    if (counters && (rc = rollout_counters_end(b, counters))) return rc;      // (what this call did, whatever the words held: as tetris_rollout_random)
     return TETRIS_OK;
 }
 

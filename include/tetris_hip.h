@@ -345,11 +345,14 @@ int tetris_step_policy_dev(tetris_batch *b, const uint8_t *d_player, const int16
  * un-chained on the batch's stream: tetris_rollout_is_chained and the chained / direct-dispatch paths do not apply.
  * CAPACITY: this policy clears about 0.39 lines per piece in one-player games and does not die, so an episode is not ended by
  * the game but by the 39 936-draw limit: after about 40 000 steps it is ended with TETRIS_ERR_STREAM (see above) and reset
- * like any finished game.                                                                                                */
+ * like any finished game.
+ * `counters[k] +=` is exactly what THIS call did, whatever the per-game words held before it (see tetris_rollout_random).  */
 int tetris_rollout_policy(tetris_batch *b, int launches, int steps_per_launch, const int16_t *d_weights, int per_game,
                           uint64_t first_step, int ms, uint64_t counters[4], float *elapsed_ms);
 /* the per-game words tetris_rollout_totals sums: d_totals uint32 [4][N] = {env_steps, episodes, lines_cleared, garbage_sent}
- * of every game — a population's fitness without a host loop.  Asynchronous.                                             */
+ * of every game — a population's fitness without a host loop.  Asynchronous.  The words are cumulative MODULO 2^32 and are
+ * delivered as they stand (a game passes 2^32 env-steps after a few hours of the built-in rollout): the difference of two
+ * readings, taken modulo 2^32, is exact as long as the game counted fewer than 2^32 in between.                          */
 int tetris_rollout_game_totals_dev(tetris_batch *b, uint32_t *d_totals);
 
 /* ---- acting on a network's (r, t, piece) evaluation on the device ---------------------------------------------------------
@@ -559,12 +562,21 @@ int tetris_traj_batch_dev(tetris_batch *b, const tetris_traj *traj, const tetris
  * seed16 = (12345 + 7919 game + 104729 episode) mod 65536.  Runs `launches` kernel launches of
  * `steps_per_launch` env-steps each on all N games (state stays in registers inside a launch).
  * counters[4] += {env_steps, episodes, lines_cleared, garbage_lines_sent}.  elapsed_ms (optional)
- * = HIP-event time from before the first to after the last launch on the batch's stream.        */
+ * = HIP-event time from before the first to after the last launch on the batch's stream.
+ * COUNTERS.  Every game keeps four cumulative uint32 words (tetris_rollout_game_totals_dev), which
+ * count modulo 2^32.  `counters[k] +=` is exactly what THIS call did, whatever the words held
+ * before it: the call keeps a copy of the words, and afterwards sums (after - before) mod 2^32 per
+ * game into 64 bits — outside the timed region.  That holds as long as no single game counts
+ * 2^32 within the one call.  `step` is 64 bits wide everywhere (policy draw, acting player =
+ * step mod P of the 64-bit step); a global game id is 32 bits (tetris_set_game_offset).          */
 int tetris_rollout_random(tetris_batch *b, int launches, int steps_per_launch, uint32_t policy_seed,
                           uint64_t first_step, int ms, uint64_t counters[4], float *elapsed_ms);
 /* The launches of tetris_rollout_random alone: nothing but the `launches` step kernels lies between the two HIP events
  * and between call and return (plus one final stream synchronisation) — the region bench.py times.  Counters are read
- * with tetris_rollout_totals before and after, outside that region.                                                */
+ * with tetris_rollout_totals before and after, outside that region (exact while no per-game word wraps in between: see
+ * tetris_rollout_totals).  A chained call numbers its launches with epochs below 0x7FFF0000 and restarts the numbering at a
+ * drained point before it would get there; a single chained call of 0x7FFF0000 launches or more cannot be numbered and is
+ * refused with TETRIS_E_ARG before anything is enqueued.                                                             */
 int tetris_rollout_launch(tetris_batch *b, int launches, int steps_per_launch, uint32_t policy_seed,
                           uint64_t first_step, int ms, float *elapsed_ms);
 
@@ -644,6 +656,15 @@ int tetris_debug_clock_khz(tetris_batch *b, int *khz);
  * which = 3: on the batch's stream; which = -1: on a stream of its own, as workgroups that hold `percent` % of the device's
  * wave slots meanwhile (a co-tenant).  Asynchronous.                                                                   */
 int tetris_debug_stall(tetris_batch *b, int which, int microseconds, int percent);
+/* TEST AID, nothing in the product calls it: the epoch numbering of chained launches (tetris_set_chained).  A chained call gives
+ * its launches consecutive epoch numbers, continuing where the batch's last chained call stopped, and restarts them from 0 (every
+ * wave's epoch word cleared on the batch's stream) when the call's last number would reach 0x7FFF0000 — after about two hours of
+ * back-to-back launches.  set_epoch >= 0: at a drained point (the batch's stream and the chain streams are synchronised), make
+ * the batch look as if `set_epoch` chained launches had already run: every wave's epoch word and the batch's count become
+ * `set_epoch`; TETRIS_E_ARG for set_epoch >= 0x7FFF0000.  set_epoch < 0: nothing is changed.  *epoch (optional) = the batch's count
+ * afterwards: after a call of L launches that restarted it reads L, after one that did not, the count before the call + L.
+ * Synchronises.                                                                                                         */
+int tetris_debug_chain_epoch(tetris_batch *b, long long set_epoch, uint32_t *epoch);
 /* Environment variables read by the library (measurement aids; none changes a result):
  *   TETRIS_NO_CHAIN=1   batches are created with chained launches off (tetris_set_chained)
  *   TETRIS_NO_DUO=1     two-player single steps through k_game<2> (both players of a game in one lane) instead of k_duo
@@ -669,7 +690,9 @@ int tetris_rollout_is_chained(tetris_batch *b, int steps_per_launch);
 
 /* Global id of this batch's game 0 (default 0): the built-in rollout keys its policy and its
  * reset-seed schedule by global game id, so that N batches on N GPUs simulate N*n_games distinct
- * games (the reference's equivalent: N worker containers, docker-compose.yaml:27).               */
+ * games (the reference's equivalent: N worker containers, docker-compose.yaml:27).
+ * A global game id is 32 bits: the call keeps the LOW 32 BITS of first_game_id, and the id of
+ * game i is (first_game_id + i) mod 2^32 — the ids may wrap inside a batch.                      */
 int tetris_set_game_offset(tetris_batch *b, uint64_t first_game_id);
 
 /* ---- split mode: the two players of a game on different GPUs (BASELINE config 5) ------------------------------
@@ -708,7 +731,10 @@ int tetris_split_rollout_stage_dev(tetris_batch *b, int stage, uint32_t policy_s
                                    const uint32_t *const d_words[4], uint32_t *d_out);
 /* cumulative counters of the built-in rollouts of this batch: totals[4] = {env_steps, episodes, lines_cleared,
  * garbage_sent}, each the sum over the games of a per-game word the step kernels keep (env_steps is COUNTED on the
- * device, one increment per game and step, not computed from the launch arguments); synchronous.                  */
+ * device, one increment per game and step, not computed from the launch arguments); synchronous.
+ * The per-game words are uint32 and cumulative MODULO 2^32; totals[k] is the sum of those words AS THEY STAND.  The
+ * difference of two readings is therefore what happened in between only while no game's word wrapped in between (a
+ * wrap takes 2^32 off); tetris_rollout_random / tetris_rollout_policy take the difference per game modulo 2^32 instead. */
 int tetris_rollout_totals(tetris_batch *b, uint64_t totals[4]);
 
 /* Run the batch on a caller-owned HIP stream (e.g. torch's current stream) so that its kernels are ordered with the

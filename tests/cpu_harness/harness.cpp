@@ -262,6 +262,7 @@ int tetris_debug_table_limit(tetris_batch* b, int chunks) {
 }
 int tetris_debug_code_objects(int* count, uint64_t* bytes) { if (count) *count = 0; if (bytes) *bytes = 0; return TETRIS_OK; }
 int tetris_debug_stall(tetris_batch*, int, int, int) { return TETRIS_OK; }
+int tetris_debug_chain_epoch(tetris_batch*, long long, uint32_t*) { return fail(TETRIS_E_ARG, "chained launches exist on the GPU only"); }
 int tetris_debug_clock_khz(tetris_batch*, int* khz) { if (khz) *khz = 0; return TETRIS_OK; }
 int tetris_rollout_is_chained(tetris_batch*, int) { return 0; }
 int tetris_set_game_offset(tetris_batch* b, uint64_t first) { b->game_offset = (uint32_t)first; return TETRIS_OK; }
@@ -468,14 +469,29 @@ int tetris_rollout_launch(tetris_batch* b, int launches, int steps_per_launch, u
     return rc;
 }
 
+// the counters of one rollout call, as the product takes them: a copy of the per-game words before, and afterwards
+// (now - then) mod 2^32 per game summed in 64 bits (the words are cumulative and wrap)
+static std::vector<uint32_t> game_words(tetris_batch* b) {
+    std::vector<uint32_t> w((size_t)4 * b->N);
+    for (int i = 0; i < b->N; i++) {
+        unsigned long long t[4];
+        totals_of_game(geo_of_batch(b), i, t);
+        for (int k = 0; k < 4; k++) w[(size_t)k * b->N + i] = (uint32_t)t[k];
+    }
+    return w;
+}
+static void add_counted_since(tetris_batch* b, const std::vector<uint32_t>& before, uint64_t counters[4]) {
+    const std::vector<uint32_t> now = game_words(b);
+    for (int k = 0; k < 4; k++)
+        for (int i = 0; i < b->N; i++) counters[k] += (uint32_t)(now[(size_t)k * b->N + i] - before[(size_t)k * b->N + i]);
+}
+
 int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step, int ms,
                           uint64_t counters[4], float* elapsed_ms) {
-    uint64_t before[4], after[4];
-    tetris_rollout_totals(b, before);
+    const std::vector<uint32_t> before = game_words(b);
     int rc = tetris_rollout_launch(b, launches, steps_per_launch, policy_seed, first_step, ms, elapsed_ms);
     if (rc) return rc;
-    tetris_rollout_totals(b, after);
-    if (counters) for (int k = 0; k < 4; k++) counters[k] += after[k] - before[k];
+    if (counters) add_counted_since(b, before, counters);
     return TETRIS_OK;
 }
 

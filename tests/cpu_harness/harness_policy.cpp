@@ -108,8 +108,7 @@ int tetris_rollout_policy(tetris_batch* b, int launches, int steps_per_launch, c
     if (b->split) return fail(TETRIS_E_ARG, "tetris_rollout_policy is not available on split batches");
     if (!weights) return fail(TETRIS_E_ARG, "weights is NULL");
     if (launches < 1 || steps_per_launch < 1 || steps_per_launch > 256) return fail(TETRIS_E_ARG, "launches must be >= 1, 1 <= steps_per_launch <= 256");
-    uint64_t before[4], after[4];
-    tetris_rollout_totals(b, before);
+    const std::vector<uint32_t> before = game_words(b);
     // the harness looks at the flag words after every launch, so the margin only has to cover one launch
     const uint32_t saved = b->margin;
     b->margin = (uint32_t)(2 * steps_per_launch + 16);
@@ -130,8 +129,7 @@ int tetris_rollout_policy(tetris_batch* b, int launches, int steps_per_launch, c
     b->margin = saved;
     if (elapsed_ms) *elapsed_ms = 0.0f;
     if (rc) return rc;
-    tetris_rollout_totals(b, after);
-    if (counters) for (int k = 0; k < 4; k++) counters[k] += after[k] - before[k];
+    if (counters) add_counted_since(b, before, counters);
     return TETRIS_OK;
 }
 

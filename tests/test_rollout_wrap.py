@@ -1,0 +1,485 @@
+"""The built-in rollout where a long job ends up: the chained launches' epoch numbering at its restart, the per-game counter
+words at 2^32, 64-bit step numbers and 32-bit game ids at their word boundaries (include/tetris_hip.h: tetris_rollout_random,
+tetris_rollout_launch, tetris_rollout_policy, tetris_rollout_totals, tetris_set_game_offset, tetris_debug_chain_epoch).
+
+A training run reaches each of these after hours of one batch; a test of ordinary length reaches none, so the tests put the batch
+there: the epoch through the test aid tetris_debug_chain_epoch (and read it back after every call: the proof that a call did or
+did not restart the numbering), the counter words through snapshot / restore (blob words 1..4 = G_EPISODE, G_STEPS, G_LINES,
+G_SENT), step numbers and game ids through the calls' own arguments.  Every comparison is exact equality with the oracle:
+counters, per-game words, every board."""
+import numpy as np
+import pytest
+
+from oracle import oracle as orc
+from tests import engines
+from tests.test_policy_device import W_B, Buf, Model
+
+MAX = 0x7FFF0000            # CHAIN_EPOCH_MAX (drl-tetris_amd/csrc/tetris_kernels.h): the numbering restarts before it gets here
+FELL_BACK = 4
+M32 = 0xFFFFFFFF
+W_EPISODE, W_STEPS, W_LINES, W_SENT = 1, 2, 3, 4          # blob words of a game (tetris_layout.h); counters[] order: steps, episodes, lines, sent
+COUNTER_WORDS = (W_STEPS, W_EPISODE, W_LINES, W_SENT)
+NAMES = ("env_steps", "episodes", "lines", "sent")
+
+
+def _ids(n, offset=0):
+    return (offset + np.arange(n, dtype=np.int64)) & M32
+
+
+def _pair(kind, n, P, pieces=(0, 1, 2, 3, 4, 5, 6), offset=0):
+    seeds = orc.episode_seed(_ids(n, offset), 0)
+    eng = engines.make(kind, n, P, pieces=pieces, seeds=seeds)
+    ref = engines.make("oracle", n, P, pieces=pieces, seeds=seeds)
+    if offset:
+        eng.set_game_offset(offset)
+    return eng, ref
+
+
+class Follower:
+    """The oracle follows the engine call by call: same first_step, same ms, the episode array carried along."""
+
+    def __init__(self, eng, ref, S=1, ms=400, offset=0, episode=None):
+        self.eng, self.ref, self.S, self.ms, self.offset = eng, ref, S, ms, offset
+        self.episode = np.zeros(ref.n_games, np.uint32) if episode is None else episode
+        self.step = 0
+
+    def call(self, launches, where=""):
+        c, _ = self.eng.rollout_random(launches, self.S, first_step=self.step, ms=self.ms)
+        _, want = self.ref.rollout_random(launches * self.S, first_step=self.step, ms=self.ms, episode=self.episode,
+                                          game_offset=self.offset & M32)
+        self.step += launches * self.S
+        assert c.tolist() == want.tolist(), f"{where}: counters of a call of {launches} launches ending at step {self.step}"
+        return c
+
+    def launch(self, launches, before, where="", also=(0, 0, 0, 0)):
+        """the same through rollout_launch, which reads nothing first and so waits for nothing the streams hold: `before` =
+        rollout_totals() taken ahead of whatever the caller enqueued, `also` = what that work counts into the words itself"""
+        self.eng.rollout_launch(launches, self.S, first_step=self.step, ms=self.ms)
+        c = self.eng.rollout_totals() - before
+        _, want = self.ref.rollout_random(launches * self.S, first_step=self.step, ms=self.ms, episode=self.episode,
+                                          game_offset=self.offset & M32)
+        self.step += launches * self.S
+        assert c.tolist() == (want + np.asarray(also, np.uint64)).tolist(), f"{where}: counters of a call of {launches} launches ending at step {self.step}"
+
+
+# ================================================================ 1. / 2. the restart of the epoch numbering (GPU only)
+def _set_path(eng, path):
+    if path == "streams":
+        eng.set_direct_dispatch(False)
+    elif path == "queues":
+        eng.set_xcd_affine(0)
+
+
+# path, players, games, steps per launch, launches per call
+RESTART_CASES = ([("streams", 1, n, 1, L) for n in (33, 1057) for L in (1, 3, 20)] + [("streams", 2, 545, 1, L) for L in (1, 3, 20)] +
+                 [("queues", 1, 33, 1, 20), ("queues", 1, 1057, 1, 20), ("queues", 2, 545, 1, 20),
+                  ("affine", 1, 33, 1, 20), ("affine", 1, 1057, 1, 20), ("affine", 2, 545, 1, 20)] +
+                 [("streams", 1, n, 4, L) for n in (33, 1057) for L in (1, 3, 20)] +
+                 [("queues", 1, 33, 4, 20), ("queues", 1, 1057, 4, 20), ("affine", 1, 33, 4, 20), ("affine", 1, 1057, 4, 20)])
+
+
+class Chained(Follower):
+    """Follower that also pins, after every call: no error bit, still chained, the launch path, and the epoch count read back."""
+
+    def __init__(self, eng, ref, path, S=1, ms=400):
+        super().__init__(eng, ref, S, ms)
+        self.path = path
+        assert eng.rollout_is_chained(S)
+
+    def chained_call(self, launches, epoch_after, where, launch_only=None):
+        if launch_only is None:
+            self.call(launches, where)
+        else:
+            self.launch(launches, launch_only[0], where, launch_only[1])
+        eng = self.eng
+        assert eng.take_errors() == 0, where
+        assert eng.rollout_is_chained(self.S), where
+        direct = self.path != "streams" and launches >= 16           # (direct dispatch starts at 16 launches)
+        assert eng.rollout_was_direct() == direct, where
+        if direct and self.path == "affine" and eng.n_players == 1:
+            assert eng.rollout_was_affine(), where
+        if self.path == "queues":
+            assert not eng.rollout_was_affine(), where
+        got = eng.debug_chain_epoch()
+        print(f"{where}: epoch read back {got:#x}")
+        assert got == epoch_after, f"{where}: the batch's epoch count is {got:#x}, expected {epoch_after:#x}"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path,P,n,S,L", RESTART_CASES)
+def test_the_epoch_numbering_restarts_at_its_limit_and_the_rollout_goes_on_exact(path, P, n, S, L):
+    """Calls that end just below CHAIN_EPOCH_MAX do not restart, the first call whose last number would reach it does (by one
+    launch, and — the `>=` edge — by a call whose sum is exactly the limit), and the chain goes on from the low numbers."""
+    eng, ref = _pair("hip", n, P)
+    _set_path(eng, path)
+    f = Chained(eng, ref, path, S)
+    e0 = eng.debug_chain_epoch()
+    f.chained_call(40, e0 + 40, "1. 40 launches, undisturbed")
+    assert eng.debug_chain_epoch(MAX - 2 * L - 1) == MAX - 2 * L - 1
+    f.chained_call(L, MAX - L - 1, "2. well below the limit: no restart")
+    f.chained_call(L, MAX - 1, "3. ends at MAX - 1: no restart")
+    f.chained_call(1, 1, "4. one launch more: restart")
+    assert eng.debug_chain_epoch(MAX - L) == MAX - L
+    f.chained_call(L, L, "5. the sum is exactly MAX: restart")
+    f.chained_call(L, 2 * L, "6. chained on from the low numbers")
+    engines.assert_same_state(eng, ref, where="after the last call")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", ["streams", "queues", "affine"])
+def test_a_restart_behind_asynchronous_work_on_the_batchs_stream(path):
+    """A step_rt_dev with auto-reset is enqueued on the batch's stream immediately before the restarting call, no synchronisation
+    in between: the memset that clears the epoch words, the step and the chained launches must be ordered."""
+    n, P, L = 1057, 1, 20
+    eng, ref = _pair("hip", n, P)
+    _set_path(eng, path)
+    f = Chained(eng, ref, path)
+    f.chained_call(40, eng.debug_chain_epoch() + 40, "undisturbed")
+    rng = np.random.default_rng(7)
+    r, t = rng.integers(0, 4, n).astype(np.uint8), rng.integers(0, 10, n).astype(np.uint8)
+    rot, trans = Buf("hip", (n,), np.uint8).set(r), Buf("hip", (n,), np.uint8).set(t)
+    eng.debug_chain_epoch(MAX - L)
+    done = ref.step_rt(r, t, None)                                   # the oracle steps the same action first
+    d = np.nonzero(done)[0].astype(np.int32)
+    f.episode[d] += 1
+    ref.reset(d, seeds=orc.episode_seed(d, f.episode[d]))
+    before = eng.rollout_totals()                                    # (synchronises: nothing may drain the stream between the step and the launches)
+    eng.step_rt_dev(rot.ptr, trans.ptr, None, None, None, None, auto_reset=True)
+    f.chained_call(L, L, "restart behind a step on the batch's stream", launch_only=(before, (0, len(d), 0, 0)))
+    f.chained_call(L, 2 * L, "chained on")
+    engines.assert_same_state(eng, ref, where="after the last call")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", ["streams", "affine"])
+def test_a_restart_directly_after_a_snapshot_restore_round_trip(path):
+    """the host rewrites the whole state (restore), then the next chained call restarts the numbering"""
+    n, P, L = 545, 2, 20
+    eng, ref = _pair("hip", n, P)
+    _set_path(eng, path)
+    f = Chained(eng, ref, path)
+    f.chained_call(40, eng.debug_chain_epoch() + 40, "undisturbed")
+    blob = eng.snapshot()
+    eng.rollout_random(7, 1, first_step=f.step)                      # moves on ...
+    eng.debug_chain_epoch(MAX - L)
+    eng.restore(blob)                                                # ... and is put back by the host
+    f.chained_call(L, L, "restart after restore")
+    f.chained_call(L, 2 * L, "chained on")
+    engines.assert_same_state(eng, ref, where="after the last call")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("direct", [False, True])
+def test_a_fall_back_inside_a_restarted_call(direct):
+    """tests/test_chain_fallback.py's late predecessor in a call that has just restarted the numbering: chain_recover runs with
+    epoch0 == 0 over words a memset has just cleared.  The fell-back bit is what keeps the case from passing without the path."""
+    n, P, stalled = 545, 2, 50
+    eng, ref = _pair("hip", n, P)
+    eng.set_direct_dispatch(direct)
+    f = Chained(eng, ref, "affine" if direct else "streams")        # (the queues as they come: XCD-affine where the kernels are)
+    f.chained_call(40, eng.debug_chain_epoch() + 40, "undisturbed")
+    eng.set_chain_spin_limit(2000)                                   # ~1 ms
+    eng.debug_chain_epoch(MAX - stalled)                             # the next call restarts
+    before = eng.rollout_totals()                                    # (synchronises: nothing may drain the streams between the stall and the launches)
+    eng.debug_stall(1, 30000)                                        # the call's second launch (and every third after it) starts 30 ms late
+    f.launch(stalled, before, "the stalled call")
+    assert eng.rollout_was_direct() == direct
+    assert eng.take_errors() == FELL_BACK
+    assert eng.take_errors() == 0                                    # reported once
+    assert not eng.rollout_is_chained(1)
+    assert eng.debug_chain_epoch() == stalled                        # the call restarted
+    f.call(10, "un-chained")
+    eng.set_chained(True)
+    eng.set_chain_spin_limit(0)
+    assert eng.rollout_is_chained(1)
+    f.chained_call(28, stalled + 28, "chained again, from the words the recovery left")
+    engines.assert_same_state(eng, ref, where="after the last call")
+
+
+@pytest.mark.gpu
+def test_a_chained_call_too_long_to_be_numbered_is_refused_and_the_aid_checks_its_argument():
+    pkg = __import__("__graft_entry__").package()
+    eng, _ = _pair("hip", 33, 1)
+    assert eng.rollout_is_chained(1)
+    eng.rollout_random(3, 1)
+    blob, epoch = eng.snapshot(), eng.debug_chain_epoch()
+    for launches in (MAX, MAX + 5, 0x7FFFFFFF):
+        with pytest.raises(pkg.TetrisError, match="0x7FFF0000"):
+            eng.rollout_launch(launches, 1)
+        with pytest.raises(pkg.TetrisError, match="0x7FFF0000"):
+            eng.rollout_random(launches, 1)
+    assert np.array_equal(eng.snapshot(), blob) and eng.take_errors() == 0 and eng.debug_chain_epoch() == epoch
+    for bad in (MAX, MAX + 1, 1 << 40):
+        with pytest.raises(pkg.TetrisError, match="0x7FFF0000"):
+            eng.debug_chain_epoch(bad)
+    assert eng.debug_chain_epoch() == epoch
+    assert eng.debug_chain_epoch(MAX - 1) == MAX - 1                 # the largest number a launch may carry
+
+
+def test_the_harness_has_no_epoch_numbering():
+    pkg = __import__("__graft_entry__").package()
+    eng, _ = _pair("harness", 4, 1)
+    with pytest.raises(pkg.TetrisError, match="GPU"):
+        eng.debug_chain_epoch()
+
+
+# ================================================================ 3. / 4. launch paths of the counter and word-boundary cases
+# name -> (steps per launch, GPU only).  On the harness "unchained" and "fused" are its one loop with S = 1 and S = 4.
+PATHS = {"unchained": (1, False), "fused": (4, False), "streams": (1, True), "queues": (1, True), "affine": (1, True)}
+
+
+def _path_params(players, chained_players=(1, 2)):
+    out = []
+    for path, (S, gpu_only) in PATHS.items():
+        for P in players:
+            if gpu_only and P not in chained_players:
+                continue                                             # (launches are chained for one and two players only)
+            for kind in ("harness", "hip"):
+                if kind == "harness" and gpu_only:
+                    continue
+                out.append(pytest.param(kind, path, P, id=f"{kind}-{path}-P{P}", marks=[pytest.mark.gpu] if kind == "hip" else []))
+    return out
+
+
+def _games(kind, path):
+    return 1057 if kind == "hip" and PATHS[path][1] else 70
+
+
+def _prepare_path(eng, kind, path, P):
+    S = PATHS[path][0]
+    if kind != "hip":
+        return S
+    if path == "unchained":
+        eng.set_chained(False)
+    _set_path(eng, path)
+    assert eng.rollout_is_chained(S) == (path != "unchained" and (P == 1 or (P == 2 and S == 1)))
+    return S
+
+
+def _assert_path(eng, kind, path, P, launches):
+    if kind != "hip":
+        return
+    S = PATHS[path][0]
+    chained = path != "unchained" and (P == 1 or (P == 2 and S == 1))
+    assert eng.rollout_was_direct() == (chained and path != "streams" and launches >= 16), path      # (direct dispatch starts at 16 launches)
+    if path == "affine" and P == 1:
+        assert eng.rollout_was_affine()
+    if path in ("queues", "streams", "unchained"):
+        assert not eng.rollout_was_affine()
+
+
+# ================================================================ 3. per-game counter words at 2^32
+def _per_game_counts(n, P, pieces, seeds, offset, episode, steps, first_step, ms):
+    """What every game counts in the call, from one-game shards of the oracle (its rollout returns sums): int64 [4][n] in the
+    order of counters[]."""
+    out = np.zeros((4, n), np.int64)
+    for g in range(n):
+        one = orc.OracleBatch(1, P, 20, 10, pieces=pieces, seeds=seeds[g:g + 1])
+        _, c = one.rollout_random(steps, first_step=first_step, ms=ms, episode=episode[g:g + 1].copy(), game_offset=int((offset + g) & M32))
+        out[:, g] = c.astype(np.int64)
+    return out
+
+
+def _preset_words(n, K, words):
+    """The presets of the issue for a call of K steps per game: uint32 [n] per blob word."""
+    g = np.arange(n, dtype=np.int64)
+    preset = {
+        # ends below the wrap, exactly at 0xFFFFFFFF, exactly at 0, or past it; every fifth game stays at 0
+        W_STEPS: np.where(g % 5 == 4, 0, (1 << 32) - K + (g % 5) - 2),
+        W_EPISODE: np.where(g % 2 == 0, 0xFFFFFFFF, 0xFFFFFFFE),
+        W_LINES: 0xFFFFFFFF - (g % 3),
+        W_SENT: 0xFFFFFFFF - (g % 3),
+    }
+    return {w: (preset[w] & M32).astype(np.uint32) for w in words}
+
+
+def _write_words(eng, preset):
+    blob = eng.snapshot()
+    for w, v in preset.items():
+        blob[:, w] = v
+    eng.restore(blob)
+
+
+def _census(preset, counts, words, where):
+    """at least one wrapped and one un-wrapped game for each preset word, on the oracle's own per-game counts"""
+    line = []
+    for k, w in enumerate(COUNTER_WORDS):
+        if w not in words:
+            continue
+        wrapped = preset[w].astype(np.int64) + counts[k] > M32
+        line.append(f"{NAMES[k]} {int(wrapped.sum())} wrapped / {int((~wrapped).sum())} not")
+        assert wrapped.any() and not wrapped.all(), f"{where}: {NAMES[k]}: {line[-1]} — the case does not cross the wrap with both kinds of game"
+    print(f"census {where}: " + "; ".join(line))
+
+
+def _assert_words(eng, kind, preset, counts, where):
+    n = eng.n_games
+    tot = Buf(kind, (4, n), np.uint32, 0xFFFF)
+    eng.rollout_game_totals_dev(tot.ptr)
+    eng.sync()
+    got = tot.get().astype(np.int64)
+    for k, w in enumerate(COUNTER_WORDS):
+        before = preset[w].astype(np.int64) if w in preset else np.zeros(n, np.int64)
+        want = (before + counts[k]) & M32
+        assert np.array_equal(got[k], want), f"{where}: per-game word {NAMES[k]}: games {np.nonzero(got[k] != want)[0][:5]}"
+    assert eng.rollout_totals().astype(np.int64).tolist() == got.sum(axis=1).tolist(), f"{where}: rollout_totals is the sum of the words as they stand"
+
+
+# (words preset, pieces, ms, steps per game by player count): the episode words need games that end (3 000 ms per step), the line
+# words need lines (O pieces only clear and send an order of magnitude more than all seven).  The steps: on the oracle a game of
+# one / two / three players at 3 000 ms ends 1-2 / 0-2 / 1-2 times in 40 / 60 / 120 steps, so of the games that hold 0xFFFFFFFF
+# and 0xFFFFFFFE some wrap and some do not; in 300 steps of O pieces 28-32 of 70 games clear no line at all.
+WORD_GROUPS = {"steps-episodes": ((W_STEPS, W_EPISODE), (0, 1, 2, 3, 4, 5, 6), 3000, {1: 40, 2: 60, 3: 120}),
+               "steps-lines-sent": ((W_STEPS, W_LINES, W_SENT), (6,), 400, {1: 300, 2: 300, 3: 300})}
+
+
+@pytest.mark.parametrize("group", list(WORD_GROUPS))
+@pytest.mark.parametrize("kind,path,P", _path_params((1, 2, 3)))
+def test_rollout_random_counts_what_the_call_did_when_per_game_words_wrap(kind, path, P, group):
+    """counters[] of a call whose per-game words pass 2^32 equal the oracle's; the words themselves are (preset + the game's own
+    count) mod 2^32; the boards — and with them the seed schedule across the wrap of the episode word — equal the oracle's."""
+    words, pieces, ms, K = WORD_GROUPS[group]
+    K = K[P]
+    n = _games(kind, path)
+    eng, ref = _pair(kind, n, P, pieces=pieces)
+    S = _prepare_path(eng, kind, path, P)
+    launches = K // S
+    preset = _preset_words(n, K, words)
+    _write_words(eng, preset)
+    episode = preset[W_EPISODE].copy() if W_EPISODE in preset else np.zeros(n, np.uint32)
+    counts = _per_game_counts(n, P, pieces, orc.episode_seed(_ids(n), 0), 0, episode, K, 0, ms)
+    _census(preset, counts, words, f"{group} {path} P={P} n={n}")
+    f = Follower(eng, ref, S, ms, episode=episode)
+    c = f.call(launches, "the call across the wrap")
+    _assert_path(eng, kind, path, P, launches)
+    assert c.astype(np.int64).tolist() == counts.sum(axis=1).tolist()        # (the shards add up to the whole)
+    _assert_words(eng, kind, preset, counts, "after the call")
+    engines.assert_same_state(eng, ref, where="after the call across the wrap")
+    assert eng.take_errors() == 0
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("P,S", [(1, 1), (2, 1), (1, 4), (2, 4)])
+def test_rollout_policy_counts_what_the_call_did_when_per_game_words_wrap(kind, P, S):
+    """the same for tetris_rollout_policy (un-chained; one step per launch and fused) against the model of test_policy_device.py.
+    The policy does not die in a test's length, so the episode word does not move: env-steps, lines and sent cross the wrap (in
+    12 steps the model's games clear 1-4 lines and send 0-4 with one player, 0-3 and 0-1 with two)."""
+    n, K, pieces = 70, 12, (0, 1, 2, 3, 4, 5, 6)
+    eng, ref = _pair(kind, n, P, pieces=pieces)
+    words = (W_STEPS, W_LINES, W_SENT)
+    preset = _preset_words(n, K, words + (W_EPISODE,))
+    _write_words(eng, preset)
+    m = Model(ref)
+    m.episode = preset[W_EPISODE].astype(np.int64)
+    m.rollout(W_B, K)
+    _census(preset, m.totals, words, f"policy P={P} S={S}")
+    w = Buf(kind, (8,), np.int16).set(W_B)
+    c, _ = eng.rollout_policy(w.ptr, K // S, S)
+    assert c.astype(np.int64).tolist() == m.totals.sum(axis=1).tolist()
+    _assert_words(eng, kind, preset, m.totals, "after the call")
+    engines.assert_same_state(eng, ref, where="after the policy's call across the wrap")
+    assert eng.take_errors() == 0
+
+
+# ================================================================ 4. step numbers and game ids at their word boundaries
+# first_step with one step per launch, first_step with four (the boundary inside one fused launch)
+STEP_CASES = [(2**32 - 7, 2**32 - 2, "crosses 2^32"), (2**40 + 2**32 - 3, 2**40 + 2**32 - 3, "high word neither 0 nor 1")]
+
+
+@pytest.mark.parametrize("first_step,first_fused,what", STEP_CASES, ids=["2^32-7", "2^40+2^32-3"])
+@pytest.mark.parametrize("kind,path,P", _path_params((1, 2, 3, 4)))
+def test_rollout_random_across_a_step_number_boundary(kind, path, P, first_step, first_fused, what):
+    """20 env-steps from `first_step` (one per launch; with four per launch from `first_fused`, so that the boundary falls inside
+    one launch): the policy draw takes both words of the step, the acting player is step mod P of the
+    64-bit step (a step cut to 32 bits changes it for P = 3: 2^32 mod 3 = 1)."""
+    n = _games(kind, path)
+    eng, ref = _pair(kind, n, P)
+    S = _prepare_path(eng, kind, path, P)
+    f = Follower(eng, ref, S)
+    f.step = first_step if S == 1 else first_fused
+    assert (f.step % 2**32) + 20 > 2**32 and (S == 1 or 2**32 - (f.step % 2**32) < S)
+    c = f.call(20 // S, what)
+    _assert_path(eng, kind, path, P, 20 // S)
+    assert int(c[0]) == 20 * n
+    engines.assert_same_state(eng, ref, where=what)
+    assert eng.take_errors() == 0
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("P,S", [(3, 1), (2, 1), (3, 4), (2, 4)])
+def test_rollout_policy_across_2_to_the_32_steps(kind, P, S):
+    """tetris_rollout_policy from first_step = 2^32 - 3: with one step per launch the host computes the evaluation kernel's acting
+    player (first_step mod P), in a fused launch the lane does"""
+    n, K, first = 24, 8, 2**32 - 3
+    eng, ref = _pair(kind, n, P)
+    m = Model(ref)
+    m.rollout(W_B, K, first_step=first)
+    w = Buf(kind, (8,), np.int16).set(W_B)
+    c, _ = eng.rollout_policy(w.ptr, K // S, S, first_step=first)
+    assert c.astype(np.int64).tolist() == m.totals.sum(axis=1).tolist()
+    engines.assert_same_state(eng, ref, where="policy rollout across step 2^32")
+
+
+OFFSETS = [2**31 - 40, 2**32 - 40, 2**32 + 5]
+
+
+def _assert_seeds(eng, offset, episode, where):
+    """every game's seed16 (blob word 0, low 16 bits) is the schedule's for its 32-bit id and its episode"""
+    n = eng.n_games
+    got = eng.snapshot()[:, 0] & 0xFFFF
+    want = orc.episode_seed(_ids(n, offset), episode.astype(np.int64)).view(np.uint16)
+    assert np.array_equal(got, want), f"{where}: seed16 of games {np.nonzero(got != want)[0][:5]}"
+
+
+@pytest.mark.parametrize("offset", OFFSETS, ids=["2^31-40", "2^32-40", "2^32+5"])
+@pytest.mark.parametrize("kind,path,P", _path_params((1, 2, 3)))
+def test_rollout_random_with_game_ids_at_the_word_boundaries(kind, path, P, offset):
+    """tetris_set_game_offset keeps 32 bits: ids that cross 2^31, that wrap inside the batch (2^32 - 40) and an offset above
+    2^32.  3 000 ms per step, so that most games end and are re-seeded by id and episode."""
+    n, K, ms = _games(kind, path), 60, 3000
+    eng, ref = _pair(kind, n, P, offset=offset)
+    S = _prepare_path(eng, kind, path, P)
+    f = Follower(eng, ref, S, ms, offset=offset)
+    c = f.call(K // S, f"offset {offset:#x}")
+    _assert_path(eng, kind, path, P, K // S)
+    assert int(c[1]) >= n // 2, "too few episodes ended: the seed schedule is hardly inside the comparison"
+    engines.assert_same_state(eng, ref, where=f"offset {offset:#x}")
+    _assert_seeds(eng, offset, f.episode, f"offset {offset:#x}")
+    assert eng.take_errors() == 0
+
+
+@pytest.mark.parametrize("offset", OFFSETS, ids=["2^31-40", "2^32-40", "2^32+5"])
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("P", [1, 2])
+def test_step_rt_dev_auto_reset_and_reset_dev_with_game_ids_at_the_word_boundaries(kind, P, offset):
+    """the reset-seed schedule in the single-step kernels' own code: step_rt_dev with auto-reset (3 000 ms per step: games end),
+    then reset_dev of every third game with the built-in schedule"""
+    n, steps, ms = 70, 40, 3000
+    eng, ref = _pair(kind, n, P, offset=offset)
+    ids, episode = _ids(n, offset), np.zeros(n, np.int64)
+    rng = np.random.default_rng(offset % 1000)
+    rot, trans, pl = Buf(kind, (n,), np.uint8), Buf(kind, (n,), np.uint8), Buf(kind, (n,), np.uint8)
+    ended = 0
+    for s in range(steps):
+        r, t = rng.integers(0, 4, n).astype(np.uint8), rng.integers(0, 10, n).astype(np.uint8)
+        player = np.full(n, s % P, np.uint8)
+        rot.set(r), trans.set(t), pl.set(player)
+        eng.step_rt_dev(rot.ptr, trans.ptr, pl.ptr, None, None, None, ms=ms, auto_reset=True)
+        eng.sync()
+        d = np.nonzero(ref.step_rt(r, t, player, ms=ms))[0].astype(np.int32)
+        episode[d] += 1
+        ended += len(d)
+        if len(d):
+            ref.reset(d, seeds=orc.episode_seed(ids[d], episode[d]))
+    assert ended >= n // 2, "too few episodes ended"
+    engines.assert_same_state(eng, ref, where="step_rt_dev with auto-reset")
+    _assert_seeds(eng, offset, episode, "step_rt_dev with auto-reset")
+    mask = (np.arange(n) % 3 == 0).astype(np.uint8)
+    eng.reset_dev(Buf(kind, (n,), np.uint8).set(mask).ptr, None)
+    eng.sync()
+    d = np.nonzero(mask)[0].astype(np.int32)
+    episode[d] += 1
+    ref.reset(d, seeds=orc.episode_seed(ids[d], episode[d]))
+    engines.assert_same_state(eng, ref, where="reset_dev with the built-in schedule")
+    _assert_seeds(eng, offset, episode, "reset_dev")
+    assert eng.take_errors() == 0

@@ -128,7 +128,13 @@ def test_split_rollout_kernels_at_1500_ms_per_step():
     _split_rollout_matches_oracle_rollout(4096, 160, 1500)
 
 
-def _split_rollout_matches_oracle_rollout(N, STEPS, ms):
+def test_split_rollout_stages_across_2_to_the_32_steps():
+    """tetris_split_rollout_stage_dev takes a 64-bit step: 40 steps from 2^32 - 3, so a stage 3 with step = 2^32 - 1 finishes
+    that step and deals step 2^32 (`step + 1` must not be cut to 32 bits: policy draw and acting player = step mod 2)"""
+    _split_rollout_matches_oracle_rollout(4096, 40, 400, first_step=2**32 - 3)
+
+
+def _split_rollout_matches_oracle_rollout(N, STEPS, ms, first_step=0):
     import importlib
     import os
 
@@ -141,7 +147,7 @@ def _split_rollout_matches_oracle_rollout(N, STEPS, ms):
         try:
             tg.bind(side)
             so = mod.SplitOpponents(N, side=side, peer=1 - side, dist=tg, seeds=orc.episode_seed(np.arange(N), 0))
-            so.rollout(STEPS, ms=ms)
+            so.rollout(STEPS, first_step=first_step, ms=ms)
             results[side] = (so.batch.observe(), so.batch.rollout_totals())
             so.close()
         except Exception as e:
@@ -155,7 +161,7 @@ def _split_rollout_matches_oracle_rollout(N, STEPS, ms):
         t.join()
     assert not errors, errors
     ref = orc.OracleBatch(N, 2, 20, 10, seeds=orc.episode_seed(np.arange(N), 0))
-    _, want = ref.rollout_random(STEPS, ms=ms, threads=min(32, len(os.sched_getaffinity(0))))
+    _, want = ref.rollout_random(STEPS, first_step=first_step, ms=ms, threads=min(32, len(os.sched_getaffinity(0))))
     rec, ro, lw = ref.observe()
     t0, t1 = results[0][1], results[1][1]
     assert int(t0[0]) == int(want[0]) == int(t1[0]) == N * STEPS          # env-steps, counted on the device
