@@ -12,6 +12,7 @@
 #include "tetris_act.h"
 #include "tetris_traj.h"
 #include "tetris_batch.h"
+#include "tetris_host.h"
 
 namespace te {}
 using namespace te;
@@ -377,24 +378,6 @@ __global__ __launch_bounds__(NT) void k_traj_batch(TrajBatchArgs ba) {
             *reinterpret_cast<uint32_t*>(out + k) = *reinterpret_cast<const uint32_t*>(tile + k);
     }
     for (uint32_t k = done + (uint32_t)lane; k < bytes; k += NT) out[k] = tile[k];
-}
-
-// Runtime value -> template argument, on the host.  with_value<LO, HI>(v, f) calls f(std::integral_constant<int, v>) when
-// LO <= v <= HI and returns whether it did; with_flag(v, f) calls f(std::true_type or std::false_type); with_shape<LO, HI>(P, flag, f)
-// calls f(P, FLAG) with both.  f is a generic lambda that names its kernel with them (k_game<P(), MODE, TINT()>).  The bounds decide
-// which instantiations a translation unit holds: player counts 1..2 of k_game, k_plan_* and k_policy_step live in tetris_hip.hip,
-// 3..4 in tetris_hip_multi.hip.
-template <int LO, int HI, class F>
-static bool with_value(int v, F&& f) {
-    if constexpr (LO > HI) return false;
-    else if (v == LO) { f(std::integral_constant<int, LO>{}); return true; }
-    else return with_value<LO + 1, HI>(v, f);
-}
-template <class F>
-static void with_flag(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
-template <int LO, int HI, class F>
-static bool with_shape(int P, bool flag, F&& f) {
-    return with_value<LO, HI>(P, [&](auto p) { with_flag(flag, [&](auto t) { f(p, t); }); });
 }
 
 // launches k_game<P, mode, tint> for P = 3, 4 (tetris_hip_multi.hip)

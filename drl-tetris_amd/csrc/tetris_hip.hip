@@ -960,12 +960,7 @@ __global__ __launch_bounds__(256) void k_set_dead(Geo geo, int n, const int32_t*
 struct tetris_batch;
 static void chain_release(tetris_batch* b);
 static int chain_recover(tetris_batch* b);
-static thread_local std::string g_err;
 static int default_direct_min();
-static int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
 #define HIP_TRY(expr)                                                                                            \
     do {                                                                                                         \
         hipError_t e_ = (expr);                                                                                  \
@@ -1180,6 +1175,8 @@ struct tetris_batch {
     size_t select_blocks_cap = 0;
 };
 
+static HostShape shape_of(const tetris_batch* b) { return {b->N, b->P, b->H, b->nw, b->split, b->tint}; }
+
 static Geo geo_of_batch(tetris_batch* b) {
     Geo g = {b->d_state, b->d_gstate, (size_t)b->N, b->P, b->nw, (size_t)b->stride};
     return g;
@@ -1192,7 +1189,7 @@ static KArgs base_args(tetris_batch* b, int n, const int32_t* d_idx) {
     {   // tables are shared between batches: take pointer and size together (another batch may be growing them)
         std::lock_guard<std::mutex> lock(g_tab_mutex);
         a.table = b->tab->d_table;
-        a.n_draws = (uint32_t)(b->tab->n_chunks < b->table_limit ? b->tab->n_chunks : b->table_limit) * CHUNK;
+        a.n_draws = table_draws(b->tab->n_chunks, b->table_limit);
     }
     a.start = b->tab->d_start; a.combo_pow = b->tab->d_pow; a.margin = b->margin;
     a.H = b->H; a.n_games = b->N; a.n_stride = b->stride; a.n_players = b->P; a.nw = b->nw; a.n = n; a.idx = d_idx; a.game_offset = b->game_offset;
@@ -1391,11 +1388,7 @@ static int finish_call(tetris_batch* b, bool drained = false) {
     }
     if (f[F_CHAIN] && (rc = chain_recover(b))) return rc;       // waves of a chained launch gave up: their games are finished un-chained
     if ((rc = service_flags(b))) return rc;                     // before the argument error below: an extend request is never dropped
-    if (f[F_BADARG]) {
-        f[F_BADARG] = 0;
-        return fail(TETRIS_E_ARG, "output capacity exceeded (max_lists / max_keys too small)");
-    }
-    return TETRIS_OK;
+    return take_capacity_error(f);
 }
 
 // every entry point starts here; `enqueues`: the call may put work on one of the batch's streams (all but the pure waits)
@@ -1442,10 +1435,8 @@ struct HostCall {
     }
     // game indices: validated, then staged (-> d_idx)
     int idx(const int32_t* idx, int n) {
-        if (n < 0 || (!idx && n > b->N)) return fail(TETRIS_E_ARG, "n out of range");
-        for (int i = 0; idx && i < n; i++)
-            if (idx[i] < 0 || idx[i] >= b->N) return fail(TETRIS_E_ARG, "game index out of range");
-        return in(idx, (size_t)n, &d_idx);
+        int rc = check_idx(shape_of(b), idx, n);
+        return rc ? rc : in(idx, (size_t)n, &d_idx);
     }
     // `count` T on the device for the kernel (*d); finish() copies them to `dst`, or leaves them in the pinned half for the caller
     // to read (*h) when dst is NULL
@@ -1471,13 +1462,6 @@ struct HostCall {
     }
 };
 
-// every player index < P (player NULL: nothing to check)
-static int check_players(const tetris_batch* b, const uint8_t* player, int n) {
-    for (int i = 0; player && i < n; i++)
-        if (player[i] >= b->P) return fail(TETRIS_E_ARG, "player index out of range");
-    return TETRIS_OK;
-}
-
 // The rest of a synchronous step: done [n] and lines / dead [P][n] on the device, the launch, io.finish(), then lines / dead to the
 // caller as [n][P]
 template <int MODE>
@@ -1487,17 +1471,13 @@ static int finish_step(HostCall& io, KArgs& a, int n, uint8_t* done, uint8_t* li
     int rc = io.out(done, (size_t)n, &a.done);
     if (rc || (rc = io.out(nullptr, (size_t)n * P, &a.lines, &hl)) || (rc = io.out(nullptr, (size_t)n * P, &a.dead, &hd))) return rc;
     if ((rc = launch_game<MODE>(io.b, a)) || (rc = io.finish())) return rc;
-    for (int i = 0; i < n; i++)
-        for (int p = 0; p < P; p++) {
-            if (lines) lines[(size_t)i * P + p] = hl[(size_t)p * n + i];
-            if (dead) dead[(size_t)i * P + p] = hd[(size_t)p * n + i];
-        }
+    lines_dead_unpack(shape_of(io.b), n, hl, hd, lines, dead);
     return TETRIS_OK;
 }
 
 extern "C" {
 
-const char* tetris_last_error(void) { return g_err.c_str(); }
+const char* tetris_last_error(void) { return last_error(); }
 
 int tetris_device_count(void) {
     int n = 0;
@@ -1580,18 +1560,8 @@ static hipError_t device_chain_streams(int device, hipStream_t out[CHAIN_STREAMS
 
 static int create_impl(tetris_batch** out, int n_games, int n_players, int height, int width, const uint8_t piece_map[7],
                        int device, const int16_t* seeds, int split, int side, int flags = 0) {
-    if (!out) return fail(TETRIS_E_ARG, "out is NULL");
-    *out = nullptr;
-    if (n_games < 1) return fail(TETRIS_E_ARG, "n_games must be >= 1");
-    if (n_players < 1 || n_players > TETRIS_MAX_PLAYERS) return fail(TETRIS_E_ARG, "n_players must be 1..4");
-    if (n_players > 2 && split) return fail(TETRIS_E_ARG, "split batches are two-player games");
-    if ((long long)n_games * n_players > (1ll << 23))       // the state allocation stays below 4 GiB (32-bit buffer offsets): 8M boards x 69 words
-        return fail(TETRIS_E_ARG, "n_games * n_players must be <= 2^23");
-    if (height < 4 || height > MAX_H) return fail(TETRIS_E_ARG, "height must be in [4, 31]");
-    if (width != NCOL) return fail(TETRIS_E_ARG, "width must be 10 (the reference hard-codes 10, gamePlay.cpp:202)");
-    if (!piece_map) return fail(TETRIS_E_ARG, "piece_map is NULL");
-    for (int i = 0; i < 7; i++)
-        if (piece_map[i] > 6) return fail(TETRIS_E_ARG, "piece_map entries must be 0..6");
+    int rc = create_check(out, n_games, n_players, height, width, piece_map, split, side, flags);
+    if (rc) return rc;
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev < 1)
@@ -1646,7 +1616,7 @@ static int create_impl(tetris_batch** out, int n_games, int n_players, int heigh
     memset(b->flags, 0, NFLAGS * sizeof(uint32_t));
     CREATE_TRY(hipMemsetAsync(b->d_gstate, 0, gstate_bytes, b->stream));
     CREATE_TRY(hipMemsetAsync(b->d_state, 0, state_bytes, b->stream));
-    int rc = tables_acquire(&b->tab, device, piece_map, b->stream);
+    rc = tables_acquire(&b->tab, device, piece_map, b->stream);
     if (rc) { std::string keep = g_err; tetris_destroy(b); return fail(rc, keep); }
     HostCall io{b};
     const int16_t* d_seeds;
@@ -1706,8 +1676,7 @@ int tetris_debug_xcd_skew(tetris_batch* b, int skew) {
 int tetris_debug_table_limit(tetris_batch* b, int chunks) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if (chunks < 0 || chunks > MAX_CHUNKS) return fail(TETRIS_E_ARG, "chunks must be 0..64");
-    if ((rc = finish_call(b))) return rc;
+    if ((rc = table_limit_check(chunks)) || (rc = finish_call(b))) return rc;
     b->table_limit = chunks ? chunks : MAX_CHUNKS;
     return TETRIS_OK;
 }
@@ -1821,13 +1790,11 @@ int tetris_create(tetris_batch** out, int n_games, int n_players, int height, in
 
 int tetris_create_ex(tetris_batch** out, int n_games, int n_players, int height, int width, const uint8_t piece_map[7], int device,
                      const int16_t* seeds, int flags) {
-    if (flags & ~TETRIS_FLAG_COLOURS) return fail(TETRIS_E_ARG, "unknown flag");
     return create_impl(out, n_games, n_players, height, width, piece_map, device, seeds, 0, 0, flags);
 }
 
 int tetris_create_split(tetris_batch** out, int n_games, int side, int height, int width, const uint8_t piece_map[7], int device,
                         const int16_t* seeds) {
-    if (side != 0 && side != 1) return fail(TETRIS_E_ARG, "side must be 0 or 1");
     return create_impl(out, n_games, 1, height, width, piece_map, device, seeds, 1, side);
 }
 
@@ -1840,13 +1807,8 @@ int tetris_set_stream(tetris_batch* b, void* hip_stream, int external) {
 }
 
 static int split_stage_launch(tetris_batch* b, int stage, KArgs& a, const uint32_t* const d_words[4], uint32_t* d_out) {
-    if (!b->split) return fail(TETRIS_E_ARG, "not a split batch (tetris_create_split)");
-    if (stage < 0 || stage > 3) return fail(TETRIS_E_ARG, "stage must be 0, 1, 2 or 3 (= 2 of this step + 0 of the next)");
-    if (stage != 2 && !d_out) return fail(TETRIS_E_ARG, "stages 0, 1 and 3 need d_out");
-    // words a stage reads: stage 1 = both A words (+ player 0's B on side 1); stages 2 and 3 = the opponent's B
-    if (stage > 0 && !d_words) return fail(TETRIS_E_ARG, "stages 1, 2 and 3 need d_words");
-    if (stage == 1 && (!d_words[0] || !d_words[1] || (b->side == 1 && !d_words[2]))) return fail(TETRIS_E_ARG, "stage 1 needs both A words (and player 0's B words on side 1)");
-    if (stage >= 2 && !d_words[b->side == 0 ? 3 : 2]) return fail(TETRIS_E_ARG, "stages 2 and 3 need the opponent's B words");
+    int rc = split_stage_check(shape_of(b), b->side, stage, d_words, d_out);
+    if (rc) return rc;
     b->home_async = true;
     for (int k = 0; k < 4; k++) a.xw[k] = d_words ? d_words[k] : nullptr;
     a.shadow = b->d_shadow; a.xout = d_out; a.split_side = b->side;
@@ -1860,7 +1822,7 @@ int tetris_split_stage_dev(tetris_batch* b, int stage, const uint8_t* d_rot, con
                            const uint32_t* const d_words[4], uint32_t* d_out, uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if ((stage == 0 || stage == 3) && (!d_rot || !d_trans)) return fail(TETRIS_E_ARG, "stages 0 and 3 need rot/trans (stage 3: of the NEXT step)");
+    if ((rc = split_step_check(stage, d_rot, d_trans))) return rc;
     KArgs a = base_args(b, b->N, nullptr);
     a.rot = d_rot; a.trans = d_trans; a.player = d_acting; a.ms = ms;
     a.done = d_done; a.lines = d_lines; a.dead = d_dead;
@@ -1893,12 +1855,10 @@ int tetris_rollout_totals(tetris_batch* b, uint64_t totals[4]) {
 int tetris_take_errors(tetris_batch* b, uint32_t* bits) {
     int rc = check_batch(b, false);
     if (rc) return rc;
-    if (!bits) return fail(TETRIS_E_ARG, "bits is NULL");
-    if ((rc = finish_call(b))) return rc;
+    if ((rc = take_errors_check(bits)) || (rc = finish_call(b))) return rc;
     volatile uint32_t* f = b->flags;
-    *bits = (f[F_FIFO] ? TETRIS_ERR_FIFO : 0u) | (f[F_EXHAUSTED] ? TETRIS_ERR_STREAM : 0u) | (b->chain_fell_back ? TETRIS_ERR_CHAIN_FELL_BACK : 0u) |
-            (f[F_LISTS] ? TETRIS_ERR_LISTS : 0u);
-    f[F_FIFO] = 0; f[F_EXHAUSTED] = 0; f[F_LISTS] = 0; b->chain_fell_back = false;
+    *bits = take_error_bits(f) | (b->chain_fell_back ? TETRIS_ERR_CHAIN_FELL_BACK : 0u);
+    b->chain_fell_back = false;
     return TETRIS_OK;
 }
 
@@ -1922,31 +1882,12 @@ int tetris_reset(tetris_batch* b, const int32_t* idx, int n, const int16_t* seed
 
 // host keys [n][P][K] -> device [K][P][n]; host lens [n][P] -> device [P][n]
 static int stage_keys(HostCall& io, int n, const uint8_t* keys, const uint8_t* lens, int max_keys, KArgs& a) {
-    if (!keys || !lens || max_keys < 1) return fail(TETRIS_E_ARG, "keys/lens/max_keys");
+    int rc = keys_check(keys, lens, max_keys);
+    if (rc) return rc;
     const int P = io.b->P;
     Stage *sk, *sl;
-    int rc = io.take((size_t)n * P * max_keys, &sk);
-    if (rc || (rc = io.take((size_t)n * P, &sl))) return rc;
-    uint8_t* hk = (uint8_t*)sk->h;
-    uint8_t* hl = (uint8_t*)sl->h;
-    for (int i = 0; i < n; i++)
-        for (int p = 0; p < P; p++) {
-            const int len = lens[(size_t)i * P + p];
-            if (len > max_keys) return fail(TETRIS_E_ARG, "lens[i][p] > max_keys");
-            hl[(size_t)p * n + i] = (uint8_t)len;
-        }
-    // [n][P][K] -> [K][P][n], blocked over games so that reads stay in L1 and every write run is contiguous
-    // (the naive order writes with a stride of n bytes: 52 ms instead of ~2 ms for 64k two-player games)
-    const int BLK = 512;
-    for (int i0 = 0; i0 < n; i0 += BLK) {
-        const int i1 = i0 + BLK < n ? i0 + BLK : n;
-        for (int k = 0; k < max_keys; k++)
-            for (int p = 0; p < P; p++) {
-                uint8_t* dst = hk + ((size_t)k * P + p) * n;
-                const uint8_t* src = keys + (size_t)p * max_keys + k;
-                for (int i = i0; i < i1; i++) dst[i] = src[(size_t)i * P * max_keys];
-            }
-    }
+    if ((rc = io.take((size_t)n * P * max_keys, &sk)) || (rc = io.take((size_t)n * P, &sl))) return rc;
+    if ((rc = keys_pack(shape_of(io.b), n, keys, lens, max_keys, (uint8_t*)sk->h, (uint8_t*)sl->h))) return rc;
     if ((rc = io.send(sk, (size_t)n * P * max_keys)) || (rc = io.send(sl, (size_t)n * P))) return rc;
     a.keys = (const uint8_t*)sk->d; a.lens = (const uint8_t*)sl->d; a.max_keys = max_keys;
     return TETRIS_OK;
@@ -1992,10 +1933,7 @@ int tetris_step_rt_dev_ex(tetris_batch* b, const uint8_t* d_rot, const uint8_t* 
                           uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead, int flags) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if (!d_rot || !d_trans) return fail(TETRIS_E_ARG, "rot/trans are NULL");
-    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
-    if ((flags & TETRIS_STEP_AUTO_RESET) && b->split) return fail(TETRIS_E_ARG, "auto-reset is not available on split batches");
-    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
+    if ((rc = step_rt_check(shape_of(b), d_rot, d_trans, flags)) || (rc = gate_launch(b, GATE_GROUP))) return rc;
     KArgs a = base_args(b, b->N, nullptr);
     a.rot = d_rot; a.trans = d_trans; a.player = d_player; a.ms = ms;
     a.done = d_done; a.lines = d_lines; a.dead = d_dead;
@@ -2007,11 +1945,7 @@ int tetris_step_rt_observe_dev(tetris_batch* b, const uint8_t* d_rot, const uint
                                uint8_t* d_visual, uint8_t* d_vector, uint8_t* d_piece) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if (!d_rot || !d_trans) return fail(TETRIS_E_ARG, "rot/trans are NULL");
-    if (!d_visual || !d_vector || !d_piece) return fail(TETRIS_E_ARG, "visual/vector/piece are NULL");
-    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
-    if (b->split) return fail(TETRIS_E_ARG, "tetris_step_rt_observe_dev is not available on split batches");
-    if (b->P > 2) return fail(TETRIS_E_ARG, "the packed observation is defined for one or two players (own / opponent's board: state_unpack.py:88-137)");
+    if ((rc = step_rt_observe_check(shape_of(b), d_rot, d_trans, flags, d_visual, d_vector, d_piece))) return rc;
     const bool fused = !b->tint && b->H % 2 == 0 && ((uintptr_t)d_visual & 3u) == 0 && ((uintptr_t)d_vector & 3u) == 0;
     if (!fused) {             // colour batches, odd heights, unaligned outputs: the same two kernels back to back
         if ((rc = tetris_step_rt_dev_ex(b, d_rot, d_trans, d_player, ms, d_done, d_lines, d_dead, flags))) return rc;
@@ -2053,8 +1987,7 @@ int tetris_step_rt_dev(tetris_batch* b, const uint8_t* d_rot, const uint8_t* d_t
 int tetris_reset_dev(tetris_batch* b, const uint8_t* d_mask, const int16_t* d_seeds) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if (b->split) return fail(TETRIS_E_ARG, "tetris_reset_dev is not available on split batches");
-    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
+    if ((rc = not_on_split(shape_of(b), "tetris_reset_dev")) || (rc = gate_launch(b, GATE_GROUP))) return rc;
     KArgs a = base_args(b, b->N, nullptr);
     a.mask = d_mask; a.seeds = d_seeds;
     return d_seeds ? launch_game<M_RESET>(b, a) : launch_game<M_RESET_SCHED>(b, a);
@@ -2064,9 +1997,8 @@ int tetris_step_rt(tetris_batch* b, const uint8_t* rot, const uint8_t* trans, co
                    uint8_t* lines, uint8_t* dead) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if (!rot || !trans) return fail(TETRIS_E_ARG, "rot/trans are NULL");
     const int n = b->N;
-    if ((rc = check_players(b, player, n))) return rc;
+    if ((rc = step_rt_check(shape_of(b), rot, trans, 0)) || (rc = check_players(shape_of(b), player, n))) return rc;
     KArgs a = base_args(b, n, nullptr);
     a.ms = ms;
     HostCall io{b};
@@ -2102,9 +2034,7 @@ int tetris_observe_packed_dev(tetris_batch* b, const int32_t* d_idx, int n, cons
                               uint8_t* d_vector, uint8_t* d_piece) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if (!d_visual || !d_vector || !d_piece) return fail(TETRIS_E_ARG, "visual/vector/piece are NULL");
-    if (b->P > 2) return fail(TETRIS_E_ARG, "the packed observation is defined for one or two players (own / opponent's board: state_unpack.py:88-137)");
-    if (n < 0 || (!d_idx && n > b->N)) return fail(TETRIS_E_ARG, "n out of range");
+    if ((rc = observe_packed_check(shape_of(b), d_idx != nullptr, n, d_visual, d_vector, d_piece))) return rc;
     if (n == 0) return TETRIS_OK;
     b->home_async = true;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
@@ -2139,12 +2069,12 @@ int tetris_observe_packed(tetris_batch* b, const int32_t* idx, int n, const uint
                           uint8_t* piece) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if (!visual || !vector || !piece) return fail(TETRIS_E_ARG, "visual/vector/piece are NULL");
+    if ((rc = observe_packed_outputs_check(visual, vector, piece))) return rc;
     HostCall io{b};
     if ((rc = io.idx(idx, n))) return rc;
     if (n == 0) return TETRIS_OK;
     const uint8_t* d_player;
-    if ((rc = check_players(b, player, n)) || (rc = io.in(player, (size_t)n, &d_player))) return rc;
+    if ((rc = check_players(shape_of(b), player, n)) || (rc = io.in(player, (size_t)n, &d_player))) return rc;
     const size_t pn = (size_t)b->P * n;
     uint8_t *d_visual, *d_vector, *d_piece;
     if ((rc = io.out(visual, pn * b->H * NCOL, &d_visual)) || (rc = io.out(vector, pn * 12, &d_vector)) || (rc = io.out(piece, pn, &d_piece))) return rc;
@@ -2200,7 +2130,7 @@ int tetris_enumerate_drops(tetris_batch* b, const int32_t* idx, int n, const uin
     if ((rc = io.idx(idx, n))) return rc;
     if (n == 0) return TETRIS_OK;
     const uint8_t* d_player;
-    if ((rc = check_players(b, player, n)) || (rc = io.in(player, (size_t)n, &d_player))) return rc;
+    if ((rc = check_players(shape_of(b), player, n)) || (rc = io.in(player, (size_t)n, &d_player))) return rc;
     const size_t lanes = (size_t)n * 40;
     uint8_t *d_valid, *d_cleared;
     int8_t* d_land_y;
@@ -2215,11 +2145,7 @@ int tetris_enumerate_drops_dev_ex(tetris_batch* b, const int32_t* d_idx, int n, 
                                   int8_t* d_land_y, uint8_t* d_cleared, uint32_t* d_after, int flags) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if (!d_valid || !d_land_y || !d_cleared) return fail(TETRIS_E_ARG, "valid/land_y/cleared are NULL");
-    if (n < 0 || (!d_idx && n > b->N)) return fail(TETRIS_E_ARG, "n out of range");
-    if (flags & ~TETRIS_ENUM_PLANAR) return fail(TETRIS_E_ARG, "unknown flag");
-    if ((flags & TETRIS_ENUM_PLANAR) && ((((uintptr_t)d_valid | (uintptr_t)d_land_y | (uintptr_t)d_cleared) & 3u) || ((uintptr_t)d_after & 15u)))
-        return fail(TETRIS_E_ARG, "planar outputs: valid / land_y / cleared must be 4-byte aligned, after 16-byte aligned");
+    if ((rc = enumerate_check(shape_of(b), d_idx != nullptr, n, d_valid, d_land_y, d_cleared, d_after, flags))) return rc;
     if (n == 0) return TETRIS_OK;
     b->home_async = true;
     dim3 grid((unsigned)((n + ENUM_BOARDS - 1) / ENUM_BOARDS)), block(ENUM_BLOCK);
@@ -2258,9 +2184,7 @@ int tetris_get_actions(tetris_batch* b, const int32_t* idx, int n, const uint8_t
                        int32_t* count, int max_lists, int max_keys) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if (!keys || !lens || !count || max_lists < 1 || max_keys < 1 || max_keys > 255) return fail(TETRIS_E_ARG, "keys/lens/count/max_*");
-    if (n < 0 || (!idx && n > b->N)) return fail(TETRIS_E_ARG, "n out of range");
-    if ((rc = check_players(b, player, n))) return rc;
+    if ((rc = get_actions_check(shape_of(b), idx != nullptr, n, player, keys, lens, count, max_lists, max_keys))) return rc;
     const int CHUNK_GAMES = 1024;                    // bounds the staging buffers
     const size_t L = PLAN_LANE_LISTS;                // lists one (x, rotation) start can produce
     std::vector<int32_t> ident;
@@ -2282,23 +2206,7 @@ int tetris_get_actions(tetris_batch* b, const int32_t* idx, int n, const uint8_t
         });
         if (hipGetLastError() != hipSuccess) return fail(TETRIS_E_HIP, "k_actions launch failed");
         if ((rc = io.finish())) return rc;
-        for (int i = 0; i < m; i++) {
-            int total = 0;
-            bool over = false;
-            for (int xi = 0; xi < 10; xi++)               // the reference enumerates x-major, rotation-minor
-                for (int r = 0; r < 4; r++) {
-                    const size_t lane = (size_t)i * 40 + r * 10 + xi;
-                    for (int k = 0; k < hc[lane]; k++) {
-                        if (total >= max_lists) { over = true; break; }
-                        const int len = hl[lane * L + k];
-                        lens[(size_t)(g0 + i) * max_lists + total] = (uint8_t)len;
-                        memcpy(keys + ((size_t)(g0 + i) * max_lists + total) * max_keys, hk + (lane * L + k) * max_keys, (size_t)len);
-                        total++;
-                    }
-                }
-            count[g0 + i] = total;
-            if (over) return fail(TETRIS_E_ARG, "more than max_lists key lists for one game");
-        }
+        if ((rc = get_actions_gather(m, hc, hl, hk, max_lists, max_keys, keys + (size_t)g0 * max_lists * max_keys, lens + (size_t)g0 * max_lists, count + g0))) return rc;
     }
     return TETRIS_OK;
 }
@@ -2307,22 +2215,6 @@ int tetris_get_actions(tetris_batch* b, const int32_t* idx, int n, const uint8_t
 // Games per k_actions + k_plan_lists pair: bounds the slab scratch (40 x 16 slab entries of max_keys + 1 bytes per game: 128 MB
 // at 4 096 games and 48 keys); a batch of more games enqueues one pair per chunk, ordered by the stream.
 static const int PLAN_CHUNK = 4096;
-
-static int plan_check(tetris_batch* b, const char* what) {
-    if (b->split) return fail(TETRIS_E_ARG, std::string(what) + " is not available on split batches");
-    return TETRIS_OK;
-}
-
-static PlanArgs plan_args(tetris_batch* b, const uint8_t* d_player, const int32_t* d_count, const uint8_t* d_lens, const uint8_t* d_keys,
-                          int max_lists, int max_keys, int ms) {
-    PlanArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.a = base_args(b, b->N, nullptr);
-    pa.a.ms = ms;
-    pa.player = d_player; pa.count = d_count; pa.lens = d_lens; pa.keys = d_keys;
-    pa.max_lists = max_lists; pa.max_keys = max_keys;
-    return pa;
-}
 
 // which: 0 simulate, 1 step, 2 step with auto-reset
 static int launch_plan_kernel(tetris_batch* b, int which, dim3 grid, const PlanArgs& pa, int fin) {
@@ -2336,10 +2228,7 @@ int tetris_action_lists_dev(tetris_batch* b, const uint8_t* d_player, int max_li
                             uint8_t* d_lens, uint8_t* d_keys) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if ((rc = plan_check(b, "tetris_action_lists_dev"))) return rc;
-    if (!d_count || !d_lens || !d_keys) return fail(TETRIS_E_ARG, "count/lens/keys are NULL");
-    if (max_lists < 1 || max_keys < 1 || max_keys > 254) return fail(TETRIS_E_ARG, "max_lists >= 1, 1 <= max_keys <= 254");
-    if (flags & ~TETRIS_LISTS_KEEP_NULL) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((rc = action_lists_check(shape_of(b), d_count, d_lens, d_keys, max_lists, max_keys, flags))) return rc;
     const int chunk = b->N < PLAN_CHUNK ? b->N : PLAN_CHUNK;
     const int KS = max_keys + 1;                 // one key more than the caller takes: a list that does not fit shows as one
     const size_t lanes = (size_t)chunk * 40;
@@ -2383,12 +2272,9 @@ int tetris_simulate_lists_dev(tetris_batch* b, const uint8_t* d_player, const in
                               uint8_t* d_dead) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if ((rc = plan_check(b, "tetris_simulate_lists_dev"))) return rc;
-    if (!d_count || !d_lens || !d_keys || !d_cols) return fail(TETRIS_E_ARG, "count/lens/keys/cols are NULL");
-    if (max_lists < 1 || max_lists > 65535 || max_keys < 1 || max_keys > 255) return fail(TETRIS_E_ARG, "1 <= max_lists <= 65535, 1 <= max_keys <= 255");
-    if (flags & ~TETRIS_SIM_FINALIZE) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((rc = simulate_lists_check(shape_of(b), d_count, d_lens, d_keys, max_lists, max_keys, flags, d_cols))) return rc;
     if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    PlanArgs pa = plan_args(b, d_player, d_count, d_lens, d_keys, max_lists, max_keys, ms);
+    PlanArgs pa = plan_args(base_args(b, b->N, nullptr), d_player, d_count, d_lens, d_keys, max_lists, max_keys, ms);
     pa.cols = d_cols;
     const int fin = (flags & TETRIS_SIM_FINALIZE) ? 1 : 0;
     if (fin) { pa.a.done = d_done; pa.a.lines = d_lines; pa.a.dead = d_dead; }
@@ -2400,12 +2286,9 @@ int tetris_step_lists_dev(tetris_batch* b, const uint8_t* d_player, const int32_
                           uint8_t* d_dead) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if ((rc = plan_check(b, "tetris_step_lists_dev"))) return rc;
-    if (!d_choice || !d_count || !d_lens || !d_keys) return fail(TETRIS_E_ARG, "choice/count/lens/keys are NULL");
-    if (max_lists < 1 || max_keys < 1 || max_keys > 255) return fail(TETRIS_E_ARG, "max_lists >= 1, 1 <= max_keys <= 255");
-    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((rc = step_lists_check(shape_of(b), d_choice, d_count, d_lens, d_keys, max_lists, max_keys, flags))) return rc;
     if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    PlanArgs pa = plan_args(b, d_player, d_count, d_lens, d_keys, max_lists, max_keys, ms);
+    PlanArgs pa = plan_args(base_args(b, b->N, nullptr), d_player, d_count, d_lens, d_keys, max_lists, max_keys, ms);
     pa.choice = d_choice;
     pa.a.done = d_done; pa.a.lines = d_lines; pa.a.dead = d_dead;
     return launch_plan_kernel(b, (flags & TETRIS_STEP_AUTO_RESET) ? 2 : 1, dim3((unsigned)((b->N + 63) / 64)), pa, 0);
@@ -2415,20 +2298,10 @@ int tetris_plan_deltas_dev(tetris_batch* b, const uint8_t* d_player, const int32
                            float small_fill, int flags, void* d_deltas, void* d_sums, uint8_t* d_small) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if ((rc = plan_check(b, "tetris_plan_deltas_dev"))) return rc;
-    if (!d_count || !d_cols || !d_deltas) return fail(TETRIS_E_ARG, "count/cols/deltas are NULL");
-    if (max_lists < 1 || max_lists > PD_BLOCK) return fail(TETRIS_E_ARG, "1 <= max_lists <= 256");
-    if (flags & ~(TETRIS_DELTAS_F16 | TETRIS_DELTAS_LIST_MAJOR)) return fail(TETRIS_E_ARG, "unknown flag");
-    if ((((uintptr_t)d_deltas) | ((uintptr_t)d_sums)) & 15u) return fail(TETRIS_E_ARG, "deltas / sums must be 16-byte aligned");
-    if (((uintptr_t)d_cols) & 3u) return fail(TETRIS_E_ARG, "cols must be 4-byte aligned");
-    b->home_async = true;
+    static_assert(PD_BLOCK == PLAN_DELTAS_MAX_LISTS, "list k = thread k");
     PlanDeltaArgs da;
-    memset(&da, 0, sizeof da);
-    da.geo = geo_of_batch(b);
-    da.H = b->H; da.n = b->N;
-    da.player = d_player; da.count = d_count; da.cols = d_cols;
-    da.max_lists = max_lists; da.small_fill = small_fill;
-    da.deltas = d_deltas; da.sums = d_sums; da.small = d_small;
+    if ((rc = plan_deltas_args(shape_of(b), geo_of_batch(b), d_player, d_count, d_cols, max_lists, small_fill, flags, d_deltas, d_sums, d_small, da))) return rc;
+    b->home_async = true;
     const dim3 grid((unsigned)((b->N + 127) / 128) * 128u), block(PD_BLOCK);     // whole groups of 8 XCDs x 16 games
     const bool major = (flags & TETRIS_DELTAS_LIST_MAJOR) != 0;
     if (flags & TETRIS_DELTAS_F16) {
@@ -2854,8 +2727,7 @@ int tetris_rollout_launch(tetris_batch* b, int launches, int steps_per_launch, u
     const Clock::time_point t_entry = Clock::now();
     int rc = check_batch(b);
     if (rc) return rc;
-    if (launches < 1 || steps_per_launch < 0) return fail(TETRIS_E_ARG, "launches must be >= 1, steps_per_launch >= 0");
-    if (steps_per_launch > 256) return fail(TETRIS_E_ARG, "steps_per_launch must be <= 256");
+    if ((rc = rollout_launch_check(launches, steps_per_launch))) return rc;
     // A step may consume 2 piece draws per player, and the host learns of a board that came close to the end of the RNG
     // tables only through the flag words, up to 2 * GATE_GROUP + 1 launches late (gate_launch): the low-water margin
     // covers what those launches can consume.  Nothing in this loop waits for the GPU unless the host runs that far ahead.
@@ -2973,20 +2845,8 @@ __global__ __launch_bounds__(256) void k_policy_pick(PolicyArgs pa) {
 }
 // (k_policy_totals: beside k_totals)
 
-static int policy_check(tetris_batch* b, const char* what) {
-    if (b->split) return fail(TETRIS_E_ARG, std::string(what) + " is not available on split batches");
-    return TETRIS_OK;
-}
-
 static PolicyArgs policy_args(tetris_batch* b, const uint8_t* d_player, const int16_t* d_weights, int per_game, int ms) {
-    PolicyArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.a = base_args(b, b->N, nullptr);
-    pa.a.ms = ms; pa.a.steps = 1;
-    pa.player = d_player; pa.weights = d_weights; pa.per_game = per_game ? 1 : 0;
-    pa.fixed_player = -1;
-    pa.scores = b->d_policy_scores;
-    return pa;
+    return policy_args(base_args(b, b->N, nullptr), d_player, d_weights, per_game, ms, b->d_policy_scores);
 }
 
 static int policy_scores_buffer(tetris_batch* b) {
@@ -3017,8 +2877,7 @@ extern "C" {
 int tetris_rt_features_dev(tetris_batch* b, const uint8_t* d_player, int16_t* d_features) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if ((rc = policy_check(b, "tetris_rt_features_dev"))) return rc;
-    if (!d_features) return fail(TETRIS_E_ARG, "features is NULL");
+    if ((rc = policy_check(shape_of(b), "tetris_rt_features_dev", !d_features, "features is NULL"))) return rc;
     if ((rc = gate_launch(b, GATE_GROUP))) return rc;
     PolicyArgs pa = policy_args(b, d_player, nullptr, 0, 0);
     pa.features = d_features;
@@ -3031,8 +2890,7 @@ int tetris_policy_rt_dev(tetris_batch* b, const uint8_t* d_player, const int16_t
                          uint8_t* d_trans, int32_t* d_score) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if ((rc = policy_check(b, "tetris_policy_rt_dev"))) return rc;
-    if (!d_weights || !d_rot || !d_trans) return fail(TETRIS_E_ARG, "weights/rot/trans are NULL");
+    if ((rc = policy_check(shape_of(b), "tetris_policy_rt_dev", !d_weights || !d_rot || !d_trans, "weights/rot/trans are NULL"))) return rc;
     if ((rc = policy_scores_buffer(b))) return rc;
     if ((rc = gate_launch(b, GATE_GROUP))) return rc;
     PolicyArgs pa = policy_args(b, d_player, d_weights, per_game, 0);
@@ -3047,9 +2905,7 @@ int tetris_step_policy_dev(tetris_batch* b, const uint8_t* d_player, const int16
                            uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead, uint8_t* d_rot, uint8_t* d_trans) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if ((rc = policy_check(b, "tetris_step_policy_dev"))) return rc;
-    if (!d_weights) return fail(TETRIS_E_ARG, "weights is NULL");
-    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((rc = policy_check(shape_of(b), "tetris_step_policy_dev", !d_weights, "weights is NULL", flags))) return rc;
     if ((rc = policy_scores_buffer(b))) return rc;
     if ((rc = gate_launch(b, GATE_GROUP))) return rc;
     PolicyArgs pa = policy_args(b, d_player, d_weights, per_game, ms);
@@ -3062,8 +2918,7 @@ int tetris_step_policy_dev(tetris_batch* b, const uint8_t* d_player, const int16
 int tetris_rollout_game_totals_dev(tetris_batch* b, uint32_t* d_totals) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if ((rc = policy_check(b, "tetris_rollout_game_totals_dev"))) return rc;
-    if (!d_totals) return fail(TETRIS_E_ARG, "totals is NULL");
+    if ((rc = policy_check(shape_of(b), "tetris_rollout_game_totals_dev", !d_totals, "totals is NULL"))) return rc;
     if ((rc = gate_launch(b, GATE_GROUP))) return rc;
     hipLaunchKernelGGL(k_policy_totals, dim3((unsigned)((b->N + 255) / 256)), dim3(256), 0, b->stream, geo_of_batch(b), d_totals);
     HIP_TRY(hipGetLastError());
@@ -3108,9 +2963,7 @@ int tetris_rollout_policy(tetris_batch* b, int launches, int steps_per_launch, c
                           uint64_t first_step, int ms, uint64_t counters[4], float* elapsed_ms) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if ((rc = policy_check(b, "tetris_rollout_policy"))) return rc;
-    if (!d_weights) return fail(TETRIS_E_ARG, "weights is NULL");
-    if (launches < 1 || steps_per_launch < 1 || steps_per_launch > 256) return fail(TETRIS_E_ARG, "launches must be >= 1, 1 <= steps_per_launch <= 256");
+    if ((rc = rollout_policy_check(shape_of(b), d_weights, launches, steps_per_launch))) return rc;
     if ((rc = policy_scores_buffer(b))) return rc;
     if (counters && (rc = rollout_counters_begin(b))) return rc;
     if ((rc = rollout_policy_launches(b, launches, steps_per_launch, d_weights, per_game, first_step, ms, elapsed_ms))) return rc;
@@ -3121,35 +2974,6 @@ int tetris_rollout_policy(tetris_batch* b, int launches, int steps_per_launch, c
 }  // extern "C"
 
 // ---------------------------------------------------------------- acting on a network's evaluation (tetris_act.h)
-// the argument checks, then the kernel arguments
-static int act_args(tetris_batch* b, const tetris_act_eval* e, const char* what, ActArgs& aa) {
-    if (!e) return fail(TETRIS_E_ARG, "the argument struct is NULL");
-    if (b->split) return fail(TETRIS_E_ARG, std::string(what) + " is not available on split batches");
-    if (!e->d_action_eval || !e->d_rot || !e->d_trans) return fail(TETRIS_E_ARG, "action_eval/rot/trans are NULL");
-    if (e->n_pieces != 1 && e->n_pieces != 7) return fail(TETRIS_E_ARG, "n_pieces must be 1 or 7");
-    if (e->d_state_eval && e->n_values != 1 && e->n_values != 7 && e->n_values != 8) return fail(TETRIS_E_ARG, "n_values must be 1, 7 or 8");
-    if (e->d_value && !e->d_state_eval) return fail(TETRIS_E_ARG, "value needs state_eval");
-    if (e->mode < TETRIS_ACT_ARGMAX || e->mode > TETRIS_ACT_EPSILON) return fail(TETRIS_E_ARG, "unknown mode");
-    if (e->flags & ~(TETRIS_ACT_F16 | TETRIS_ACT_VALUE_F16)) return fail(TETRIS_E_ARG, "unknown flag");
-    if (e->mode == TETRIS_ACT_RANK && !e->table) return fail(TETRIS_E_ARG, "the RANK mode needs a table");
-    if (e->d_entropy && e->mode != TETRIS_ACT_PI) return fail(TETRIS_E_ARG, "entropy is an output of the PI mode");
-    if (((uintptr_t)e->d_action_eval) & 15u) return fail(TETRIS_E_ARG, "action_eval must be 16-byte aligned");
-    memset(&aa, 0, sizeof aa);
-    aa.a = base_args(b, b->N, nullptr);
-    aa.a.steps = 1;
-    aa.player = e->d_player;
-    aa.action_eval = e->d_action_eval; aa.state_eval = e->d_state_eval;
-    aa.K = e->n_pieces; aa.V = e->d_state_eval ? e->n_values : 1;
-    aa.eval_f16 = (e->flags & TETRIS_ACT_F16) ? 1 : 0; aa.value_f16 = (e->flags & TETRIS_ACT_VALUE_F16) ? 1 : 0;
-    aa.mode = e->mode;
-    aa.seed = e->sample_seed; aa.draw_lo = (uint32_t)e->draw; aa.draw_hi = (uint32_t)(e->draw >> 32);
-    aa.epsilon = e->epsilon;
-    if (e->mode == TETRIS_ACT_RANK) memcpy(aa.table, e->table, sizeof aa.table);
-    aa.rot = e->d_rot; aa.trans = e->d_trans; aa.piece = e->d_piece;
-    aa.eval = e->d_eval; aa.value = e->d_value; aa.entropy = e->d_entropy;
-    return TETRIS_OK;
-}
-
 static dim3 act_grid(const tetris_batch* b) { return dim3((unsigned)((b->N + ACT_BLOCK - 1) / ACT_BLOCK)); }
 
 extern "C" {
@@ -3158,9 +2982,9 @@ int tetris_select_eval_dev(tetris_batch* b, const tetris_act_eval* e) {
     int rc = check_batch(b);
     if (rc) return rc;
     ActArgs aa;
-    if ((rc = act_args(b, e, "tetris_select_eval_dev", aa))) return rc;
+    if ((rc = act_args(shape_of(b), e, "tetris_select_eval_dev", aa))) return rc;
     if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    aa.a = base_args(b, b->N, nullptr);          // (the gate may have extended the RNG tables)
+    aa.a = base_args(b, b->N, nullptr);          // (behind the gate: it may have extended the RNG tables)
     aa.a.steps = 1;
     hipLaunchKernelGGL((k_act_select<256>), act_grid(b), dim3(256), 0, b->stream, aa);
     HIP_TRY(hipGetLastError());
@@ -3171,7 +2995,7 @@ int tetris_step_eval_dev(tetris_batch* b, const tetris_act_eval* e, int ms, int 
                          uint8_t* d_dead) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((rc = step_eval_check(flags))) return rc;
     // two launches: the step fused behind the selection in one kernel took 1.6-2.2 times as long
     if ((rc = tetris_select_eval_dev(b, e))) return rc;
     return tetris_step_rt_dev_ex(b, e->d_rot, e->d_trans, e->d_player, ms, d_done, d_lines, d_dead, flags);
@@ -3182,9 +3006,7 @@ int tetris_step_eval_observe_dev(tetris_batch* b, const tetris_act_eval* e, int 
                                  uint8_t* d_obs_piece) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if (!d_visual || !d_vector || !d_obs_piece) return fail(TETRIS_E_ARG, "visual/vector/piece are NULL");
-    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
-    if (b->P > 2) return fail(TETRIS_E_ARG, "the packed observation is defined for one or two players (own / opponent's board: state_unpack.py:88-137)");
+    if ((rc = step_eval_observe_check(shape_of(b), flags, d_visual, d_vector, d_obs_piece))) return rc;
     if ((rc = tetris_select_eval_dev(b, e))) return rc;
     return tetris_step_rt_observe_dev(b, e->d_rot, e->d_trans, e->d_player, ms, d_done, d_lines, d_dead, flags, d_next_player,
                                       d_visual, d_vector, d_obs_piece);
@@ -3193,41 +3015,6 @@ int tetris_step_eval_observe_dev(tetris_batch* b, const tetris_act_eval* e, int 
 }  // extern "C"
 
 // ---------------------------------------------------------------- trajectory windows (tetris_traj.h)
-// the argument checks, then the kernel arguments
-static int traj_record_args(tetris_batch* b, const tetris_traj* traj, int row, const tetris_act_eval* e, const uint8_t* d_done,
-                            const uint8_t* d_dead, TrajRecordArgs& ra) {
-    if (!traj || !e) return fail(TETRIS_E_ARG, "the window or the argument struct is NULL");
-    if (b->split) return fail(TETRIS_E_ARG, "tetris_traj_record_dev is not available on split batches");
-    if (b->P > 2) return fail(TETRIS_E_ARG, "the reward is defined for one or two players (tetris_environment.py:135-144)");
-    if (!traj->d_action || !traj->d_prob || !traj->d_value || !traj->d_reward || !traj->d_done) return fail(TETRIS_E_ARG, "an array of the window is NULL");
-    if (row < 0 || row >= traj->capacity) return fail(TETRIS_E_ARG, "row outside the window");
-    if (!e->d_rot || !e->d_trans || !e->d_piece || !e->d_eval) return fail(TETRIS_E_ARG, "rot/trans/piece/eval of the acting call are NULL");
-    if (!d_done || !d_dead) return fail(TETRIS_E_ARG, "done/dead are NULL");
-    const size_t n = (size_t)b->N, at = (size_t)row * n;
-    ra.n = b->N; ra.n_players = b->P;
-    ra.rot = e->d_rot; ra.trans = e->d_trans; ra.piece = e->d_piece; ra.player = e->d_player;
-    ra.eval = e->d_eval; ra.value = e->d_value;
-    ra.done = d_done; ra.dead = d_dead;
-    ra.action = traj->d_action + at * 4; ra.prob = traj->d_prob + at;
-    ra.value0 = traj->d_value + at; ra.value1 = traj->d_value + (size_t)traj->capacity * n + at;
-    ra.reward = traj->d_reward + at; ra.done_out = traj->d_done + at;
-    return TETRIS_OK;
-}
-
-static int traj_adv_args(tetris_batch* b, const tetris_traj* traj, int rows, float gamma, float lambda_adv, float lambda_value,
-                         const float* d_boot, float* d_adv, float* d_target, uint8_t* d_closed, TrajAdvArgs& aa) {
-    if (!traj) return fail(TETRIS_E_ARG, "the window is NULL");
-    if (!traj->d_value || !traj->d_reward || !traj->d_done) return fail(TETRIS_E_ARG, "value/reward/done of the window are NULL");
-    if (!d_adv || !d_target) return fail(TETRIS_E_ARG, "adv/target are NULL");
-    if (rows < 1 || rows > traj->capacity) return fail(TETRIS_E_ARG, "rows outside [1, capacity]");
-    aa.n = b->N; aa.rows = rows;
-    aa.plane = (size_t)traj->capacity * (size_t)b->N;
-    aa.value = traj->d_value; aa.reward = traj->d_reward; aa.done = traj->d_done; aa.boot = d_boot;
-    aa.gamma = gamma; aa.lambda_adv = lambda_adv; aa.lambda_value = lambda_value;
-    aa.adv = d_adv; aa.target = d_target; aa.closed = d_closed;
-    return TETRIS_OK;
-}
-
 extern "C" {
 
 int tetris_traj_record_dev(tetris_batch* b, const tetris_traj* traj, int row, const tetris_act_eval* e, const uint8_t* d_done,
@@ -3235,7 +3022,7 @@ int tetris_traj_record_dev(tetris_batch* b, const tetris_traj* traj, int row, co
     int rc = check_batch(b);
     if (rc) return rc;
     TrajRecordArgs ra;
-    if ((rc = traj_record_args(b, traj, row, e, d_done, d_dead, ra))) return rc;
+    if ((rc = traj_record_args(shape_of(b), traj, row, e, d_done, d_dead, ra))) return rc;
     hipLaunchKernelGGL((k_traj_record<256>), dim3((unsigned)((b->N + 255) / 256)), dim3(256), 0, b->stream, ra);
     HIP_TRY(hipGetLastError());
     return TETRIS_OK;
@@ -3246,7 +3033,7 @@ int tetris_traj_advantages_dev(tetris_batch* b, const tetris_traj* traj, int row
     int rc = check_batch(b);
     if (rc) return rc;
     TrajAdvArgs aa;
-    if ((rc = traj_adv_args(b, traj, rows, gamma, lambda_adv, lambda_value, d_boot, d_adv, d_target, d_closed, aa))) return rc;
+    if ((rc = traj_adv_args(shape_of(b), traj, rows, gamma, lambda_adv, lambda_value, d_boot, d_adv, d_target, d_closed, aa))) return rc;
     hipLaunchKernelGGL((k_traj_advantages<TRAJ_THREADS>), dim3((unsigned)((b->N + TRAJ_BLOCK - 1) / TRAJ_BLOCK)), dim3(TRAJ_THREADS), 0,
                        b->stream, aa);
     HIP_TRY(hipGetLastError());
@@ -3256,65 +3043,13 @@ int tetris_traj_advantages_dev(tetris_batch* b, const tetris_traj* traj, int row
 }  // extern "C"
 
 // ---------------------------------------------------------------- a window's states and sample sets (tetris_batch.h)
-// the checks the three calls share: the rules of tetris_traj_record_dev
-static int traj_batch_rules(tetris_batch* b, const char* what) {
-    if (b->split) return fail(TETRIS_E_ARG, (std::string(what) + " is not available on split batches").c_str());
-    if (b->P > 2) return fail(TETRIS_E_ARG, "the packed observation is defined for one or two players (own / opponent's board: state_unpack.py:88-137)");
-    return TETRIS_OK;
-}
-
-static int traj_obs_check(tetris_batch* b, const tetris_traj_obs* obs) {
-    if (!obs || !obs->d_obs) return fail(TETRIS_E_ARG, "the observation records are NULL");
-    if (((uintptr_t)obs->d_obs) & 15u) return fail(TETRIS_E_ARG, "d_obs must be 16-byte aligned");
-    if (obs->capacity < 1 || (unsigned long long)obs->capacity * (unsigned long long)b->N >= (1ull << 31)) return fail(TETRIS_E_ARG, "the window must hold between 1 and 2^31 - 1 entries");
-    return TETRIS_OK;
-}
-
-static int traj_select_args(tetris_batch* b, const uint8_t* d_mask, int rows, int flags, int32_t* d_index, long long cap, int32_t* d_count,
-                            TrajSelectArgs& sa) {
-    int rc = traj_batch_rules(b, "tetris_traj_select_dev");
-    if (rc) return rc;
-    if (!d_mask || !d_index || !d_count) return fail(TETRIS_E_ARG, "mask/index/count are NULL");
-    if (flags & ~TETRIS_SELECT_AUGMENT) return fail(TETRIS_E_ARG, "unknown flag");
-    if (rows < 1 || cap < 0) return fail(TETRIS_E_ARG, "rows < 1 or cap < 0");
-    if ((unsigned long long)rows * (unsigned long long)b->N >= (1ull << 31)) return fail(TETRIS_E_ARG, "rows * N must be below 2^31");
-    sa.mask = d_mask; sa.total = (uint32_t)rows * (uint32_t)b->N; sa.augment = flags & TETRIS_SELECT_AUGMENT;
-    sa.index = d_index; sa.cap = cap; sa.count = d_count;
-    sa.nblocks = (int)((sa.total + SELECT_ELEMS - 1) / SELECT_ELEMS);
-    sa.blocks = nullptr;
-    return TETRIS_OK;
-}
-
-static int traj_batch_args(tetris_batch* b, const tetris_traj* traj, const tetris_traj_obs* obs, const float* d_adv_in, const float* d_target_in,
-                           const int32_t* d_index, int M, const tetris_traj_batch* out, TrajBatchArgs& ba) {
-    int rc = traj_batch_rules(b, "tetris_traj_batch_dev");
-    if (rc) return rc;
-    if (!traj || !out || !d_index) return fail(TETRIS_E_ARG, "the window, the outputs or the index list are NULL");
-    if ((rc = traj_obs_check(b, obs))) return rc;
-    if (!traj->d_action || !traj->d_prob || !traj->d_reward || !traj->d_done) return fail(TETRIS_E_ARG, "an array of the window is NULL");
-    if (traj->capacity != obs->capacity) return fail(TETRIS_E_ARG, "the window and its observation records differ in capacity");
-    if (M < 0) return fail(TETRIS_E_ARG, "M < 0");
-    ba.m = M; ba.n_slots = b->P; ba.H = b->H;
-    ba.total = (uint32_t)traj->capacity * (uint32_t)b->N;
-    ba.index = d_index; ba.obs = obs->d_obs;
-    ba.action = traj->d_action; ba.prob = traj->d_prob; ba.reward = traj->d_reward; ba.done = traj->d_done;
-    ba.adv = d_adv_in; ba.target = d_target_in;
-    ba.visual = out->d_visual; ba.vector = out->d_vector; ba.piece = out->d_piece; ba.action_out = out->d_action;
-    ba.prob_out = out->d_prob; ba.adv_out = out->d_adv; ba.target_out = out->d_target; ba.reward_out = out->d_reward;
-    ba.done_out = out->d_done; ba.valid = out->d_valid;
-    return TETRIS_OK;
-}
-
 extern "C" {
 
 int tetris_traj_observe_dev(tetris_batch* b, const tetris_traj_obs* obs, int row, const uint8_t* d_player) {
     int rc = check_batch(b);
     if (rc) return rc;
-    if ((rc = traj_batch_rules(b, "tetris_traj_observe_dev")) || (rc = traj_obs_check(b, obs))) return rc;
-    if (row < 0 || row >= obs->capacity) return fail(TETRIS_E_ARG, "row outside the window");
     TrajObserveArgs oa;
-    oa.geo = geo_of_batch(b); oa.n = b->N; oa.n_players = b->P; oa.player = d_player;
-    oa.obs = obs->d_obs + (size_t)row * (size_t)b->N * (size_t)b->P * OBS_WORDS;
+    if ((rc = traj_observe_args(shape_of(b), geo_of_batch(b), obs, row, d_player, oa))) return rc;
     b->home_async = true;
     hipLaunchKernelGGL((k_traj_observe<256>), dim3((unsigned)((b->N + 255) / 256), (unsigned)b->P), dim3(256), 0, b->stream, oa);
     HIP_TRY(hipGetLastError());
@@ -3326,7 +3061,7 @@ int tetris_traj_select_dev(tetris_batch* b, const uint8_t* d_mask, int rows, int
     int rc = check_batch(b);
     if (rc) return rc;
     TrajSelectArgs sa;
-    if ((rc = traj_select_args(b, d_mask, rows, flags, d_index, cap, d_count, sa))) return rc;
+    if ((rc = traj_select_args(shape_of(b), d_mask, rows, flags, d_index, cap, d_count, sa))) return rc;
     if ((size_t)sa.nblocks + 1 > b->select_blocks_cap) {
         if (b->d_select_blocks) { HIP_TRY(hipStreamSynchronize(b->stream)); (void)hipFree(b->d_select_blocks); }
         b->d_select_blocks = nullptr; b->select_blocks_cap = 0;
@@ -3348,7 +3083,7 @@ int tetris_traj_batch_dev(tetris_batch* b, const tetris_traj* traj, const tetris
     int rc = check_batch(b);
     if (rc) return rc;
     TrajBatchArgs ba;
-    if ((rc = traj_batch_args(b, traj, obs, d_adv_in, d_target_in, d_index, M, out, ba))) return rc;
+    if ((rc = traj_batch_args(shape_of(b), traj, obs, d_adv_in, d_target_in, d_index, M, out, ba))) return rc;
     if (M == 0) return TETRIS_OK;
     b->home_async = true;
     const size_t lds = ba.visual ? (size_t)BATCH_BLOCK * b->H * NCOL : 0;          // at most 19 840 bytes (31 rows)

@@ -1,0 +1,477 @@
+// The host-side rules of the C ABI (include/tetris_hip.h) that do not depend on where memory lives or how work is launched: the
+// argument checks of the entry points, the filling of the kernels' argument structs, the repacking of host arrays, the mapping
+// of flag words to TETRIS_ERR_* bits, and the thread's last error.  No HIP in here.  tetris_hip.hip (hipcc) and
+// tests/cpu_harness/harness.cpp (g++, the CPU build of the same kernel bodies) both include it, so the CPU suite runs the lines
+// that ship.  Nothing here needs either side's tetris_batch: a HostShape says what the rules ask of a batch.
+//
+// The builders fill everything of an argument struct except its embedded KArgs `a`, or take it as `base`: the caller makes it
+// with its own base_args, the product after its run-ahead gate (the gate may have extended the RNG tables).
+#pragma once
+#include <string.h>
+
+#include <string>
+#include <type_traits>
+
+#include "tetris_kernels.h"
+#include "tetris_plan.h"
+#include "tetris_policy.h"
+#include "tetris_act.h"
+#include "tetris_traj.h"
+#include "tetris_batch.h"
+
+namespace te {
+
+struct HostShape { int N, P, H, nw, split, tint; };
+
+// ---------------------------------------------------------------- the thread's last error (tetris_last_error)
+static thread_local std::string g_err;
+static inline int fail(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
+}
+static inline const char* last_error() { return g_err.c_str(); }
+
+static const char* const PACKED_ONE_OR_TWO = "the packed observation is defined for one or two players (own / opponent's board: state_unpack.py:88-137)";
+static inline int not_on_split(const HostShape& s, const char* what) {
+    if (s.split) return fail(TETRIS_E_ARG, std::string(what) + " is not available on split batches");
+    return TETRIS_OK;
+}
+
+// Runtime value -> template argument.  with_value<LO, HI>(v, f) calls f(std::integral_constant<int, v>) when LO <= v <= HI and
+// returns whether it did; with_flag(v, f) calls f(std::true_type or std::false_type); with_shape<LO, HI>(P, flag, f) calls
+// f(P, FLAG) with both.  f is a generic lambda that names its kernel or body with them (k_game<P(), MODE, TINT()>).  In the
+// product the bounds decide which instantiations a translation unit holds: player counts 1..2 of k_game, k_plan_* and
+// k_policy_step live in tetris_hip.hip, 3..4 in tetris_hip_multi.hip.
+template <int LO, int HI, class F>
+static bool with_value(int v, F&& f) {
+    if constexpr (LO > HI) return false;
+    else if (v == LO) { f(std::integral_constant<int, LO>{}); return true; }
+    else return with_value<LO + 1, HI>(v, f);
+}
+template <class F>
+static void with_flag(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+template <int LO, int HI, class F>
+static bool with_shape(int P, bool flag, F&& f) {
+    return with_value<LO, HI>(P, [&](auto p) { with_flag(flag, [&](auto t) { f(p, t); }); });
+}
+
+// ---------------------------------------------------------------- create, game indices, players
+// tetris_create (flags 0, side 0), tetris_create_ex (side 0), tetris_create_split (n_players 1, flags 0); *out = NULL from the
+// first check of create_impl on
+template <class B>
+static inline int create_check(B** out, int n_games, int n_players, int height, int width, const uint8_t piece_map[7], int split, int side, int flags) {
+    if (flags & ~TETRIS_FLAG_COLOURS) return fail(TETRIS_E_ARG, "unknown flag");
+    if (side != 0 && side != 1) return fail(TETRIS_E_ARG, "side must be 0 or 1");
+    if (!out) return fail(TETRIS_E_ARG, "out is NULL");
+    *out = nullptr;
+    if (n_games < 1) return fail(TETRIS_E_ARG, "n_games must be >= 1");
+    if (n_players < 1 || n_players > TETRIS_MAX_PLAYERS) return fail(TETRIS_E_ARG, "n_players must be 1..4");
+    if (n_players > 2 && split) return fail(TETRIS_E_ARG, "split batches are two-player games");
+    if ((long long)n_games * n_players > (1ll << 23))       // the state allocation stays below 4 GiB (32-bit buffer offsets): 8M boards x 69 words
+        return fail(TETRIS_E_ARG, "n_games * n_players must be <= 2^23");
+    if (height < 4 || height > MAX_H) return fail(TETRIS_E_ARG, "height must be in [4, 31]");
+    if (width != NCOL) return fail(TETRIS_E_ARG, "width must be 10 (the reference hard-codes 10, gamePlay.cpp:202)");
+    if (!piece_map) return fail(TETRIS_E_ARG, "piece_map is NULL");
+    for (int i = 0; i < 7; i++)
+        if (piece_map[i] > 6) return fail(TETRIS_E_ARG, "piece_map entries must be 0..6");
+    return TETRIS_OK;
+}
+
+// n games, the first n (`indexed` false) or those an index list names
+static inline int check_count(const HostShape& s, bool indexed, int n) {
+    if (n < 0 || (!indexed && n > s.N)) return fail(TETRIS_E_ARG, "n out of range");
+    return TETRIS_OK;
+}
+static inline int check_idx(const HostShape& s, const int32_t* idx, int n) {
+    int rc = check_count(s, idx != nullptr, n);
+    if (rc) return rc;
+    for (int i = 0; idx && i < n; i++)
+        if (idx[i] < 0 || idx[i] >= s.N) return fail(TETRIS_E_ARG, "game index out of range");
+    return TETRIS_OK;
+}
+// every player index < P (player NULL: nothing to check)
+static inline int check_players(const HostShape& s, const uint8_t* player, int n) {
+    for (int i = 0; player && i < n; i++)
+        if (player[i] >= s.P) return fail(TETRIS_E_ARG, "player index out of range");
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- key lists in, lines / dead out
+static inline int keys_check(const uint8_t* keys, const uint8_t* lens, int max_keys) {
+    if (!keys || !lens || max_keys < 1) return fail(TETRIS_E_ARG, "keys/lens/max_keys");
+    return TETRIS_OK;
+}
+// host keys [n][P][K] -> hk [K][P][n]; host lens [n][P] -> hl [P][n]
+static inline int keys_pack(const HostShape& s, int n, const uint8_t* keys, const uint8_t* lens, int max_keys, uint8_t* hk, uint8_t* hl) {
+    const int P = s.P;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < P; p++) {
+            const int len = lens[(size_t)i * P + p];
+            if (len > max_keys) return fail(TETRIS_E_ARG, "lens[i][p] > max_keys");
+            hl[(size_t)p * n + i] = (uint8_t)len;
+        }
+    // [n][P][K] -> [K][P][n], blocked over games so that reads stay in L1 and every write run is contiguous
+    // (the naive order writes with a stride of n bytes: 52 ms instead of ~2 ms for 64k two-player games)
+    const int BLK = 512;
+    for (int i0 = 0; i0 < n; i0 += BLK) {
+        const int i1 = i0 + BLK < n ? i0 + BLK : n;
+        for (int k = 0; k < max_keys; k++)
+            for (int p = 0; p < P; p++) {
+                uint8_t* dst = hk + ((size_t)k * P + p) * n;
+                const uint8_t* src = keys + (size_t)p * max_keys + k;
+                for (int i = i0; i < i1; i++) dst[i] = src[(size_t)i * P * max_keys];
+            }
+    }
+    return TETRIS_OK;
+}
+// a step's lines / dead [P][n] -> the caller's [n][P] (each may be NULL)
+static inline void lines_dead_unpack(const HostShape& s, int n, const uint8_t* hl, const uint8_t* hd, uint8_t* lines, uint8_t* dead) {
+    const int P = s.P;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < P; p++) {
+            if (lines) lines[(size_t)i * P + p] = hl[(size_t)p * n + i];
+            if (dead) dead[(size_t)i * P + p] = hd[(size_t)p * n + i];
+        }
+}
+
+// ---------------------------------------------------------------- tetris_get_actions
+static inline int get_actions_check(const HostShape& s, bool indexed, int n, const uint8_t* player, const uint8_t* keys, const uint8_t* lens,
+                                    const int32_t* count, int max_lists, int max_keys) {
+    if (!keys || !lens || !count || max_lists < 1 || max_keys < 1 || max_keys > 255) return fail(TETRIS_E_ARG, "keys/lens/count/max_*");
+    int rc = check_count(s, indexed, n);
+    if (rc) return rc;
+    return check_players(s, player, n);
+}
+// The lists of m games as k_actions left them — hc [m * 40] lists per (rotation, x) start, hl their lengths and hk their keys,
+// PLAN_LANE_LISTS per start — into the caller's keys [m][max_lists][max_keys], lens [m][max_lists] and count [m]: x-major,
+// rotation-minor, as the reference enumerates.  A game with more than max_lists lists: its count is written, then the error.
+static inline int get_actions_gather(int m, const uint8_t* hc, const uint8_t* hl, const uint8_t* hk, int max_lists, int max_keys, uint8_t* keys,
+                                     uint8_t* lens, int32_t* count) {
+    const size_t L = PLAN_LANE_LISTS;
+    for (int i = 0; i < m; i++) {
+        int total = 0;
+        bool over = false;
+        for (int xi = 0; xi < 10; xi++)
+            for (int r = 0; r < 4; r++) {
+                const size_t lane = (size_t)i * 40 + r * 10 + xi;
+                for (int k = 0; k < hc[lane]; k++) {
+                    if (total >= max_lists) { over = true; break; }
+                    const int len = hl[lane * L + k];
+                    lens[(size_t)i * max_lists + total] = (uint8_t)len;
+                    memcpy(keys + ((size_t)i * max_lists + total) * max_keys, hk + (lane * L + k) * max_keys, (size_t)len);
+                    total++;
+                }
+            }
+        count[i] = total;
+        if (over) return fail(TETRIS_E_ARG, "more than max_lists key lists for one game");
+    }
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- steps, resets, observations on the device
+// tetris_step_rt_dev_ex (and tetris_step_rt: flags 0)
+static inline int step_rt_check(const HostShape& s, const uint8_t* rot, const uint8_t* trans, int flags) {
+    if (!rot || !trans) return fail(TETRIS_E_ARG, "rot/trans are NULL");
+    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((flags & TETRIS_STEP_AUTO_RESET) && s.split) return fail(TETRIS_E_ARG, "auto-reset is not available on split batches");
+    return TETRIS_OK;
+}
+static inline int step_rt_observe_check(const HostShape& s, const uint8_t* rot, const uint8_t* trans, int flags, const uint8_t* visual,
+                                        const uint8_t* vector, const uint8_t* piece) {
+    if (!rot || !trans) return fail(TETRIS_E_ARG, "rot/trans are NULL");
+    if (!visual || !vector || !piece) return fail(TETRIS_E_ARG, "visual/vector/piece are NULL");
+    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
+    if (s.split) return fail(TETRIS_E_ARG, "tetris_step_rt_observe_dev is not available on split batches");
+    if (s.P > 2) return fail(TETRIS_E_ARG, PACKED_ONE_OR_TWO);
+    return TETRIS_OK;
+}
+static inline int observe_packed_outputs_check(const uint8_t* visual, const uint8_t* vector, const uint8_t* piece) {
+    if (!visual || !vector || !piece) return fail(TETRIS_E_ARG, "visual/vector/piece are NULL");
+    return TETRIS_OK;
+}
+static inline int observe_packed_check(const HostShape& s, bool indexed, int n, const uint8_t* visual, const uint8_t* vector, const uint8_t* piece) {
+    int rc = observe_packed_outputs_check(visual, vector, piece);
+    if (rc) return rc;
+    if (s.P > 2) return fail(TETRIS_E_ARG, PACKED_ONE_OR_TWO);
+    return check_count(s, indexed, n);
+}
+static inline int enumerate_check(const HostShape& s, bool indexed, int n, const void* valid, const void* land_y, const void* cleared, const void* after,
+                                  int flags) {
+    if (!valid || !land_y || !cleared) return fail(TETRIS_E_ARG, "valid/land_y/cleared are NULL");
+    int rc = check_count(s, indexed, n);
+    if (rc) return rc;
+    if (flags & ~TETRIS_ENUM_PLANAR) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((flags & TETRIS_ENUM_PLANAR) && ((((uintptr_t)valid | (uintptr_t)land_y | (uintptr_t)cleared) & 3u) || ((uintptr_t)after & 15u)))
+        return fail(TETRIS_E_ARG, "planar outputs: valid / land_y / cleared must be 4-byte aligned, after 16-byte aligned");
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- planning (tetris_plan.h)
+static inline int action_lists_check(const HostShape& s, const int32_t* count, const uint8_t* lens, const uint8_t* keys, int max_lists, int max_keys,
+                                     int flags) {
+    int rc = not_on_split(s, "tetris_action_lists_dev");
+    if (rc) return rc;
+    if (!count || !lens || !keys) return fail(TETRIS_E_ARG, "count/lens/keys are NULL");
+    if (max_lists < 1 || max_keys < 1 || max_keys > 254) return fail(TETRIS_E_ARG, "max_lists >= 1, 1 <= max_keys <= 254");
+    if (flags & ~TETRIS_LISTS_KEEP_NULL) return fail(TETRIS_E_ARG, "unknown flag");
+    return TETRIS_OK;
+}
+static inline int simulate_lists_check(const HostShape& s, const int32_t* count, const uint8_t* lens, const uint8_t* keys, int max_lists, int max_keys,
+                                       int flags, const uint32_t* cols) {
+    int rc = not_on_split(s, "tetris_simulate_lists_dev");
+    if (rc) return rc;
+    if (!count || !lens || !keys || !cols) return fail(TETRIS_E_ARG, "count/lens/keys/cols are NULL");
+    if (max_lists < 1 || max_lists > 65535 || max_keys < 1 || max_keys > 255) return fail(TETRIS_E_ARG, "1 <= max_lists <= 65535, 1 <= max_keys <= 255");
+    if (flags & ~TETRIS_SIM_FINALIZE) return fail(TETRIS_E_ARG, "unknown flag");
+    return TETRIS_OK;
+}
+static inline int step_lists_check(const HostShape& s, const int32_t* choice, const int32_t* count, const uint8_t* lens, const uint8_t* keys,
+                                   int max_lists, int max_keys, int flags) {
+    int rc = not_on_split(s, "tetris_step_lists_dev");
+    if (rc) return rc;
+    if (!choice || !count || !lens || !keys) return fail(TETRIS_E_ARG, "choice/count/lens/keys are NULL");
+    if (max_lists < 1 || max_keys < 1 || max_keys > 255) return fail(TETRIS_E_ARG, "max_lists >= 1, 1 <= max_keys <= 255");
+    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
+    return TETRIS_OK;
+}
+static inline PlanArgs plan_args(const KArgs& base, const uint8_t* d_player, const int32_t* d_count, const uint8_t* d_lens, const uint8_t* d_keys,
+                                 int max_lists, int max_keys, int ms) {
+    PlanArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.a = base;
+    pa.a.ms = ms;
+    pa.player = d_player; pa.count = d_count; pa.lens = d_lens; pa.keys = d_keys;
+    pa.max_lists = max_lists; pa.max_keys = max_keys;
+    return pa;
+}
+// tetris_plan_deltas_dev: the checks, then the kernel arguments (a game's lists are the threads of one workgroup of k_plan_deltas)
+constexpr int PLAN_DELTAS_MAX_LISTS = 256;
+static inline int plan_deltas_args(const HostShape& s, const Geo& geo, const uint8_t* d_player, const int32_t* d_count, const uint32_t* d_cols,
+                                   int max_lists, float small_fill, int flags, void* d_deltas, void* d_sums, uint8_t* d_small, PlanDeltaArgs& da) {
+    int rc = not_on_split(s, "tetris_plan_deltas_dev");
+    if (rc) return rc;
+    if (!d_count || !d_cols || !d_deltas) return fail(TETRIS_E_ARG, "count/cols/deltas are NULL");
+    if (max_lists < 1 || max_lists > PLAN_DELTAS_MAX_LISTS) return fail(TETRIS_E_ARG, "1 <= max_lists <= 256");
+    if (flags & ~(TETRIS_DELTAS_F16 | TETRIS_DELTAS_LIST_MAJOR)) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((((uintptr_t)d_deltas) | ((uintptr_t)d_sums)) & 15u) return fail(TETRIS_E_ARG, "deltas / sums must be 16-byte aligned");
+    if (((uintptr_t)d_cols) & 3u) return fail(TETRIS_E_ARG, "cols must be 4-byte aligned");
+    memset(&da, 0, sizeof da);
+    da.geo = geo;
+    da.H = s.H; da.n = s.N;
+    da.player = d_player; da.count = d_count; da.cols = d_cols;
+    da.max_lists = max_lists; da.small_fill = small_fill;
+    da.deltas = d_deltas; da.sums = d_sums; da.small = d_small;
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- heuristic policy (tetris_policy.h)
+// the five calls: not on split batches, `missing` pointers (reported as `missing_text`), flags of the step
+static inline int policy_check(const HostShape& s, const char* what, bool missing, const char* missing_text, int flags = 0) {
+    int rc = not_on_split(s, what);
+    if (rc) return rc;
+    if (missing) return fail(TETRIS_E_ARG, missing_text);
+    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
+    return TETRIS_OK;
+}
+static inline int rollout_policy_check(const HostShape& s, const int16_t* d_weights, int launches, int steps_per_launch) {
+    int rc = policy_check(s, "tetris_rollout_policy", !d_weights, "weights is NULL");
+    if (rc) return rc;
+    if (launches < 1 || steps_per_launch < 1 || steps_per_launch > 256) return fail(TETRIS_E_ARG, "launches must be >= 1, 1 <= steps_per_launch <= 256");
+    return TETRIS_OK;
+}
+static inline PolicyArgs policy_args(const KArgs& base, const uint8_t* d_player, const int16_t* d_weights, int per_game, int ms, int32_t* d_scores) {
+    PolicyArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.a = base;
+    pa.a.ms = ms; pa.a.steps = 1;
+    pa.player = d_player; pa.weights = d_weights; pa.per_game = per_game ? 1 : 0;
+    pa.fixed_player = -1;
+    pa.scores = d_scores;
+    return pa;
+}
+
+// ---------------------------------------------------------------- acting on a network's evaluation (tetris_act.h)
+// the argument checks, then the kernel arguments (all but aa.a)
+static inline int act_args(const HostShape& s, const tetris_act_eval* e, const char* what, ActArgs& aa) {
+    if (!e) return fail(TETRIS_E_ARG, "the argument struct is NULL");
+    int rc = not_on_split(s, what);
+    if (rc) return rc;
+    if (!e->d_action_eval || !e->d_rot || !e->d_trans) return fail(TETRIS_E_ARG, "action_eval/rot/trans are NULL");
+    if (e->n_pieces != 1 && e->n_pieces != 7) return fail(TETRIS_E_ARG, "n_pieces must be 1 or 7");
+    if (e->d_state_eval && e->n_values != 1 && e->n_values != 7 && e->n_values != 8) return fail(TETRIS_E_ARG, "n_values must be 1, 7 or 8");
+    if (e->d_value && !e->d_state_eval) return fail(TETRIS_E_ARG, "value needs state_eval");
+    if (e->mode < TETRIS_ACT_ARGMAX || e->mode > TETRIS_ACT_EPSILON) return fail(TETRIS_E_ARG, "unknown mode");
+    if (e->flags & ~(TETRIS_ACT_F16 | TETRIS_ACT_VALUE_F16)) return fail(TETRIS_E_ARG, "unknown flag");
+    if (e->mode == TETRIS_ACT_RANK && !e->table) return fail(TETRIS_E_ARG, "the RANK mode needs a table");
+    if (e->d_entropy && e->mode != TETRIS_ACT_PI) return fail(TETRIS_E_ARG, "entropy is an output of the PI mode");
+    if (((uintptr_t)e->d_action_eval) & 15u) return fail(TETRIS_E_ARG, "action_eval must be 16-byte aligned");
+    memset(&aa, 0, sizeof aa);
+    aa.player = e->d_player;
+    aa.action_eval = e->d_action_eval; aa.state_eval = e->d_state_eval;
+    aa.K = e->n_pieces; aa.V = e->d_state_eval ? e->n_values : 1;
+    aa.eval_f16 = (e->flags & TETRIS_ACT_F16) ? 1 : 0; aa.value_f16 = (e->flags & TETRIS_ACT_VALUE_F16) ? 1 : 0;
+    aa.mode = e->mode;
+    aa.seed = e->sample_seed; aa.draw_lo = (uint32_t)e->draw; aa.draw_hi = (uint32_t)(e->draw >> 32);
+    aa.epsilon = e->epsilon;
+    if (e->mode == TETRIS_ACT_RANK) memcpy(aa.table, e->table, sizeof aa.table);
+    aa.rot = e->d_rot; aa.trans = e->d_trans; aa.piece = e->d_piece;
+    aa.eval = e->d_eval; aa.value = e->d_value; aa.entropy = e->d_entropy;
+    return TETRIS_OK;
+}
+static inline int step_eval_check(int flags) {
+    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
+    return TETRIS_OK;
+}
+static inline int step_eval_observe_check(const HostShape& s, int flags, const uint8_t* visual, const uint8_t* vector, const uint8_t* piece) {
+    int rc = observe_packed_outputs_check(visual, vector, piece);
+    if (rc || (rc = step_eval_check(flags))) return rc;
+    if (s.P > 2) return fail(TETRIS_E_ARG, PACKED_ONE_OR_TWO);
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- trajectory windows (tetris_traj.h)
+// the argument checks, then the kernel arguments
+static inline int traj_record_args(const HostShape& s, const tetris_traj* traj, int row, const tetris_act_eval* e, const uint8_t* d_done,
+                                   const uint8_t* d_dead, TrajRecordArgs& ra) {
+    if (!traj || !e) return fail(TETRIS_E_ARG, "the window or the argument struct is NULL");
+    int rc = not_on_split(s, "tetris_traj_record_dev");
+    if (rc) return rc;
+    if (s.P > 2) return fail(TETRIS_E_ARG, "the reward is defined for one or two players (tetris_environment.py:135-144)");
+    if (!traj->d_action || !traj->d_prob || !traj->d_value || !traj->d_reward || !traj->d_done) return fail(TETRIS_E_ARG, "an array of the window is NULL");
+    if (row < 0 || row >= traj->capacity) return fail(TETRIS_E_ARG, "row outside the window");
+    if (!e->d_rot || !e->d_trans || !e->d_piece || !e->d_eval) return fail(TETRIS_E_ARG, "rot/trans/piece/eval of the acting call are NULL");
+    if (!d_done || !d_dead) return fail(TETRIS_E_ARG, "done/dead are NULL");
+    const size_t n = (size_t)s.N, at = (size_t)row * n;
+    ra.n = s.N; ra.n_players = s.P;
+    ra.rot = e->d_rot; ra.trans = e->d_trans; ra.piece = e->d_piece; ra.player = e->d_player;
+    ra.eval = e->d_eval; ra.value = e->d_value;
+    ra.done = d_done; ra.dead = d_dead;
+    ra.action = traj->d_action + at * 4; ra.prob = traj->d_prob + at;
+    ra.value0 = traj->d_value + at; ra.value1 = traj->d_value + (size_t)traj->capacity * n + at;
+    ra.reward = traj->d_reward + at; ra.done_out = traj->d_done + at;
+    return TETRIS_OK;
+}
+
+static inline int traj_adv_args(const HostShape& s, const tetris_traj* traj, int rows, float gamma, float lambda_adv, float lambda_value,
+                                const float* d_boot, float* d_adv, float* d_target, uint8_t* d_closed, TrajAdvArgs& aa) {
+    if (!traj) return fail(TETRIS_E_ARG, "the window is NULL");
+    if (!traj->d_value || !traj->d_reward || !traj->d_done) return fail(TETRIS_E_ARG, "value/reward/done of the window are NULL");
+    if (!d_adv || !d_target) return fail(TETRIS_E_ARG, "adv/target are NULL");
+    if (rows < 1 || rows > traj->capacity) return fail(TETRIS_E_ARG, "rows outside [1, capacity]");
+    aa.n = s.N; aa.rows = rows;
+    aa.plane = (size_t)traj->capacity * (size_t)s.N;
+    aa.value = traj->d_value; aa.reward = traj->d_reward; aa.done = traj->d_done; aa.boot = d_boot;
+    aa.gamma = gamma; aa.lambda_adv = lambda_adv; aa.lambda_value = lambda_value;
+    aa.adv = d_adv; aa.target = d_target; aa.closed = d_closed;
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- a window's states and sample sets (tetris_batch.h)
+// the checks the three calls share: the rules of tetris_traj_record_dev
+static inline int traj_batch_rules(const HostShape& s, const char* what) {
+    int rc = not_on_split(s, what);
+    if (rc) return rc;
+    if (s.P > 2) return fail(TETRIS_E_ARG, PACKED_ONE_OR_TWO);
+    return TETRIS_OK;
+}
+
+static inline int traj_obs_check(const HostShape& s, const tetris_traj_obs* obs) {
+    if (!obs || !obs->d_obs) return fail(TETRIS_E_ARG, "the observation records are NULL");
+    if (((uintptr_t)obs->d_obs) & 15u) return fail(TETRIS_E_ARG, "d_obs must be 16-byte aligned");
+    if (obs->capacity < 1 || (unsigned long long)obs->capacity * (unsigned long long)s.N >= (1ull << 31)) return fail(TETRIS_E_ARG, "the window must hold between 1 and 2^31 - 1 entries");
+    return TETRIS_OK;
+}
+
+static inline int traj_observe_args(const HostShape& s, const Geo& geo, const tetris_traj_obs* obs, int row, const uint8_t* d_player, TrajObserveArgs& oa) {
+    int rc;
+    if ((rc = traj_batch_rules(s, "tetris_traj_observe_dev")) || (rc = traj_obs_check(s, obs))) return rc;
+    if (row < 0 || row >= obs->capacity) return fail(TETRIS_E_ARG, "row outside the window");
+    oa.geo = geo; oa.n = s.N; oa.n_players = s.P; oa.player = d_player;
+    oa.obs = obs->d_obs + (size_t)row * (size_t)s.N * (size_t)s.P * OBS_WORDS;
+    return TETRIS_OK;
+}
+
+// (sa.blocks, the counts per workgroup, is the product's own scratch: NULL here)
+static inline int traj_select_args(const HostShape& s, const uint8_t* d_mask, int rows, int flags, int32_t* d_index, long long cap, int32_t* d_count,
+                                   TrajSelectArgs& sa) {
+    int rc = traj_batch_rules(s, "tetris_traj_select_dev");
+    if (rc) return rc;
+    if (!d_mask || !d_index || !d_count) return fail(TETRIS_E_ARG, "mask/index/count are NULL");
+    if (flags & ~TETRIS_SELECT_AUGMENT) return fail(TETRIS_E_ARG, "unknown flag");
+    if (rows < 1 || cap < 0) return fail(TETRIS_E_ARG, "rows < 1 or cap < 0");
+    if ((unsigned long long)rows * (unsigned long long)s.N >= (1ull << 31)) return fail(TETRIS_E_ARG, "rows * N must be below 2^31");
+    sa.mask = d_mask; sa.total = (uint32_t)rows * (uint32_t)s.N; sa.augment = flags & TETRIS_SELECT_AUGMENT;
+    sa.index = d_index; sa.cap = cap; sa.count = d_count;
+    sa.nblocks = (int)((sa.total + SELECT_ELEMS - 1) / SELECT_ELEMS);
+    sa.blocks = nullptr;
+    return TETRIS_OK;
+}
+
+static inline int traj_batch_args(const HostShape& s, const tetris_traj* traj, const tetris_traj_obs* obs, const float* d_adv_in, const float* d_target_in,
+                                  const int32_t* d_index, int M, const tetris_traj_batch* out, TrajBatchArgs& ba) {
+    int rc = traj_batch_rules(s, "tetris_traj_batch_dev");
+    if (rc) return rc;
+    if (!traj || !out || !d_index) return fail(TETRIS_E_ARG, "the window, the outputs or the index list are NULL");
+    if ((rc = traj_obs_check(s, obs))) return rc;
+    if (!traj->d_action || !traj->d_prob || !traj->d_reward || !traj->d_done) return fail(TETRIS_E_ARG, "an array of the window is NULL");
+    if (traj->capacity != obs->capacity) return fail(TETRIS_E_ARG, "the window and its observation records differ in capacity");
+    if (M < 0) return fail(TETRIS_E_ARG, "M < 0");
+    ba.m = M; ba.n_slots = s.P; ba.H = s.H;
+    ba.total = (uint32_t)traj->capacity * (uint32_t)s.N;
+    ba.index = d_index; ba.obs = obs->d_obs;
+    ba.action = traj->d_action; ba.prob = traj->d_prob; ba.reward = traj->d_reward; ba.done = traj->d_done;
+    ba.adv = d_adv_in; ba.target = d_target_in;
+    ba.visual = out->d_visual; ba.vector = out->d_vector; ba.piece = out->d_piece; ba.action_out = out->d_action;
+    ba.prob_out = out->d_prob; ba.adv_out = out->d_adv; ba.target_out = out->d_target; ba.reward_out = out->d_reward;
+    ba.done_out = out->d_done; ba.valid = out->d_valid;
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- rollout, split stages, RNG tables, flag words
+static inline int rollout_launch_check(int launches, int steps_per_launch) {
+    if (launches < 1 || steps_per_launch < 0) return fail(TETRIS_E_ARG, "launches must be >= 1, steps_per_launch >= 0");
+    if (steps_per_launch > 256) return fail(TETRIS_E_ARG, "steps_per_launch must be <= 256");
+    return TETRIS_OK;
+}
+// tetris_split_stage_dev's own rule, then those of both split calls
+static inline int split_step_check(int stage, const uint8_t* d_rot, const uint8_t* d_trans) {
+    if ((stage == 0 || stage == 3) && (!d_rot || !d_trans)) return fail(TETRIS_E_ARG, "stages 0 and 3 need rot/trans (stage 3: of the NEXT step)");
+    return TETRIS_OK;
+}
+static inline int split_stage_check(const HostShape& s, int side, int stage, const uint32_t* const d_words[4], const uint32_t* d_out) {
+    if (!s.split) return fail(TETRIS_E_ARG, "not a split batch (tetris_create_split)");
+    if (stage < 0 || stage > 3) return fail(TETRIS_E_ARG, "stage must be 0, 1, 2 or 3 (= 2 of this step + 0 of the next)");
+    if (stage != 2 && !d_out) return fail(TETRIS_E_ARG, "stages 0, 1 and 3 need d_out");
+    // words a stage reads: stage 1 = both A words (+ player 0's B on side 1); stages 2 and 3 = the opponent's B
+    if (stage > 0 && !d_words) return fail(TETRIS_E_ARG, "stages 1, 2 and 3 need d_words");
+    if (stage == 1 && (!d_words[0] || !d_words[1] || (side == 1 && !d_words[2]))) return fail(TETRIS_E_ARG, "stage 1 needs both A words (and player 0's B words on side 1)");
+    if (stage >= 2 && !d_words[side == 0 ? 3 : 2]) return fail(TETRIS_E_ARG, "stages 2 and 3 need the opponent's B words");
+    return TETRIS_OK;
+}
+static inline int table_limit_check(int chunks) {
+    if (chunks < 0 || chunks > MAX_CHUNKS) return fail(TETRIS_E_ARG, "chunks must be 0..64");
+    return TETRIS_OK;
+}
+// draws of the RNG tables a batch's kernels may use (KArgs::n_draws)
+static inline uint32_t table_draws(int n_chunks, int table_limit) { return (uint32_t)(n_chunks < table_limit ? n_chunks : table_limit) * CHUNK; }
+
+// F_BADARG, read and cleared at the end of a call
+template <class W>
+static inline int take_capacity_error(W* f) {
+    if (!f[F_BADARG]) return TETRIS_OK;
+    f[F_BADARG] = 0;
+    return fail(TETRIS_E_ARG, "output capacity exceeded (max_lists / max_keys too small)");
+}
+// tetris_take_errors: the sticky flag words, read and cleared, as TETRIS_ERR_* bits (W: the product's words are volatile)
+static inline int take_errors_check(const uint32_t* bits) {
+    if (!bits) return fail(TETRIS_E_ARG, "bits is NULL");
+    return TETRIS_OK;
+}
+template <class W>
+static inline uint32_t take_error_bits(W* f) {
+    const uint32_t bits = (f[F_FIFO] ? TETRIS_ERR_FIFO : 0u) | (f[F_EXHAUSTED] ? TETRIS_ERR_STREAM : 0u) | (f[F_LISTS] ? TETRIS_ERR_LISTS : 0u);
+    f[F_FIFO] = 0; f[F_EXHAUSTED] = 0; f[F_LISTS] = 0;
+    return bits;
+}
+
+}  // namespace te

@@ -7,20 +7,13 @@
 //
 // Both mappings of the product run here as they do there: one step per call goes through the [40][N] score array (spread
 // mapping), fused rollout launches through the lane that evaluates its own candidates.
+// The calls' checks and policy_args are the product's (tetris_host.h).
 #include "harness_plan.cpp"
 
-#include "../../drl-tetris_amd/csrc/tetris_policy.h"
-
+// (the [40][N] scores live in a vector of the call)
 static PolicyArgs policy_args(tetris_batch* b, const uint8_t* player, const int16_t* weights, int per_game, int ms, std::vector<int32_t>& scores) {
-    PolicyArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.a = base_args(b, b->N, nullptr);
-    pa.a.ms = ms; pa.a.steps = 1;
-    pa.player = player; pa.weights = weights; pa.per_game = per_game ? 1 : 0;
-    pa.fixed_player = -1;
     scores.assign((size_t)POLICY_CANDIDATES * b->N, 0);
-    pa.scores = scores.data();
-    return pa;
+    return policy_args(base_args(b, b->N, nullptr), player, weights, per_game, ms, scores.data());
 }
 
 template <bool FEAT>
@@ -29,37 +22,25 @@ static void policy_eval_all(tetris_batch* b, const PolicyArgs& pa) {
         for (int i = 0; i < b->N; i++) policy_eval_lane<FEAT>(pa, i, c, SHAPES.s);
 }
 
-template <bool TINT, bool ROLL, bool AUTO, bool FROM_SCORES>
+template <bool ROLL, bool AUTO, bool FROM_SCORES>
 static void policy_step_all(tetris_batch* b, const PolicyArgs& pa) {
-    for (int i = 0; i < b->N; i++) {
-        if (b->P == 1) policy_step_lane<1, TINT, ROLL, AUTO, FROM_SCORES>(pa, i, SHAPES.s, false);
-        else if (b->P == 2) policy_step_lane<2, TINT, ROLL, AUTO, FROM_SCORES>(pa, i, SHAPES.s, false);
-        else if (b->P == 3) policy_step_lane<3, TINT, ROLL, AUTO, FROM_SCORES>(pa, i, SHAPES.s, false);
-        else policy_step_lane<4, TINT, ROLL, AUTO, FROM_SCORES>(pa, i, SHAPES.s, false);
-    }
+    for (int i = 0; i < b->N; i++)
+        with_shape<1, 4>(b->P, b->tint != 0, [&](auto P, auto TINT) { policy_step_lane<P(), TINT(), ROLL, AUTO, FROM_SCORES>(pa, i, SHAPES.s, false); });
 }
 
 // which: 0 step, 1 step with auto-reset, 2 one rollout step from the scores, 3 fused rollout steps (as launch_policy_step)
 static void policy_step_which(tetris_batch* b, int which, const PolicyArgs& pa) {
-    if (b->tint) {
-        if (which == 0) policy_step_all<true, false, false, true>(b, pa);
-        else if (which == 1) policy_step_all<true, false, true, true>(b, pa);
-        else if (which == 2) policy_step_all<true, true, true, true>(b, pa);
-        else policy_step_all<true, true, true, false>(b, pa);
-    } else {
-        if (which == 0) policy_step_all<false, false, false, true>(b, pa);
-        else if (which == 1) policy_step_all<false, false, true, true>(b, pa);
-        else if (which == 2) policy_step_all<false, true, true, true>(b, pa);
-        else policy_step_all<false, true, true, false>(b, pa);
-    }
+    if (which == 0) policy_step_all<false, false, true>(b, pa);
+    else if (which == 1) policy_step_all<false, true, true>(b, pa);
+    else if (which == 2) policy_step_all<true, true, true>(b, pa);
+    else policy_step_all<true, true, false>(b, pa);
 }
 
 extern "C" {
 
 int tetris_rt_features_dev(tetris_batch* b, const uint8_t* player, int16_t* features) {
-    if (b->split) return fail(TETRIS_E_ARG, "tetris_rt_features_dev is not available on split batches");
-    if (!features) return fail(TETRIS_E_ARG, "features is NULL");
-    int rc = finish_call(b); if (rc) return rc;
+    int rc = policy_check(shape_of(b), "tetris_rt_features_dev", !features, "features is NULL");
+    if (rc || (rc = finish_call(b))) return rc;
     std::vector<int32_t> scores;
     PolicyArgs pa = policy_args(b, player, nullptr, 0, 0, scores);
     pa.features = features;
@@ -69,9 +50,8 @@ int tetris_rt_features_dev(tetris_batch* b, const uint8_t* player, int16_t* feat
 
 int tetris_policy_rt_dev(tetris_batch* b, const uint8_t* player, const int16_t* weights, int per_game, uint8_t* rot, uint8_t* trans,
                          int32_t* score) {
-    if (b->split) return fail(TETRIS_E_ARG, "tetris_policy_rt_dev is not available on split batches");
-    if (!weights || !rot || !trans) return fail(TETRIS_E_ARG, "weights/rot/trans are NULL");
-    int rc = finish_call(b); if (rc) return rc;
+    int rc = policy_check(shape_of(b), "tetris_policy_rt_dev", !weights || !rot || !trans, "weights/rot/trans are NULL");
+    if (rc || (rc = finish_call(b))) return rc;
     std::vector<int32_t> scores;
     PolicyArgs pa = policy_args(b, player, weights, per_game, 0, scores);
     pa.rot = rot; pa.trans = trans; pa.score = score;
@@ -82,10 +62,8 @@ int tetris_policy_rt_dev(tetris_batch* b, const uint8_t* player, const int16_t* 
 
 int tetris_step_policy_dev(tetris_batch* b, const uint8_t* player, const int16_t* weights, int per_game, int ms, int flags,
                            uint8_t* done, uint8_t* lines, uint8_t* dead, uint8_t* rot, uint8_t* trans) {
-    if (b->split) return fail(TETRIS_E_ARG, "tetris_step_policy_dev is not available on split batches");
-    if (!weights) return fail(TETRIS_E_ARG, "weights is NULL");
-    if (flags & ~TETRIS_STEP_AUTO_RESET) return fail(TETRIS_E_ARG, "unknown flag");
-    int rc = finish_call(b); if (rc) return rc;
+    int rc = policy_check(shape_of(b), "tetris_step_policy_dev", !weights, "weights is NULL", flags);
+    if (rc || (rc = finish_call(b))) return rc;
     std::vector<int32_t> scores;
     PolicyArgs pa = policy_args(b, player, weights, per_game, ms, scores);
     pa.a.done = done; pa.a.lines = lines; pa.a.dead = dead;
@@ -96,24 +74,22 @@ int tetris_step_policy_dev(tetris_batch* b, const uint8_t* player, const int16_t
 }
 
 int tetris_rollout_game_totals_dev(tetris_batch* b, uint32_t* totals) {
-    if (b->split) return fail(TETRIS_E_ARG, "tetris_rollout_game_totals_dev is not available on split batches");
-    if (!totals) return fail(TETRIS_E_ARG, "totals is NULL");
-    int rc = finish_call(b); if (rc) return rc;
+    int rc = policy_check(shape_of(b), "tetris_rollout_game_totals_dev", !totals, "totals is NULL");
+    if (rc || (rc = finish_call(b))) return rc;
     for (int i = 0; i < b->N; i++) policy_game_totals_lane(geo_of_batch(b), i, totals);
     return TETRIS_OK;
 }
 
 int tetris_rollout_policy(tetris_batch* b, int launches, int steps_per_launch, const int16_t* weights, int per_game, uint64_t first_step,
                           int ms, uint64_t counters[4], float* elapsed_ms) {
-    if (b->split) return fail(TETRIS_E_ARG, "tetris_rollout_policy is not available on split batches");
-    if (!weights) return fail(TETRIS_E_ARG, "weights is NULL");
-    if (launches < 1 || steps_per_launch < 1 || steps_per_launch > 256) return fail(TETRIS_E_ARG, "launches must be >= 1, 1 <= steps_per_launch <= 256");
+    int rc = rollout_policy_check(shape_of(b), weights, launches, steps_per_launch);
+    if (rc) return rc;
     const std::vector<uint32_t> before = game_words(b);
     // the harness looks at the flag words after every launch, so the margin only has to cover one launch
     const uint32_t saved = b->margin;
     b->margin = (uint32_t)(2 * steps_per_launch + 16);
     if (b->margin < saved) b->margin = saved;
-    int rc = finish_call(b);
+    rc = finish_call(b);
     std::vector<int32_t> scores;
     for (int l = 0; l < launches && !rc; l++) {
         PolicyArgs pa = policy_args(b, nullptr, weights, per_game, ms, scores);

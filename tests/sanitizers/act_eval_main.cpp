@@ -14,6 +14,25 @@
 
 static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
 
+// one call with one bad argument per shared rule of this area (drl-tetris_amd/csrc/tetris_host.h): refused, nothing touched
+#define REFUSED(call) \
+    do { if ((call) != TETRIS_E_ARG) { fprintf(stderr, "%s: not refused\n", #call); return 1; } } while (0)
+
+static int refusals(tetris_batch* b, tetris_act_eval e, uint8_t* done, uint8_t* visual, uint8_t* vector, uint8_t* piece) {
+    tetris_act_eval bad = e;
+    bad.n_pieces = 5;
+    REFUSED(tetris_select_eval_dev(b, &bad));                                                              // act_args
+    REFUSED(tetris_step_eval_dev(b, &e, 400, 2, done, nullptr, nullptr));                                  // step_eval_check
+    REFUSED(tetris_step_eval_observe_dev(b, &e, 400, 0, done, nullptr, nullptr, nullptr, nullptr, vector, piece));   // step_eval_observe_check
+    REFUSED(tetris_step_rt_dev_ex(b, nullptr, e.d_trans, nullptr, 400, done, nullptr, nullptr, 0));        // step_rt_check
+    REFUSED(tetris_step_rt_observe_dev(b, e.d_rot, e.d_trans, nullptr, 400, done, nullptr, nullptr, 4, nullptr, visual, vector, piece));   // step_rt_observe_check
+    REFUSED(tetris_observe_packed_dev(b, nullptr, 66, nullptr, visual, vector, piece));                    // observe_packed_check
+    uint32_t cols[4] = {0};
+    int32_t count[1] = {0};
+    REFUSED(tetris_plan_deltas_dev(b, nullptr, count, cols, 257, 1e-3f, 0, cols, nullptr, nullptr));       // plan_deltas_args
+    return 0;
+}
+
 static int run(int P, int K, bool f16) {
     const int N = 65, H = 20;
     const uint8_t map[7] = {0, 1, 2, 3, 4, 5, 6};
@@ -59,6 +78,7 @@ static int run(int P, int K, bool f16) {
         for (int i = 0; i < N && !rc; i++) if (rot[i] > 3 || trans[i] > 9 || piece[i] >= K) { fprintf(stderr, "choice out of range\n"); rc = 1; }
         // a round that ended is reset by hand where the step did not (every other observe step runs without auto-reset)
         if (!rc && !(step & 1)) rc = tetris_reset_dev(b, done.data(), nullptr);
+        if (!rc && step == 23) rc = refusals(b, e, done.data(), visual.data(), vector.data(), obs_piece.data());
     }
     if (rc) fprintf(stderr, "P=%d K=%d f16=%d: rc %d: %s\n", P, K, (int)f16, rc, tetris_last_error());
     tetris_destroy(b);

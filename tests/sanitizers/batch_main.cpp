@@ -14,6 +14,10 @@
 
 static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
 
+// one call with one bad argument per shared rule of this area (drl-tetris_amd/csrc/tetris_host.h): refused, nothing touched
+#define REFUSED(call) \
+    do { if ((call) != TETRIS_E_ARG) { fprintf(stderr, "%s: not refused\n", #call); return 1; } } while (0)
+
 static int run(int P, int H) {
     const int N = 65, T = 5;
     const uint8_t map[7] = {0, 1, 2, 3, 4, 5, 6};
@@ -69,6 +73,13 @@ static int run(int P, int H) {
         tetris_traj_batch only = {};
         only.d_vector = vector.data() + 0;
         if (!rc) rc = tetris_traj_batch_dev(b, &traj, &obs, nullptr, nullptr, index.data(), M, &only);
+    }
+    if (!rc) {
+        int32_t index[1] = {0}, count = 0;
+        tetris_traj_batch none = {};
+        REFUSED(tetris_traj_observe_dev(b, &obs, T, nullptr));                                        // traj_observe_args
+        REFUSED(tetris_traj_select_dev(b, mask.data(), 0, 0, index, 1, &count));                      // traj_select_args
+        REFUSED(tetris_traj_batch_dev(b, &traj, &obs, nullptr, nullptr, index, -1, &none));           // traj_batch_args
     }
     if (rc) fprintf(stderr, "P=%d H=%d: rc %d: %s\n", P, H, rc, tetris_last_error());
     tetris_destroy(b);

@@ -141,8 +141,48 @@ static int queue() {
     return 0;
 }
 
+// one call with one bad argument per shared rule of this area (drl-tetris_amd/csrc/tetris_host.h): refused, nothing touched
+#define REFUSED(call) \
+    do { if ((call) != TETRIS_E_ARG) { fprintf(stderr, "%s: not refused\n", #call); return 1; } } while (0)
+
+static int refusals() {
+    const int P = 2;
+    tetris_batch* b = nullptr;
+    REFUSED(tetris_create(&b, N, P, 3, 10, O_ONLY, 0, nullptr));                                                      // create_check
+    CHECK(tetris_create(&b, N, P, H, 10, O_ONLY, 0, nullptr));
+    const int32_t past[1] = {N};
+    std::vector<uint8_t> keys((size_t)N * P * 4), lens((size_t)N * P, 5), player(N, 2), l_lens((size_t)N * L), l_keys((size_t)N * L * K), out((size_t)N * P * H * 10);
+    std::vector<int32_t> count(N, -7);
+    std::vector<uint32_t> cols(16);
+    const int16_t weights[8] = {76, -71, -18, -51, 0, 0, 0, 0};
+    REFUSED(tetris_reset(b, past, 1, nullptr));                                                                       // check_idx
+    REFUSED(tetris_step_rt(b, keys.data(), keys.data(), player.data(), 400, nullptr, nullptr, nullptr));              // check_players
+    REFUSED(tetris_step_keys(b, nullptr, N, nullptr, lens.data(), 4, 400, nullptr, nullptr, nullptr));                // keys_check
+    REFUSED(tetris_make_actions(b, nullptr, N, keys.data(), lens.data(), 4));                                         // keys_pack
+    REFUSED(tetris_get_actions(b, nullptr, N, nullptr, l_keys.data(), l_lens.data(), count.data(), 0, K));            // get_actions_check
+    REFUSED(tetris_get_actions(b, nullptr, N, nullptr, l_keys.data(), l_lens.data(), count.data(), 2, K));            // get_actions_gather
+    if (count[0] != 2 || count[1] != -7) { fprintf(stderr, "get_actions: count %d, %d\n", count[0], count[1]); return 1; }
+    REFUSED(tetris_observe_packed(b, nullptr, N, nullptr, nullptr, out.data(), out.data()));                          // observe_packed_outputs_check
+    REFUSED(tetris_enumerate_drops(b, nullptr, N + 1, nullptr, out.data(), (int8_t*)out.data(), out.data(), nullptr)); // enumerate_check
+    REFUSED(tetris_action_lists_dev(b, nullptr, L, 255, 0, count.data(), l_lens.data(), l_keys.data()));              // action_lists_check
+    REFUSED(tetris_simulate_lists_dev(b, nullptr, count.data(), l_lens.data(), l_keys.data(), L, K, 400, 2, cols.data(), nullptr, nullptr, nullptr));   // simulate_lists_check
+    REFUSED(tetris_step_lists_dev(b, nullptr, nullptr, count.data(), l_lens.data(), l_keys.data(), L, K, 400, 0, nullptr, nullptr, nullptr));           // step_lists_check
+    REFUSED(tetris_step_policy_dev(b, nullptr, nullptr, 0, 400, 0, nullptr, nullptr, nullptr, nullptr, nullptr));     // policy_check
+    REFUSED(tetris_rollout_policy(b, 1, 0, weights, 0, 0, 400, nullptr, nullptr));                                    // rollout_policy_check
+    REFUSED(tetris_rollout_launch(b, 0, 1, 0xD71, 0, 400, nullptr));                                                  // rollout_launch_check
+    REFUSED(tetris_split_rollout_stage_dev(b, 0, 0xD71, 0, 400, nullptr, cols.data()));                               // split_stage_check
+    REFUSED(tetris_debug_table_limit(b, 65));                                                                         // table_limit_check
+    REFUSED(tetris_take_errors(b, nullptr));                                                                          // take_errors_check
+    tetris_destroy(b);
+    CHECK(tetris_create_split(&b, N, 0, H, 10, O_ONLY, 0, nullptr));
+    REFUSED(tetris_reset_dev(b, nullptr, nullptr));                                                                   // not_on_split
+    REFUSED(tetris_split_stage_dev(b, 0, nullptr, nullptr, nullptr, 400, nullptr, cols.data(), nullptr, nullptr, nullptr));   // split_step_check
+    tetris_destroy(b);
+    return 0;
+}
+
 int main() {
-    if (draws(1) || draws(2) || queue()) return 1;
+    if (draws(1) || draws(2) || queue() || refusals()) return 1;
     printf("capacity: draw limit at the end of the allocation (1 and 2 players, 7 step paths) and the ninth packet: clean\n");
     return 0;
 }

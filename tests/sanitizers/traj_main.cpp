@@ -13,6 +13,10 @@
 
 static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
 
+// one call with one bad argument per shared rule of this area (drl-tetris_amd/csrc/tetris_host.h): refused, nothing touched
+#define REFUSED(call) \
+    do { if ((call) != TETRIS_E_ARG) { fprintf(stderr, "%s: not refused\n", #call); return 1; } } while (0)
+
 static int run(int P) {
     const int N = 65, H = 8, T = 19;
     const uint8_t map[7] = {0, 1, 2, 3, 4, 5, 6};
@@ -53,6 +57,13 @@ static int run(int P) {
     for (int rows : {1, 16, 17, T})
         if (!rc) rc = tetris_traj_advantages_dev(b, &traj, rows, P == 2 ? -0.98f : 0.98f, 0.96f, 0.95f, rows & 1 ? boot.data() : nullptr, adv.data(),
                                                  target.data(), rows == 16 ? nullptr : closed.data());
+    if (!rc) {
+        tetris_act_eval e;
+        memset(&e, 0, sizeof e);
+        e.d_rot = rot.data(); e.d_trans = trans.data(); e.d_piece = piece.data(); e.d_eval = chosen.data();
+        REFUSED(tetris_traj_record_dev(b, &traj, T, &e, done.data(), dead.data()));                                              // traj_record_args
+        REFUSED(tetris_traj_advantages_dev(b, &traj, T + 1, 0.98f, 0.96f, 0.95f, nullptr, adv.data(), target.data(), nullptr));   // traj_adv_args
+    }
     if (!rc && !ended) { fprintf(stderr, "no game ended\n"); rc = 1; }
     if (rc) fprintf(stderr, "P=%d: rc %d: %s\n", P, rc, tetris_last_error());
     tetris_destroy(b);
