@@ -68,6 +68,13 @@ class TrajBatch(C.Structure):
 
 
 SELECT_AUGMENT = 1            # TETRIS_SELECT_AUGMENT
+class Replay(C.Structure):
+    """mirrors `struct tetris_replay` (include/tetris_hip.h)"""
+    _fields_ = [("capacity", C.c_int), ("k_step", C.c_int), ("d_obs", C.c_void_p), ("d_action", C.c_void_p), ("d_prob", C.c_void_p),
+                ("d_adv", C.c_void_p), ("d_target", C.c_void_p), ("d_reward", C.c_void_p), ("d_done", C.c_void_p), ("d_flags", C.c_void_p),
+                ("d_prio", C.c_void_p), ("d_cursor", C.c_void_p)]
+
+
 MIRROR_BIT = 1 << 31          # bit 31 of an index of tetris_traj_batch_dev: the mirrored sample
 
 
@@ -169,6 +176,12 @@ _SIGNATURES = {
     "tetris_traj_observe_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tetris_traj_select_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
     "tetris_traj_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "tetris_replay_add_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_int]),
+    "tetris_replay_sample_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tetris_replay_update_prios_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "tetris_replay_gather_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tetris_observe_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_observe_packed_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_create_split": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -575,6 +588,41 @@ class TetrisBatch:
         self._check(self.lib.tetris_traj_batch_dev(self._h, C.byref(traj) if traj is not None else None,
                                                    C.byref(obs) if obs is not None else None, adv, target, index, int(m),
                                                    C.byref(out) if out is not None else None))
+
+    # -- experience replay (include/tetris_hip.h: tetris_replay_add_dev and the three after it)
+    def replay(self, capacity, k_step, obs, action, prob, adv, target, reward, done, flags, prio, cursor):
+        """The buffer struct of the four calls below over raw DEVICE addresses: obs uint32 [C][S][12] (16-byte aligned), action
+        uint8 [C][4], prob / adv / target / reward float32 [C], done / flags uint8 [C], prio float32 [C - k_step], cursor int32
+        [4]; C = capacity.  The caller zeroes them once."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        r = Replay()
+        r.capacity, r.k_step = int(capacity), int(k_step)
+        r.d_obs, r.d_action, r.d_prob, r.d_adv, r.d_target = val(obs), val(action), val(prob), val(adv), val(target)
+        r.d_reward, r.d_done, r.d_flags, r.d_prio, r.d_cursor = val(reward), val(done), val(flags), val(prio), val(cursor)
+        return r
+
+    def replay_add_dev(self, rp, traj, obs, mask, rows, adv=None, target=None, prio=None, augment=False):
+        """The entries of mask uint8 [rows][N] of the window (traj, obs; adv / target / prio float32 [T][N] or None) into the
+        ring, game-major; augment: every game's run once more, flagged as mirrored.  The cursor moves on the device."""
+        ref = lambda x: C.byref(x) if x is not None else None                     # noqa: E731
+        self._check(self.lib.tetris_replay_add_dev(self._h, ref(rp), ref(traj), ref(obs), adv, target, prio, mask, int(rows),
+                                                   SELECT_AUGMENT if augment else 0))
+
+    def replay_sample_dev(self, rp, m, alpha, beta, seed, draw, index, weight, count, rank=None, key=None):
+        """Rank-based prioritised sampling without replacement: index int32 [m] (-1 past min(m, n)), weight float32 [m], count int32
+        [1]; rank int32 / key float32 [max_size] or None."""
+        self._check(self.lib.tetris_replay_sample_dev(self._h, C.byref(rp) if rp is not None else None, int(m), float(alpha), float(beta),
+                                                      int(seed) & 0xFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF, index, weight, count, rank, key))
+
+    def replay_update_prios_dev(self, rp, index, prio, m):
+        """prio[index[j]] = prio_new[j] for the m indices inside [0, max_size)"""
+        self._check(self.lib.tetris_replay_update_prios_dev(self._h, C.byref(rp) if rp is not None else None, index, prio, int(m)))
+
+    def replay_gather_dev(self, rp, index, m, steps, out):
+        """The k-step views of index int32 [m] into out = traj_batch(...) sized for m * steps samples (sample j * steps + s =
+        ring position index[j] + s; mirrored where the entry's flag says so)."""
+        self._check(self.lib.tetris_replay_gather_dev(self._h, C.byref(rp) if rp is not None else None, index, int(m), int(steps),
+                                                      C.byref(out) if out is not None else None))
 
     def rollout_game_totals_dev(self, totals):
         """The per-game words rollout_totals sums: totals uint32 [4][N] = env-steps, episodes, lines cleared, garbage lines sent."""

@@ -110,12 +110,24 @@ struct TrajBatchArgs {
     float* reward_out;
     uint8_t* done_out;              // [M]
     uint8_t* valid;                 // [M]
+    // tetris_replay_gather_dev (tetris_replay.h): steps > 0 makes sample j the ring position index[j / steps] + j % steps, valid
+    // for an index in [0, limit), mirrored by bit 0 of flags[position]; 0: the window's own index list, as above
+    int steps;
+    uint32_t limit;                 // max_size
+    const uint8_t* flags;           // [C]
 };
 
 struct BatchEntry { uint32_t at; bool valid, mirror; };
 TE_HD BatchEntry batch_entry(const TrajBatchArgs& ba, int j) {
-    const uint32_t v = (uint32_t)ba.index[j];
     BatchEntry en;
+    if (ba.steps > 0) {
+        const uint32_t base = (uint32_t)ba.index[j / ba.steps];
+        en.valid = base < ba.limit;         // (limit + k_step = C = total: base + j % steps stays inside the ring)
+        en.at = en.valid ? base + (uint32_t)(j % ba.steps) : 0u;
+        en.mirror = en.valid && (ba.flags[en.at] & 1u) != 0;
+        return en;
+    }
+    const uint32_t v = (uint32_t)ba.index[j];
     en.at = v & ~BATCH_MIRROR;
     en.mirror = (v & BATCH_MIRROR) != 0;
     en.valid = en.at < ba.total;            // (-1: 0x7FFFFFFF, never below T * N < 2^31)

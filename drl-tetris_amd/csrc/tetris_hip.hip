@@ -1173,6 +1173,12 @@ struct tetris_batch {
     // tetris_traj_select_dev: the counts per workgroup and their scan (grown on demand)
     int32_t* d_select_blocks = nullptr;
     size_t select_blocks_cap = 0;
+    // tetris_replay_add_dev: the entries per game and their scan; tetris_replay_sample_dev: the sort's pairs, ranks and
+    // histograms (both grown on demand)
+    uint32_t* d_replay_offsets = nullptr;
+    size_t replay_offsets_cap = 0;
+    uint32_t* d_replay_sort = nullptr;
+    size_t replay_sort_cap = 0;
 };
 
 static HostShape shape_of(const tetris_batch* b) { return {b->N, b->P, b->H, b->nw, b->split, b->tint}; }
@@ -1522,6 +1528,8 @@ int tetris_destroy(tetris_batch* b) {
     (void)hipFree(b->d_policy_scores);
     (void)hipFree(b->d_words_before);
     (void)hipFree(b->d_select_blocks);
+    (void)hipFree(b->d_replay_offsets);
+    (void)hipFree(b->d_replay_sort);
     for (Stage& s : b->stage) s.release();
     b->recover_idx.release();
     if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -3088,6 +3096,96 @@ int tetris_traj_batch_dev(tetris_batch* b, const tetris_traj* traj, const tetris
     b->home_async = true;
     const size_t lds = ba.visual ? (size_t)BATCH_BLOCK * b->H * NCOL : 0;          // at most 19 840 bytes (31 rows)
     hipLaunchKernelGGL((k_traj_batch<BATCH_BLOCK>), dim3((unsigned)((M + BATCH_BLOCK - 1) / BATCH_BLOCK), (unsigned)b->P), dim3(BATCH_BLOCK), lds,
+                       b->stream, ba);
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- experience replay (tetris_replay.h)
+// a scratch array of the batch, grown on demand: the stream is drained before an array it may still use is freed
+static int grow_scratch(tetris_batch* b, uint32_t*& p, size_t& cap, size_t words) {
+    if (words <= cap) return TETRIS_OK;
+    if (p) { HIP_TRY(hipStreamSynchronize(b->stream)); (void)hipFree(p); }
+    p = nullptr; cap = 0;
+    HIP_TRY(hipMalloc((void**)&p, words * sizeof(uint32_t)));
+    cap = words;
+    return TETRIS_OK;
+}
+
+// four passes from (key, pos) back into (key, pos), through (okey, opos)
+static void launch_sort(tetris_batch* b, SortArgs so, uint32_t* key, uint32_t* pos, uint32_t* okey, uint32_t* opos) {
+    const dim3 tiles((unsigned)so.ntiles), block(SORT_THREADS);
+    for (int pass = 0; pass < 4; pass++) {
+        sort_pass(so, pass, key, pos, okey, opos);
+        hipLaunchKernelGGL((k_sort_histogram<SORT_THREADS>), tiles, block, 0, b->stream, so);
+        hipLaunchKernelGGL((k_sort_scan<SORT_SCAN_SPAN>), dim3(SORT_RADIX), dim3(SORT_SCAN_SPAN), 0, b->stream, so);
+        hipLaunchKernelGGL((k_sort_scatter<SORT_THREADS>), tiles, block, 0, b->stream, so);
+    }
+}
+
+extern "C" {
+
+int tetris_replay_add_dev(tetris_batch* b, const tetris_replay* rp, const tetris_traj* traj, const tetris_traj_obs* obs,
+                          const float* d_adv_in, const float* d_target_in, const float* d_prio_in, const uint8_t* d_mask, int rows,
+                          int flags) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    ReplayAddArgs aa;
+    if ((rc = replay_add_args(shape_of(b), rp, traj, obs, d_adv_in, d_target_in, d_prio_in, d_mask, rows, flags, aa))) return rc;
+    if ((rc = grow_scratch(b, b->d_replay_offsets, b->replay_offsets_cap, (size_t)b->N + 1))) return rc;
+    aa.offsets = b->d_replay_offsets;
+    b->home_async = true;
+    const dim3 grid((unsigned)((b->N + 255) / 256)), block(256);
+    hipLaunchKernelGGL((k_replay_add_count<256>), grid, block, 0, b->stream, aa);
+    hipLaunchKernelGGL((k_replay_add_scan<SELECT_THREADS>), dim3(1), dim3(SELECT_THREADS), 0, b->stream, aa);
+    hipLaunchKernelGGL((k_replay_add_scatter<256>), grid, block, 0, b->stream, aa);
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+int tetris_replay_sample_dev(tetris_batch* b, const tetris_replay* rp, int M, float alpha, float beta, uint32_t seed, uint64_t draw,
+                             int32_t* d_index, float* d_weight, int32_t* d_count, int32_t* d_rank, float* d_key) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    ReplaySampleArgs sa;
+    if ((rc = replay_sample_args(shape_of(b), rp, M, alpha, beta, seed, draw, d_index, d_weight, d_count, d_rank, d_key, sa))) return rc;
+    if ((rc = grow_scratch(b, b->d_replay_sort, b->replay_sort_cap, replay_scratch_words(sa.max_size)))) return rc;
+    const SortArgs so = replay_sample_scratch(sa, b->d_replay_sort);
+    b->home_async = true;
+    const dim3 all((unsigned)((sa.max_size + 255u) / 256u)), block(256);
+    hipLaunchKernelGGL((k_replay_prio_keys<256>), all, block, 0, b->stream, sa);
+    launch_sort(b, so, sa.key_a, sa.pos_a, sa.key_b, sa.pos_b);
+    hipLaunchKernelGGL((k_replay_sample_keys<256>), all, block, 0, b->stream, sa);
+    launch_sort(b, so, sa.key_b, sa.pos_b, sa.key_a, sa.pos_a);
+    hipLaunchKernelGGL((k_replay_emit<256>), dim3((unsigned)((M + 255) / 256 > 0 ? (M + 255) / 256 : 1)), block, 0, b->stream, sa);
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+int tetris_replay_update_prios_dev(tetris_batch* b, const tetris_replay* rp, const int32_t* d_index, const float* d_prio_new, int M) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    ReplayUpdateArgs ua;
+    if ((rc = replay_update_args(shape_of(b), rp, d_index, d_prio_new, M, ua))) return rc;
+    if (M == 0) return TETRIS_OK;
+    b->home_async = true;
+    hipLaunchKernelGGL((k_replay_update<256>), dim3((unsigned)((M + 255) / 256)), dim3(256), 0, b->stream, ua);
+    HIP_TRY(hipGetLastError());
+    return TETRIS_OK;
+}
+
+int tetris_replay_gather_dev(tetris_batch* b, const tetris_replay* rp, const int32_t* d_index, int M, int steps,
+                             const tetris_traj_batch* out) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    TrajBatchArgs ba;
+    if ((rc = replay_gather_args(shape_of(b), rp, d_index, M, steps, out, ba))) return rc;
+    if (ba.m == 0) return TETRIS_OK;
+    b->home_async = true;
+    const size_t lds = ba.visual ? (size_t)BATCH_BLOCK * b->H * NCOL : 0;
+    hipLaunchKernelGGL((k_traj_batch<BATCH_BLOCK>), dim3((unsigned)((ba.m + BATCH_BLOCK - 1) / BATCH_BLOCK), (unsigned)b->P), dim3(BATCH_BLOCK), lds,
                        b->stream, ba);
     HIP_TRY(hipGetLastError());
     return TETRIS_OK;

@@ -18,6 +18,7 @@
 #include "tetris_act.h"
 #include "tetris_traj.h"
 #include "tetris_batch.h"
+#include "tetris_replay.h"
 
 namespace te {
 
@@ -424,6 +425,115 @@ static inline int traj_batch_args(const HostShape& s, const tetris_traj* traj, c
     ba.visual = out->d_visual; ba.vector = out->d_vector; ba.piece = out->d_piece; ba.action_out = out->d_action;
     ba.prob_out = out->d_prob; ba.adv_out = out->d_adv; ba.target_out = out->d_target; ba.reward_out = out->d_reward;
     ba.done_out = out->d_done; ba.valid = out->d_valid;
+    ba.steps = 0; ba.limit = 0u; ba.flags = nullptr;
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- experience replay (tetris_replay.h)
+// the buffer's rules, shared by the four calls; `arrays`: the call touches the entries' arrays, not the priorities alone
+static inline int replay_ring(const HostShape& s, const tetris_replay* rp, const char* what, bool arrays, ReplayRing& r) {
+    int rc = traj_batch_rules(s, what);
+    if (rc) return rc;
+    if (!rp) return fail(TETRIS_E_ARG, "the replay buffer is NULL");
+    if (rp->k_step < 0) return fail(TETRIS_E_ARG, "k_step must be >= 0");
+    const long long max_size = (long long)rp->capacity - rp->k_step;
+    if (max_size < 1 || max_size > REPLAY_MAX_SIZE) return fail(TETRIS_E_ARG, "max_size = capacity - k_step must be in [1, 2^24]");
+    if (!rp->d_prio || !rp->d_cursor) return fail(TETRIS_E_ARG, "prio/cursor of the replay buffer are NULL");
+    if (arrays) {
+        if (!rp->d_obs || !rp->d_action || !rp->d_prob || !rp->d_adv || !rp->d_target || !rp->d_reward || !rp->d_done || !rp->d_flags)
+            return fail(TETRIS_E_ARG, "an array of the replay buffer is NULL");
+        if (((uintptr_t)rp->d_obs) & 15u) return fail(TETRIS_E_ARG, "d_obs of the replay buffer must be 16-byte aligned");
+    }
+    r.capacity = rp->capacity; r.k_step = rp->k_step; r.max_size = (int)max_size; r.n_slots = s.P;
+    r.obs = rp->d_obs; r.action = rp->d_action; r.prob = rp->d_prob; r.adv = rp->d_adv; r.target = rp->d_target; r.reward = rp->d_reward;
+    r.done = rp->d_done; r.flags = rp->d_flags; r.prio = rp->d_prio; r.cursor = rp->d_cursor;
+    return TETRIS_OK;
+}
+
+// (aa.offsets, the entries per game, is the product's own scratch: NULL here)
+static inline int replay_add_args(const HostShape& s, const tetris_replay* rp, const tetris_traj* traj, const tetris_traj_obs* obs, const float* d_adv_in,
+                                  const float* d_target_in, const float* d_prio_in, const uint8_t* d_mask, int rows, int flags, ReplayAddArgs& aa) {
+    int rc = replay_ring(s, rp, "tetris_replay_add_dev", true, aa.rp);
+    if (rc) return rc;
+    if (!traj || !d_mask) return fail(TETRIS_E_ARG, "the window or the mask are NULL");
+    if ((rc = traj_obs_check(s, obs))) return rc;
+    if (!traj->d_action || !traj->d_prob || !traj->d_reward || !traj->d_done) return fail(TETRIS_E_ARG, "an array of the window is NULL");
+    if (traj->capacity != obs->capacity) return fail(TETRIS_E_ARG, "the window and its observation records differ in capacity");
+    if (flags & ~TETRIS_SELECT_AUGMENT) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((unsigned long long)(rows < 0 ? 0 : rows) * (unsigned long long)s.N >= (1ull << 31)) return fail(TETRIS_E_ARG, "rows * N must be below 2^31");
+    if (rows < 1 || rows > traj->capacity) return fail(TETRIS_E_ARG, "rows outside [1, capacity]");
+    aa.n = s.N; aa.rows = rows; aa.augment = flags & TETRIS_SELECT_AUGMENT;
+    aa.mask = d_mask; aa.obs = obs->d_obs; aa.action = traj->d_action; aa.prob = traj->d_prob; aa.reward = traj->d_reward; aa.done = traj->d_done;
+    aa.adv = d_adv_in; aa.target = d_target_in; aa.prio = d_prio_in;
+    aa.offsets = nullptr;
+    return TETRIS_OK;
+}
+
+// words of the sort's scratch for max_size entries: two (key, position) pairs, the ranks, the histograms and the digits' totals
+static inline int sort_tiles(uint32_t max_size) { return (int)((max_size + SORT_TILE - 1) / SORT_TILE); }
+static inline size_t replay_scratch_words(uint32_t max_size) { return 5 * (size_t)max_size + (size_t)SORT_RADIX * sort_tiles(max_size) + SORT_RADIX; }
+// (scratch: replay_scratch_words(max_size) words of the caller's own; sorts: the two sorts' arguments, pass and in / out set per pass)
+static inline int replay_sample_args(const HostShape& s, const tetris_replay* rp, int M, float alpha, float beta, uint32_t seed, uint64_t draw,
+                                     int32_t* d_index, float* d_weight, int32_t* d_count, int32_t* d_rank, float* d_key, ReplaySampleArgs& sa) {
+    ReplayRing r;
+    int rc = replay_ring(s, rp, "tetris_replay_sample_dev", false, r);
+    if (rc) return rc;
+    if (!d_index || !d_weight || !d_count) return fail(TETRIS_E_ARG, "index/weight/count are NULL");
+    if (M < 0) return fail(TETRIS_E_ARG, "M < 0");
+    memset(&sa, 0, sizeof sa);
+    sa.max_size = (uint32_t)r.max_size; sa.m = M; sa.prio = r.prio; sa.cursor = r.cursor;
+    sa.alpha = alpha; sa.alpha_beta = alpha * beta;
+    sa.seed = seed; sa.draw_lo = (uint32_t)draw; sa.draw_hi = (uint32_t)(draw >> 32);
+    sa.index = d_index; sa.weight = d_weight; sa.count = d_count; sa.rank_out = d_rank; sa.key_out = d_key;
+    return TETRIS_OK;
+}
+// the scratch's parts: pair a, pair b, the ranks; -> the sort's arguments over the rest (pass, in and out are set per pass)
+static inline SortArgs replay_sample_scratch(ReplaySampleArgs& sa, uint32_t* scratch) {
+    const size_t m = sa.max_size;
+    sa.key_a = scratch; sa.pos_a = scratch + m; sa.key_b = scratch + 2 * m; sa.pos_b = scratch + 3 * m;
+    sa.rank = reinterpret_cast<int32_t*>(scratch + 4 * m);
+    SortArgs so;
+    memset(&so, 0, sizeof so);
+    so.total = sa.max_size; so.ntiles = sort_tiles(sa.max_size);
+    so.hist = scratch + 5 * m; so.totals = so.hist + (size_t)SORT_RADIX * so.ntiles;
+    return so;
+}
+// pass p of a sort that starts and, after four passes, ends in (key, pos); (okey, opos): the other pair
+static inline void sort_pass(SortArgs& so, int pass, uint32_t* key, uint32_t* pos, uint32_t* okey, uint32_t* opos) {
+    so.pass = pass;
+    so.key_in = (pass & 1) ? okey : key; so.pos_in = (pass & 1) ? opos : pos;
+    so.key_out = (pass & 1) ? key : okey; so.pos_out = (pass & 1) ? pos : opos;
+}
+
+static inline int replay_update_args(const HostShape& s, const tetris_replay* rp, const int32_t* d_index, const float* d_prio_new, int M, ReplayUpdateArgs& ua) {
+    ReplayRing r;
+    int rc = replay_ring(s, rp, "tetris_replay_update_prios_dev", false, r);
+    if (rc) return rc;
+    if (!d_index || !d_prio_new) return fail(TETRIS_E_ARG, "index/prio are NULL");
+    if (M < 0) return fail(TETRIS_E_ARG, "M < 0");
+    ua.prio = r.prio; ua.max_size = (uint32_t)r.max_size; ua.index = d_index; ua.value = d_prio_new; ua.m = M;
+    return TETRIS_OK;
+}
+
+// the gather is tetris_traj_batch_dev's kernel over the ring: ba.m = M * steps samples
+static inline int replay_gather_args(const HostShape& s, const tetris_replay* rp, const int32_t* d_index, int M, int steps, const tetris_traj_batch* out,
+                                     TrajBatchArgs& ba) {
+    ReplayRing r;
+    int rc = replay_ring(s, rp, "tetris_replay_gather_dev", true, r);
+    if (rc) return rc;
+    if (!d_index || !out) return fail(TETRIS_E_ARG, "the index list or the outputs are NULL");
+    if (M < 0) return fail(TETRIS_E_ARG, "M < 0");
+    if (steps < 1 || steps > r.k_step + 1) return fail(TETRIS_E_ARG, "steps outside [1, k_step + 1]");
+    if ((unsigned long long)M * (unsigned long long)steps >= (1ull << 31)) return fail(TETRIS_E_ARG, "M * steps must be below 2^31");
+    ba.m = M * steps; ba.n_slots = s.P; ba.H = s.H;
+    ba.total = (uint32_t)r.capacity;
+    ba.index = d_index; ba.obs = r.obs;
+    ba.action = r.action; ba.prob = r.prob; ba.reward = r.reward; ba.done = r.done;
+    ba.adv = r.adv; ba.target = r.target;
+    ba.visual = out->d_visual; ba.vector = out->d_vector; ba.piece = out->d_piece; ba.action_out = out->d_action;
+    ba.prob_out = out->d_prob; ba.adv_out = out->d_adv; ba.target_out = out->d_target; ba.reward_out = out->d_reward;
+    ba.done_out = out->d_done; ba.valid = out->d_valid;
+    ba.steps = steps; ba.limit = (uint32_t)r.max_size; ba.flags = r.flags;
     return TETRIS_OK;
 }
 

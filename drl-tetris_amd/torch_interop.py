@@ -294,6 +294,13 @@ class TorchEnv:
         also holds the packed observation records (observe / select / batch)."""
         return Trajectory(self, capacity, states)
 
+    # ---- experience replay (include/tetris_hip.h: tetris_replay_add_dev and the three after it): the buffer of
+    # sventon_agent_dqn_trainer.do_training (agents/sventon_agent/sventon_agent_dqn_trainer.py:30-100)
+    def replay(self, capacity, k_step=1, seed=0):
+        """A prioritised replay of `capacity` entries (the reference's max_size argument) with k-step views: -> Replay (device
+        tensors, allocated once).  seed: the key of the sampling draws."""
+        return Replay(self, capacity, k_step, seed)
+
 
 class Trajectory:
     """A trajectory window of a TorchEnv: T = capacity rows of n games, time-major device tensors
@@ -394,3 +401,97 @@ class Trajectory:
         t, out = self._batches[M]
         env.b.traj_batch_dev(self._traj, self._obs, env._ptr(index), M, out, adv=env._ptr(self.adv), target=env._ptr(self.target))
         return t
+
+
+class Replay:
+    """The prioritised experience replay of a TorchEnv (agents/agent_utils/experience_replay.py in its rank mode), on the device:
+    capacity C entries of which max_size = C - k_step take samples, as device tensors
+        obs int32 [C, S, 12] (the packed observation record), action uint8 [C, 4], prob / adv / target / reward float32 [C],
+        done / flags uint8 [C] (flags bit 0: the mirrored sample), prio float32 [max_size], cursor int32 [4] (current_idx,
+        current_size, samples offered so far, entries dropped).
+    add(tr, rows) takes the finished entries of a Trajectory(states=True) window, sample(M, alpha, beta, draw) the reference's
+    get_random_sample, gather(index, steps) the k-step views as the trainer's arrays, update_prios(index, prio) the new
+    priorities.  Nothing waits for the GPU but len() and dropped(), which read the cursor."""
+
+    def __init__(self, env, capacity, k_step=1, seed=0):
+        torch = env.torch
+        C_, k = int(capacity), int(k_step)
+        assert k >= 0 and 1 <= C_ - k <= 1 << 24, "k_step >= 0 and 1 <= capacity - k_step <= 2^24"
+        assert env.b.n_players <= 2, "the packed observation is defined for one or two players"
+        self.env, self.capacity, self.k_step, self.max_size, self.seed = env, C_, k, C_ - k, int(seed)
+        u8, f32, i32 = (dict(dtype=d, device=env.dev) for d in (torch.uint8, torch.float32, torch.int32))
+        self.obs, self.action = torch.zeros(C_, env.b.n_players, 12, **i32), torch.zeros(C_, 4, **u8)
+        self.prob, self.adv, self.target, self.reward = (torch.zeros(C_, **f32) for _ in range(4))
+        self.done, self.flags = torch.zeros(C_, **u8), torch.zeros(C_, **u8)
+        self.prio, self.cursor = torch.zeros(self.max_size, **f32), torch.zeros(4, **i32)
+        self.count = torch.zeros(1, **i32)
+        p = env._ptr
+        self._rp = env.b.replay(C_, k, p(self.obs), p(self.action), p(self.prob), p(self.adv), p(self.target), p(self.reward), p(self.done),
+                                p(self.flags), p(self.prio), p(self.cursor))
+        self._samples, self._batches = {}, {}
+
+    def add(self, tr, rows, mask=None, augment=True, prio=None):
+        """The entries of mask uint8 [rows, n] (None: closed of the window's last advantages call) of the window tr, game-major,
+        with its adv / target; augment: every game's run once more as the mirrored samples; prio float32 [rows, n] (None: 2.0,
+        the reference's "very large prio")."""
+        env, torch = self.env, self.env.torch
+        assert hasattr(tr, "obs"), "the window was made without states=True"
+        n = env.b.n_games
+        if mask is None:
+            assert 1 <= rows <= tr._rows, "no advantages call covers these rows"
+            mask = tr.closed
+        assert mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.numel() >= rows * n
+        if prio is not None:
+            assert prio.dtype == torch.float32 and prio.is_cuda and prio.is_contiguous() and prio.numel() >= rows * n
+        p = env._ptr
+        env.b.replay_add_dev(self._rp, tr._traj, tr._obs, p(mask), rows, adv=p(tr.adv), target=p(tr.target), prio=p(prio), augment=augment)
+
+    def sample(self, M, alpha, beta, draw=0, rank=False):
+        """get_random_sample(M, alpha, beta) in rank mode: -> (index int32 [M], weight float32 [M], count int32 [1]) device tensors,
+        reused per M: the min(M, len) entries drawn without replacement, -1 / 0 past them.  The draw is keyed by (seed, position,
+        draw): pass the update's number as `draw`.  rank=True: also self.rank int32 [max_size] and self.key float32 [max_size]."""
+        env, torch = self.env, self.env.torch
+        M = int(M)
+        if M not in self._samples:
+            self._samples[M] = (torch.zeros(max(M, 1), dtype=torch.int32, device=env.dev), torch.zeros(max(M, 1), dtype=torch.float32, device=env.dev))
+        index, weight = self._samples[M]
+        if rank and getattr(self, "rank", None) is None:
+            self.rank = torch.zeros(self.max_size, dtype=torch.int32, device=env.dev)
+            self.key = torch.zeros(self.max_size, dtype=torch.float32, device=env.dev)
+        p = env._ptr
+        env.b.replay_sample_dev(self._rp, M, alpha, beta, self.seed, draw, p(index), p(weight), p(self.count),
+                                rank=p(self.rank) if rank else None, key=p(self.key) if rank else None)
+        return index[:M], weight[:M], self.count
+
+    def gather(self, index, steps=1):
+        """The k-step views of index (int32 device tensor [M]; -1: none) -> TrajectoryBatch(visual [S, M, steps, H, 10], vector [S,
+        M, steps, 12], piece [S, M, steps], action [M, steps, 3], prob, adv, target, reward, done, valid [M, steps]) device tensors,
+        reused per (M, steps); 1 <= steps <= k_step + 1."""
+        from collections import namedtuple
+        env, torch = self.env, self.env.torch
+        assert index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.dim() == 1
+        M, K, S, H = index.numel(), int(steps), env.b.n_players, env.b.height
+        assert 1 <= K <= self.k_step + 1, "steps outside [1, k_step + 1]"
+        if (M, K) not in self._batches:
+            u8, f32 = dict(dtype=torch.uint8, device=env.dev), dict(dtype=torch.float32, device=env.dev)
+            kind = namedtuple("TrajectoryBatch", "visual vector piece action prob adv target reward done valid")
+            t = kind(torch.zeros(S, M, K, H, 10, **u8), torch.zeros(S, M, K, 12, **u8), torch.zeros(S, M, K, **u8), torch.zeros(M, K, 3, **u8),
+                     torch.zeros(M, K, **f32), torch.zeros(M, K, **f32), torch.zeros(M, K, **f32), torch.zeros(M, K, **f32), torch.zeros(M, K, **u8),
+                     torch.zeros(M, K, **u8))
+            self._batches[(M, K)] = (t, env.b.traj_batch(*[env._ptr(x) for x in t]))
+        t, out = self._batches[(M, K)]
+        env.b.replay_gather_dev(self._rp, env._ptr(index), M, K, out)
+        return t
+
+    def update_prios(self, index, prio):
+        """prio[index[j]] = prio[j] (update_prios); -1 entries are skipped"""
+        torch = self.env.torch
+        assert index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.dim() == 1
+        assert prio.dtype == torch.float32 and prio.is_cuda and prio.is_contiguous() and prio.numel() == index.numel()
+        self.env.b.replay_update_prios_dev(self._rp, self.env._ptr(index), self.env._ptr(prio), index.numel())
+
+    def __len__(self):
+        return int(self.cursor[1].item())
+
+    def dropped(self):
+        return int(self.cursor[3].item())

@@ -556,6 +556,93 @@ int tetris_traj_select_dev(tetris_batch *b, const uint8_t *d_mask, int rows, int
 int tetris_traj_batch_dev(tetris_batch *b, const tetris_traj *traj, const tetris_traj_obs *obs, const float *d_adv_in,
                           const float *d_target_in, const int32_t *d_index, int M, const tetris_traj_batch *out);
 
+/* ---- experience replay: a prioritised ring on the device — add, rank sample, update_prios, k-step gather -----------------
+ * replaces: agents/agent_utils/experience_replay.py as sventon_agent_dqn_trainer.do_training drives it
+ * (agents/sventon_agent/sventon_agent_dqn_trainer.py:30-100) in its 'rank' sample mode (the only one the reference can run:
+ * experience_replay.py:52 reads an undefined name in the other).  Four calls; device pointers, asynchronous on the batch's
+ * stream; one and two players; the batch's games are neither read nor written.  TETRIS_E_ARG for three or four players, split
+ * batches and NULLs, as for the trajectory windows.
+ *
+ * THE BUFFER (struct tetris_replay, caller-owned device memory): capacity C is the reference's max_size argument (_max_size),
+ * k_step >= 0, max_size = C - k_step with 1 <= max_size <= 2^24 (a rank stays exact as a float32).  Positions are handed out
+ * below max_size only; rows max_size .. C-1 are never written (experience_replay.py:17-18, 26-30), so they hold what the
+ * caller put there — zeros — and a k-step view near the end reads them, as the reference's does.
+ *   d_obs uint32 [C][S][12] the packed observation record of tetris_traj_obs, 16-byte aligned; d_action uint8 [C][4];
+ *   d_prob, d_adv, d_target, d_reward float32 [C]; d_done uint8 [C]; d_flags uint8 [C] (bit 0: the mirrored sample);
+ *   d_prio float32 [max_size]; d_cursor int32 [4] = current_idx, current_size, samples offered so far modulo 2^32, entries
+ *   dropped.  The cursor lives on the device: no call reads it on the host.  The caller zeroes everything once.
+ *
+ * ADD (replaces: add_samples / add_indices, experience_replay.py:108-138, fed with process_trajectory(augment=...)'s output,
+ * trajectory.py:56-109): the entries of d_mask uint8 [rows][N] (typically d_closed; any non-zero byte counts) of the window
+ * (traj, obs, d_adv_in, d_target_in float32 [T][N] or NULL: zeros) go in GAME-MAJOR: game 0's entries in ascending t, then game
+ * 1's, ...; with TETRIS_SELECT_AUGMENT each game's run is followed directly by the same run with d_flags = 1 (augment_data's
+ * [x, x2] per trajectory, trajectory.py:102-106; the record and the action are stored unmirrored, the gather makes the
+ * image).  Game-major because k_step_view (fcns.py:4-9) takes the next row for a sample's successor; a run selected by `closed`
+ * ends in a done, where compute_targets cuts.  A mask whose runs do not end in a done gives k-step views that run on into the
+ * next game's entries, as the reference's views across two trajectories do.  d_prio[pos] = d_prio_in ? d_prio_in[t][n] : 2.0f
+ * (the reference's "very large prio", trajectory.py:82); d_flags = 0 for the plain copy.  With k entries in all the
+ * reference's rule is applied once: if current_idx + k > max_size then current_size = current_idx, current_idx = 0; positions
+ * [current_idx, current_idx + k) are written; current_idx += k; current_size = max(current_size, current_idx); d_cursor[2]
+ * += k.  Where k > max_size (the reference raises) the first max_size entries are written, current_idx = max_size and
+ * d_cursor[3] += k - max_size.  Three launches, none waits for another workgroup.
+ * TETRIS_E_ARG: a NULL rp, traj, obs, d_mask or array of either; the rules of the buffer above; capacities of traj and obs
+ * that differ; rows outside [1, T]; rows N >= 2^31; an unknown flag.
+ *
+ * SAMPLE (replaces: get_random_sample in rank mode, experience_replay.py:42-74).  With n = d_cursor[1], read on the device:
+ *   rank_i = 1 + n - ordinal_rank(d_prio[i]), i < n  (1 + n - scipy.stats.rankdata(.., 'ordinal'): the highest priority has
+ *            rank 1, among equal priorities the later position the smaller rank; -0.0 equals +0.0; NaN priorities rank
+ *            somewhere, unspecified, and no access leaves the arrays whatever the bits)
+ *   w_i    = powf((float)rank_i, -alpha)
+ *   u_i    = ((philox4x32_10(key (seed, 0), counter (i, draw low, draw high, 0))[0] >> 8) + 1) * 2^-24, in (0, 1], exact
+ *   key_i  = (-logf(u_i)) / w_i, the division correctly rounded, nothing contracted; a -0.0 key sorts as 0.0
+ * The min(M, n) entries of smallest key go to d_index int32 [M] by ascending key, ties by ascending position; entries past
+ * that count are -1 with weight 0; d_count[0] = min(M, n).  This is weighted sampling without replacement by exponential keys
+ * (Efraimidis & Spirakis 2006): the distribution of successive draws without replacement with probabilities proportional to
+ * w, which is what np.random.choice(replace=False, p=p) draws from; the reference's sequence itself hangs on numpy's global
+ * generator.  d_weight[j] = powf((float)rank / (float)n, alpha * beta) with the product rounded once in float32: the
+ * reference's is_weights, since ((n p)^-beta) / max(..) = (p_min / p)^beta = (rank / n)^(alpha beta) needs no normalising sum
+ * (and neither do the keys: they are invariant under scaling of p).  d_rank int32 [max_size] and d_key float32 [max_size] are
+ * optional outputs (NULL to skip), entries i < n: the reference's `rank` and what the selection was made on.
+ * TETRIS_E_ARG: NULL rp, d_prio, d_cursor, d_index, d_weight or d_count; the rules of the buffer; M < 0.
+ *
+ * UPDATE_PRIOS (replaces: update_prios, experience_replay.py:140-141): d_prio[d_index[j]] = d_prio_new[j], j < M, for indices
+ * in [0, max_size); others, -1 among them, are skipped.  The indices of one sample call are distinct; with repeats which
+ * value lands is unspecified (the reference keeps the last).
+ * TETRIS_E_ARG: NULL rp, d_prio, d_index or d_prio_new; the rules of the buffer; M < 0.
+ *
+ * GATHER (replaces: retrieve_samples_by_idx on the k-step views, experience_replay.py:143-150, fcns.py:4-9, with state_fcn
+ * and the mirror of augment_data): 1 <= steps <= k_step + 1; out is a tetris_traj_batch sized for M * steps samples.  Sample
+ * j * steps + s is ring position d_index[j] + s: the bytes tetris_traj_batch_dev gives for that record and row entry, mirrored
+ * (columns reversed, piece_swap, the `next` quirk, t -> 9 - t) when bit 0 of d_flags there is set.  A d_index[j] outside
+ * [0, max_size) gives zeros and d_valid = 0 for all of its `steps` samples.  So d_visual is [S][M][steps][H][10], the
+ * trainer's visual_states_k; its [:, :, 0] is un_k_step(x, 0).
+ * TETRIS_E_ARG: NULL rp, array of it, d_index or out; the rules of the buffer; M < 0; steps outside [1, k_step + 1];
+ * M * steps >= 2^31.                                                                                                       */
+typedef struct tetris_replay {
+    int       capacity;    /* C */
+    int       k_step;
+    uint32_t *d_obs;       /* [C][S][12], 16-byte aligned */
+    uint8_t  *d_action;    /* [C][4] */
+    float    *d_prob;      /* [C] */
+    float    *d_adv;       /* [C] */
+    float    *d_target;    /* [C] */
+    float    *d_reward;    /* [C] */
+    uint8_t  *d_done;      /* [C] */
+    uint8_t  *d_flags;     /* [C]  bit 0: the mirrored sample */
+    float    *d_prio;      /* [C - k_step] */
+    int32_t  *d_cursor;    /* [4] */
+} tetris_replay;
+int tetris_replay_add_dev(tetris_batch *b, const tetris_replay *rp, const tetris_traj *traj, const tetris_traj_obs *obs,
+                          const float *d_adv_in, const float *d_target_in, const float *d_prio_in, const uint8_t *d_mask,
+                          int rows, int flags);
+int tetris_replay_sample_dev(tetris_batch *b, const tetris_replay *rp, int M, float alpha, float beta, uint32_t seed,
+                             uint64_t draw, int32_t *d_index, float *d_weight, int32_t *d_count, int32_t *d_rank,
+                             float *d_key);
+int tetris_replay_update_prios_dev(tetris_batch *b, const tetris_replay *rp, const int32_t *d_index, const float *d_prio_new,
+                                   int M);
+int tetris_replay_gather_dev(tetris_batch *b, const tetris_replay *rp, const int32_t *d_index, int M, int steps,
+                             const tetris_traj_batch *out);
+
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
  * t = w1 mod 10), acting player = step mod P, perform_action, auto-reset of finished games with
