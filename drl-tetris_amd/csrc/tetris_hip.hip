@@ -955,1886 +955,6 @@ __global__ __launch_bounds__(256) void k_set_dead(Geo geo, int n, const int32_t*
     if (t < n * geo.P) set_dead_body(geo, t, idx, dead);
 }
 
-// ============================================================================ host side
-
-struct tetris_batch;
-static void chain_release(tetris_batch* b);
-static int chain_recover(tetris_batch* b);
-static int default_direct_min();
-#define HIP_TRY(expr)                                                                                            \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess)                                                                                    \
-            return fail(TETRIS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                        \
-    } while (0)
-
-// RNG tables, shared by every batch on the same device with the same piece map
-struct Tables {
-    int device = -1;
-    uint8_t map[8] = {0};
-    int only_sz = 0;
-    int refs = 0;
-    uint32_t* d_mt = nullptr;        // [624][65536]
-    float* d_w = nullptr;            // [7][65536]
-    uint64_t* d_start = nullptr;     // [65536] per-seed start entries
-    double* d_pow = nullptr;         // [256]
-    uint8_t* d_table = nullptr;      // [(chunk * 65536 + seed) * 624 + r], capacity `cap_chunks`
-    int n_chunks = 0, cap_chunks = 0;
-    std::vector<uint8_t*> retired;   // outgrown tables: other streams may still be reading them
-};
-static const size_t CHUNK_BYTES = (size_t)65536 * CHUNK;
-static std::mutex g_tab_mutex;
-static std::vector<Tables*> g_tables;
-
-static int tables_extend(Tables* t, hipStream_t stream) {
-    if (t->n_chunks >= MAX_CHUNKS) return fail(TETRIS_E_STREAM, "RNG tables: MAX_CHUNKS reached");
-    if (t->n_chunks == t->cap_chunks) {            // grow: new allocation, copy, retire the old one
-        int cap = t->cap_chunks ? t->cap_chunks * 2 : 2;
-        if (cap > MAX_CHUNKS) cap = MAX_CHUNKS;
-        uint8_t* d = nullptr;
-        HIP_TRY(hipMalloc((void**)&d, CHUNK_BYTES * cap));
-        if (t->n_chunks) HIP_TRY(hipMemcpyAsync(d, t->d_table, CHUNK_BYTES * t->n_chunks, hipMemcpyDeviceToDevice, stream));
-        if (t->d_table) t->retired.push_back(t->d_table);
-        t->d_table = d;
-        t->cap_chunks = cap;
-    }
-    MapArg m;
-    memcpy(m.m, t->map, 8);
-    hipLaunchKernelGGL(k_gen_chunk, dim3(256), dim3(256), 0, stream, t->d_mt, t->d_w, t->d_table + CHUNK_BYTES * t->n_chunks,
-                       t->d_start, t->n_chunks, m, t->only_sz);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    t->n_chunks++;
-    return TETRIS_OK;
-}
-
-static void tables_free(Tables* t) {
-    (void)hipFree(t->d_mt); (void)hipFree(t->d_w); (void)hipFree(t->d_start); (void)hipFree(t->d_pow);
-    (void)hipFree(t->d_table);
-    for (uint8_t* c : t->retired) (void)hipFree(c);
-    delete t;
-}
-
-static int tables_build(Tables* t, hipStream_t stream);
-
-static int tables_acquire(Tables** out, int device, const uint8_t map[7], hipStream_t stream) {
-    std::lock_guard<std::mutex> lock(g_tab_mutex);
-    for (Tables* t : g_tables)
-        if (t->device == device && memcmp(t->map, map, 7) == 0) { t->refs++; *out = t; return TETRIS_OK; }
-    Tables* t = new (std::nothrow) Tables();
-    if (!t) return fail(TETRIS_E_HIP, "out of host memory");
-    t->device = device;
-    memcpy(t->map, map, 7);
-    t->only_sz = 1;                                             // PythonHandle.h:116-121 set_pieces
-    for (int i = 0; i < 7; i++) if (map[i] != 2 && map[i] != 3) t->only_sz = 0;
-    int rc = tables_build(t, stream);
-    if (rc) { std::string keep = g_err; tables_free(t); return fail(rc, keep); }
-    t->refs = 1;
-    g_tables.push_back(t);
-    *out = t;
-    return TETRIS_OK;
-}
-
-static int tables_build(Tables* t, hipStream_t stream) {
-    HIP_TRY(hipMalloc((void**)&t->d_mt, (size_t)624 * 65536 * 4));
-    HIP_TRY(hipMalloc((void**)&t->d_w, (size_t)7 * 65536 * 4));
-    HIP_TRY(hipMalloc((void**)&t->d_start, 65536 * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc((void**)&t->d_pow, 256 * sizeof(double)));
-    double powtab[256];
-    for (int c = 0; c < 256; c++) powtab[c] = pow((double)c, 1.4 + (double)c * 0.01);   // Combo.cpp:41, host libm
-    HIP_TRY(hipMemcpyAsync(t->d_pow, powtab, sizeof powtab, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_gen_seed, dim3(256), dim3(256), 0, stream, t->d_mt);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    for (int c = 0; c < 2; c++) {
-        int rc = tables_extend(t, stream);
-        if (rc) return rc;
-    }
-    return TETRIS_OK;
-}
-
-static void tables_release(Tables* t) {
-    std::lock_guard<std::mutex> lock(g_tab_mutex);
-    if (--t->refs > 0) return;
-    for (size_t i = 0; i < g_tables.size(); i++)
-        if (g_tables[i] == t) { g_tables.erase(g_tables.begin() + i); break; }
-    tables_free(t);
-}
-
-// grow-on-demand device + pinned-host staging pair
-struct Stage {
-    void* h = nullptr;
-    void* d = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return TETRIS_OK;
-        size_t want = bytes < 4096 ? 4096 : bytes + bytes / 2;
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        h = d = nullptr; cap = 0;
-        HIP_TRY(hipHostMalloc(&h, want, hipHostMallocDefault));
-        HIP_TRY(hipMalloc(&d, want));
-        cap = want;
-        return TETRIS_OK;
-    }
-    void release() {
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        h = d = nullptr; cap = 0;
-    }
-};
-constexpr int STAGES = 6;                // most pairs one synchronous call stages through (HostCall): step_keys, step_rt, enumerate_drops
-
-// 120: the host may be 241 launches (~1 ms of GPU work at 64k boards) ahead of what it has seen finish.  With 32 (round 2: 65
-// launches, 0.26 ms) a host thread that loses its core for a fraction of a millisecond — other tenants' jobs share the box's CPUs —
-// starves the GPU: 8192-launch runs measured 4.2-5.1 us per launch in bad minutes against 4.02-4.21 with 120, and 4.02 either way in
-// good ones (profiles/r03/gate_depth_ab.txt).  The low-water margin of the RNG tables is sized from it (< one chunk of 624 draws).
-constexpr int GATE_GROUP = 120;
-#include "tetris_aql.h"
-
-// One call of tetris_rollout_launch: what every launch path needs to build its launches (rollout_args), and, kept in
-// tetris_batch::chain_call for the last chained call, what chain_recover needs to finish abandoned games un-chained.
-struct RolloutCall {
-    uint32_t epoch0 = 0;                 // chained: the epoch before the call's first launch (launch l publishes epoch0 + l + 1)
-    uint64_t first_step = 0;
-    int steps_per_launch = 0;
-    uint32_t policy_seed = 0;
-    int ms = 0;
-    int launches = 0;
-    bool chained = false;
-};
-
-struct tetris_batch {
-    int device = 0, N = 0, P = 0, H = 0;
-    int stride = 0;                      // games per row of the state arrays: N + padding (see create_impl)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    uint32_t* d_state = nullptr;
-    uint32_t* d_gstate = nullptr;
-    uint32_t* flags = nullptr;           // te::Flag words: pinned, host-coherent, written by kernels with plain stores
-    unsigned long long* d_counters = nullptr;
-    unsigned long long* h_counters = nullptr;   // pinned [8]
-    Tables* tab = nullptr;
-    uint32_t margin = 2 * (2 * GATE_GROUP + 2) + 16;         // low-water mark of the RNG tables (draws); covers the launches in flight (gate below)
-    uint32_t game_offset = 0;
-    int split = 0, side = 0;
-    int tint = 0, nw = NWORDS;           // colour planes tracked; words per player-board
-    int use_duo = 1;                     // two-player rollout / step_rt through k_duo (TETRIS_NO_DUO=1 in the environment: k_game<2>)
-    uint32_t* d_shadow = nullptr;        // split mode, side 1
-    hipStream_t own_stream = nullptr;
-    // chained launches (k_chain): two extra streams, one epoch word per wave, the number of the last chained launch
-    hipStream_t chain_stream[CHAIN_STREAMS] = {};     // the device's (device_chain_streams): shared with its other batches, never destroyed
-    hipEvent_t chain_ev[CHAIN_STREAMS + 1] = {};      // [k]: end of chain stream k's last launch (join); [CHAIN_STREAMS]: fork from the batch's stream
-    hipEvent_t worker_gate_ev[CHAIN_STREAMS][2] = {}; // run-ahead gates of the per-stream enqueue threads (tetris_rollout_launch)
-    uint32_t* d_chain = nullptr;
-    uint32_t* d_words_before = nullptr;  // the per-game counter words [4][N] as a rollout call found them (rollout_counters_begin)
-    uint32_t chain_epoch = 0;
-    int use_chain = 1;                   // TETRIS_NO_CHAIN=1 in the environment: every rollout launch on the batch's one stream
-    int use_graph = 0;                   // TETRIS_GRAPH=1: un-chained rollout launches replayed from HIP graphs (profiling aid)
-    long long chain_capacity[2] = {-1, -1};   // wave slots of the device for the chained kernel, [fused] (computed on first use)
-    int chain_depth = 0;                 // launches in flight = streams rotated over (3, or 2 where only two launches fit; 0: not chained)
-    bool chain_pending = false;          // chained launches were enqueued since the last drain
-    uint32_t chain_spin_limit = CHAIN_SPIN_LIMIT;     // polls before a waiting wave gives up (tetris_set_chain_spin_limit)
-    RolloutCall chain_call;              // the chained call in progress (or the last one)
-    bool chain_fell_back = false;        // a chained call was finished un-chained since the last tetris_take_errors (TETRIS_ERR_CHAIN_FELL_BACK)
-    uint32_t* h_chain = nullptr;         // host copy of the epoch words (chain_recover)
-    hipStream_t stall_stream = nullptr;  // tetris_debug_stall(.., -1, ..)
-    // direct dispatch of the chained launches (tetris_aql.h): queues of the batch's own; off when anything about it failed
-    int direct_min = 16;                 // calls of at least this many launches go through the device's own queues; 0: never (TETRIS_DIRECT=0 / TETRIS_DIRECT_MIN, tetris_set_direct_dispatch)
-    bool last_direct = false;            // the last rollout call went through those queues
-    bool direct_used = false;            // ... and so did some call of this batch (its destruction waits for the queues)
-    int use_affine = 1;                  // XCD-affine launches (k_chain_affine) where the device's queues allow them; TETRIS_AFFINE=0 / tetris_set_xcd_affine
-    bool last_affine = false;            // the last rollout call ran them
-    uint32_t xcd_skew = 0;               // test aid (tetris_debug_xcd_skew): added to the queues' measured start XCDs
-    int table_limit = MAX_CHUNKS;        // test aid (tetris_debug_table_limit): this batch's kernels see at most that many chunks of the tables
-    int affine_failures = 0;             // calls in which a workgroup found itself misplaced (three: the affine form is switched off)
-    bool home_async = false;             // asynchronous (_dev) work was enqueued on the batch's stream since the last drain
-    // something was enqueued on one of the batch's streams since the last drain.  Whatever enqueues sets it (check_batch, HostCall,
-    // service_flags): on the batch's own stream finish_call skips the drain without it, also in a call's second drain (get_actions)
-    bool busy = true;
-    // Run-ahead gate of the asynchronous entry points: every GATE_GROUP launches an event is recorded; before a new group is
-    // enqueued the host waits for the event of the group before the previous one.  At most 2 * GATE_GROUP + 1 launches are
-    // therefore in flight whose flag words the host has not seen; `margin` is sized for that many steps.
-    hipEvent_t gate_ev[2] = {nullptr, nullptr};
-    int gate_count = 0;                  // launches since the last recorded event
-    int gate_slot = 0;                   // event to record next
-    int gate_pending[2] = {0, 0};        // event has been recorded and not waited for
-    Stage stage[STAGES];                 // the synchronous calls' staging pairs (HostCall hands them out in order)
-    Stage recover_idx;                   // chain_recover's game lists: it runs inside finish_call, while a call's outputs still wait in `stage`
-    // tetris_action_lists_dev: device scratch for the slabs of one chunk of games (grown on demand), the identity index the
-    // chunks' k_actions launches read their game numbers from, and the status words k_actions writes its own overflow flag to
-    // (the compaction finds every overflow itself, per game, and reports it as F_LISTS instead)
-    uint8_t* d_plan_slabs = nullptr;
-    size_t plan_slab_cap = 0;
-    int32_t* d_iota = nullptr;
-    uint32_t* d_plan_status = nullptr;
-    // the heuristic policy's spread mapping: the 40 scores of every game, [40][N], from k_policy_eval to the kernel that chooses
-    int32_t* d_policy_scores = nullptr;
-    // tetris_traj_select_dev: the counts per workgroup and their scan (grown on demand)
-    int32_t* d_select_blocks = nullptr;
-    size_t select_blocks_cap = 0;
-    // tetris_replay_add_dev: the entries per game and their scan; tetris_replay_sample_dev: the sort's pairs, ranks and
-    // histograms (both grown on demand)
-    uint32_t* d_replay_offsets = nullptr;
-    size_t replay_offsets_cap = 0;
-    uint32_t* d_replay_sort = nullptr;
-    size_t replay_sort_cap = 0;
-};
-
-static HostShape shape_of(const tetris_batch* b) { return {b->N, b->P, b->H, b->nw, b->split, b->tint}; }
-
-static Geo geo_of_batch(tetris_batch* b) {
-    Geo g = {b->d_state, b->d_gstate, (size_t)b->N, b->P, b->nw, (size_t)b->stride};
-    return g;
-}
-
-static KArgs base_args(tetris_batch* b, int n, const int32_t* d_idx) {
-    KArgs a;
-    memset(&a, 0, sizeof a);
-    a.state = b->d_state; a.gstate = b->d_gstate; a.status = b->flags;
-    {   // tables are shared between batches: take pointer and size together (another batch may be growing them)
-        std::lock_guard<std::mutex> lock(g_tab_mutex);
-        a.table = b->tab->d_table;
-        a.n_draws = table_draws(b->tab->n_chunks, b->table_limit);
-    }
-    a.start = b->tab->d_start; a.combo_pow = b->tab->d_pow; a.margin = b->margin;
-    a.H = b->H; a.n_games = b->N; a.n_stride = b->stride; a.n_players = b->P; a.nw = b->nw; a.n = n; a.idx = d_idx; a.game_offset = b->game_offset;
-    return a;
-}
-
-template <int MODE>
-static int launch_game(tetris_batch* b, const KArgs& a) {
-    dim3 grid((unsigned)((a.n + 255) / 256)), block(256);
-    if constexpr (MODE == M_ROLLOUT || MODE == M_STEP_RT || MODE == M_STEP_RT_AUTO) {
-        if (b->P == 2 && !b->tint && !a.idx && b->use_duo && (MODE != M_ROLLOUT || a.steps == 1)) {
-            // two-player full-batch single steps: players in adjacent half-waves (k_duo), 32 games per wave.  Measured on
-            // MI355X at 64k games: 9.37 us vs 9.73 us for k_game<2> at one step per launch, but 4.4 vs 3.9 us per step when
-            // 16 steps are fused, so fused rollouts stay on k_game<2>.
-            hipLaunchKernelGGL((k_duo<MODE>), dim3((unsigned)((a.n + 127) / 128)), block, 0, b->stream, a);
-            HIP_TRY(hipGetLastError());
-            return TETRIS_OK;
-        }
-    }
-    // (three and four players per game: the same kernel with all players of a game in one lane; it spills, and nothing is tuned for it)
-    const bool here = with_shape<1, 2>(b->P, b->tint != 0, [&](auto P, auto TINT) {
-        hipLaunchKernelGGL((k_game<P(), MODE, TINT()>), grid, block, 0, b->stream, a);
-    });
-    if (!here && tetris_launch_game_multi(b->P, b->tint, MODE, grid, block, b->stream, a)) return fail(TETRIS_E_ARG, "no kernel for this player count / mode");
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-// Games per wave of a chained launch: CHAIN_LANES for one player, 32 for two (k_duo: the players in adjacent half-waves).
-static int chain_lanes(const tetris_batch* b) { return b->P == 1 ? CHAIN_LANES : 32; }
-// workgroups (one wave each) of a chained launch
-static uint32_t chain_waves(const tetris_batch* b) { return (uint32_t)((b->N + chain_lanes(b) - 1) / chain_lanes(b)); }
-
-// Chained launches are deadlock-free only if the waves of all launches in flight can be resident together: the waves of
-// launch E spin (in their slots) until the same waves of launch E - 1 have published, so E - 1 must never be short of a slot
-// because of them.  At most `chain_depth` launches are in flight — the streams rotated over: CHAIN_STREAMS (3), or 2 where only two
-// launches fit (E follows E - depth on its stream, so the oldest launch in flight never waits for an epoch: its predecessor has
-// completed).  The occupancy API can be
-// one workgroup per CU too high for kernels of this SGPR count (MI355X_MICROARCH.md, correctness boundaries): one is
-// subtracted.  64k single-player boards: 1 024 waves per launch, 15 x 256 slots.  64k two-player boards (k_duo, 220
-// VGPRs: 8 waves per CU): 2 048 waves per launch, 7 x 256 slots — does not fit, those launches stay on one stream.
-// `fused`: the call's launches make another number of steps than one (one player only: rollout_chained) — k_chain_fused, which has
-// a footprint of its own: what fits and the census are asked of the kernel that will be launched.
-static bool chain_is_fused(const tetris_batch* b, int steps_per_launch) { return b->P == 1 && steps_per_launch != 1; }
-static const void* chain_kernel(tetris_batch* b, bool fused, long long* waves) {
-    *waves = chain_waves(b);
-    return b->P == 1 ? (fused ? (const void*)k_chain_fused<1> : (const void*)k_chain<1>) : (const void*)k_duo<M_ROLLOUT, true>;
-}
-// `blocks` workgroups of the chained kernel on stream `st`; `start` / `stop` (may be NULL): events attached to the kernel itself
-static hipError_t launch_chain_kernel(tetris_batch* b, bool fused, uint32_t blocks, hipStream_t st, const KArgs& a, hipEvent_t start = nullptr,
-                                      hipEvent_t stop = nullptr) {
-    if (b->P == 1 && fused) hipExtLaunchKernelGGL((k_chain_fused<1>), dim3(blocks), dim3(64), 0, st, start, stop, 0, a);
-    else if (b->P == 1) hipExtLaunchKernelGGL((k_chain<1>), dim3(blocks), dim3(64), 0, st, start, stop, 0, a);
-    else hipExtLaunchKernelGGL((k_duo<M_ROLLOUT, true>), dim3(blocks), dim3(64), 0, st, start, stop, 0, a);
-    return hipGetLastError();
-}
-// `waves` workgroups of the chained kernel resident at once?  Asked of the device itself: one census launch (chain_census).
-static bool chain_census_ok(tetris_batch* b, bool fused, long long waves) {
-    uint32_t* d = nullptr;
-    if (hipMalloc((void**)&d, 2 * CHAIN_STRIDE * sizeof(uint32_t)) != hipSuccess) return false;
-    bool ok = false;
-    uint32_t h[2] = {0, 1};
-    KArgs a;
-    memset(&a, 0, sizeof a);
-    a.steps = -1; a.chain = d; a.epoch = (uint32_t)waves; a.chain_spin_limit = 4000;       // a few ms at most, and only where the answer is no
-    if (hipMemsetAsync(d, 0, 2 * CHAIN_STRIDE * sizeof(uint32_t), b->own_stream) == hipSuccess) {
-        if (launch_chain_kernel(b, fused, (uint32_t)waves, b->own_stream, a) == hipSuccess && hipMemcpyAsync(&h[0], d, 4, hipMemcpyDeviceToHost, b->own_stream) == hipSuccess &&
-            hipMemcpyAsync(&h[1], d + CHAIN_STRIDE, 4, hipMemcpyDeviceToHost, b->own_stream) == hipSuccess &&
-            hipStreamSynchronize(b->own_stream) == hipSuccess)
-            ok = h[0] == (uint32_t)waves && h[1] == 0;
-    }
-    (void)hipFree(d);
-    return ok;
-}
-
-static bool chain_fits(tetris_batch* b, bool fused) {
-    long long waves = 0;
-    const void* fn = chain_kernel(b, fused, &waves);
-    long long& capacity = b->chain_capacity[fused ? 1 : 0];
-    // TETRIS_CHAIN_DEPTH=1..3 (measurement aid): at most that many launches in flight.  1 = the chained kernel on ONE stream: its
-    // dispatches are then serialised by the stream — the reference point for per-dispatch PMC counters (profiles/pmc_summary.py).
-    static const int cap = [] { const char* e = getenv("TETRIS_CHAIN_DEPTH"); const int v = e ? atoi(e) : CHAIN_STREAMS; return v < 1 ? 1 : (v > CHAIN_STREAMS ? CHAIN_STREAMS : v); }();
-    if (capacity < 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0) != hipSuccess) per_cu = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device) != hipSuccess) cus = 0;
-        // The API's answer less one workgroup per CU is taken on trust (the API can be one too high: MI355X_MICROARCH.md, correctness
-        // boundaries).  A batch that would chain only WITH that last workgroup per CU — 64k two-player boards: two launches of
-        // 2 048 waves are exactly the 16 x 256 slots a 116-register kernel has — asks the device: a census launch of that many
-        // waves of the very kernel, once per batch.
-        capacity = per_cu > 1 ? (long long)(per_cu - 1) * cus : 0;
-        const long long full = (long long)per_cu * cus;
-        int want = 0;
-        for (int d = cap; d >= 2 && !want; d--)
-            if (d * waves <= full) want = d;
-        if (want && want * waves > capacity && b->stream == b->own_stream && chain_census_ok(b, fused, want * waves)) capacity = want * waves;
-    }
-    b->chain_depth = 0;
-    for (int d = cap; d >= 1 && !b->chain_depth; d--)
-        if (d * waves <= capacity) b->chain_depth = d;
-    return b->chain_depth >= (cap == 1 ? 1 : 2);
-}
-
-// Looks at the flag words WITHOUT enqueuing or waiting for anything: answers a pending "extend the RNG tables" request
-// (the generation kernel goes on the batch's stream, i.e. before every launch made after this call).
-static int service_flags(tetris_batch* b) {
-    volatile uint32_t* f = b->flags;
-    const uint32_t want = f[F_EXTEND];
-    if (want) {
-        std::lock_guard<std::mutex> lock(g_tab_mutex);
-        // not yet answered (requests carry the size their kernel saw); at MAX_CHUNKS (the batch's table_limit) the tables stay as
-        // they are and a game that outruns them is ended with ERR_STREAM
-        if (want >= (uint32_t)b->tab->n_chunks * CHUNK && b->tab->n_chunks < b->table_limit) {
-            int rc = tables_extend(b->tab, b->stream);
-            if (rc) return rc;
-            b->busy = true;
-        }
-        f[F_EXTEND] = 0;
-    }
-    return TETRIS_OK;
-}
-
-// Waits for an event by polling it `spins` times before the blocking wait: a thread blocked in hipEventSynchronize is woken
-// through an interrupt — 10-20 us late at best, milliseconds when the scheduler has given its core away meanwhile.
-static hipError_t poll_event(hipEvent_t e, int spins) {
-    hipError_t qe = hipErrorNotReady;
-    for (int spin = 0; spin < spins && qe == hipErrorNotReady; spin++) qe = hipEventQuery(e);
-    return qe == hipErrorNotReady ? hipEventSynchronize(e) : qe;
-}
-
-// One more asynchronous launch is about to be enqueued: bound the run-ahead (see tetris_batch) and service the flags.
-static int gate_launch(tetris_batch* b, int group) {
-    if (b->gate_count >= group) {
-        const int k = b->gate_slot;
-        if (b->gate_pending[k]) {                               // the group before the previous one must have finished
-            // polled (the GPU has only the launches of two groups, ~0.26 ms, to live on)
-            HIP_TRY(poll_event(b->gate_ev[k], 2000000));
-            b->gate_pending[k] = 0;
-        }
-        HIP_TRY(hipEventRecord(b->gate_ev[k], b->stream));
-        b->gate_pending[k] = 1;
-        b->gate_slot = k ^ 1;
-        b->gate_count = 0;
-    }
-    b->gate_count++;
-    {
-        bool on_chain = false;
-        for (hipStream_t st : b->chain_stream) on_chain |= b->stream == st;
-        if (!on_chain) b->home_async = true;
-    }
-    return service_flags(b);
-}
-
-// Waits for a stream by polling it for a while before falling back to the blocking wait: a blocked host thread is woken
-// through an interrupt, 10-20 us after the GPU is done — as long as a whole 20-launch rollout of 64k boards.
-static hipError_t drain_stream(hipStream_t st) {
-    for (int spin = 0; spin < 20000; spin++) {
-        const hipError_t e = hipStreamQuery(st);
-        if (e != hipErrorNotReady) return e;
-    }
-    return hipStreamSynchronize(st);
-}
-
-// drain the batch's stream(s), then the flag words: sticky errors surface, the RNG tables are extended when a board came close to their end
-// `drained`: the caller has already seen an event complete that is ordered behind everything the batch's streams held (a stream
-// query makes the runtime push a marker through the queue and wait for it: ~6 us per stream even when the stream is idle)
-static int finish_call(tetris_batch* b, bool drained = false) {
-    if (!b->busy && !b->chain_pending && b->stream == b->own_stream) {      // drained already and nothing enqueued since: only the flag words
-        int rc0 = service_flags(b);
-        if (rc0) return rc0;
-        if (!b->busy) return TETRIS_OK;           // (an extension would have enqueued work)
-    }
-    if (b->chain_pending && !drained)
-        for (int k = 0; k < CHAIN_STREAMS; k++) HIP_TRY(drain_stream(b->chain_stream[k]));
-    b->chain_pending = false;
-    if (!drained) HIP_TRY(drain_stream(b->stream));
-    b->home_async = false;
-    b->busy = false;
-    b->gate_count = 0; b->gate_pending[0] = b->gate_pending[1] = 0;
-    volatile uint32_t* f = b->flags;
-    // (F_EXHAUSTED / F_FIFO: capacity errors are confined to the games they happened in — tetris_take_errors)
-    int rc = TETRIS_OK;
-    // a workgroup of an affine launch was not where its queue's calibration put it (it left its games alone): that form stays off,
-    // and the games it — and whoever waited for it — left behind are finished like abandoned ones
-    const bool misplaced = f[F_PLACE] != 0;
-    if (misplaced) {
-        // The games such workgroups — and whoever waited for them — left behind are finished like abandoned ones.  A queue's start XCD
-        // moves when the driver re-maps hardware queues (many queues in the process); the next call expects what this one saw.
-        // Not the caller's business unless it keeps happening: chaining stays as it was, the affine form goes after three such calls.
-        const int keep_chain = b->use_chain;
-        const bool keep_fell_back = b->chain_fell_back;
-        f[F_PLACE] = 0;
-        if ((rc = chain_recover(b))) return rc;
-        b->use_chain = keep_chain; b->chain_fell_back = keep_fell_back;
-        if (++b->affine_failures >= 3) b->use_affine = 0;
-    }
-    if (f[F_CHAIN] && (rc = chain_recover(b))) return rc;       // waves of a chained launch gave up: their games are finished un-chained
-    if ((rc = service_flags(b))) return rc;                     // before the argument error below: an extend request is never dropped
-    return take_capacity_error(f);
-}
-
-// every entry point starts here; `enqueues`: the call may put work on one of the batch's streams (all but the pure waits)
-static int check_batch(tetris_batch* b, bool enqueues = true) {
-    if (!b) return fail(TETRIS_E_ARG, "null batch");
-    HIP_TRY(hipSetDevice(b->device));
-    if (enqueues) b->busy = true;
-    return TETRIS_OK;
-}
-
-// The host traffic of one synchronous call (the entry points that take and return host arrays), on the batch's stream.  An input
-// goes from the caller's array to a pinned half, then to the device; an output gets a device half for the kernel, and finish()
-// copies it back to its pinned half, drains (finish_call) and only then copies it on to the caller's array.  The k-th input or
-// output of a call takes b->stage[k] (a NULL input keeps its place), so one call's buffers never alias, and every copy queued
-// here sets b->busy.
-struct HostCall {
-    tetris_batch* const b;
-    const int32_t* d_idx = nullptr;      // idx(): the call's game indices on the device (NULL: the first n games)
-    int used = 0, n_out = 0;
-    struct Out { const Stage* s; size_t bytes; void* dst; } outs[STAGES];
-
-    // the next pair, `bytes` long at least (the caller fills its pinned half, or the kernel its device half)
-    int take(size_t bytes, Stage** s) {
-        if (used >= STAGES) return fail(TETRIS_E_ARG, "internal: a call takes more than STAGES staging buffers");
-        *s = &b->stage[used++];
-        return (*s)->ensure(bytes + 16);
-    }
-    // pinned half -> device half
-    int send(const Stage* s, size_t bytes) {
-        b->busy = true;
-        HIP_TRY(hipMemcpyAsync(s->d, s->h, bytes, hipMemcpyHostToDevice, b->stream));
-        return TETRIS_OK;
-    }
-    // `count` T of the caller's -> the device (*d; src NULL: *d = NULL)
-    template <class T> int in(const T* src, size_t count, const T** d) {
-        *d = nullptr;
-        if (!src) { used++; return TETRIS_OK; }
-        Stage* s;
-        int rc = take(count * sizeof(T), &s);
-        if (rc) return rc;
-        memcpy(s->h, src, count * sizeof(T));
-        *d = (const T*)s->d;
-        return send(s, count * sizeof(T));
-    }
-    // game indices: validated, then staged (-> d_idx)
-    int idx(const int32_t* idx, int n) {
-        int rc = check_idx(shape_of(b), idx, n);
-        return rc ? rc : in(idx, (size_t)n, &d_idx);
-    }
-    // `count` T on the device for the kernel (*d); finish() copies them to `dst`, or leaves them in the pinned half for the caller
-    // to read (*h) when dst is NULL
-    template <class T> int out(void* dst, size_t count, T** d, const T** h = nullptr) {
-        Stage* s;
-        int rc = take(count * sizeof(T), &s);
-        if (rc) return rc;
-        outs[n_out++] = {s, count * sizeof(T), dst};
-        *d = (T*)s->d;
-        if (h) *h = (const T*)s->h;
-        return TETRIS_OK;
-    }
-    int finish() {
-        for (int k = 0; k < n_out; k++) {
-            b->busy = true;
-            HIP_TRY(hipMemcpyAsync(outs[k].s->h, outs[k].s->d, outs[k].bytes, hipMemcpyDeviceToHost, b->stream));
-        }
-        int rc = finish_call(b);
-        if (rc) return rc;
-        for (int k = 0; k < n_out; k++)
-            if (outs[k].dst) memcpy(outs[k].dst, outs[k].s->h, outs[k].bytes);
-        return TETRIS_OK;
-    }
-};
-
-// The rest of a synchronous step: done [n] and lines / dead [P][n] on the device, the launch, io.finish(), then lines / dead to the
-// caller as [n][P]
-template <int MODE>
-static int finish_step(HostCall& io, KArgs& a, int n, uint8_t* done, uint8_t* lines, uint8_t* dead) {
-    const int P = io.b->P;
-    const uint8_t *hl, *hd;
-    int rc = io.out(done, (size_t)n, &a.done);
-    if (rc || (rc = io.out(nullptr, (size_t)n * P, &a.lines, &hl)) || (rc = io.out(nullptr, (size_t)n * P, &a.dead, &hd))) return rc;
-    if ((rc = launch_game<MODE>(io.b, a)) || (rc = io.finish())) return rc;
-    lines_dead_unpack(shape_of(io.b), n, hl, hd, lines, dead);
-    return TETRIS_OK;
-}
-
-extern "C" {
-
-const char* tetris_last_error(void) { return last_error(); }
-
-int tetris_device_count(void) {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) return fail(TETRIS_E_HIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
-    return n;
-}
-
-int tetris_device_name(int device, char* buf, int len) {
-    if (!buf || len < 1) return fail(TETRIS_E_ARG, "buf/len");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    snprintf(buf, (size_t)len, "%s (%s, %d CUs)", prop.name, prop.gcnArchName, prop.multiProcessorCount);
-    return TETRIS_OK;
-}
-
-int tetris_record_size(void) { return (int)sizeof(tetris_record); }
-int tetris_layout_words(void) { return NWORDS; }
-int tetris_snapshot_words(const tetris_batch* b) { return b ? NGWORDS + b->P * b->nw : 0; }
-int tetris_table_chunks(const tetris_batch* b) { return b && b->tab ? b->tab->n_chunks : 0; }
-void* tetris_device_state(tetris_batch* b) { return b ? b->d_state : nullptr; }
-void* tetris_stream(tetris_batch* b) { return b ? (void*)b->stream : nullptr; }
-
-int tetris_destroy(tetris_batch* b) {
-    if (!b) return TETRIS_OK;
-    (void)hipSetDevice(b->device);
-    for (hipStream_t st : b->chain_stream) if (st) (void)hipStreamSynchronize(st);      // (a call that failed half-way may have left launches there)
-    chain_release(b);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    if (b->tab) tables_release(b->tab);
-    (void)hipFree(b->d_shadow); (void)hipFree(b->d_state); (void)hipFree(b->d_gstate); (void)hipFree(b->d_counters);
-    if (b->flags) (void)hipHostFree(b->flags);
-    if (b->h_counters) (void)hipHostFree(b->h_counters);
-    for (hipEvent_t e : b->gate_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : b->chain_ev) if (e) (void)hipEventDestroy(e);
-    for (auto& pair : b->worker_gate_ev) for (hipEvent_t e : pair) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(b->d_chain);
-    free(b->h_chain);
-    if (b->stall_stream) { (void)hipStreamSynchronize(b->stall_stream); (void)hipStreamDestroy(b->stall_stream); }
-    if (b->direct_used) { aql::Device* dev = aql::device_for(b->device); if (dev->ok) aql::quiesce(dev->qs); }      // (a test's idle kernel may still sit there)
-    (void)hipFree(b->d_plan_slabs); (void)hipFree(b->d_iota); (void)hipFree(b->d_plan_status);
-    (void)hipFree(b->d_policy_scores);
-    (void)hipFree(b->d_words_before);
-    (void)hipFree(b->d_select_blocks);
-    (void)hipFree(b->d_replay_offsets);
-    (void)hipFree(b->d_replay_sort);
-    for (Stage& s : b->stage) s.release();
-    b->recover_idx.release();
-    if (b->ev0) (void)hipEventDestroy(b->ev0);
-    if (b->ev1) (void)hipEventDestroy(b->ev1);
-    if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
-    delete b;
-    return TETRIS_OK;
-}
-
-// The chain streams of a device, made once and shared by all its batches (chained calls of a device's batches exclude each
-// other: chain_acquire).  Per batch they cost three more streams each, and the runtime deals streams onto few hardware
-// queues: a batch created after two others ran its chained 20-launch calls at 11-13 us per launch instead of 5, its streams
-// sharing queues (profiles/r03/direct_dispatch.txt).
-// Every chain stream gets a stream priority of its own.  Not for the priorities' sake: the runtime keeps one hardware queue per
-// priority level apart from the four (GPU_MAX_HW_QUEUES) it deals ordinary streams onto in turn, and two chain streams on ONE
-// hardware queue do not overlap (measured with GPU_MAX_HW_QUEUES=2: 5.07 us per launch with equal priorities, 3.99 with three
-// different ones; with four queues 4.00 either way: profiles/r02/hw_queues.txt).
-static std::mutex g_dev_streams_mutex;
-static hipStream_t g_dev_streams[64][CHAIN_STREAMS] = {};
-static hipError_t device_chain_streams(int device, hipStream_t out[CHAIN_STREAMS]) {
-    std::lock_guard<std::mutex> lock(g_dev_streams_mutex);
-    hipStream_t* st = g_dev_streams[device & 63];
-    if (!st[0]) {
-        int lo = 0, hi = 0;
-        const bool spread = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo - hi + 1 >= CHAIN_STREAMS;
-        hipStream_t made[CHAIN_STREAMS] = {};
-        for (int k = 0; k < CHAIN_STREAMS; k++) {
-            const hipError_t ce = spread ? hipStreamCreateWithPriority(&made[k], hipStreamNonBlocking, hi + k) : hipStreamCreateWithFlags(&made[k], hipStreamNonBlocking);
-            if (ce != hipSuccess) { for (int j = 0; j < k; j++) (void)hipStreamDestroy(made[j]); return ce; }
-        }
-        for (int k = 0; k < CHAIN_STREAMS; k++) st[k] = made[k];
-    }
-    for (int k = 0; k < CHAIN_STREAMS; k++) out[k] = st[k];
-    return hipSuccess;
-}
-
-static int create_impl(tetris_batch** out, int n_games, int n_players, int height, int width, const uint8_t piece_map[7],
-                       int device, const int16_t* seeds, int split, int side, int flags = 0) {
-    int rc = create_check(out, n_games, n_players, height, width, piece_map, split, side, flags);
-    if (rc) return rc;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return fail(TETRIS_E_HIP, std::string("no HIP device available (this library has no CPU path): ") +
-                                      (e != hipSuccess ? hipGetErrorString(e) : "device count 0"));
-    if (device < 0 || device >= ndev) return fail(TETRIS_E_ARG, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
-    tetris_batch* b = new (std::nothrow) tetris_batch();
-    if (!b) return fail(TETRIS_E_HIP, "out of host memory");
-    b->device = device; b->N = n_games; b->P = n_players; b->H = height;
-    b->stride = n_games;
-    b->tint = (flags & TETRIS_FLAG_COLOURS) ? 1 : 0;
-    { const char* e = getenv("TETRIS_NO_DUO"); b->use_duo = !(e && e[0] == '1'); }
-    { const char* e = getenv("TETRIS_NO_CHAIN"); b->use_chain = !(e && e[0] == '1'); }
-    b->direct_min = default_direct_min();
-    { const char* e = getenv("TETRIS_AFFINE"); b->use_affine = !(e && e[0] == '0'); }
-    { const char* e = getenv("TETRIS_GRAPH"); b->use_graph = (e && e[0] == '1'); }
-    { const char* e = getenv("TETRIS_CHAIN_SPIN_LIMIT"); if (e && atoll(e) > 0) b->chain_spin_limit = (uint32_t)atoll(e); }
-    b->nw = b->tint ? NWORDS_TINT : NWORDS;
-#define CREATE_TRY(expr)                                                                    \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            tetris_destroy(b);                                                              \
-            return fail(TETRIS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-        }                                                                                   \
-    } while (0)
-    CREATE_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    b->own_stream = b->stream;
-    CREATE_TRY(hipEventCreate(&b->ev0));
-    CREATE_TRY(hipEventCreate(&b->ev1));
-    {   // the chain streams belong to the DEVICE (device_chain_streams below): every batch of a device uses the same three
-        hipError_t ce = device_chain_streams(device, b->chain_stream);
-        CREATE_TRY(ce);
-    }
-    for (int k = 0; k < CHAIN_STREAMS + 1; k++) CREATE_TRY(hipEventCreateWithFlags(&b->chain_ev[k], hipEventDisableTiming));
-    for (int k = 0; k < CHAIN_STREAMS; k++) for (int j = 0; j < 2; j++) CREATE_TRY(hipEventCreateWithFlags(&b->worker_gate_ev[k][j], hipEventDisableTiming));
-    {
-        const size_t chain_bytes = (((size_t)n_games + 15) / 16) * sizeof(uint32_t) * CHAIN_STRIDE;       // (one word per wave; at least 16 games per wave)
-        CREATE_TRY(hipMalloc((void**)&b->d_chain, chain_bytes));
-        CREATE_TRY(hipMemsetAsync(b->d_chain, 0, chain_bytes, b->stream));
-    }
-    CREATE_TRY(hipEventCreateWithFlags(&b->gate_ev[0], hipEventDisableTiming));
-    CREATE_TRY(hipEventCreateWithFlags(&b->gate_ev[1], hipEventDisableTiming));
-    const size_t state_bytes = state_words((size_t)b->stride, n_players, b->nw) * 4, gstate_bytes = gstate_words((size_t)b->stride) * 4;
-    CREATE_TRY(hipMalloc((void**)&b->d_state, state_bytes));
-    CREATE_TRY(hipMalloc((void**)&b->d_gstate, gstate_bytes));
-    CREATE_TRY(hipMalloc((void**)&b->d_counters, 8 * sizeof(unsigned long long)));
-    CREATE_TRY(hipHostMalloc((void**)&b->h_counters, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-    // flag words: host memory the GPU can write (fine-grained, so a store is visible to the host while the kernel runs)
-    CREATE_TRY(hipHostMalloc((void**)&b->flags, NFLAGS * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(b->flags, 0, NFLAGS * sizeof(uint32_t));
-    CREATE_TRY(hipMemsetAsync(b->d_gstate, 0, gstate_bytes, b->stream));
-    CREATE_TRY(hipMemsetAsync(b->d_state, 0, state_bytes, b->stream));
-    rc = tables_acquire(&b->tab, device, piece_map, b->stream);
-    if (rc) { std::string keep = g_err; tetris_destroy(b); return fail(rc, keep); }
-    HostCall io{b};
-    const int16_t* d_seeds;
-    if ((rc = io.in(seeds, (size_t)n_games, &d_seeds))) { std::string keep = g_err; tetris_destroy(b); return fail(rc, keep); }
-    b->split = split; b->side = side;
-    if (split && side == 1) CREATE_TRY(hipMalloc((void**)&b->d_shadow, (size_t)(UNDO_WORDS + b->nw) * (size_t)b->stride * 4));
-    KArgs a = base_args(b, n_games, nullptr);
-    a.seeds = d_seeds;
-    a.steps = side;
-    rc = split ? launch_game<M_SPLIT_INIT>(b, a) : launch_game<M_INIT>(b, a);
-    if (!rc) rc = io.finish();
-    if (rc) { std::string keep = g_err; tetris_destroy(b); return fail(rc, keep); }
-    *out = b;
-    return TETRIS_OK;
-}
-
-int tetris_set_chained(tetris_batch* b, int on) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = finish_call(b))) return rc;
-    b->use_chain = on ? 1 : 0;
-    return TETRIS_OK;
-}
-
-static int default_direct_min() {
-    const char* off = getenv("TETRIS_DIRECT");
-    if (off && off[0] == '0') return 0;
-    const char* e = getenv("TETRIS_DIRECT_MIN");
-    const int v = e ? atoi(e) : 16;
-    return v < 1 ? 16 : v;
-}
-
-int tetris_set_direct_dispatch(tetris_batch* b, int min_launches) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = finish_call(b))) return rc;
-    b->direct_min = min_launches < 0 ? default_direct_min() : min_launches;
-    return TETRIS_OK;
-}
-
-int tetris_set_xcd_affine(tetris_batch* b, int on) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = finish_call(b))) return rc;
-    b->use_affine = on ? 1 : 0;
-    return TETRIS_OK;
-}
-
-int tetris_debug_xcd_skew(tetris_batch* b, int skew) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = finish_call(b))) return rc;
-    b->xcd_skew = (uint32_t)skew & 7u;
-    return TETRIS_OK;
-}
-
-int tetris_debug_table_limit(tetris_batch* b, int chunks) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = table_limit_check(chunks)) || (rc = finish_call(b))) return rc;
-    b->table_limit = chunks ? chunks : MAX_CHUNKS;
-    return TETRIS_OK;
-}
-
-int tetris_debug_code_objects(int* count, uint64_t* bytes) {
-    if (!count || !bytes) return fail(TETRIS_E_ARG, "count / bytes is NULL");
-    std::vector<std::vector<char>> images;
-    std::string why;
-    *count = 0; *bytes = 0;
-    if (!aql::own_code_objects(images, why)) return TETRIS_OK;      // (none: the caller sees count == 0)
-    *count = (int)images.size();
-    for (auto& img : images) *bytes += img.size();
-    return TETRIS_OK;
-}
-
-int tetris_rollout_was_direct(tetris_batch* b) {
-    int rc = check_batch(b, false);
-    if (rc) return rc;
-    return b->last_direct ? (b->last_affine ? 2 : 1) : 0;
-}
-
-int tetris_set_chain_spin_limit(tetris_batch* b, uint32_t polls) {
-    int rc = check_batch(b, false);
-    if (rc) return rc;
-    if ((rc = finish_call(b))) return rc;
-    b->chain_spin_limit = polls ? polls : CHAIN_SPIN_LIMIT;
-    return TETRIS_OK;
-}
-
-// Test aid (tests of the give-up path of chained launches; nothing in the product calls it): enqueues a kernel that does nothing for
-// `microseconds` — which = 0..2: on that chain stream (the launches the next rollout puts there start late); 3: on the batch's
-// stream; -1: on a stream of its own, as 1024-thread workgroups that take `percent` % of the device's wave slots meanwhile.
-int tetris_debug_stall(tetris_batch* b, int which, int microseconds, int percent) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (which < -1 || which > 3 || microseconds < 0 || microseconds > 2000000 || percent < 0 || percent > 100) return fail(TETRIS_E_ARG, "which / microseconds / percent");
-    const unsigned long long ticks = (unsigned long long)microseconds * 100ull;
-    if (which >= 0 && which < 3 && b->direct_min > 0) {
-        // the device's own queues (tetris_aql.h), if they exist: the idle kernel goes to the one that stands for that stream as well —
-        // whichever way the next call's launches go, the ones with that number start late
-        aql::Device* dev = aql::device_for(b->device);
-        std::string why;
-        if (dev->ok && aql::make_queues(dev, why) && dev->blocker.ok) {
-            struct { const uint32_t* go; unsigned long long ticks; } args = {nullptr, ticks};
-            aql::Pending pd;
-            aql::write_dispatch(dev->qs, pd, which, dev->blocker, &args, sizeof args, 1, HSA_FENCE_SCOPE_AGENT, HSA_FENCE_SCOPE_AGENT, hsa_signal_t{});
-            aql::ring(dev->qs, pd);
-            b->direct_used = true;
-        }
-    }
-    if (which >= 0) {
-        hipStream_t st = which == 3 ? b->stream : b->chain_stream[which % CHAIN_STREAMS];
-        if (which < 3) b->chain_pending = true;
-        hipLaunchKernelGGL(k_blocker, dim3(1), dim3(64), 0, st, (const uint32_t*)nullptr, ticks);
-    } else {
-        if (!b->stall_stream) HIP_TRY(hipStreamCreateWithFlags(&b->stall_stream, hipStreamNonBlocking));
-        int cus = 0;
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
-        const int blocks = (int)((long long)cus * 2 * percent / 100);        // 2 x 1024 threads = the 32 wave slots of a CU
-        if (blocks > 0) hipLaunchKernelGGL(k_blocker, dim3((unsigned)blocks), dim3(1024), 0, b->stall_stream, (const uint32_t*)nullptr, ticks);
-    }
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-// Test aid (tests of the restart of the epoch numbering, tetris_rollout_launch; nothing in the product calls it): at a drained point
-// every wave's epoch word and the batch's count of chained launches become `set_epoch`, the way chain_recover leaves them.
-int tetris_debug_chain_epoch(tetris_batch* b, long long set_epoch, uint32_t* epoch) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (set_epoch >= (long long)CHAIN_EPOCH_MAX) return fail(TETRIS_E_ARG, "set_epoch must be below 0x7FFF0000");
-    if ((rc = finish_call(b))) return rc;
-    if (set_epoch >= 0) {
-        hipStream_t const home = b->own_stream;
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        for (int k = 0; k < CHAIN_STREAMS; k++) HIP_TRY(hipStreamSynchronize(b->chain_stream[k]));
-        HIP_TRY(hipStreamSynchronize(home));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b->d_chain, (int)set_epoch, (((size_t)b->N + 15) / 16) * CHAIN_STRIDE, home));
-        HIP_TRY(hipStreamSynchronize(home));
-        b->chain_epoch = (uint32_t)set_epoch;
-    }
-    if (epoch) *epoch = b->chain_epoch;
-    return TETRIS_OK;
-}
-
-// Measurement aid: the GPU's shader clock right now, in kHz (a 50 us probe kernel on the batch's stream; synchronous).  The
-// chained period follows it: DESIGN.md, section 6.
-int tetris_debug_clock_khz(tetris_batch* b, int* khz) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (!khz) return fail(TETRIS_E_ARG, "khz is NULL");
-    HIP_TRY(hipMemsetAsync(b->d_counters + 4, 0, 2 * sizeof(unsigned long long), b->stream));
-    hipLaunchKernelGGL(k_clock_probe, dim3(1), dim3(64), 0, b->stream, 5000ull, b->d_counters + 4);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_counters + 4, b->d_counters + 4, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
-    if ((rc = finish_call(b))) return rc;
-    *khz = b->h_counters[5] ? (int)(b->h_counters[4] * 100000ull / b->h_counters[5]) : 0;
-    return TETRIS_OK;
-}
-
-int tetris_set_game_offset(tetris_batch* b, uint64_t first_game_id) {
-    if (!b) return fail(TETRIS_E_ARG, "null batch");
-    b->game_offset = (uint32_t)first_game_id;
-    return TETRIS_OK;
-}
-
-int tetris_create(tetris_batch** out, int n_games, int n_players, int height, int width, const uint8_t piece_map[7],
-                  int device, const int16_t* seeds) {
-    return create_impl(out, n_games, n_players, height, width, piece_map, device, seeds, 0, 0);
-}
-
-int tetris_create_ex(tetris_batch** out, int n_games, int n_players, int height, int width, const uint8_t piece_map[7], int device,
-                     const int16_t* seeds, int flags) {
-    return create_impl(out, n_games, n_players, height, width, piece_map, device, seeds, 0, 0, flags);
-}
-
-int tetris_create_split(tetris_batch** out, int n_games, int side, int height, int width, const uint8_t piece_map[7], int device,
-                        const int16_t* seeds) {
-    return create_impl(out, n_games, 1, height, width, piece_map, device, seeds, 1, side);
-}
-
-int tetris_set_stream(tetris_batch* b, void* hip_stream, int external) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    b->stream = external ? (hipStream_t)hip_stream : b->own_stream;      // NULL + external = the legacy default stream
-    return TETRIS_OK;
-}
-
-static int split_stage_launch(tetris_batch* b, int stage, KArgs& a, const uint32_t* const d_words[4], uint32_t* d_out) {
-    int rc = split_stage_check(shape_of(b), b->side, stage, d_words, d_out);
-    if (rc) return rc;
-    b->home_async = true;
-    for (int k = 0; k < 4; k++) a.xw[k] = d_words ? d_words[k] : nullptr;
-    a.shadow = b->d_shadow; a.xout = d_out; a.split_side = b->side;
-    dim3 grid((unsigned)((b->N + 255) / 256)), block(256);
-    with_value<0, 3>(stage, [&](auto STAGE) { hipLaunchKernelGGL((k_split<STAGE(), false>), grid, block, 0, b->stream, a); });
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_split_stage_dev(tetris_batch* b, int stage, const uint8_t* d_rot, const uint8_t* d_trans, const uint8_t* d_acting, int ms,
-                           const uint32_t* const d_words[4], uint32_t* d_out, uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = split_step_check(stage, d_rot, d_trans))) return rc;
-    KArgs a = base_args(b, b->N, nullptr);
-    a.rot = d_rot; a.trans = d_trans; a.player = d_acting; a.ms = ms;
-    a.done = d_done; a.lines = d_lines; a.dead = d_dead;
-    return split_stage_launch(b, stage, a, d_words, d_out);
-}
-
-int tetris_split_rollout_stage_dev(tetris_batch* b, int stage, uint32_t policy_seed, uint64_t step, int ms, const uint32_t* const d_words[4],
-                                   uint32_t* d_out) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    KArgs a = base_args(b, b->N, nullptr);
-    a.ms = ms; a.policy_seed = policy_seed; a.first_step = step; a.steps = 1;
-    return split_stage_launch(b, stage, a, d_words, d_out);
-}
-
-int tetris_rollout_totals(tetris_batch* b, uint64_t totals[4]) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (!totals) return fail(TETRIS_E_ARG, "totals is NULL");
-    HIP_TRY(hipMemsetAsync(b->d_counters, 0, 8 * sizeof(unsigned long long), b->stream));
-    const int tot_blocks = b->N >= 65536 ? 64 : (b->N + 1023) / 1024;
-    hipLaunchKernelGGL(k_totals, dim3(tot_blocks), dim3(256), 0, b->stream, geo_of_batch(b), b->d_counters);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_counters, b->d_counters, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
-    if ((rc = finish_call(b))) return rc;
-    for (int k = 0; k < 4; k++) totals[k] = b->h_counters[k];
-    return TETRIS_OK;
-}
-
-int tetris_take_errors(tetris_batch* b, uint32_t* bits) {
-    int rc = check_batch(b, false);
-    if (rc) return rc;
-    if ((rc = take_errors_check(bits)) || (rc = finish_call(b))) return rc;
-    volatile uint32_t* f = b->flags;
-    *bits = take_error_bits(f) | (b->chain_fell_back ? TETRIS_ERR_CHAIN_FELL_BACK : 0u);
-    b->chain_fell_back = false;
-    return TETRIS_OK;
-}
-
-int tetris_sync(tetris_batch* b) {
-    int rc = check_batch(b, false);
-    if (rc) return rc;
-    return finish_call(b);
-}
-
-int tetris_reset(tetris_batch* b, const int32_t* idx, int n, const int16_t* seeds) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    HostCall io{b};
-    if ((rc = io.idx(idx, n))) return rc;
-    if (n == 0) return io.finish();             // still a synchronisation point: sticky errors surface, tables get extended
-    KArgs a = base_args(b, n, io.d_idx);
-    if ((rc = io.in(seeds, (size_t)n, &a.seeds))) return rc;
-    if ((rc = b->split ? launch_game<M_SPLIT_RESET>(b, a) : launch_game<M_RESET>(b, a))) return rc;
-    return io.finish();
-}
-
-// host keys [n][P][K] -> device [K][P][n]; host lens [n][P] -> device [P][n]
-static int stage_keys(HostCall& io, int n, const uint8_t* keys, const uint8_t* lens, int max_keys, KArgs& a) {
-    int rc = keys_check(keys, lens, max_keys);
-    if (rc) return rc;
-    const int P = io.b->P;
-    Stage *sk, *sl;
-    if ((rc = io.take((size_t)n * P * max_keys, &sk)) || (rc = io.take((size_t)n * P, &sl))) return rc;
-    if ((rc = keys_pack(shape_of(io.b), n, keys, lens, max_keys, (uint8_t*)sk->h, (uint8_t*)sl->h))) return rc;
-    if ((rc = io.send(sk, (size_t)n * P * max_keys)) || (rc = io.send(sl, (size_t)n * P))) return rc;
-    a.keys = (const uint8_t*)sk->d; a.lens = (const uint8_t*)sl->d; a.max_keys = max_keys;
-    return TETRIS_OK;
-}
-
-int tetris_make_actions(tetris_batch* b, const int32_t* idx, int n, const uint8_t* keys, const uint8_t* lens, int max_keys) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    HostCall io{b};
-    if ((rc = io.idx(idx, n))) return rc;
-    if (n == 0) return TETRIS_OK;
-    KArgs a = base_args(b, n, io.d_idx);
-    if ((rc = stage_keys(io, n, keys, lens, max_keys, a))) return rc;
-    if ((rc = launch_game<M_MAKE>(b, a))) return rc;
-    return io.finish();
-}
-
-int tetris_finish_actions(tetris_batch* b, const int32_t* idx, int n, int ms, uint8_t* done, uint8_t* lines, uint8_t* dead) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    HostCall io{b};
-    if ((rc = io.idx(idx, n))) return rc;
-    if (n == 0) return TETRIS_OK;
-    KArgs a = base_args(b, n, io.d_idx);
-    a.ms = ms;
-    return finish_step<M_FINISH>(io, a, n, done, lines, dead);
-}
-
-int tetris_step_keys(tetris_batch* b, const int32_t* idx, int n, const uint8_t* keys, const uint8_t* lens, int max_keys,
-                     int ms, uint8_t* done, uint8_t* lines, uint8_t* dead) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    HostCall io{b};
-    if ((rc = io.idx(idx, n))) return rc;
-    if (n == 0) return TETRIS_OK;
-    KArgs a = base_args(b, n, io.d_idx);
-    a.ms = ms;
-    if ((rc = stage_keys(io, n, keys, lens, max_keys, a))) return rc;
-    return finish_step<M_STEP_KEYS>(io, a, n, done, lines, dead);
-}
-
-int tetris_step_rt_dev_ex(tetris_batch* b, const uint8_t* d_rot, const uint8_t* d_trans, const uint8_t* d_player, int ms,
-                          uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead, int flags) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = step_rt_check(shape_of(b), d_rot, d_trans, flags)) || (rc = gate_launch(b, GATE_GROUP))) return rc;
-    KArgs a = base_args(b, b->N, nullptr);
-    a.rot = d_rot; a.trans = d_trans; a.player = d_player; a.ms = ms;
-    a.done = d_done; a.lines = d_lines; a.dead = d_dead;
-    return (flags & TETRIS_STEP_AUTO_RESET) ? launch_game<M_STEP_RT_AUTO>(b, a) : launch_game<M_STEP_RT>(b, a);
-}
-
-int tetris_step_rt_observe_dev(tetris_batch* b, const uint8_t* d_rot, const uint8_t* d_trans, const uint8_t* d_player, int ms,
-                               uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead, int flags, const uint8_t* d_next_player,
-                               uint8_t* d_visual, uint8_t* d_vector, uint8_t* d_piece) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = step_rt_observe_check(shape_of(b), d_rot, d_trans, flags, d_visual, d_vector, d_piece))) return rc;
-    const bool fused = !b->tint && b->H % 2 == 0 && ((uintptr_t)d_visual & 3u) == 0 && ((uintptr_t)d_vector & 3u) == 0;
-    if (!fused) {             // colour batches, odd heights, unaligned outputs: the same two kernels back to back
-        if ((rc = tetris_step_rt_dev_ex(b, d_rot, d_trans, d_player, ms, d_done, d_lines, d_dead, flags))) return rc;
-        return tetris_observe_packed_dev(b, nullptr, b->N, d_next_player, d_visual, d_vector, d_piece);
-    }
-    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    KArgs a = base_args(b, b->N, nullptr);
-    a.rot = d_rot; a.trans = d_trans; a.player = d_player; a.ms = ms;
-    a.done = d_done; a.lines = d_lines; a.dead = d_dead;
-    a.next_player = d_next_player; a.obs_visual = d_visual; a.obs_vector = d_vector; a.obs_piece = d_piece;
-    const int nw = b->H * NCOL / 4;
-        const size_t lds = ((size_t)SHAPE_WORDS + (size_t)64 * nw) * 4;
-    const dim3 grid((unsigned)((b->N + 63) / 64)), block(64);
-    const bool autoreset = (flags & TETRIS_STEP_AUTO_RESET) != 0;
-    if (b->P == 2 && b->use_duo) {
-        // two players: one player per lane (k_duo) — every lane builds the one board it holds
-        const size_t lds2 = ((size_t)4 * 64 * nw + 16) * 4;
-        if (lds2 > 48 * 1024) {
-            const void* fn = autoreset ? (const void*)k_duo<M_STEP_RT_AUTO, false, true> : (const void*)k_duo<M_STEP_RT, false, true>;
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        }
-        const dim3 grid2((unsigned)((b->N + 127) / 128)), block2(256);
-        if (autoreset) hipLaunchKernelGGL((k_duo<M_STEP_RT_AUTO, false, true>), grid2, block2, lds2, b->stream, a);
-        else hipLaunchKernelGGL((k_duo<M_STEP_RT, false, true>), grid2, block2, lds2, b->stream, a);
-    } else {
-        with_shape<1, 2>(b->P, autoreset, [&](auto P, auto AUTO) {
-            hipLaunchKernelGGL((k_step_observe<P(), AUTO() ? M_STEP_RT_AUTO : M_STEP_RT>), grid, block, lds, b->stream, a);
-        });
-    }
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_step_rt_dev(tetris_batch* b, const uint8_t* d_rot, const uint8_t* d_trans, const uint8_t* d_player, int ms,
-                       uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead) {
-    return tetris_step_rt_dev_ex(b, d_rot, d_trans, d_player, ms, d_done, d_lines, d_dead, 0);
-}
-
-int tetris_reset_dev(tetris_batch* b, const uint8_t* d_mask, const int16_t* d_seeds) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = not_on_split(shape_of(b), "tetris_reset_dev")) || (rc = gate_launch(b, GATE_GROUP))) return rc;
-    KArgs a = base_args(b, b->N, nullptr);
-    a.mask = d_mask; a.seeds = d_seeds;
-    return d_seeds ? launch_game<M_RESET>(b, a) : launch_game<M_RESET_SCHED>(b, a);
-}
-
-int tetris_step_rt(tetris_batch* b, const uint8_t* rot, const uint8_t* trans, const uint8_t* player, int ms, uint8_t* done,
-                   uint8_t* lines, uint8_t* dead) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    const int n = b->N;
-    if ((rc = step_rt_check(shape_of(b), rot, trans, 0)) || (rc = check_players(shape_of(b), player, n))) return rc;
-    KArgs a = base_args(b, n, nullptr);
-    a.ms = ms;
-    HostCall io{b};
-    if ((rc = io.in(rot, (size_t)n, &a.rot)) || (rc = io.in(trans, (size_t)n, &a.trans)) || (rc = io.in(player, (size_t)n, &a.player))) return rc;
-    return finish_step<M_STEP_RT>(io, a, n, done, lines, dead);
-}
-
-int tetris_observe_records(tetris_batch* b, const int32_t* idx, int n, tetris_record* records, uint8_t* round_over,
-                           int8_t* last_winner) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    HostCall io{b};
-    if ((rc = io.idx(idx, n))) return rc;
-    if (n == 0) return TETRIS_OK;
-    const size_t rec_bytes = (size_t)n * b->P * sizeof(tetris_record);
-    tetris_record* d_rec;
-    uint8_t* d_round_over;
-    int8_t* d_last_winner;
-    Stage* rec;                         // (records NULL: the kernel writes them all the same, nothing copies them back)
-    if ((rc = records ? io.out(records, (size_t)n * b->P, &d_rec) : io.take(rec_bytes, &rec))) return rc;
-    if (!records) d_rec = (tetris_record*)rec->d;
-    if ((rc = io.out(round_over, (size_t)n, &d_round_over)) || (rc = io.out(last_winner, (size_t)n, &d_last_winner))) return rc;
-    dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    HIP_TRY(hipMemsetAsync(d_rec, 0, rec_bytes, b->stream));      // struct padding stays deterministic
-    with_shape<1, 4>(b->P, b->tint != 0, [&](auto P, auto TINT) {
-        hipLaunchKernelGGL((k_observe<P(), TINT()>), grid, block, 0, b->stream, geo_of_batch(b), n, io.d_idx, b->H, d_rec, d_round_over, d_last_winner);
-    });
-    HIP_TRY(hipGetLastError());
-    return io.finish();
-}
-
-int tetris_observe_packed_dev(tetris_batch* b, const int32_t* d_idx, int n, const uint8_t* d_player, uint8_t* d_visual,
-                              uint8_t* d_vector, uint8_t* d_piece) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = observe_packed_check(shape_of(b), d_idx != nullptr, n, d_visual, d_vector, d_piece))) return rc;
-    if (n == 0) return TETRIS_OK;
-    b->home_async = true;
-    dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (b->H % 2 == 0 && ((uintptr_t)d_visual & 3u) == 0 && ((uintptr_t)d_vector & 3u) == 0) {
-        // one wave per workgroup (<= 20 KB of LDS): several workgroups per CU overlap their load / build / store phases
-        constexpr int OB = 64;
-        const int nw = b->H * NCOL / 4;
-        const size_t lds = (size_t)OB * nw * 4;
-        dim3 ogrid((unsigned)((n + OB - 1) / OB), (unsigned)b->P), oblock(OB);
-        with_value<1, 2>(b->P, [&](auto P) {
-            hipLaunchKernelGGL((k_observe_packed<P(), OB>), ogrid, oblock, lds, b->stream, geo_of_batch(b), n, d_idx, d_player, b->H,
-                               d_visual, d_vector, d_piece);
-        });
-        HIP_TRY(hipGetLastError());
-        return TETRIS_OK;
-    }
-    const size_t lds = (size_t)256 * b->H * NCOL;             // odd heights (boards are not word-aligned in `visual`): byte tile
-    if (lds > 48 * 1024) {      // up to 79 KB of the CU's 160 KB for 31-row boards
-        const void* fn = nullptr;
-        with_value<1, 2>(b->P, [&](auto P) { fn = (const void*)k_observe_packed_bytes<P()>; });
-        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    with_value<1, 2>(b->P, [&](auto P) {
-        hipLaunchKernelGGL(k_observe_packed_bytes<P()>, grid, block, lds, b->stream, geo_of_batch(b), n, d_idx, d_player, b->H, d_visual,
-                           d_vector, d_piece);
-    });
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_observe_packed(tetris_batch* b, const int32_t* idx, int n, const uint8_t* player, uint8_t* visual, uint8_t* vector,
-                          uint8_t* piece) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = observe_packed_outputs_check(visual, vector, piece))) return rc;
-    HostCall io{b};
-    if ((rc = io.idx(idx, n))) return rc;
-    if (n == 0) return TETRIS_OK;
-    const uint8_t* d_player;
-    if ((rc = check_players(shape_of(b), player, n)) || (rc = io.in(player, (size_t)n, &d_player))) return rc;
-    const size_t pn = (size_t)b->P * n;
-    uint8_t *d_visual, *d_vector, *d_piece;
-    if ((rc = io.out(visual, pn * b->H * NCOL, &d_visual)) || (rc = io.out(vector, pn * 12, &d_vector)) || (rc = io.out(piece, pn, &d_piece))) return rc;
-    if ((rc = tetris_observe_packed_dev(b, io.d_idx, n, d_player, d_visual, d_vector, d_piece))) return rc;
-    return io.finish();
-}
-
-static int snapshot_impl(tetris_batch* b, const int32_t* idx, int n, uint32_t* blob, int restore) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (!blob) return fail(TETRIS_E_ARG, "blob is NULL");
-    HostCall io{b};
-    if ((rc = io.idx(idx, n))) return rc;
-    if (n == 0) return TETRIS_OK;
-    const size_t total = (size_t)n * (NGWORDS + b->P * b->nw);
-    const uint32_t* d_in;
-    uint32_t* d_out;
-    if ((rc = restore ? io.in((const uint32_t*)blob, total, &d_in) : io.out(blob, total, &d_out))) return rc;
-    hipLaunchKernelGGL(k_snapshot, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, b->stream, geo_of_batch(b), n, io.d_idx,
-                       restore ? (uint32_t*)d_in : d_out, restore);
-    HIP_TRY(hipGetLastError());
-    return io.finish();
-}
-
-int tetris_snapshot(tetris_batch* b, const int32_t* idx, int n, uint32_t* blob) { return snapshot_impl(b, idx, n, blob, 0); }
-int tetris_restore(tetris_batch* b, const int32_t* idx, int n, const uint32_t* blob) {
-    return snapshot_impl(b, idx, n, (uint32_t*)blob, 1);
-}
-
-int tetris_set_dead(tetris_batch* b, const int32_t* idx, int n, const uint8_t* dead) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (!dead) return fail(TETRIS_E_ARG, "dead is NULL");
-    HostCall io{b};
-    const uint8_t* d_dead;
-    if ((rc = io.idx(idx, n))) return rc;
-    if (n == 0) return TETRIS_OK;
-    if ((rc = io.in(dead, (size_t)n * b->P, &d_dead))) return rc;
-    hipLaunchKernelGGL(k_set_dead, dim3((unsigned)((n * b->P + 255) / 256)), dim3(256), 0, b->stream, geo_of_batch(b), n, io.d_idx, d_dead);
-    HIP_TRY(hipGetLastError());
-    return io.finish();
-}
-
-int tetris_enumerate_drops_dev_ex(tetris_batch* b, const int32_t* d_idx, int n, const uint8_t* d_player, uint8_t* d_valid,
-                                  int8_t* d_land_y, uint8_t* d_cleared, uint32_t* d_after, int flags);
-
-int tetris_enumerate_drops(tetris_batch* b, const int32_t* idx, int n, const uint8_t* player, uint8_t* valid, int8_t* land_y,
-                           uint8_t* cleared, uint32_t* after) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (!valid || !land_y || !cleared) return fail(TETRIS_E_ARG, "valid/land_y/cleared are NULL");
-    HostCall io{b};
-    if ((rc = io.idx(idx, n))) return rc;
-    if (n == 0) return TETRIS_OK;
-    const uint8_t* d_player;
-    if ((rc = check_players(shape_of(b), player, n)) || (rc = io.in(player, (size_t)n, &d_player))) return rc;
-    const size_t lanes = (size_t)n * 40;
-    uint8_t *d_valid, *d_cleared;
-    int8_t* d_land_y;
-    uint32_t* d_after = nullptr;
-    if ((rc = io.out(valid, lanes, &d_valid)) || (rc = io.out(land_y, lanes, &d_land_y)) || (rc = io.out(cleared, lanes, &d_cleared)) ||
-        (after && (rc = io.out(after, lanes * NCOL, &d_after)))) return rc;
-    if ((rc = tetris_enumerate_drops_dev_ex(b, io.d_idx, n, d_player, d_valid, d_land_y, d_cleared, d_after, 0))) return rc;
-    return io.finish();
-}
-
-int tetris_enumerate_drops_dev_ex(tetris_batch* b, const int32_t* d_idx, int n, const uint8_t* d_player, uint8_t* d_valid,
-                                  int8_t* d_land_y, uint8_t* d_cleared, uint32_t* d_after, int flags) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = enumerate_check(shape_of(b), d_idx != nullptr, n, d_valid, d_land_y, d_cleared, d_after, flags))) return rc;
-    if (n == 0) return TETRIS_OK;
-    b->home_async = true;
-    dim3 grid((unsigned)((n + ENUM_BOARDS - 1) / ENUM_BOARDS)), block(ENUM_BLOCK);
-    const Geo geo = geo_of_batch(b);
-    const bool planar = (flags & TETRIS_ENUM_PLANAR) != 0;
-    with_shape<1, 4>(b->P, planar, [&](auto P, auto PLANAR) {
-        hipLaunchKernelGGL((k_enumerate<P(), PLANAR()>), grid, block, 0, b->stream, geo, n, d_idx, d_player, b->H, d_valid, d_land_y, d_cleared, d_after);
-    });
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_enumerate_drops_dev(tetris_batch* b, const int32_t* d_idx, int n, const uint8_t* d_player, uint8_t* d_valid,
-                               int8_t* d_land_y, uint8_t* d_cleared, uint32_t* d_after) {
-    return tetris_enumerate_drops_dev_ex(b, d_idx, n, d_player, d_valid, d_land_y, d_cleared, d_after, 0);
-}
-
-int tetris_timer_start(tetris_batch* b) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(b->ev0, b->stream));
-    return TETRIS_OK;
-}
-
-int tetris_timer_stop(tetris_batch* b, float* elapsed_ms) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (!elapsed_ms) return fail(TETRIS_E_ARG, "elapsed_ms is NULL");
-    HIP_TRY(hipEventRecord(b->ev1, b->stream));
-    HIP_TRY(hipEventSynchronize(b->ev1));
-    HIP_TRY(hipEventElapsedTime(elapsed_ms, b->ev0, b->ev1));
-    return TETRIS_OK;
-}
-
-int tetris_get_actions(tetris_batch* b, const int32_t* idx, int n, const uint8_t* player, uint8_t* keys, uint8_t* lens,
-                       int32_t* count, int max_lists, int max_keys) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = get_actions_check(shape_of(b), idx != nullptr, n, player, keys, lens, count, max_lists, max_keys))) return rc;
-    const int CHUNK_GAMES = 1024;                    // bounds the staging buffers
-    const size_t L = PLAN_LANE_LISTS;                // lists one (x, rotation) start can produce
-    std::vector<int32_t> ident;
-    for (int g0 = 0; g0 < n; g0 += CHUNK_GAMES) {    // (each chunk drains before its lists are read: HostCall::finish)
-        const int m = (n - g0 < CHUNK_GAMES) ? n - g0 : CHUNK_GAMES;
-        const size_t lanes = (size_t)m * 40;
-        const int32_t* h_idx = idx ? idx + g0 : nullptr;
-        if (!h_idx && g0 > 0) { ident.resize(m); for (int i = 0; i < m; i++) ident[i] = g0 + i; h_idx = ident.data(); }
-        HostCall io{b};
-        const uint8_t *d_player, *hc, *hl, *hk;
-        uint8_t *d_cnt, *d_len, *d_key;
-        if ((rc = io.idx(h_idx, m)) || (rc = io.in(player ? player + g0 : nullptr, (size_t)m, &d_player)) ||
-            (rc = io.out(nullptr, lanes, &d_cnt, &hc)) || (rc = io.out(nullptr, lanes * L, &d_len, &hl)) ||
-            (rc = io.out(nullptr, lanes * L * max_keys, &d_key, &hk))) return rc;
-        dim3 grid((unsigned)((lanes + 63) / 64)), block(64);
-        with_value<1, 4>(b->P, [&](auto P) {
-            hipLaunchKernelGGL(k_actions<P()>, grid, block, 0, b->stream, geo_of_batch(b), m, io.d_idx, d_player, b->H, d_cnt, d_len, d_key,
-                               PLAN_LANE_LISTS, max_keys, b->flags);
-        });
-        if (hipGetLastError() != hipSuccess) return fail(TETRIS_E_HIP, "k_actions launch failed");
-        if ((rc = io.finish())) return rc;
-        if ((rc = get_actions_gather(m, hc, hl, hk, max_lists, max_keys, keys + (size_t)g0 * max_lists * max_keys, lens + (size_t)g0 * max_lists, count + g0))) return rc;
-    }
-    return TETRIS_OK;
-}
-
-// ---------------------------------------------------------------- planning: action lists, simulated afterstates, list steps
-// Games per k_actions + k_plan_lists pair: bounds the slab scratch (40 x 16 slab entries of max_keys + 1 bytes per game: 128 MB
-// at 4 096 games and 48 keys); a batch of more games enqueues one pair per chunk, ordered by the stream.
-static const int PLAN_CHUNK = 4096;
-
-// which: 0 simulate, 1 step, 2 step with auto-reset
-static int launch_plan_kernel(tetris_batch* b, int which, dim3 grid, const PlanArgs& pa, int fin) {
-    const bool here = with_shape<1, 2>(b->P, b->tint != 0, [&](auto P, auto TINT) { launch_plan<P(), TINT()>(which, grid, b->stream, pa, fin); });
-    if (!here && tetris_launch_plan_multi(b->P, b->tint, which, grid, b->stream, pa, fin)) return fail(TETRIS_E_ARG, "no planning kernel for this player count");
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_action_lists_dev(tetris_batch* b, const uint8_t* d_player, int max_lists, int max_keys, int flags, int32_t* d_count,
-                            uint8_t* d_lens, uint8_t* d_keys) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = action_lists_check(shape_of(b), d_count, d_lens, d_keys, max_lists, max_keys, flags))) return rc;
-    const int chunk = b->N < PLAN_CHUNK ? b->N : PLAN_CHUNK;
-    const int KS = max_keys + 1;                 // one key more than the caller takes: a list that does not fit shows as one
-    const size_t lanes = (size_t)chunk * 40;
-    const size_t need = lanes + lanes * PLAN_LANE_LISTS + lanes * PLAN_LANE_LISTS * KS;
-    if (!b->d_iota) {
-        std::vector<int32_t> iota((size_t)b->N);
-        for (int i = 0; i < b->N; i++) iota[i] = i;
-        HIP_TRY(hipMalloc((void**)&b->d_iota, (size_t)b->N * 4));
-        HIP_TRY(hipMemcpy(b->d_iota, iota.data(), (size_t)b->N * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void**)&b->d_plan_status, NFLAGS * 4));
-    }
-    if (need > b->plan_slab_cap) {
-        if (b->d_plan_slabs) { HIP_TRY(hipStreamSynchronize(b->stream)); (void)hipFree(b->d_plan_slabs); }
-        b->d_plan_slabs = nullptr; b->plan_slab_cap = 0;
-        HIP_TRY(hipMalloc((void**)&b->d_plan_slabs, need));
-        b->plan_slab_cap = need;
-    }
-    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    uint8_t* s_cnt = b->d_plan_slabs;
-    uint8_t* s_len = s_cnt + lanes;
-    uint8_t* s_key = s_len + lanes * PLAN_LANE_LISTS;
-    const Geo geo = geo_of_batch(b);
-    for (int g0 = 0; g0 < b->N; g0 += chunk) {
-        const int m = b->N - g0 < chunk ? b->N - g0 : chunk;
-        const int32_t* d_idx = b->d_iota + g0;
-        const uint8_t* pl = d_player ? d_player + g0 : nullptr;
-        const dim3 grid((unsigned)(((size_t)m * 40 + 63) / 64)), block(64);
-        with_value<1, 4>(b->P, [&](auto P) {
-            hipLaunchKernelGGL(k_actions<P()>, grid, block, 0, b->stream, geo, m, d_idx, pl, b->H, s_cnt, s_len, s_key, PLAN_LANE_LISTS, KS, b->d_plan_status);
-        });
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_plan_lists, dim3((unsigned)m), block, 0, b->stream, s_cnt, s_len, s_key, KS, g0, max_lists, max_keys,
-                           (flags & TETRIS_LISTS_KEEP_NULL) ? 1 : 0, d_count, d_lens, d_keys, b->flags);
-        HIP_TRY(hipGetLastError());
-    }
-    return TETRIS_OK;
-}
-
-int tetris_simulate_lists_dev(tetris_batch* b, const uint8_t* d_player, const int32_t* d_count, const uint8_t* d_lens, const uint8_t* d_keys,
-                              int max_lists, int max_keys, int ms, int flags, uint32_t* d_cols, uint8_t* d_done, uint8_t* d_lines,
-                              uint8_t* d_dead) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = simulate_lists_check(shape_of(b), d_count, d_lens, d_keys, max_lists, max_keys, flags, d_cols))) return rc;
-    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    PlanArgs pa = plan_args(base_args(b, b->N, nullptr), d_player, d_count, d_lens, d_keys, max_lists, max_keys, ms);
-    pa.cols = d_cols;
-    const int fin = (flags & TETRIS_SIM_FINALIZE) ? 1 : 0;
-    if (fin) { pa.a.done = d_done; pa.a.lines = d_lines; pa.a.dead = d_dead; }
-    return launch_plan_kernel(b, 0, dim3((unsigned)((b->N + 63) / 64), (unsigned)max_lists), pa, fin);
-}
-
-int tetris_step_lists_dev(tetris_batch* b, const uint8_t* d_player, const int32_t* d_choice, const int32_t* d_count, const uint8_t* d_lens,
-                          const uint8_t* d_keys, int max_lists, int max_keys, int ms, int flags, uint8_t* d_done, uint8_t* d_lines,
-                          uint8_t* d_dead) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = step_lists_check(shape_of(b), d_choice, d_count, d_lens, d_keys, max_lists, max_keys, flags))) return rc;
-    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    PlanArgs pa = plan_args(base_args(b, b->N, nullptr), d_player, d_count, d_lens, d_keys, max_lists, max_keys, ms);
-    pa.choice = d_choice;
-    pa.a.done = d_done; pa.a.lines = d_lines; pa.a.dead = d_dead;
-    return launch_plan_kernel(b, (flags & TETRIS_STEP_AUTO_RESET) ? 2 : 1, dim3((unsigned)((b->N + 63) / 64)), pa, 0);
-}
-
-int tetris_plan_deltas_dev(tetris_batch* b, const uint8_t* d_player, const int32_t* d_count, const uint32_t* d_cols, int max_lists,
-                           float small_fill, int flags, void* d_deltas, void* d_sums, uint8_t* d_small) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    static_assert(PD_BLOCK == PLAN_DELTAS_MAX_LISTS, "list k = thread k");
-    PlanDeltaArgs da;
-    if ((rc = plan_deltas_args(shape_of(b), geo_of_batch(b), d_player, d_count, d_cols, max_lists, small_fill, flags, d_deltas, d_sums, d_small, da))) return rc;
-    b->home_async = true;
-    const dim3 grid((unsigned)((b->N + 127) / 128) * 128u), block(PD_BLOCK);     // whole groups of 8 XCDs x 16 games
-    const bool major = (flags & TETRIS_DELTAS_LIST_MAJOR) != 0;
-    if (flags & TETRIS_DELTAS_F16) {
-        if (major) hipLaunchKernelGGL((k_plan_deltas<uint16_t, true>), grid, block, 0, b->stream, da);
-        else hipLaunchKernelGGL((k_plan_deltas<uint16_t, false>), grid, block, 0, b->stream, da);
-    } else {
-        if (major) hipLaunchKernelGGL((k_plan_deltas<float, true>), grid, block, 0, b->stream, da);
-        else hipLaunchKernelGGL((k_plan_deltas<float, false>), grid, block, 0, b->stream, da);
-    }
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-// Chained launches of two batches at once would need room for four launches; only one batch per device chains at a time
-// (another one that comes along meanwhile puts its launches on one stream).
-static std::mutex g_chain_mutex;
-static tetris_batch* g_chain_owner[64] = {nullptr};
-static bool chain_acquire(tetris_batch* b) {
-    std::lock_guard<std::mutex> lock(g_chain_mutex);
-    tetris_batch*& owner = g_chain_owner[b->device & 63];
-    if (owner && owner != b) return false;
-    owner = b;
-    return true;
-}
-static void chain_release(tetris_batch* b) {
-    std::lock_guard<std::mutex> lock(g_chain_mutex);
-    tetris_batch*& owner = g_chain_owner[b->device & 63];
-    if (owner == b) owner = nullptr;
-}
-
-static bool rollout_chained(tetris_batch* b, int steps_per_launch) {
-    return b->use_chain && !b->tint && !b->split && b->stream == b->own_stream &&
-           (b->P == 1 || (b->P == 2 && steps_per_launch == 1 && b->use_duo)) && chain_fits(b, chain_is_fused(b, steps_per_launch));
-}
-
-int tetris_rollout_is_chained(tetris_batch* b, int steps_per_launch) {
-    int rc = check_batch(b, false);
-    if (rc) return rc;
-    return rollout_chained(b, steps_per_launch) ? 1 : 0;
-}
-
-// Waves of a chained call gave up waiting (F_CHAIN): with every stream drained, each wave's epoch word names the last launch that
-// finished its games (chain_wait).  The games of the waves that are behind are stepped on to the call's last launch by the
-// un-chained kernel on the batch's stream, group by group (waves that stopped at the same launch), then the epoch words are set
-// to the final epoch and chaining is switched off for this batch (a device that starved a launch once is shared with something:
-// tetris_set_chained(b, 1) switches it back on).  Bit-exact: a wave that gives up has not touched its games.
-static int chain_recover(tetris_batch* b) {
-    volatile uint32_t* f = b->flags;
-    const RolloutCall& call = b->chain_call;
-    const int lanes = chain_lanes(b);
-    const int waves = (int)chain_waves(b);
-    hipStream_t const home = b->own_stream;
-    struct StreamGuard { tetris_batch* b; hipStream_t keep; ~StreamGuard() { b->stream = keep; } } guard{b, b->stream};
-    b->stream = home;
-    const size_t bytes = (size_t)waves * CHAIN_STRIDE * sizeof(uint32_t);
-    if (!b->h_chain && !(b->h_chain = (uint32_t*)malloc((((size_t)b->N + 15) / 16) * sizeof(uint32_t) * CHAIN_STRIDE))) return fail(TETRIS_E_HIP, "out of host memory");
-    HIP_TRY(hipMemcpyAsync(b->h_chain, b->d_chain, bytes, hipMemcpyDeviceToHost, home));
-    HIP_TRY(hipStreamSynchronize(home));
-    const uint32_t last = b->chain_epoch, epoch0 = call.epoch0;
-    const int S = call.steps_per_launch;
-    std::vector<uint32_t> stops;                                  // distinct epochs at which waves stopped, ascending
-    for (int w = 0; w < waves; w++) {
-        const uint32_t c = b->h_chain[(size_t)w * CHAIN_STRIDE] & ~CHAIN_ABANDONED;
-        if (c < epoch0 || c > last) return fail(TETRIS_E_HIP, "chained launches: an epoch word is outside the range of the call that gave up; state is invalid");
-        if (c < last) stops.push_back(c);
-    }
-    std::sort(stops.begin(), stops.end());
-    stops.erase(std::unique(stops.begin(), stops.end()), stops.end());
-    const uint32_t saved_margin = b->margin;
-    struct MarginGuard { tetris_batch* b; uint32_t saved; ~MarginGuard() { b->margin = saved; } } margin_guard{b, saved_margin};
-    const int FUSE = 16;                                          // env-steps per recovery launch (the flag words are read after every launch)
-    if (b->margin < (uint32_t)(2 * FUSE * 2 + 16)) b->margin = (uint32_t)(2 * FUSE * 2 + 16);
-    std::vector<int32_t> idx;
-    for (uint32_t c : stops) {
-        idx.clear();
-        for (int w = 0; w < waves; w++)
-            if ((b->h_chain[(size_t)w * CHAIN_STRIDE] & ~CHAIN_ABANDONED) == c)
-                for (int g = w * lanes; g < (w + 1) * lanes && g < b->N; g++) idx.push_back(g);
-        unsigned long long step = call.first_step + (unsigned long long)(c - epoch0) * (unsigned long long)S;
-        unsigned long long todo = (unsigned long long)(last - c) * (unsigned long long)S;
-        while (todo > 0) {
-            const int steps = todo < (unsigned long long)FUSE ? (int)todo : FUSE;
-            // (a pair of its own, not one of b->stage: this runs inside finish_call, before the call's outputs are copied out)
-            Stage& s = b->recover_idx;
-            int rc = s.ensure(idx.size() * 4 + 16);
-            if (rc) return rc;
-            memcpy(s.h, idx.data(), idx.size() * 4);
-            HIP_TRY(hipMemcpyAsync(s.d, s.h, idx.size() * 4, hipMemcpyHostToDevice, home));
-            KArgs a = base_args(b, (int)idx.size(), (const int32_t*)s.d);
-            a.ms = call.ms; a.steps = steps; a.policy_seed = call.policy_seed; a.first_step = step;
-            if ((rc = launch_game<M_ROLLOUT>(b, a))) return rc;
-            HIP_TRY(hipStreamSynchronize(home));
-            if ((rc = service_flags(b))) return rc;                // (an extension of the RNG tables is enqueued before the next launch)
-            step += (unsigned long long)steps; todo -= (unsigned long long)steps;
-        }
-    }
-    // every wave's word = the call's last epoch, without the bit (hipMemsetD32: the lines' other words are never read)
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b->d_chain, (int)last, (size_t)waves * CHAIN_STRIDE, home));
-    HIP_TRY(hipStreamSynchronize(home));
-    f[F_CHAIN] = 0;
-    b->chain_fell_back = true;
-    b->use_chain = 0;
-    return TETRIS_OK;
-}
-
-// The arguments of launch l of a rollout call; a chained launch also gets the epoch words and the epoch it publishes.  (The table
-// pointer and size are taken under the tables' mutex, base_args: enqueue threads build arguments while the calling thread may be
-// extending the tables.)
-static KArgs rollout_args(tetris_batch* b, const RolloutCall& call, int l) {
-    KArgs a = base_args(b, b->N, nullptr);
-    a.ms = call.ms; a.steps = call.steps_per_launch; a.policy_seed = call.policy_seed;
-    a.first_step = call.first_step + (uint64_t)l * (uint64_t)call.steps_per_launch;
-    if (call.chained) { a.chain = b->d_chain; a.epoch = call.epoch0 + (uint32_t)l + 1u; a.chain_spin_limit = b->chain_spin_limit; }
-    return a;
-}
-
-using Clock = std::chrono::steady_clock;
-static double seconds(Clock::duration d) { return std::chrono::duration<double>(d).count(); }
-
-// TETRIS_TIMING=1 (debug aid): the host-side cost of a call on the streams, on stderr
-static void print_stream_timing(int launches, double gate_s, Clock::time_point t_entry, Clock::time_point t_begin, Clock::time_point t_enq,
-                                double ev1_us, const float* elapsed_ms) {
-    const Clock::time_point now = Clock::now();
-    fprintf(stderr, "[tetris timing] %d launches: host enqueue %.2f us/launch (of which gate + flags %.2f), until drained %.2f us/launch; "
-            "call entry -> first enqueue %.1f us, end event seen %.1f us after the first enqueue, whole call %.1f us, between the events %.1f us\n",
-            launches, seconds(t_enq - t_begin) * 1e6 / launches, gate_s * 1e6 / launches, seconds(now - t_begin) * 1e6 / launches,
-            seconds(t_begin - t_entry) * 1e6, ev1_us, seconds(now - t_entry) * 1e6, elapsed_ms ? *elapsed_ms * 1e3 : 0.0);
-}
-
-// TETRIS_GRAPH=1 (profiling aid): the un-chained launches are captured into HIP graphs of up to 128 kernel nodes and replayed, so
-// the host makes one call per 128 launches.  Under rocprofv3 a plain launch costs the host ~8 us — more than the kernel takes —
-// and the kernels of a profiled run are then no longer back to back; replayed from a graph they are.
-static int rollout_graph(tetris_batch* b, const RolloutCall& call, float* elapsed_ms) {
-    hipStream_t const home = b->stream;
-    const int launches = call.launches, S = call.steps_per_launch;
-    int rc = TETRIS_OK;
-    HIP_TRY(hipEventRecord(b->ev0, home));
-    for (int l0 = 0; l0 < launches; l0 += 128) {
-        const int m = launches - l0 < 128 ? launches - l0 : 128;
-        if ((rc = gate_launch(b, 1))) return rc;                      // flags are looked at between graphs: the margin below covers 128 launches
-        const uint32_t keep = b->margin;
-        if (b->margin < (uint32_t)(2 * S * 3 * 128 + 16)) b->margin = (uint32_t)(2 * S * 3 * 128 + 16);
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        HIP_TRY(hipStreamBeginCapture(home, hipStreamCaptureModeThreadLocal));
-        for (int l = l0; l < l0 + m && !rc; l++) rc = launch_game<M_ROLLOUT>(b, rollout_args(b, call, l));
-        b->margin = keep;
-        const hipError_t ce = hipStreamEndCapture(home, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        HIP_TRY(ce);
-        HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        const hipError_t le = hipGraphLaunch(exec, home);
-        const hipError_t se = hipStreamSynchronize(home);          // (the graph objects must outlive the launch)
-        (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph);
-        HIP_TRY(le); HIP_TRY(se);
-    }
-    HIP_TRY(hipEventRecord(b->ev1, home));
-    if ((rc = finish_call(b))) return rc;
-    if (elapsed_ms) HIP_TRY(hipEventElapsedTime(elapsed_ms, b->ev0, b->ev1));
-    return TETRIS_OK;
-}
-
-// Un-chained launches, one after the other on the batch's stream.  `group`: run-ahead in launches (gate_launch).
-static int rollout_plain(tetris_batch* b, const RolloutCall& call, int group, Clock::time_point t_entry, float* elapsed_ms) {
-    if (b->use_graph && call.steps_per_launch >= 1) return rollout_graph(b, call, elapsed_ms);
-    b->last_direct = false; b->last_affine = false;
-    hipStream_t const home = b->stream;
-    int rc = TETRIS_OK;
-    HIP_TRY(hipEventRecord(b->ev0, home));
-    static const bool timing = getenv("TETRIS_TIMING") != nullptr;
-    const Clock::time_point t_begin = Clock::now();
-    double gate_s = 0.0;
-    for (int l = 0; l < call.launches; l++) {
-        const Clock::time_point t_gate = Clock::now();
-        if ((rc = gate_launch(b, group))) return rc;
-        if (timing) gate_s += seconds(Clock::now() - t_gate);
-        if ((rc = launch_game<M_ROLLOUT>(b, rollout_args(b, call, l)))) return rc;
-    }
-    HIP_TRY(hipEventRecord(b->ev1, home));
-    const Clock::time_point t_enq = Clock::now();
-    HIP_TRY(poll_event(b->ev1, 200000));
-    const double ev1_us = seconds(Clock::now() - t_begin) * 1e6;
-    if ((rc = finish_call(b, true))) return rc;   // the end event is behind everything this call enqueued: no stream drains
-    if (elapsed_ms) HIP_TRY(hipEventElapsedTime(elapsed_ms, b->ev0, b->ev1));
-    if (timing) print_stream_timing(call.launches, gate_s, t_entry, t_begin, t_enq, ev1_us, elapsed_ms);
-    return TETRIS_OK;
-}
-
-// Launch l of a chained call on stream `st`.  The events are attached to the kernels themselves (hipExtLaunchKernel): the call's
-// first launch carries the start event ev0, the last launch of every stream an end event — the call's last launch ev1, the others
-// their stream's join event.  Marker packets of their own in front of the first kernel and behind the last cost the driver's
-// 20-launch region a few microseconds each.
-static hipError_t launch_chained(tetris_batch* b, const RolloutCall& call, int l, hipStream_t st) {
-    const int depth = b->chain_depth;
-    hipEvent_t const stop = l < call.launches - depth ? nullptr : (l == call.launches - 1 ? b->ev1 : b->chain_ev[l % depth]);
-    return launch_chain_kernel(b, chain_is_fused(b, call.steps_per_launch), chain_waves(b), st, rollout_args(b, call, l), l == 0 ? b->ev0 : nullptr, stop);
-}
-
-// Long chained calls are enqueued by one host thread PER CHAIN STREAM.  A launch costs the host 2.7-4.0 us depending on the process
-// (the core its thread sits on, what the box's other tenants do) and the GPU needs one every 4.03 us: in the slower processes one
-// thread could not keep up and the rollout ran at the host's pace, 4.2-4.6 us per launch (profiles/r03/host_pace.txt).  Every
-// stream's launches are independent of the others' on the host side — epoch and step of launch l follow from l — so each thread
-// enqueues every depth-th launch from `prefix` on, on its own stream with its own run-ahead gate.  The calling thread serves stream
-// 0 and keeps looking at the flag words (RNG-table extensions).
-constexpr int ENQUEUE_THREADS_MIN = 256;         // calls of at least this many launches
-static int enqueue_threaded(tetris_batch* b, const RolloutCall& call, int prefix, int group) {
-    const int launches = call.launches, depth = b->chain_depth, wgroup = std::max(8, group / depth);
-    b->chain_epoch = call.epoch0 + (uint32_t)launches;      // (a launch that fails to be enqueued leaves waves waiting: they give up, chain_recover finishes the call)
-    b->chain_pending = true;
-    std::atomic<int> failed{0}, finished{0};
-    hipError_t worker_err[CHAIN_STREAMS] = {};
-    int flag_rc = TETRIS_OK;
-    auto worker = [&](int k) {
-        hipError_t err = hipSetDevice(b->device);
-        int mine = 0, slot = 0;
-        bool pending[2] = {false, false};
-        hipStream_t const st = b->chain_stream[k];
-        for (int l = prefix + k; l < launches && err == hipSuccess && !failed.load(std::memory_order_relaxed); l += depth) {
-            if (k == 0 && !flag_rc && (flag_rc = service_flags(b))) { failed.store(1); break; }      // (this thread: the flag words, as ever)
-            if (mine >= wgroup) {                            // at most 2 * wgroup + 1 launches of this stream in flight
-                if (pending[slot] && (err = poll_event(b->worker_gate_ev[k][slot], 2000000)) != hipSuccess) break;
-                if ((err = hipEventRecord(b->worker_gate_ev[k][slot], st)) != hipSuccess) break;
-                pending[slot] = true; slot ^= 1; mine = 0;
-            }
-            mine++;
-            err = launch_chained(b, call, l, st);
-        }
-        if (err != hipSuccess) { worker_err[k] = err; failed.store(1); }
-        finished.fetch_add(1);
-    };
-    std::thread th[CHAIN_STREAMS];
-    bool inline_k[CHAIN_STREAMS] = {};
-    for (int k = 1; k < depth; k++) {
-        try { th[k] = std::thread(worker, k); } catch (...) { inline_k[k] = true; }      // (no thread to be had: this one does that stream too)
-    }
-    worker(0);
-    for (int k = 1; k < depth; k++) if (inline_k[k]) worker(k);
-    while (finished.load() < depth) {
-        if (!flag_rc && (flag_rc = service_flags(b))) failed.store(1);
-        for (int spin = 0; spin < 200 && finished.load(std::memory_order_relaxed) < depth; spin++) __builtin_ia32_pause();
-    }
-    for (int k = 0; k < depth; k++) if (th[k].joinable()) th[k].join();
-    if (flag_rc) return flag_rc;
-    for (int k = 0; k < depth; k++)
-        if (worker_err[k] != hipSuccess) return fail(TETRIS_E_HIP, std::string("chained launch (enqueue thread): ") + hipGetErrorString(worker_err[k]));
-    return TETRIS_OK;
-}
-
-// The launches of one chained call on the chain streams: launch l goes to stream l % depth.  `group`: run-ahead of the whole call
-// in launches (gate_launch).  Measurement aid (`prequeue`, TETRIS_PREQUEUE=1; bench.py's `launch_us_gpu_paced`): the chain streams
-// are parked behind a blocker kernel that runs until the host, having enqueued every launch of the call, sets a flag word in pinned
-// memory (or 200 ms have passed), so every launch is queued before the first one starts and the host's launch cost — 2.5-5 us per
-// launch, ~8 us under rocprofv3 — does not enter the period.  No run-ahead gate in such a call (it would wait for the blocker).
-static int rollout_streams(tetris_batch* b, const RolloutCall& call, int group, bool prequeue, Clock::time_point t_entry, float* elapsed_ms) {
-    b->last_direct = false; b->last_affine = false;
-    hipStream_t const home = b->stream;
-    const int launches = call.launches, depth = b->chain_depth;
-    int rc = TETRIS_OK;
-    if (prequeue) {
-        ((volatile uint32_t*)b->flags)[F_GO] = 0;
-        hipLaunchKernelGGL(k_blocker, dim3(1), dim3(64), 0, home, (const uint32_t*)(b->flags + F_GO), 20000000ull);      // <= 200 ms
-        group = 1 << 20;
-    }
-    struct GoGuard {                              // (no return path leaves the blocker waiting for its flag)
-        tetris_batch* b; bool armed;
-        ~GoGuard() { if (armed) ((volatile uint32_t*)b->flags)[F_GO] = 1; }
-    } go_guard{b, prequeue};
-    if (b->home_async || prequeue) {
-        // the chain streams start behind the blocker and the asynchronous work the batch's stream still holds (after a
-        // synchronous call it is empty and nothing has to be ordered)
-        HIP_TRY(hipEventRecord(b->chain_ev[CHAIN_STREAMS], home));
-        for (int k = 0; k < CHAIN_STREAMS; k++) HIP_TRY(hipStreamWaitEvent(b->chain_stream[k], b->chain_ev[CHAIN_STREAMS], 0));
-    }
-    static const bool timing = getenv("TETRIS_TIMING") != nullptr;
-    const Clock::time_point t_begin = Clock::now();
-    double gate_s = 0.0;
-    // (this thread enqueues the first launches of every stream itself, so the GPU has work while the other threads start up)
-    const int prefix = !prequeue && launches >= ENQUEUE_THREADS_MIN ? std::min(launches, 8 * depth) : launches;
-    for (int l = 0; l < prefix; l++) {
-        b->stream = b->chain_stream[l % depth]; b->chain_pending = true;
-        const Clock::time_point t_gate = Clock::now();
-        if ((rc = gate_launch(b, group))) return rc;
-        if (timing) gate_s += seconds(Clock::now() - t_gate);
-        // a launch that does not exist could never publish its epoch: the numbering counts only launches that were enqueued (they
-        // run to their end; ChainGuard waits for them)
-        const hipError_t le = launch_chained(b, call, l, b->stream);
-        if (le != hipSuccess) return fail(TETRIS_E_HIP, std::string("chained launch: ") + hipGetErrorString(le));
-        b->chain_epoch++;
-    }
-    b->stream = home;
-    if (prefix < launches && (rc = enqueue_threaded(b, call, prefix, group))) return rc;
-    // The host waits for the end events by polling them — an interrupt wakes a blocked thread 10-20 us late, and querying a STREAM
-    // makes the runtime push a marker through its queue and wait for it, ~6 us per stream even when it is idle.  Nothing on the GPU
-    // waits for another stream here (a cross-stream join costs the rollout ~15 us at its end); the batch's own stream is ordered
-    // behind the events for whatever comes next.
-    hipStream_t const last = b->chain_stream[(launches - 1) % depth];
-    const int used = std::min(launches, depth);
-    for (int k = 0; k < used; k++) HIP_TRY(hipStreamWaitEvent(home, b->chain_stream[k] != last ? b->chain_ev[k] : b->ev1, 0));
-    if (prequeue) { ((volatile uint32_t*)b->flags)[F_GO] = 1; go_guard.armed = false; }      // everything is queued: go
-    const Clock::time_point t_enq = Clock::now();
-    HIP_TRY(poll_event(b->ev1, 200000));
-    for (int k = 0; k < used; k++)
-        if (b->chain_stream[k] != last) HIP_TRY(poll_event(b->chain_ev[k], 200000));
-    const double ev1_us = seconds(Clock::now() - t_begin) * 1e6;
-    if ((rc = finish_call(b, true))) return rc;   // the end events are behind everything this call enqueued: no stream drains
-    if (elapsed_ms) HIP_TRY(hipEventElapsedTime(elapsed_ms, b->ev0, b->ev1));
-    if (timing) print_stream_timing(launches, gate_s, t_entry, t_begin, t_enq, ev1_us, elapsed_ms);
-    return TETRIS_OK;
-}
-
-// The launches of one chained call through the device's own queues (tetris_aql.h).  Returns with every packet retired.
-// `group`: run-ahead of the whole call in launches (as for gate_launch); b->chain_epoch has not been advanced yet.
-static int rollout_direct(tetris_batch* b, aql::Device* dev, const RolloutCall& call, int group, Clock::time_point t_entry, float* elapsed_ms) {
-    static const bool timing = getenv("TETRIS_TIMING") != nullptr;
-    if (b->home_async) { HIP_TRY(hipStreamSynchronize(b->stream)); }      // what the batch's stream still holds comes first
-    b->last_direct = true; b->direct_used = true;
-    if (timing) fprintf(stderr, "[tetris timing] call entry -> direct dispatch %.1f us\n", seconds(Clock::now() - t_entry) * 1e6);
-    aql::Queues& qs = dev->qs;
-    const int launches = call.launches, depth = b->chain_depth;
-    // one-player batches on queues that deal their blocks round-robin over the XCDs: the XCD-affine kernel (k_chain_affine), whole groups
-    // of eight workgroups, no cache maintenance between a queue's launches
-    const bool fused = chain_is_fused(b, call.steps_per_launch);
-    const aql::Kernel& one = fused ? dev->chain1_fused : dev->chain1, & one_affine = fused ? dev->chain1_fused_affine : dev->chain1_affine;
-    const bool affine = b->use_affine && qs.affine_ok && (b->P == 1 ? one_affine.ok && !one_affine.priv : dev->duo_affine.ok);
-    b->last_affine = affine;
-    const aql::Kernel& kern = affine ? (b->P == 1 ? one_affine : dev->duo_affine) : (b->P == 1 ? one : dev->duo);
-    uint32_t blocks = chain_waves(b);
-    if (affine) blocks = (blocks + 7u) & ~7u;
-    const int wgroup = std::min(aql::SLOTS / 2 - 2, std::max(8, group / depth));
-    // Fences.  The first packet of every queue ACQUIRES at system scope: whatever the host or an earlier kernel wrote (a restore
-    // through the copy engines, a step on the batch's stream) must not be met as a stale line in some XCD's L2.  No packet needs
-    // more than an agent-scope RELEASE: the chained kernels leave no dirty line behind — state and epoch words are written
-    // through (sc1), the counters are atomics performed at the memory side, the flag words live in host memory — and the
-    // host waits for the completion signals.
-    // The affine kernel keeps its state in the XCDs' L2s: its queue's LAST packet releases at system scope (memory is current when the
-    // call returns), and between first and last there is NO cache maintenance at all — except that a packet which re-uses the first
-    // slot of the argument ring acquires at agent scope (the scalar caches may still hold what the slot held 4096 launches ago).
-    const int mid = affine ? HSA_FENCE_SCOPE_NONE : HSA_FENCE_SCOPE_AGENT, last_release = affine ? HSA_FENCE_SCOPE_SYSTEM : HSA_FENCE_SCOPE_AGENT;
-    const Clock::time_point t_begin = Clock::now();
-    uint64_t h_begin = 0, h_seen = 0;
-    if (timing) (void)hsa_system_get_info(HSA_SYSTEM_INFO_TIMESTAMP, &h_begin);
-    b->chain_epoch = call.epoch0 + (uint32_t)launches;       // (a launch that never gets enqueued leaves waves waiting: they give up, chain_recover finishes the call)
-    aql::Pending pd;
-    bool gate_pending[CHAIN_STREAMS][2] = {}, done_armed[CHAIN_STREAMS] = {};
-    int mine[CHAIN_STREAMS] = {}, gate_slot[CHAIN_STREAMS] = {};
-    // whatever happens below, every packet that was written is rung in and retired before this function returns
-    auto drain = [&]() {
-        aql::ring(qs, pd);
-        bool ok = true;
-        for (int k = 0; k < depth; k++) {
-            if (!pd.wrote[k]) continue;
-            if (!done_armed[k]) {          // the call ended early: a barrier packet behind what queue k holds carries its completion signal
-                hsa_signal_store_relaxed(qs.done[k], 1);
-                aql::write_barrier(qs, pd, k, qs.done[k]);
-                done_armed[k] = true;
-                aql::ring(qs, pd);
-            }
-            ok = aql::wait_signal(qs.done[k]) && ok;
-        }
-        return ok;
-    };
-    struct DrainGuard { decltype(drain)& d; bool armed; ~DrainGuard() { if (armed) (void)d(); } } guard{drain, true};
-    // (An empty barrier packet rung in ahead of the first launch, to wake the idle queues while the host prepares, bought nothing:
-    // 5.12-5.38 us per launch with it, 5.15-5.22 without, driver's flags, alternating processes — profiles/r03/direct_dispatch.txt.)
-    hsa_signal_t start_sig = qs.first, end_sig = qs.done[(launches - 1) % depth];
-    int rc = TETRIS_OK, unflushed = 0;
-    for (int l = 0; l < launches; l++) {
-        const int k = l % depth;
-        if ((rc = service_flags(b))) return rc;
-        hsa_signal_t sig{};
-        const bool first_on_queue = l < depth, last_on_queue = l >= launches - depth;
-        if (last_on_queue) { hsa_signal_store_relaxed(qs.done[k], 1); sig = qs.done[k]; done_armed[k] = true; if (l == 0) start_sig = sig; }
-        else if (l == 0) { hsa_signal_store_relaxed(qs.first, 1); sig = qs.first; }
-        else if (mine[k] >= wgroup) {                    // at most 2 * wgroup + 1 packets of this queue outstanding
-            const int sl = gate_slot[k];
-            if (gate_pending[k][sl]) { aql::ring(qs, pd); if (!aql::wait_signal(qs.gate[k][sl])) return fail(TETRIS_E_HIP, "direct dispatch: a flow-control signal never came"); }
-            hsa_signal_store_relaxed(qs.gate[k][sl], 1);
-            sig = qs.gate[k][sl]; gate_pending[k][sl] = true; gate_slot[k] = sl ^ 1; mine[k] = 0;
-        }
-        mine[k]++;
-        KArgs a = rollout_args(b, call, l);
-        const bool ring_wraps = qs.issued[k].load() % aql::SLOTS == 0;
-        a.xcd_base = qs.xcd_base[k] + b->xcd_skew; a.xcd_slot = (uint32_t)k;
-        aql::write_dispatch(qs, pd, k, kern, &a, sizeof a, blocks, first_on_queue ? HSA_FENCE_SCOPE_SYSTEM : (ring_wraps ? HSA_FENCE_SCOPE_AGENT : mid),
-                            last_on_queue ? last_release : mid, sig);
-        // the first launches go out one by one (the GPU is idle), later ones eight at a time (one fence + read back per eight)
-        if (++unflushed >= 8 || l < 2 * depth || l == launches - 1) { aql::ring(qs, pd); unflushed = 0; }
-    }
-    b->chain_pending = true;
-    const Clock::time_point t_enq = Clock::now();
-    guard.armed = false;
-    if (!drain()) return fail(TETRIS_E_HIP, "direct dispatch: a completion signal never came");
-    b->chain_pending = false;
-    const Clock::time_point t_seen = Clock::now();
-    const double seen_us = seconds(t_seen - t_begin) * 1e6;
-    if (timing) (void)hsa_system_get_info(HSA_SYSTEM_INFO_TIMESTAMP, &h_seen);
-    float ms_events = 0.0f;
-    hsa_amd_profiling_dispatch_time_t t0{}, t1{};
-    if (hsa_amd_profiling_get_dispatch_time(dev->gpu, start_sig, &t0) == HSA_STATUS_SUCCESS &&
-        hsa_amd_profiling_get_dispatch_time(dev->gpu, end_sig, &t1) == HSA_STATUS_SUCCESS && t1.end >= t0.start)
-        ms_events = (float)((double)(t1.end - t0.start) * 1e3 / (double)dev->ts_freq);
-    if (affine)                                 // where the queues dealt from in this call (block 0 of every launch says): what the next call expects
-        for (int k = 0; k < depth; k++) {
-            const uint32_t seen = ((volatile uint32_t*)b->flags)[F_XCC0 + k];
-            if (seen & 0x100u) { qs.xcd_base[k] = seen & 7u; ((volatile uint32_t*)b->flags)[F_XCC0 + k] = 0; }
-        }
-    const bool was_misplaced = ((volatile uint32_t*)b->flags)[F_PLACE] != 0;
-    if ((rc = finish_call(b, true))) return rc;
-    if (affine && !was_misplaced) b->affine_failures = 0;
-    if (elapsed_ms) *elapsed_ms = ms_events;
-    if (timing) {
-        const double tick_us = 1e6 / (double)dev->ts_freq;
-        fprintf(stderr, "[tetris timing] %d launches, direct dispatch: host enqueue %.2f us/launch, last signal seen %.1f us after the first enqueue, between first start and last end %.1f us; "
-                "first enqueue -> first start %.1f us, last end -> seen %.1f us, after that %.1f us\n",
-                launches, seconds(t_enq - t_begin) * 1e6 / launches, seen_us, ms_events * 1e3, (double)(int64_t)(t0.start - h_begin) * tick_us,
-                (double)(int64_t)(h_seen - t1.end) * tick_us, seconds(Clock::now() - t_seen) * 1e6);
-    }
-    return TETRIS_OK;
-}
-
-int tetris_rollout_launch(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,
-                          int ms, float* elapsed_ms) {
-    const Clock::time_point t_entry = Clock::now();
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = rollout_launch_check(launches, steps_per_launch))) return rc;
-    // A step may consume 2 piece draws per player, and the host learns of a board that came close to the end of the RNG
-    // tables only through the flag words, up to 2 * GATE_GROUP + 1 launches late (gate_launch): the low-water margin
-    // covers what those launches can consume.  Nothing in this loop waits for the GPU unless the host runs that far ahead.
-    struct MarginGuard {                          // every return path below puts the margin back
-        tetris_batch* b; uint32_t saved;
-        ~MarginGuard() { b->margin = saved; }
-    } margin_guard{b, b->margin};
-    int group = steps_per_launch ? GATE_GROUP / steps_per_launch : GATE_GROUP;       // fused launches: fewer of them in flight
-    group = group < 1 ? 1 : group;
-    const uint32_t need = (uint32_t)(2 * steps_per_launch * (2 * group + 2) + 16);
-    if (b->margin < need) b->margin = need;
-    // batches on their own stream: chained launches (k_chain / k_duo<.., true>) — consecutive launches rotate over CHAIN_STREAMS
-    // streams and each wave waits for its own predecessor only, not for the slowest wave of the whole previous launch.
-    // Only when CHAIN_STREAMS launches fit on the device together (chain_fits): a waiting wave keeps its slot, so a launch whose waves
-    // wait must never be able to keep its predecessor's waves from being dispatched.
-    const bool chained = rollout_chained(b, steps_per_launch) && chain_acquire(b);
-    // Every way out of a chained call — errors included — first waits until the chain streams are idle and only then gives up the
-    // device's chaining slot: another batch that took it while launches of this one were still in flight would put more than
-    // chain_depth launches on the device (chain_fits counts on that bound).
-    struct ChainGuard {
-        tetris_batch* b; bool held; hipStream_t home;
-        ~ChainGuard() {
-            b->stream = home;                     // (base_args / launch_game / gate_launch work on b->stream)
-            if (!held) return;
-            if (b->chain_pending)
-                for (int k = 0; k < CHAIN_STREAMS; k++) (void)hipStreamSynchronize(b->chain_stream[k]);
-            chain_release(b);
-        }
-    } chain_guard{b, chained, b->stream};
-    RolloutCall call{0, first_step, steps_per_launch, policy_seed, ms, launches, chained};
-    if (!chained) return rollout_plain(b, call, group, t_entry, elapsed_ms);
-    // (a call that long could not be numbered below the CHAIN_ABANDONED bit even from 0; nothing has been enqueued yet)
-    if ((uint32_t)launches >= CHAIN_EPOCH_MAX) return fail(TETRIS_E_ARG, "a chained call takes fewer than 0x7FFF0000 launches");
-    if (b->chain_epoch + (uint32_t)launches >= CHAIN_EPOCH_MAX || b->chain_epoch + (uint32_t)launches < b->chain_epoch) {
-        // epoch numbers stay below the CHAIN_ABANDONED bit: restart the numbering (every chain stream is idle between calls)
-        HIP_TRY(hipMemsetAsync(b->d_chain, 0, (((size_t)b->N + 15) / 16) * sizeof(uint32_t) * CHAIN_STRIDE, b->stream));
-        b->chain_epoch = 0;
-        b->home_async = true;
-    }
-    call.epoch0 = b->chain_epoch;
-    b->chain_call = call;
-    const bool prequeue = getenv("TETRIS_PREQUEUE") != nullptr && launches <= 600;       // (read per call)
-    if (!prequeue && b->direct_min > 0) {
-        // the device's own queues (tetris_aql.h); anything that keeps them from being set up switches them off for this batch.  They
-        // are made by the first chained call of ANY length (loading the code object takes ~15 ms: a warm-up call's business,
-        // not that of the first long call).
-        aql::Device* dev = aql::device_for(b->device);
-        std::string why = dev->why;
-        if (!(dev->ok && aql::make_queues(dev, why))) {
-            b->direct_min = 0;
-            if (getenv("TETRIS_TIMING")) fprintf(stderr, "[tetris] direct dispatch is off: %s\n", why.c_str());
-        } else if (aql::calibrate_affine(dev), launches >= b->direct_min)       // (measured once, by whichever chained call comes first)
-            return rollout_direct(b, dev, call, group, t_entry, elapsed_ms);
-    }
-    return rollout_streams(b, call, group, prequeue, t_entry, elapsed_ms);
-}
-
-}  // extern "C"
-
-// The counters of ONE rollout call (tetris_rollout_random, tetris_rollout_policy).  The per-game words are cumulative and wrap at
-// 2^32 — a game passes 2^32 env-steps after a few hours —, so the difference of two tetris_rollout_totals sums is wrong by 2^32 for
-// every word that wraps during the call.  begin: a device copy of the words [4][N]; end: (now - then) mod 2^32 per game, summed
-// in 64 bits (k_totals_since) — exact while no single game counts 2^32 within the call.  Both are synchronous, on the batch's
-// stream, outside the event-timed region and outside tetris_rollout_launch.
-static int rollout_counters_begin(tetris_batch* b) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if (!b->d_words_before) HIP_TRY(hipMalloc((void**)&b->d_words_before, (size_t)4 * b->N * sizeof(uint32_t)));
-    hipLaunchKernelGGL(k_policy_totals, dim3((unsigned)((b->N + 255) / 256)), dim3(256), 0, b->stream, geo_of_batch(b), b->d_words_before);
-    HIP_TRY(hipGetLastError());
-    return finish_call(b);
-}
-static int rollout_counters_end(tetris_batch* b, uint64_t counters[4]) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(b->d_counters, 0, 8 * sizeof(unsigned long long), b->stream));
-    const int tot_blocks = b->N >= 65536 ? 64 : (b->N + 1023) / 1024;
-    hipLaunchKernelGGL(k_totals_since, dim3(tot_blocks), dim3(256), 0, b->stream, geo_of_batch(b), (const uint32_t*)b->d_words_before, b->d_counters);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_counters, b->d_counters, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
-    if ((rc = finish_call(b))) return rc;
-    for (int k = 0; k < 4; k++) counters[k] += b->h_counters[k];
-    return TETRIS_OK;
-}
-
-extern "C" {
-
-int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,
-                          int ms, uint64_t counters[4], float* elapsed_ms) {
-    int rc;
-    if (counters && (rc = rollout_counters_begin(b))) return rc;
-    if ((rc = tetris_rollout_launch(b, launches, steps_per_launch, policy_seed, first_step, ms, elapsed_ms))) return rc;
-    if (counters && (rc = rollout_counters_end(b, counters))) return rc;
-    return TETRIS_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- heuristic policy: features, choice, step, rollout (tetris_policy.h)
 // k_policy_eval: grid (ceil(N / 64), 40): a wave = 64 consecutive games of one candidate c = blockIdx.y, so that the state loads
 // and the feature / score stores of a wave are coalesced rows (as k_plan_sim).  One wave per workgroup with its own LDS copy of
 // the shape table.
@@ -2851,344 +971,11 @@ __global__ __launch_bounds__(256) void k_policy_pick(PolicyArgs pa) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < pa.a.n) policy_pick_lane(pa, i);
 }
-// (k_policy_totals: beside k_totals)
 
-static PolicyArgs policy_args(tetris_batch* b, const uint8_t* d_player, const int16_t* d_weights, int per_game, int ms) {
-    return policy_args(base_args(b, b->N, nullptr), d_player, d_weights, per_game, ms, b->d_policy_scores);
-}
+// ============================================================================ host side
+// (headers of this translation unit only, in dependency order: they launch the kernels above)
 
-static int policy_scores_buffer(tetris_batch* b) {
-    if (!b->d_policy_scores) HIP_TRY(hipMalloc((void**)&b->d_policy_scores, (size_t)POLICY_CANDIDATES * b->N * sizeof(int32_t)));
-    return TETRIS_OK;
-}
-
-static dim3 policy_eval_grid(const tetris_batch* b) { return dim3((unsigned)((b->N + 63) / 64), (unsigned)POLICY_CANDIDATES); }
-
-// the 40 scores of every game -> b->d_policy_scores
-static int launch_policy_scores(tetris_batch* b, const PolicyArgs& pa) {
-    hipLaunchKernelGGL((k_policy_eval<false>), policy_eval_grid(b), dim3(64), 0, b->stream, pa);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-// which: as launch_policy_step (tetris_game_kernel.h)
-static int launch_policy_step_kernel(tetris_batch* b, int which, const PolicyArgs& pa) {
-    const dim3 grid((unsigned)((b->N + 63) / 64));
-    const bool here = with_shape<1, 2>(b->P, b->tint != 0, [&](auto P, auto TINT) { launch_policy_step<P(), TINT()>(which, grid, b->stream, pa); });
-    if (!here && tetris_launch_policy_multi(b->P, b->tint, which, grid, b->stream, pa)) return fail(TETRIS_E_ARG, "no policy kernel for this player count");
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-extern "C" {
-
-int tetris_rt_features_dev(tetris_batch* b, const uint8_t* d_player, int16_t* d_features) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = policy_check(shape_of(b), "tetris_rt_features_dev", !d_features, "features is NULL"))) return rc;
-    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    PolicyArgs pa = policy_args(b, d_player, nullptr, 0, 0);
-    pa.features = d_features;
-    hipLaunchKernelGGL((k_policy_eval<true>), policy_eval_grid(b), dim3(64), 0, b->stream, pa);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_policy_rt_dev(tetris_batch* b, const uint8_t* d_player, const int16_t* d_weights, int per_game, uint8_t* d_rot,
-                         uint8_t* d_trans, int32_t* d_score) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = policy_check(shape_of(b), "tetris_policy_rt_dev", !d_weights || !d_rot || !d_trans, "weights/rot/trans are NULL"))) return rc;
-    if ((rc = policy_scores_buffer(b))) return rc;
-    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    PolicyArgs pa = policy_args(b, d_player, d_weights, per_game, 0);
-    pa.rot = d_rot; pa.trans = d_trans; pa.score = d_score;
-    if ((rc = launch_policy_scores(b, pa))) return rc;
-    hipLaunchKernelGGL(k_policy_pick, dim3((unsigned)((b->N + 255) / 256)), dim3(256), 0, b->stream, pa);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_step_policy_dev(tetris_batch* b, const uint8_t* d_player, const int16_t* d_weights, int per_game, int ms, int flags,
-                           uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead, uint8_t* d_rot, uint8_t* d_trans) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = policy_check(shape_of(b), "tetris_step_policy_dev", !d_weights, "weights is NULL", flags))) return rc;
-    if ((rc = policy_scores_buffer(b))) return rc;
-    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    PolicyArgs pa = policy_args(b, d_player, d_weights, per_game, ms);
-    pa.a.done = d_done; pa.a.lines = d_lines; pa.a.dead = d_dead;
-    pa.rot = d_rot; pa.trans = d_trans;
-    if ((rc = launch_policy_scores(b, pa))) return rc;
-    return launch_policy_step_kernel(b, (flags & TETRIS_STEP_AUTO_RESET) ? 1 : 0, pa);
-}
-
-int tetris_rollout_game_totals_dev(tetris_batch* b, uint32_t* d_totals) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = policy_check(shape_of(b), "tetris_rollout_game_totals_dev", !d_totals, "totals is NULL"))) return rc;
-    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    hipLaunchKernelGGL(k_policy_totals, dim3((unsigned)((b->N + 255) / 256)), dim3(256), 0, b->stream, geo_of_batch(b), d_totals);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-// The launches of tetris_rollout_policy, un-chained on the batch's stream.  One step per launch: the spread mapping (the scores of
-// all 40 N candidates, then one lane per game that chooses and steps); more: one launch whose lanes evaluate their own candidates.
-static int rollout_policy_launches(tetris_batch* b, int launches, int steps_per_launch, const int16_t* d_weights, int per_game,
-                                   uint64_t first_step, int ms, float* elapsed_ms) {
-    // (the margin arithmetic of tetris_rollout_launch: a step may consume 2 piece draws per player, and the host sees a request
-    // to extend the tables up to 2 * group + 1 launches late)
-    struct MarginGuard {
-        tetris_batch* b; uint32_t saved;
-        ~MarginGuard() { b->margin = saved; }
-    } margin_guard{b, b->margin};
-    int group = GATE_GROUP / steps_per_launch;
-    group = group < 1 ? 1 : group;
-    const uint32_t need = (uint32_t)(2 * steps_per_launch * (2 * group + 2) + 16);
-    if (b->margin < need) b->margin = need;
-    int rc = TETRIS_OK;
-    HIP_TRY(hipEventRecord(b->ev0, b->stream));
-    for (int l = 0; l < launches; l++) {
-        if ((rc = gate_launch(b, group))) return rc;
-        PolicyArgs pa = policy_args(b, nullptr, d_weights, per_game, ms);
-        pa.a.steps = steps_per_launch;
-        pa.a.first_step = first_step + (uint64_t)l * (uint64_t)steps_per_launch;
-        if (steps_per_launch == 1) {
-            pa.fixed_player = (int)(pa.a.first_step % (uint64_t)b->P);      // the evaluation kernel's acting player: step mod P
-            if ((rc = launch_policy_scores(b, pa))) return rc;
-            if ((rc = launch_policy_step_kernel(b, 2, pa))) return rc;
-        } else if ((rc = launch_policy_step_kernel(b, 3, pa))) return rc;
-    }
-    HIP_TRY(hipEventRecord(b->ev1, b->stream));
-    HIP_TRY(poll_event(b->ev1, 200000));
-    if ((rc = finish_call(b, true))) return rc;   // the end event is behind everything this call enqueued
-    if (elapsed_ms) HIP_TRY(hipEventElapsedTime(elapsed_ms, b->ev0, b->ev1));
-    return TETRIS_OK;
-}
-
-int tetris_rollout_policy(tetris_batch* b, int launches, int steps_per_launch, const int16_t* d_weights, int per_game,
-                          uint64_t first_step, int ms, uint64_t counters[4], float* elapsed_ms) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = rollout_policy_check(shape_of(b), d_weights, launches, steps_per_launch))) return rc;
-    if ((rc = policy_scores_buffer(b))) return rc;
-    if (counters && (rc = rollout_counters_begin(b))) return rc;
-    if ((rc = rollout_policy_launches(b, launches, steps_per_launch, d_weights, per_game, first_step, ms, elapsed_ms))) return rc;
-    if (counters && (rc = rollout_counters_end(b, counters))) return rc;      // (what this call did, whatever the words held: as tetris_rollout_random)
-    return TETRIS_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- acting on a network's evaluation (tetris_act.h)
-static dim3 act_grid(const tetris_batch* b) { return dim3((unsigned)((b->N + ACT_BLOCK - 1) / ACT_BLOCK)); }
-
-extern "C" {
-
-int tetris_select_eval_dev(tetris_batch* b, const tetris_act_eval* e) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    ActArgs aa;
-    if ((rc = act_args(shape_of(b), e, "tetris_select_eval_dev", aa))) return rc;
-    if ((rc = gate_launch(b, GATE_GROUP))) return rc;
-    aa.a = base_args(b, b->N, nullptr);          // (behind the gate: it may have extended the RNG tables)
-    aa.a.steps = 1;
-    hipLaunchKernelGGL((k_act_select<256>), act_grid(b), dim3(256), 0, b->stream, aa);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_step_eval_dev(tetris_batch* b, const tetris_act_eval* e, int ms, int flags, uint8_t* d_done, uint8_t* d_lines,
-                         uint8_t* d_dead) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = step_eval_check(flags))) return rc;
-    // two launches: the step fused behind the selection in one kernel took 1.6-2.2 times as long
-    if ((rc = tetris_select_eval_dev(b, e))) return rc;
-    return tetris_step_rt_dev_ex(b, e->d_rot, e->d_trans, e->d_player, ms, d_done, d_lines, d_dead, flags);
-}
-
-int tetris_step_eval_observe_dev(tetris_batch* b, const tetris_act_eval* e, int ms, int flags, uint8_t* d_done, uint8_t* d_lines,
-                                 uint8_t* d_dead, const uint8_t* d_next_player, uint8_t* d_visual, uint8_t* d_vector,
-                                 uint8_t* d_obs_piece) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = step_eval_observe_check(shape_of(b), flags, d_visual, d_vector, d_obs_piece))) return rc;
-    if ((rc = tetris_select_eval_dev(b, e))) return rc;
-    return tetris_step_rt_observe_dev(b, e->d_rot, e->d_trans, e->d_player, ms, d_done, d_lines, d_dead, flags, d_next_player,
-                                      d_visual, d_vector, d_obs_piece);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- trajectory windows (tetris_traj.h)
-extern "C" {
-
-int tetris_traj_record_dev(tetris_batch* b, const tetris_traj* traj, int row, const tetris_act_eval* e, const uint8_t* d_done,
-                           const uint8_t* d_dead) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    TrajRecordArgs ra;
-    if ((rc = traj_record_args(shape_of(b), traj, row, e, d_done, d_dead, ra))) return rc;
-    hipLaunchKernelGGL((k_traj_record<256>), dim3((unsigned)((b->N + 255) / 256)), dim3(256), 0, b->stream, ra);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_traj_advantages_dev(tetris_batch* b, const tetris_traj* traj, int rows, float gamma, float lambda_adv,
-                               float lambda_value, const float* d_boot, float* d_adv, float* d_target, uint8_t* d_closed) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    TrajAdvArgs aa;
-    if ((rc = traj_adv_args(shape_of(b), traj, rows, gamma, lambda_adv, lambda_value, d_boot, d_adv, d_target, d_closed, aa))) return rc;
-    hipLaunchKernelGGL((k_traj_advantages<TRAJ_THREADS>), dim3((unsigned)((b->N + TRAJ_BLOCK - 1) / TRAJ_BLOCK)), dim3(TRAJ_THREADS), 0,
-                       b->stream, aa);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- a window's states and sample sets (tetris_batch.h)
-extern "C" {
-
-int tetris_traj_observe_dev(tetris_batch* b, const tetris_traj_obs* obs, int row, const uint8_t* d_player) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    TrajObserveArgs oa;
-    if ((rc = traj_observe_args(shape_of(b), geo_of_batch(b), obs, row, d_player, oa))) return rc;
-    b->home_async = true;
-    hipLaunchKernelGGL((k_traj_observe<256>), dim3((unsigned)((b->N + 255) / 256), (unsigned)b->P), dim3(256), 0, b->stream, oa);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_traj_select_dev(tetris_batch* b, const uint8_t* d_mask, int rows, int flags, int32_t* d_index, long long cap,
-                           int32_t* d_count) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    TrajSelectArgs sa;
-    if ((rc = traj_select_args(shape_of(b), d_mask, rows, flags, d_index, cap, d_count, sa))) return rc;
-    if ((size_t)sa.nblocks + 1 > b->select_blocks_cap) {
-        if (b->d_select_blocks) { HIP_TRY(hipStreamSynchronize(b->stream)); (void)hipFree(b->d_select_blocks); }
-        b->d_select_blocks = nullptr; b->select_blocks_cap = 0;
-        HIP_TRY(hipMalloc((void**)&b->d_select_blocks, ((size_t)sa.nblocks + 1) * sizeof(int32_t)));
-        b->select_blocks_cap = (size_t)sa.nblocks + 1;
-    }
-    sa.blocks = b->d_select_blocks;
-    b->home_async = true;
-    const dim3 grid((unsigned)sa.nblocks), block(SELECT_THREADS);
-    hipLaunchKernelGGL((k_select_count<SELECT_THREADS>), grid, block, 0, b->stream, sa);
-    hipLaunchKernelGGL((k_select_scan<SELECT_THREADS>), dim3(1), block, 0, b->stream, sa);
-    hipLaunchKernelGGL((k_select_scatter<SELECT_THREADS>), grid, block, 0, b->stream, sa);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_traj_batch_dev(tetris_batch* b, const tetris_traj* traj, const tetris_traj_obs* obs, const float* d_adv_in,
-                          const float* d_target_in, const int32_t* d_index, int M, const tetris_traj_batch* out) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    TrajBatchArgs ba;
-    if ((rc = traj_batch_args(shape_of(b), traj, obs, d_adv_in, d_target_in, d_index, M, out, ba))) return rc;
-    if (M == 0) return TETRIS_OK;
-    b->home_async = true;
-    const size_t lds = ba.visual ? (size_t)BATCH_BLOCK * b->H * NCOL : 0;          // at most 19 840 bytes (31 rows)
-    hipLaunchKernelGGL((k_traj_batch<BATCH_BLOCK>), dim3((unsigned)((M + BATCH_BLOCK - 1) / BATCH_BLOCK), (unsigned)b->P), dim3(BATCH_BLOCK), lds,
-                       b->stream, ba);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- experience replay (tetris_replay.h)
-// a scratch array of the batch, grown on demand: the stream is drained before an array it may still use is freed
-static int grow_scratch(tetris_batch* b, uint32_t*& p, size_t& cap, size_t words) {
-    if (words <= cap) return TETRIS_OK;
-    if (p) { HIP_TRY(hipStreamSynchronize(b->stream)); (void)hipFree(p); }
-    p = nullptr; cap = 0;
-    HIP_TRY(hipMalloc((void**)&p, words * sizeof(uint32_t)));
-    cap = words;
-    return TETRIS_OK;
-}
-
-// four passes from (key, pos) back into (key, pos), through (okey, opos)
-static void launch_sort(tetris_batch* b, SortArgs so, uint32_t* key, uint32_t* pos, uint32_t* okey, uint32_t* opos) {
-    const dim3 tiles((unsigned)so.ntiles), block(SORT_THREADS);
-    for (int pass = 0; pass < 4; pass++) {
-        sort_pass(so, pass, key, pos, okey, opos);
-        hipLaunchKernelGGL((k_sort_histogram<SORT_THREADS>), tiles, block, 0, b->stream, so);
-        hipLaunchKernelGGL((k_sort_scan<SORT_SCAN_SPAN>), dim3(SORT_RADIX), dim3(SORT_SCAN_SPAN), 0, b->stream, so);
-        hipLaunchKernelGGL((k_sort_scatter<SORT_THREADS>), tiles, block, 0, b->stream, so);
-    }
-}
-
-extern "C" {
-
-int tetris_replay_add_dev(tetris_batch* b, const tetris_replay* rp, const tetris_traj* traj, const tetris_traj_obs* obs,
-                          const float* d_adv_in, const float* d_target_in, const float* d_prio_in, const uint8_t* d_mask, int rows,
-                          int flags) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    ReplayAddArgs aa;
-    if ((rc = replay_add_args(shape_of(b), rp, traj, obs, d_adv_in, d_target_in, d_prio_in, d_mask, rows, flags, aa))) return rc;
-    if ((rc = grow_scratch(b, b->d_replay_offsets, b->replay_offsets_cap, (size_t)b->N + 1))) return rc;
-    aa.offsets = b->d_replay_offsets;
-    b->home_async = true;
-    const dim3 grid((unsigned)((b->N + 255) / 256)), block(256);
-    hipLaunchKernelGGL((k_replay_add_count<256>), grid, block, 0, b->stream, aa);
-    hipLaunchKernelGGL((k_replay_add_scan<SELECT_THREADS>), dim3(1), dim3(SELECT_THREADS), 0, b->stream, aa);
-    hipLaunchKernelGGL((k_replay_add_scatter<256>), grid, block, 0, b->stream, aa);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_replay_sample_dev(tetris_batch* b, const tetris_replay* rp, int M, float alpha, float beta, uint32_t seed, uint64_t draw,
-                             int32_t* d_index, float* d_weight, int32_t* d_count, int32_t* d_rank, float* d_key) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    ReplaySampleArgs sa;
-    if ((rc = replay_sample_args(shape_of(b), rp, M, alpha, beta, seed, draw, d_index, d_weight, d_count, d_rank, d_key, sa))) return rc;
-    if ((rc = grow_scratch(b, b->d_replay_sort, b->replay_sort_cap, replay_scratch_words(sa.max_size)))) return rc;
-    const SortArgs so = replay_sample_scratch(sa, b->d_replay_sort);
-    b->home_async = true;
-    const dim3 all((unsigned)((sa.max_size + 255u) / 256u)), block(256);
-    hipLaunchKernelGGL((k_replay_prio_keys<256>), all, block, 0, b->stream, sa);
-    launch_sort(b, so, sa.key_a, sa.pos_a, sa.key_b, sa.pos_b);
-    hipLaunchKernelGGL((k_replay_sample_keys<256>), all, block, 0, b->stream, sa);
-    launch_sort(b, so, sa.key_b, sa.pos_b, sa.key_a, sa.pos_a);
-    hipLaunchKernelGGL((k_replay_emit<256>), dim3((unsigned)((M + 255) / 256 > 0 ? (M + 255) / 256 : 1)), block, 0, b->stream, sa);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_replay_update_prios_dev(tetris_batch* b, const tetris_replay* rp, const int32_t* d_index, const float* d_prio_new, int M) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    ReplayUpdateArgs ua;
-    if ((rc = replay_update_args(shape_of(b), rp, d_index, d_prio_new, M, ua))) return rc;
-    if (M == 0) return TETRIS_OK;
-    b->home_async = true;
-    hipLaunchKernelGGL((k_replay_update<256>), dim3((unsigned)((M + 255) / 256)), dim3(256), 0, b->stream, ua);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-int tetris_replay_gather_dev(tetris_batch* b, const tetris_replay* rp, const int32_t* d_index, int M, int steps,
-                             const tetris_traj_batch* out) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    TrajBatchArgs ba;
-    if ((rc = replay_gather_args(shape_of(b), rp, d_index, M, steps, out, ba))) return rc;
-    if (ba.m == 0) return TETRIS_OK;
-    b->home_async = true;
-    const size_t lds = ba.visual ? (size_t)BATCH_BLOCK * b->H * NCOL : 0;
-    hipLaunchKernelGGL((k_traj_batch<BATCH_BLOCK>), dim3((unsigned)((ba.m + BATCH_BLOCK - 1) / BATCH_BLOCK), (unsigned)b->P), dim3(BATCH_BLOCK), lds,
-                       b->stream, ba);
-    HIP_TRY(hipGetLastError());
-    return TETRIS_OK;
-}
-
-}  // extern "C"
+#include "tetris_lib_batch.h"
+#include "tetris_lib_rollout.h"
+#include "tetris_lib_core.h"
+#include "tetris_lib_agent.h"

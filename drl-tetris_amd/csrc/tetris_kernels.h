@@ -99,7 +99,7 @@ TE_HD void report_status(const KArgs& a, uint32_t st) {
 // A wave's epoch word holds the number of the last launch that finished this wave's games (bits 0..30).  CHAIN_ABANDONED (bit 31)
 // is OR-ed into it by a wave that gave up waiting: the waves of every later launch that see the bit pass it on — they leave their
 // games untouched too — and the host, once everything has drained, finishes the games of such waves un-chained from the epoch the
-// low bits name (tetris_hip.hip: chain_recover).  The bit is set with an atomic OR, never by storing a value the wave has read
+// low bits name (tetris_lib_rollout.h: chain_recover). The bit is set with an atomic OR, never by storing a value the wave has read
 // earlier: the predecessor may publish between the last poll and the give-up, and its epoch must survive.  (Should the predecessor
 // publish AFTER the OR, the bit is overwritten; the next launch's wave then waits for an epoch that never comes, gives up on its
 // own bound and sets the bit again; the word still names the right epoch at every moment.)
@@ -116,7 +116,7 @@ constexpr uint32_t CHAIN_SPIN_LIMIT = 1u << 22;     // default polls before a wa
 // Scoped accesses of the chained kernels' hand-off (vector memory instructions on the global aperture, no wait behind them).
 // st_flag / ld_flag: a flag word of the batch (KArgs::status, pinned host memory) at system scope (`sc0 sc1`).  The host reads
 // F_XCC0 and F_PLACE, which only the XCD-affine kernels write, after the queue's last packet has released at system scope
-// (tetris_hip.hip: rollout_direct, `last_release`).  A give-up (F_CHAIN) can also happen in a direct call without the affine form,
+// (tetris_lib_rollout.h: rollout_direct, `last_release`).  A give-up (F_CHAIN) can also happen in a direct call without the affine form,
 // whose last packet releases at agent scope only: chain_give_up drains that store itself (rare path).
 // st_xcd: the epoch word of the XCD-affine hand-off, a plain store: the line stays in this XCD's L2, where the same wave of the
 // next launch polls it with an `sc1` load (MEM_AFFINE).  A wavefront-scope relaxed atomic store is no promise of the HIP memory
@@ -176,7 +176,7 @@ TE_HD bool chain_wait(const KArgs& a, uint32_t wave, bool marker) {
 
 // Residency census of a chained kernel (a launch with a.steps < 0, the kernel's ordinary resource footprint): every wave counts
 // itself in and then waits until a.epoch waves have done so.  They can only all see the full count if that many waves of THIS
-// kernel are resident on the device at the same time — which is what chaining `depth` launches of it presumes (tetris_hip.hip:
+// kernel are resident on the device at the same time — which is what chaining `depth` launches of it presumes (tetris_lib_rollout.h:
 // chain_fits; MI355X_MICROARCH.md: the occupancy API can be off, verify with a census).  a.chain: [0] count, [CHAIN_STRIDE] != 0 = a
 // wave gave up.
 TE_HD void chain_census(const KArgs& a, bool marker) {
