@@ -50,6 +50,18 @@ class ActEval(C.Structure):
                 ("d_piece", C.c_void_p), ("d_eval", C.c_void_p), ("d_value", C.c_void_p), ("d_entropy", C.c_void_p)]
 
 
+PLAN_OUT_F16 = 4              # TETRIS_PLAN_OUT_F16
+
+
+class PlanEval(C.Structure):
+    """mirrors `struct tetris_plan_eval` (include/tetris_hip.h)"""
+    _fields_ = [("d_phi", C.c_void_p), ("d_state_eval", C.c_void_p), ("n_pieces", C.c_int), ("n_values", C.c_int), ("mode", C.c_int),
+                ("flags", C.c_int), ("sample_seed", C.c_uint32), ("reserved", C.c_uint32), ("draw", C.c_uint64), ("small_fill", C.c_float),
+                ("d_player", C.c_void_p), ("d_count", C.c_void_p), ("d_cols", C.c_void_p), ("max_lists", C.c_int), ("d_choice", C.c_void_p),
+                ("d_piece", C.c_void_p), ("d_prob", C.c_void_p), ("d_probs", C.c_void_p), ("d_value", C.c_void_p), ("d_entropy", C.c_void_p),
+                ("d_delta", C.c_void_p), ("d_sums", C.c_void_p)]
+
+
 class Traj(C.Structure):
     """mirrors `struct tetris_traj` (include/tetris_hip.h)"""
     _fields_ = [("capacity", C.c_int), ("reserved", C.c_int), ("d_action", C.c_void_p), ("d_prob", C.c_void_p), ("d_value", C.c_void_p),
@@ -160,6 +172,9 @@ _SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_plan_deltas_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "tetris_select_lists_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_step_lists_eval_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
     "tetris_rt_features_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_policy_rt_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_step_policy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -473,6 +488,35 @@ class TetrisBatch:
         16-byte aligned, max_lists <= 256."""
         self._check(self.lib.tetris_plan_deltas_dev(self._h, player, count, cols, int(max_lists), float(small_fill),
                                                     (1 if f16 else 0) | (2 if list_major else 0), deltas, sums, small))
+
+    # -- choosing a planning agent's list from phi (include/tetris_hip.h: tetris_select_lists_dev, tetris_step_lists_eval_dev)
+    def plan_eval(self, phi, count, cols, choice, n_pieces=7, f16=False, state_eval=None, n_values=1, value_f16=False, mode="argmax",
+                  player=None, seed=0, draw=0, small_fill=1e-3, max_lists=64, out_f16=False, piece=None, prob=None, probs=None, value=None,
+                  entropy=None, delta=None, sums=None, flags=0):
+        """The argument struct of the two calls below.  Array arguments are raw DEVICE addresses (int / c_void_p) or None.  mode:
+        "argmax" or "pi" (or a number).  phi [N][H][10][n_pieces] float32 (f16: binary16), state_eval [N][n_values]; count int32 [N],
+        cols uint32 [L][P][10][N] as simulate_lists_dev(finalize=False) wrote them; choice int32 [N], piece uint8 [N], prob float32
+        [N], probs float32 [N][L], value float32 [2][N], entropy float32 [N] (PI), delta / sums [N][H][10] float32 (out_f16:
+        binary16); phi / delta / sums 16-byte aligned, max_lists <= 256."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        e = PlanEval()
+        e.d_phi, e.d_state_eval, e.n_pieces, e.n_values = val(phi), val(state_eval), int(n_pieces), int(n_values)
+        e.mode = ACT_MODES[mode] if isinstance(mode, str) else int(mode)
+        e.flags = (1 if f16 else 0) | (2 if value_f16 else 0) | (PLAN_OUT_F16 if out_f16 else 0) | int(flags)
+        e.sample_seed, e.draw, e.small_fill = int(seed) & 0xFFFFFFFF, int(draw), float(small_fill)
+        e.d_player, e.d_count, e.d_cols, e.max_lists = val(player), val(count), val(cols), int(max_lists)
+        e.d_choice, e.d_piece, e.d_prob, e.d_probs = val(choice), val(piece), val(prob), val(probs)
+        e.d_value, e.d_entropy, e.d_delta, e.d_sums = val(value), val(entropy), val(delta), val(sums)
+        return e
+
+    def select_lists_dev(self, e):
+        """The list of every game chosen from the network's phi (e = plan_eval(...)); the games are not changed."""
+        self._check(self.lib.tetris_select_lists_dev(self._h, C.byref(e) if e is not None else None))
+
+    def step_lists_eval_dev(self, e, lens, keys, done, lines, dead, max_keys=48, ms=400, auto_reset=False):
+        """select_lists_dev + step_lists_dev with its choice in one call: done [N], lines / dead [P][N] (each may be None)."""
+        self._check(self.lib.tetris_step_lists_eval_dev(self._h, C.byref(e) if e is not None else None, lens, keys, int(max_keys), int(ms),
+                                                        1 if auto_reset else 0, done, lines, dead))
 
     # -- heuristic policy on the device (include/tetris_hip.h: tetris_rt_features_dev and the four after it).  Array arguments
     # are raw DEVICE addresses (int / c_void_p) or None; weights: int16 [8], or [N][8] with per_game.

@@ -92,16 +92,17 @@ TE_HD float act_pi_weight(float v) { return v > 0.0f ? v : 0.0f; }
 TE_HD float act_unit(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-08f; }       // (w >> 8) * 2^-24, exact
 
 // The inverse-CDF draw over the weights m: the first c whose running sum exceeds u * total; none: the last c with a positive
-// weight; -1: the total is not a positive finite number (the caller takes ARGMAX's choice).
-TE_HD int act_draw(const float* m, int sm, float u) {
+// weight; -1: the total is not a positive finite number (the caller takes ARGMAX's choice).  `count` weights (the 40 candidates;
+// tetris_choose.h: a game's lists); with `clamp` the array holds values v and the weights are act_pi_weight(v).
+TE_HD int act_draw(const float* m, int sm, float u, int count = ACT_CANDIDATES, bool clamp = false) {
     float total = 0.0f;
-    for (int c = 0; c < ACT_CANDIDATES; c++) total += m[c * sm];
+    for (int c = 0; c < count; c++) total += clamp ? act_pi_weight(m[c * sm]) : m[c * sm];
     if (!(total > 0.0f && total < INFINITY)) return -1;
     const float target = u * total;
     float run = 0.0f;
     int last = 0;
-    for (int c = 0; c < ACT_CANDIDATES; c++) {
-        const float w = m[c * sm];
+    for (int c = 0; c < count; c++) {
+        const float w = clamp ? act_pi_weight(m[c * sm]) : m[c * sm];
         run += w;
         if (run > target) return c;
         if (w > 0.0f) last = c;

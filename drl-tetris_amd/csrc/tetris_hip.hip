@@ -945,6 +945,152 @@ __global__ __launch_bounds__(PD_BLOCK) void k_plan_deltas(PlanDeltaArgs da) {
     }
 }
 
+// tetris_select_lists_dev: a workgroup of CHOOSE_THREADS threads takes G consecutive games (tetris_choose.h: the LDS image).
+// What the call costs is reading phi (N x H x 10 x K elements of which one in K is used) and the acting players' column words
+// (N x L x 10); nothing of size N x H x 10 x L exists.
+//   A. the phi planes: consecutive threads take consecutive cells of one game (a stride of K elements in memory, so every cache
+//      line of the games' phi is fetched once) and leave them in LDS, game-minor;
+//   B. the column sums C_c for the small rule, thread = (game, column);
+//   C. the scores: thread = (game g, slice s), lists k = s, s + S, ..: its ten column words are ten independent loads, coalesced
+//      over the games of a slice (d_cols is game-minor); a normal list walks the set bits of after ^ before, one LDS read each;
+//   D. one lane per game: total, q, choice, draw, entropy over at most 256 scores in LDS (choose_decide), the outputs that are one
+//      element per game;
+//   E. d_probs from LDS in memory order; d_sums and d_delta, thread = (game, column): the per-row counts over the normal lists as
+//      bit-sliced counters over the column words (read a second time, from L2), staged through the LDS of the phi planes and
+//      stored in memory order.
+template <int G>
+__device__ __forceinline__ void choose_store_planes(const PlanChooseArgs& ca, void* out, int g0, int ng, int HW, const float* s_plane) {
+    constexpr int LS = G + 1;
+    const size_t base = (size_t)g0 * HW;
+    for (int e = (int)threadIdx.x; e < ng * HW; e += CHOOSE_THREADS) {
+        const int g = e / HW, cell = e - g * HW;
+        choose_store(out, base + e, s_plane[cell * LS + g], ca.out_f16);
+    }
+}
+
+template <int G>
+__global__ __launch_bounds__(CHOOSE_THREADS) void k_plan_choose(PlanChooseArgs ca) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t choose_lds[];
+    constexpr int LS = G + 1, S = CHOOSE_THREADS / G;
+    const int H = ca.a.H, HW = H * NCOL, L = ca.max_lists, P = ca.a.n_players;
+    const size_t n = (size_t)ca.a.n;
+    float* s_phi = reinterpret_cast<float*>(choose_lds);
+    float* s_score = s_phi + HW * LS;
+    float* s_col = s_score + L * LS;
+    int* s_player = reinterpret_cast<int*>(s_col + NCOL * LS);
+    int *s_piece = s_player + G, *s_count = s_piece + G, *s_choice = s_count + G, *s_small = s_choice + G, *s_normal = s_small + G;
+    uint8_t* s_kind = reinterpret_cast<uint8_t*>(s_normal + G);
+    const int t = (int)threadIdx.x, g0 = (int)blockIdx.x * G, ng = imin(G, ca.a.n - g0);
+    const Geo geo = geo_of(ca.a);
+    const uint32_t mask = plan_row_mask(H);
+    if (t < G) {
+        const bool live = t < ng;
+        const int p = live ? safe_player(ca.player, g0 + t, P) : 0;
+        s_player[t] = p;
+        s_piece[t] = live ? act_piece_of(geo, (size_t)(g0 + t), p, ca.K) : 0;
+        s_count[t] = live ? plan_clamp_count(ca.count[g0 + t], L) : 0;
+    }
+    __syncthreads();
+    for (int e = t; e < ng * HW; e += CHOOSE_THREADS) {                                  // A
+        const int g = e / HW, cell = e - g * HW;
+        s_phi[cell * LS + g] = act_element(ca.phi, ((size_t)(g0 + g) * HW + cell) * ca.K + s_piece[g], ca.phi_f16);
+    }
+    __syncthreads();
+    for (int u = t; u < NCOL * G; u += CHOOSE_THREADS) {                                 // B
+        const int g = u % G, c = u / G;
+        if (g < ng) s_col[c * LS + g] = choose_column_sum(s_phi + g, LS, H, c);
+    }
+    __syncthreads();
+    {                                                                                   // C
+        const int g = t % G, s = t / G, i = g0 + g;
+        if (g < ng) {
+            const int p = s_player[g], count = s_count[g];
+            const Ref br = board_ref(geo, p, (size_t)i);
+            uint32_t before[NCOL];
+            TE_UNROLL
+            for (int c = 0; c < NCOL; c++) before[c] = word_at(br, W_COL0 + c) & mask;
+            const float plane_sum = choose_plane_sum(s_col + g, LS);
+            for (int k = s; k < count; k += S) {
+                const uint32_t* src = ca.cols + ((size_t)k * P + p) * NCOL * n + i;
+                uint32_t after[NCOL];
+                TE_UNROLL
+                for (int c = 0; c < NCOL; c++) after[c] = src[(size_t)c * n] & mask;
+                const int kind = plan_list_kind(k, count, plan_list_sum(after, before));
+                s_score[k * LS + g] = choose_score(kind, after, before, s_phi + g, LS, ca.small_fill, plane_sum);
+                s_kind[k * G + g] = (uint8_t)kind;
+            }
+        }
+    }
+    __syncthreads();
+    if (t < ng) {                                                                       // D
+        const int count = s_count[t];
+        int n_small = 0;
+        for (int k = 0; k < count; k++) n_small += s_kind[k * G + t] == PLAN_LIST_SMALL;
+        s_small[t] = n_small;
+        s_normal[t] = count - n_small;
+        float prob, entropy;
+        const int choice = choose_decide(ca, g0 + t, count, s_score + t, LS, prob, entropy);
+        choose_write(ca, g0 + t, s_piece[t], choice, prob, entropy);
+        s_choice[t] = choice;
+    }
+    __syncthreads();
+    if (ca.probs) {                                                                     // E
+        const size_t base = (size_t)g0 * L;
+        for (int e = t; e < ng * L; e += CHOOSE_THREADS) {
+            const int g = e / L, k = e - g * L;
+            ca.probs[base + e] = k < s_count[g] ? s_score[k * LS + g] : 0.0f;
+        }
+    }
+    if (ca.sums) {
+        for (int u = t; u < NCOL * G; u += CHOOSE_THREADS) {
+            const int g = u % G, c = u / G, i = g0 + g;
+            if (g >= ng) continue;
+            const int p = s_player[g], count = s_count[g], n_small = s_small[g], n_normal = s_normal[g];
+            const uint32_t bw = word_at(board_ref(geo, p, (size_t)i), W_COL0 + c) & mask;
+            const uint32_t* src = ca.cols + ((size_t)p * NCOL + c) * n + i;
+            const size_t step = (size_t)P * NCOL * n;
+            uint32_t plane[CHOOSE_COUNT_PLANES];
+            TE_UNROLL
+            for (int j = 0; j < CHOOSE_COUNT_PLANES; j++) plane[j] = 0u;
+#pragma unroll 4
+            for (int k = 0; k < count; k++) {
+                const uint32_t word = src[(size_t)k * step] & mask;
+                uint32_t carry = s_kind[k * G + g] == PLAN_LIST_NORMAL ? word : 0u;
+                TE_UNROLL
+                for (int j = 0; j < CHOOSE_COUNT_PLANES; j++) {
+                    const uint32_t both = plane[j] & carry;
+                    plane[j] ^= carry;
+                    carry = both;
+                }
+            }
+            for (int y = 0; y < H; y++) {
+                uint32_t cnt = 0;
+                TE_UNROLL
+                for (int j = 0; j < CHOOSE_COUNT_PLANES; j++) cnt |= ((plane[j] >> y) & 1u) << j;
+                s_phi[(y * NCOL + c) * LS + g] = plan_sums_value((int)cnt - n_normal * (int)((bw >> y) & 1u), n_small, ca.small_fill);
+            }
+        }
+        __syncthreads();
+        choose_store_planes<G>(ca, ca.sums, g0, ng, HW, s_phi);
+        __syncthreads();
+    }
+    if (ca.delta) {
+        for (int u = t; u < NCOL * G; u += CHOOSE_THREADS) {
+            const int g = u % G, c = u / G, i = g0 + g;
+            if (g >= ng) continue;
+            const int p = s_player[g], count = s_count[g], choice = s_choice[g];
+            const int kind = count > 0 ? (int)s_kind[choice * G + g] : (int)PLAN_LIST_PAST;
+            const uint32_t bw = word_at(board_ref(geo, p, (size_t)i), W_COL0 + c) & mask;
+            uint32_t aw = 0u;
+            if (kind == PLAN_LIST_NORMAL) aw = ca.cols[(((size_t)choice * P + p) * NCOL + c) * n + i] & mask;
+            for (int y = 0; y < H; y++)
+                s_phi[(y * NCOL + c) * LS + g] = plan_delta_value(kind, kind == PLAN_LIST_NORMAL ? plan_cell_delta(aw, bw, y) : 0, ca.small_fill);
+        }
+        __syncthreads();
+        choose_store_planes<G>(ca, ca.delta, g0, ng, HW, s_phi);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_snapshot(Geo geo, int n, const int32_t* idx, uint32_t* blob, int restore) {
     size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < (size_t)n * (NGWORDS + geo.P * geo.nw)) snapshot_body(geo, t, idx, blob, restore);

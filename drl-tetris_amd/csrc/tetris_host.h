@@ -16,6 +16,7 @@
 #include "tetris_plan.h"
 #include "tetris_policy.h"
 #include "tetris_act.h"
+#include "tetris_choose.h"
 #include "tetris_traj.h"
 #include "tetris_batch.h"
 #include "tetris_replay.h"
@@ -328,6 +329,44 @@ static inline int step_eval_observe_check(const HostShape& s, int flags, const u
     if (rc || (rc = step_eval_check(flags))) return rc;
     if (s.P > 2) return fail(TETRIS_E_ARG, PACKED_ONE_OR_TWO);
     return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- choosing a planning agent's list from phi (tetris_choose.h)
+// the argument checks, then the kernel arguments (all but ca.a)
+static inline int plan_choose_args(const HostShape& s, const tetris_plan_eval* e, const char* what, PlanChooseArgs& ca) {
+    if (!e) return fail(TETRIS_E_ARG, "the argument struct is NULL");
+    int rc = not_on_split(s, what);
+    if (rc) return rc;
+    if (!e->d_phi || !e->d_count || !e->d_cols || !e->d_choice) return fail(TETRIS_E_ARG, "phi/count/cols/choice are NULL");
+    if (e->n_pieces != 1 && e->n_pieces != 7) return fail(TETRIS_E_ARG, "n_pieces must be 1 or 7");
+    if (e->d_state_eval && e->n_values != 1 && e->n_values != 7 && e->n_values != 8) return fail(TETRIS_E_ARG, "n_values must be 1, 7 or 8");
+    if (e->d_value && !e->d_state_eval) return fail(TETRIS_E_ARG, "value needs state_eval");
+    if (e->mode != TETRIS_ACT_ARGMAX && e->mode != TETRIS_ACT_PI) return fail(TETRIS_E_ARG, "unknown mode (argmax or pi)");
+    if (e->flags & ~(TETRIS_ACT_F16 | TETRIS_ACT_VALUE_F16 | TETRIS_PLAN_OUT_F16)) return fail(TETRIS_E_ARG, "unknown flag");
+    if (e->d_entropy && e->mode != TETRIS_ACT_PI) return fail(TETRIS_E_ARG, "entropy is an output of the PI mode");
+    if (e->max_lists < 1 || e->max_lists > CHOOSE_MAX_LISTS) return fail(TETRIS_E_ARG, "1 <= max_lists <= 256");
+    if ((((uintptr_t)e->d_phi) | ((uintptr_t)e->d_delta) | ((uintptr_t)e->d_sums)) & 15u) return fail(TETRIS_E_ARG, "phi / delta / sums must be 16-byte aligned");
+    if (((uintptr_t)e->d_cols) & 3u) return fail(TETRIS_E_ARG, "cols must be 4-byte aligned");
+    memset(&ca, 0, sizeof ca);
+    ca.player = e->d_player; ca.count = e->d_count; ca.cols = e->d_cols;
+    ca.max_lists = e->max_lists; ca.small_fill = e->small_fill;
+    ca.phi = e->d_phi; ca.state_eval = e->d_state_eval;
+    ca.K = e->n_pieces; ca.V = e->d_state_eval ? e->n_values : 1;
+    ca.phi_f16 = (e->flags & TETRIS_ACT_F16) ? 1 : 0; ca.value_f16 = (e->flags & TETRIS_ACT_VALUE_F16) ? 1 : 0;
+    ca.out_f16 = (e->flags & TETRIS_PLAN_OUT_F16) ? 1 : 0;
+    ca.mode = e->mode;
+    ca.seed = e->sample_seed; ca.draw_lo = (uint32_t)e->draw; ca.draw_hi = (uint32_t)(e->draw >> 32);
+    ca.choice = e->d_choice; ca.piece = e->d_piece; ca.prob = e->d_prob; ca.probs = e->d_probs;
+    ca.value = e->d_value; ca.entropy = e->d_entropy; ca.delta = e->d_delta; ca.sums = e->d_sums;
+    return TETRIS_OK;
+}
+// tetris_step_lists_eval_dev: both halves' rules before the first half runs
+static inline int step_lists_eval_check(const HostShape& s, const tetris_plan_eval* e, const uint8_t* d_lens, const uint8_t* d_keys, int max_keys,
+                                        int flags) {
+    PlanChooseArgs ca;
+    int rc = plan_choose_args(s, e, "tetris_step_lists_eval_dev", ca);
+    if (rc) return rc;
+    return step_lists_check(s, e->d_choice, e->d_count, d_lens, d_keys, e->max_lists, max_keys, flags);
 }
 
 // ---------------------------------------------------------------- trajectory windows (tetris_traj.h)

@@ -240,6 +240,31 @@ int tetris_step_eval_observe_dev(tetris_batch* b, const tetris_act_eval* e, int 
                                       d_visual, d_vector, d_obs_piece);
 }
 
+// ---------------------------------------------------------------- choosing a planning agent's list from phi (tetris_choose.h)
+int tetris_select_lists_dev(tetris_batch* b, const tetris_plan_eval* e) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    PlanChooseArgs ca;
+    if ((rc = plan_choose_args(shape_of(b), e, "tetris_select_lists_dev", ca))) return rc;
+    if ((rc = enqueue(b, Enqueue::STEPS))) return rc;
+    ca.a = base_args(b, b->N, nullptr);          // (behind the gate: it may have extended the RNG tables)
+    ca.a.steps = 1;
+    const int G = choose_games_per_block(b->H, ca.max_lists);
+    const size_t lds = choose_lds_bytes(G, b->H, ca.max_lists);
+    const dim3 grid(blocks_for(b->N, G)), block(CHOOSE_THREADS);
+    return G == 32 ? launch(b, k_plan_choose<32>, grid, block, lds, ca) : launch(b, k_plan_choose<16>, grid, block, lds, ca);
+}
+
+int tetris_step_lists_eval_dev(tetris_batch* b, const tetris_plan_eval* e, const uint8_t* d_lens, const uint8_t* d_keys, int max_keys,
+                               int ms, int flags, uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = step_lists_eval_check(shape_of(b), e, d_lens, d_keys, max_keys, flags))) return rc;
+    if ((rc = tetris_select_lists_dev(b, e))) return rc;
+    return tetris_step_lists_dev(b, e->d_player, e->d_choice, e->d_count, d_lens, d_keys, e->max_lists, max_keys, ms, flags, d_done,
+                                 d_lines, d_dead);
+}
+
 // ---------------------------------------------------------------- trajectory windows (tetris_traj.h)
 int tetris_traj_record_dev(tetris_batch* b, const tetris_traj* traj, int row, const tetris_act_eval* e, const uint8_t* d_done,
                            const uint8_t* d_dead) {

@@ -172,6 +172,71 @@ class TorchEnv:
                               player=self._ptr(player), ms=ms, auto_reset=auto_reset)
         return self.done, self.lines, self.dead
 
+    # ---- choosing a list from the network's phi (include/tetris_hip.h: tetris_select_lists_dev, tetris_step_lists_eval_dev): the
+    # part of sherlock_agent.get_action between the network and perform_action
+    def _plan_eval(self, phi, state_eval, mode, player, seed, draw, small_fill, out_dtype, probs):
+        """-> (the argument struct, the outputs): the checks, simulate(finalize=False) and the reused output tensors of the two calls"""
+        torch, n, H = self.torch, self.b.n_games, self.b.height
+        L, _ = self._lists()
+        assert L <= 256, "choose_lists takes at most 256 lists per game"
+        assert mode in ("argmax", "pi"), "mode is 'argmax' or 'pi'"
+        out_dtype = torch.float32 if out_dtype is None else out_dtype
+        assert out_dtype in (torch.float32, torch.float16), "delta / sums are float32 or float16"
+        for t in (phi,) + (() if state_eval is None else (state_eval,)):
+            assert t.dtype in (torch.float32, torch.float16) and t.is_cuda and t.is_contiguous(), "evaluations are contiguous float32 or float16 device tensors"
+        assert phi.dim() == 4 and tuple(phi.shape[:3]) == (n, H, 10) and phi.shape[3] in (1, 7), "phi must be [n, H, 10, 7 or 1]"
+        if state_eval is not None:
+            assert state_eval.dim() == 2 and state_eval.shape[0] == n and state_eval.shape[1] in (1, 7, 8), "state_eval must be [n, 1, 7 or 8]"
+        self._check_player(player)
+        cols = self.simulate(player, finalize=False)[0]
+        if getattr(self, "choose_choice", None) is None:
+            f32 = dict(dtype=torch.float32, device=self.dev)
+            self.choose_choice = torch.zeros(n, dtype=torch.int32, device=self.dev)
+            self.choose_piece = torch.zeros(n, dtype=torch.uint8, device=self.dev)
+            self.choose_prob, self.choose_value, self.choose_entropy = torch.zeros(n, **f32), torch.zeros(2, n, **f32), torch.zeros(n, **f32)
+            self._choose_planes, self._choose_probs = {}, {}
+        if out_dtype not in self._choose_planes:
+            self._choose_planes[out_dtype] = tuple(torch.zeros(n, H, 10, dtype=out_dtype, device=self.dev) for _ in range(2))
+        delta, sums = self._choose_planes[out_dtype]
+        if probs and L not in self._choose_probs:
+            self._choose_probs[L] = torch.zeros(n, L, dtype=torch.float32, device=self.dev)
+        pr = self._choose_probs[L] if probs else None
+        e = self.b.plan_eval(self._ptr(phi), self._ptr(self.list_count), self._ptr(cols), self._ptr(self.choose_choice), n_pieces=phi.shape[3],
+                             f16=phi.dtype == torch.float16, state_eval=self._ptr(state_eval),
+                             n_values=1 if state_eval is None else state_eval.shape[1],
+                             value_f16=state_eval is not None and state_eval.dtype == torch.float16, mode=mode, player=self._ptr(player),
+                             seed=seed, draw=draw, small_fill=small_fill, max_lists=L, out_f16=out_dtype == torch.float16,
+                             piece=self._ptr(self.choose_piece), prob=self._ptr(self.choose_prob), probs=self._ptr(pr),
+                             value=None if state_eval is None else self._ptr(self.choose_value),
+                             entropy=self._ptr(self.choose_entropy) if mode == "pi" else None, delta=self._ptr(delta), sums=self._ptr(sums))
+        self._choose_last = (e, phi, state_eval, player)             # the tensors are kept alive with the struct
+        outs = (self.choose_choice, self.choose_piece, self.choose_prob, None if state_eval is None else self.choose_value,
+                self.choose_entropy if mode == "pi" else 0.0, delta, sums) + ((pr,) if probs else ())
+        return e, outs
+
+    def choose_lists(self, phi, state_eval=None, mode="argmax", player=None, seed=0, draw=0, small_fill=1e-3, out_dtype=None, probs=False):
+        """The list of every game (lists of the last action_lists(player) call) from the network's phi [n, H, 10, K] (K = 7, or 1
+        with the piece in the state vector; float32 or float16): simulate(finalize=False), then one kernel that scores every list
+        with the plane of the piece the game holds, normalises and chooses by mode "argmax" or "pi" (the draw is keyed by (seed,
+        global game id, draw): pass the agent's step as `draw`).  The [n, H, 10, L] deltas are never formed.
+        -> (choice int32 [n], piece uint8 [n], prob float32 [n] = pi(a), value float32 [2, n] or None, entropy: float32 [n] for
+        "pi", else 0.0, delta [n, H, 10] = the chosen list's deltas, sums [n, H, 10] = the sum over the lists; out_dtype:
+        torch.float32 (default) or torch.float16) and with probs=True also probs float32 [n, L] — device tensors, reused; choice
+        feeds step_lists unchanged.  The games are not changed; nothing waits for the GPU."""
+        e, outs = self._plan_eval(phi, state_eval, mode, player, seed, draw, small_fill, out_dtype, probs)
+        self.b.select_lists_dev(e)
+        return outs
+
+    def step_lists_eval(self, phi, state_eval=None, mode="argmax", player=None, seed=0, draw=0, small_fill=1e-3, out_dtype=None, probs=False,
+                        ms=400, auto_reset=False):
+        """choose_lists + step_lists in one call: -> (done [n], lines [P, n], dead [P, n]) + choose_lists' outputs; auto_reset as
+        for step_rt."""
+        e, outs = self._plan_eval(phi, state_eval, mode, player, seed, draw, small_fill, out_dtype, probs)
+        _, K = self._lists()
+        self.b.step_lists_eval_dev(e, self._ptr(self.list_lens), self._ptr(self.list_keys), self._ptr(self.done), self._ptr(self.lines),
+                                   self._ptr(self.dead), max_keys=K, ms=ms, auto_reset=auto_reset)
+        return (self.done, self.lines, self.dead) + outs
+
     # ---- heuristic policy on the device (include/tetris_hip.h: tetris_rt_features_dev and the four after it)
     def _policy_buffers(self):
         if getattr(self, "policy_rot", None) is not None:

@@ -297,6 +297,80 @@ int tetris_plan_deltas_dev(tetris_batch *b, const uint8_t *d_player, const int32
                            int max_lists, float small_fill, int flags,
                            void *d_deltas, void *d_sums, uint8_t *d_small);
 
+/* ---- choosing a planning agent's action list on the device from phi ------------------------------------------------------
+ * replaces: the part of sherlock_agent.get_action between the network and perform_action (agents/sherlock_agent/
+ * sherlock_agent.py:91-156 with sherlock_utils.py:34-63): the plane of the held piece out of the network's phi_eval
+ * [N][H][10][K], p_unnormalized[k] = sum over (y, x) of deltas[.., k] * phi_p, the normalisation over the lists, the choice by
+ * argmax or by the distribution, and (a_idx, piece, pi(a), v_piece, v_mean, delta(s, a), delta_sum(s)) for the trajectory —
+ * without the [N][H][10][L] deltas tensor: the calls read the columns tetris_simulate_lists_dev (no TETRIS_SIM_FINALIZE) wrote.
+ * (The PPO trainer recomputes pi(a) from delta and delta_sum alone, sherlock_agent_ppo_trainer.py:37-54: the sum over the lists
+ * of p_unnormalized is sum(delta_sum * phi).)  The reference also names pareto and epsilon here, but sherlock_utils has no such
+ * functions (sherlock_agent.py:124-136 would raise): they are out of scope.
+ * Device pointers, asynchronous on the batch's stream, run-ahead bounded and RNG-table requests serviced as for
+ * tetris_step_rt_dev_ex; one to four players, every height, colour batches included; not on split batches.
+ * For game i:
+ *   SETUP   p = d_player[i] (NULL: player 0; out-of-range entries are clamped).  PIECE = the index tetris_observe_packed gives
+ *           for p's board now, limited to K - 1; K = n_pieces is 7 or 1.  count = d_count[i] clamped into [0, L], L = max_lists
+ *           (1 <= L <= 256).  `before`, `after_k` (d_cols [L][P][10][N]), their masking to rows 0..H-1 and the list kinds
+ *           (normal, SMALL, past count) are those of tetris_plan_deltas_dev.  w(y, x) = d_phi[i][y][x][PIECE], float32 or IEEE
+ *           binary16 (TETRIS_ACT_F16), taken to float32 exactly.
+ *   SCORES  float32 arithmetic, nothing contracted.  A normal list: score_k starts at +0.0f; columns c = 0..9 in turn, within
+ *           a column rows y = 0..H-1 in turn; a cell whose delta is +1 does score += w(y, c), a cell whose delta is -1 does
+ *           score -= w(y, c), a cell whose delta is 0 nothing (so the reference's 0 * inf = NaN is NOT reproduced).  A SMALL
+ *           list: score_k = small_fill * W, one multiply, with C_c = the sequential sum of w(y, c) over y = 0..H-1 from +0.0f and
+ *           W = ((C_0 + C_1) + C_2) + ... + C_9.  (small_fill = 0 is the reference, whose uint8 fields turn its 1e-3 into 0.)
+ *           total = the sequential sum of score_k over k = 0..count-1 from +0.0f; q_k = score_k / total, correctly rounded,
+ *           whatever the bits.
+ *   CHOICE  count = 0: choice 0, d_prob and d_entropy 0, d_delta zeros.  If any q_k (k < count) is NaN: choice 0, entropy 0
+ *           (sherlock_utils.py:49-51, 59-60).  Otherwise
+ *           TETRIS_ACT_ARGMAX  the highest q_k, among equals the lowest k (compared with `>`);
+ *           TETRIS_ACT_PI      weights m_k = q_k > 0 ? q_k : 0; u from Philox4x32-10 with the key and counter of
+ *                              tetris_select_eval_dev — key (sample_seed, 0), counter (global game id, low word of `draw`, high
+ *                              word of `draw`, 0), u = (w0 >> 8) * 2^-24; sum(m) = the float32 sum in index order; the choice is
+ *                              the first k < count whose running sum (the same partial sums) is > u * sum(m), if there is none
+ *                              the last k with m_k > 0, and if sum(m) is not a positive finite number ARGMAX's choice.
+ *           Every path ends with 0 <= choice < max(count, 1).
+ *   OUTPUTS all optional except d_choice:
+ *           d_choice  int32 [N]    feeds tetris_step_lists_dev unchanged
+ *           d_piece   uint8 [N]    the piece index used
+ *           d_prob    float32 [N]  q_choice
+ *           d_probs   float32 [N][L]  q_k for k < count, 0 from count on
+ *           d_value   float32 [2][N]  from d_state_eval [N][V] exactly as in tetris_act_eval (TETRIS_ACT_VALUE_F16)
+ *           d_entropy float32 [N]  PI only: -sum over k < count of q_k * logf(q_k + 1e-8f), in index order, accurate logf
+ *           d_delta   [N][H][10]   the plane tetris_plan_deltas_dev would write for the chosen list
+ *           d_sums    [N][H][10]   the same bits as tetris_plan_deltas_dev's d_sums
+ *           d_delta and d_sums are float32, or IEEE binary16 (rounded to nearest even) with TETRIS_PLAN_OUT_F16.
+ * TETRIS_E_ARG: a NULL argument struct, d_phi, d_count, d_cols or d_choice; n_pieces not 1 or 7; d_state_eval with n_values
+ * not 1, 7 or 8; a mode other than ARGMAX and PI; d_value without d_state_eval; d_entropy outside PI; an unknown flag;
+ * max_lists outside [1, 256]; a d_phi, d_delta or d_sums that is not 16-byte aligned; a split batch.                        */
+#define TETRIS_PLAN_OUT_F16 4   /* d_delta / d_sums are IEEE binary16 instead of float32 (beside TETRIS_ACT_F16 = 1, TETRIS_ACT_VALUE_F16 = 2) */
+typedef struct tetris_plan_eval {
+    const void     *d_phi;          /* [N][H][10][n_pieces] float32, or binary16 with TETRIS_ACT_F16; 16-byte aligned */
+    const void     *d_state_eval;   /* [N][n_values], or NULL */
+    int             n_pieces;       /* K */
+    int             n_values;       /* V */
+    int             mode;           /* TETRIS_ACT_ARGMAX or TETRIS_ACT_PI */
+    int             flags;          /* TETRIS_ACT_F16 | TETRIS_ACT_VALUE_F16 | TETRIS_PLAN_OUT_F16 */
+    uint32_t        sample_seed;
+    uint32_t        reserved;       /* 0 */
+    uint64_t        draw;           /* the number of this draw, e.g. the agent's step */
+    float           small_fill;
+    const uint8_t  *d_player;       /* [N] or NULL */
+    const int32_t  *d_count;        /* [N] */
+    const uint32_t *d_cols;         /* [L][P][10][N] */
+    int             max_lists;      /* L */
+    int32_t        *d_choice;       /* [N] */
+    uint8_t        *d_piece;
+    float          *d_prob, *d_probs, *d_value, *d_entropy;
+    void           *d_delta, *d_sums;   /* [N][H][10] each; 16-byte aligned */
+} tetris_plan_eval;
+/* the choice and its outputs.  The batch's state is not written.                                                          */
+int tetris_select_lists_dev(tetris_batch *b, const tetris_plan_eval *e);
+/* the choice and perform_action of it: tetris_select_lists_dev followed by tetris_step_lists_dev with d_choice, bit for bit
+ * (d_lens / d_keys / max_keys / ms / flags / d_done / d_lines / d_dead as there; a NULL d_lens or d_keys: TETRIS_E_ARG).   */
+int tetris_step_lists_eval_dev(tetris_batch *b, const tetris_plan_eval *e, const uint8_t *d_lens, const uint8_t *d_keys,
+                               int max_keys, int ms, int flags, uint8_t *d_done, uint8_t *d_lines, uint8_t *d_dead);
+
 /* ---- heuristic policy on the device: a one-piece look-ahead over the 40 SVENton (rotation, translation) actions -----------
  * The scripted player the golden traces were recorded with (tests/golden/policies.py: GreedyRT), for every game of a batch at
  * once: a fixed-strength opponent for two-player training, the inner loop of feature-based learning (one weight vector per
