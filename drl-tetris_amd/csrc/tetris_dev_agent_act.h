@@ -1,0 +1,423 @@
+// Kernels of libtetris_hip.so, part 5: the acting, window and replay half of tetris_lib_agent.h: acting on a network's evaluation,
+// trajectory windows, a window's states, sample sets and minibatches, experience replay and its radix sort.  Needs
+// tetris_dev_observe.h (obs_row_words, obs_row_halves).  Every kernel here has one named block size: its launch bounds and its
+// launch in tetris_lib_agent.h both use it.
+
+// ---- acting on a network's evaluation (tetris_act.h).  A workgroup takes ACT_BLOCK consecutive games: it loads their piece
+// indices, streams their contiguous ACT_BLOCK x 40 K elements of action_eval with 16-byte loads (every cache line is touched
+// whichever piece a game holds, so it is read once, coalesced, instead of 40 strided elements per lane), keeps the elements of
+// each game's piece and lays them into LDS candidate-major with a stride of ACT_LDS_STRIDE floats; then one lane per game
+// chooses from its column.  RANK's 40 x 40 comparisons are spread over the workgroup's lanes, one (game, candidate) pair at a
+// time.
+struct ActShared {
+    float x[ACT_CANDIDATES * ACT_LDS_STRIDE];     // the values, [c][game]
+    float m[ACT_CANDIDATES * ACT_LDS_STRIDE];     // the weights of the sampling modes
+    float table[ACT_CANDIDATES];
+    int piece[ACT_BLOCK];
+};
+typedef uint32_t act_u32x4 __attribute__((ext_vector_type(4)));
+
+// element j of a 16-byte vector as float32 (j is not a constant: selects, no indexed registers)
+template <bool F16>
+__device__ __forceinline__ float act_vector_element(const act_u32x4& q, int j) {
+    const int w = F16 ? j >> 1 : j;
+    const uint32_t word = w == 0 ? q.x : w == 1 ? q.y : w == 2 ? q.z : q.w;
+    return F16 ? act_f16_to_f32((uint16_t)((j & 1) ? word >> 16 : word & 0xFFFFu)) : u2f(word);
+}
+
+// The block's elements, 16 bytes per lane and load.  Element e of the block belongs to game e / (40 K), candidate (e mod 40 K) / K
+// and piece e mod K; 40 K is a multiple of the 4 or 8 elements of a vector, so a vector lies inside one game and (K = 7) holds
+// at most two elements of the game's piece: only those are converted and stored.
+template <int NT, int K, bool F16>
+__device__ __forceinline__ void act_gather(const ActArgs& aa, int g0, int ng, ActShared& sh) {
+    constexpr int EPV = F16 ? 8 : 4, PER_GAME = ACT_CANDIDATES * K;
+    static_assert(PER_GAME % EPV == 0, "a 16-byte vector must not cross two games");
+    const act_u32x4* src = (const act_u32x4*)((const char*)aa.action_eval + (size_t)g0 * PER_GAME * (F16 ? 2 : 4));
+    const int nvec = ng * (PER_GAME / EPV);
+#pragma unroll 4
+    for (int v = threadIdx.x; v < nvec; v += NT) {
+        const act_u32x4 q = src[v];
+        const int e0 = v * EPV, game = e0 / PER_GAME, rem = e0 - game * PER_GAME;
+        if (K == 1) {
+#pragma unroll
+            for (int j = 0; j < EPV; j++) sh.x[(rem + j) * ACT_LDS_STRIDE + game] = act_vector_element<F16>(q, j);
+        } else {
+            int j = sh.piece[game] - rem % K;                 // the first element of the vector that belongs to the piece
+            j = j < 0 ? j + K : j;
+            if (j < EPV) sh.x[((rem + j) / K) * ACT_LDS_STRIDE + game] = act_vector_element<F16>(q, j);
+            if (EPV > K && j + K < EPV) sh.x[((rem + j + K) / K) * ACT_LDS_STRIDE + game] = act_vector_element<F16>(q, j + K);
+        }
+    }
+}
+
+// games g0 .. g0 + ng - 1 by a workgroup of NT threads: every thread passes the barriers; thread t < ng chooses for game g0 + t
+// and writes its outputs
+template <int NT>
+__device__ __forceinline__ void act_block_choose(const ActArgs& aa, int g0, int ng, ActShared& sh) {
+    static_assert(NT % ACT_BLOCK == 0 && NT >= ACT_BLOCK, "whole waves of ACT_BLOCK lanes");
+    const int t = threadIdx.x;
+    if (t < ACT_BLOCK) sh.piece[t] = t < ng ? act_piece_of(geo_of(aa.a), (size_t)(g0 + t), safe_player(aa.player, g0 + t, aa.a.n_players), aa.K) : 0;
+    if (t < ACT_CANDIDATES) sh.table[t] = aa.table[t];
+    __syncthreads();
+    if (aa.K == 7) {
+        if (aa.eval_f16) act_gather<NT, 7, true>(aa, g0, ng, sh); else act_gather<NT, 7, false>(aa, g0, ng, sh);
+    } else {
+        if (aa.eval_f16) act_gather<NT, 1, true>(aa, g0, ng, sh); else act_gather<NT, 1, false>(aa, g0, ng, sh);
+    }
+    __syncthreads();
+    const bool rank = aa.mode == ACT_RANK;
+    if (rank) {                                       // lane = (game, candidate): its 39 rivals from LDS, conflict-free
+        const int g = t & (ACT_BLOCK - 1);
+        if (g < ng)
+            for (int c = t / ACT_BLOCK; c < ACT_CANDIDATES; c += NT / ACT_BLOCK)
+                sh.m[c * ACT_LDS_STRIDE + g] = sh.table[act_rank(sh.x + g, ACT_LDS_STRIDE, c) - 1];
+        __syncthreads();
+    }
+    if (t >= ng) return;
+    const int c = act_choose(aa, g0 + t, sh.table, sh.x + t, ACT_LDS_STRIDE, sh.m + t, ACT_LDS_STRIDE, rank);
+    act_write(aa, g0 + t, sh.piece[t], c, sh.x + t, ACT_LDS_STRIDE);
+}
+
+// tetris_select_eval_dev: the choice and its outputs
+constexpr int ACT_THREADS = 256;
+__global__ __launch_bounds__(ACT_THREADS) void k_act_select(ActArgs aa) {
+    __shared__ ActShared sh;
+    const int g0 = blockIdx.x * ACT_BLOCK, ng = imin(ACT_BLOCK, aa.a.n - g0);
+    act_block_choose<ACT_THREADS>(aa, g0, ng, sh);
+}
+
+// ---- trajectory windows (tetris_traj.h).  Recording is one lane per game.
+constexpr int TRAJ_LANE_THREADS = 256;      // k_traj_record and k_traj_observe: a lane per record
+__global__ __launch_bounds__(TRAJ_LANE_THREADS) void k_traj_record(TrajRecordArgs ra) {
+    const int i = blockIdx.x * TRAJ_LANE_THREADS + threadIdx.x;
+    if (i < ra.n) traj_record_game(ra, i);
+}
+
+// The backward recurrence is sequential in t per game, so a lane that read its rows from memory as it went would pay a memory
+// round trip per row with 64-1 024 waves on the whole GPU.  A workgroup of five waves takes TRAJ_BLOCK consecutive games:
+// waves 1-4 stream tiles of TRAJ_TILE rows x 64 games — wave 1 the rewards, 2 value[0], 3 value[1], 4 the dones, each lane 16
+// independent loads of its game's column, every load of a wave one contiguous 256 bytes (64 for the dones) — last tile first
+// into one half of a double-buffered LDS image while wave 0, one lane per game, walks the other half backward and stores
+// adv / target / closed, a contiguous row segment per store.  LDS rows are 64 words: lane l reads and writes bank l mod 32 of
+// its half-wave, no conflicts.  Any N (lanes past N load nothing and store nothing), any rows (the last tile is the short one).
+constexpr int TRAJ_THREADS = 5 * 64;      // one scanning wave and one loading wave per array
+struct TrajShared {
+    uint32_t w[2][4][TRAJ_TILE][TRAJ_BLOCK];      // [buffer][reward, value 0, value 1, done][row][game]
+};
+
+// rows t0 .. t0 + nr - 1 of array `which`, game g, into one buffer's column `lane` (all 16 loads issued before the first store;
+// constant indices after unrolling: registers, no scratch)
+__device__ __forceinline__ void traj_load_tile(const TrajAdvArgs& aa, int which, int g, bool live, int t0, int nr, int lane,
+                                               uint32_t (*dst)[TRAJ_TILE][TRAJ_BLOCK]) {
+    uint32_t v[TRAJ_TILE];
+    const size_t at = (size_t)t0 * aa.n + g;
+    if (which == 3) {
+        const uint8_t* src = aa.done + at;
+#pragma unroll
+        for (int j = 0; j < TRAJ_TILE; j++) v[j] = (live && j < nr) ? (uint32_t)src[(size_t)j * aa.n] : 0u;
+    } else {
+        const float* src = (which == 0 ? aa.reward : which == 1 ? aa.value : aa.value + aa.plane) + at;
+#pragma unroll
+        for (int j = 0; j < TRAJ_TILE; j++) v[j] = (live && j < nr) ? f2u(src[(size_t)j * aa.n]) : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < TRAJ_TILE; j++) dst[which][j][lane] = v[j];
+}
+
+__global__ __launch_bounds__(TRAJ_THREADS) void k_traj_advantages(TrajAdvArgs aa) {
+    __shared__ TrajShared sh;
+    const int lane = threadIdx.x & (TRAJ_BLOCK - 1), wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / TRAJ_BLOCK);
+    const int g = blockIdx.x * TRAJ_BLOCK + lane;
+    const bool live = g < aa.n;
+    const int ntiles = (aa.rows + TRAJ_TILE - 1) / TRAJ_TILE;
+    TrajScan s;
+    traj_scan_begin(s, (wave == 0 && live && aa.boot) ? aa.boot[g] : 0.0f);
+    if (wave != 0) traj_load_tile(aa, wave - 1, g, live, (ntiles - 1) * TRAJ_TILE, aa.rows - (ntiles - 1) * TRAJ_TILE, lane, sh.w[0]);
+    __syncthreads();
+    int cur = 0;
+    for (int k = ntiles - 1; k >= 0; k--, cur ^= 1) {
+        const int t0 = k * TRAJ_TILE, nr = imin(TRAJ_TILE, aa.rows - t0);
+        if (wave == 0) {
+#pragma unroll 4
+            for (int j = nr - 1; j >= 0; j--) {
+                float adv, target;
+                traj_scan_row(s, aa, u2f(sh.w[cur][0][j][lane]), u2f(sh.w[cur][1][j][lane]), u2f(sh.w[cur][2][j][lane]),
+                              sh.w[cur][3][j][lane] != 0u, adv, target);
+                if (live) {
+                    const size_t at = (size_t)(t0 + j) * aa.n + g;
+                    aa.adv[at] = adv;
+                    aa.target[at] = target;
+                    if (aa.closed) aa.closed[at] = (uint8_t)s.seen;
+                }
+            }
+        } else if (k > 0) {
+            traj_load_tile(aa, wave - 1, g, live, t0 - TRAJ_TILE, TRAJ_TILE, lane, sh.w[cur ^ 1]);
+        }
+        __syncthreads();
+    }
+}
+
+// ---- a window's states and sample sets (tetris_batch.h)
+// tetris_traj_observe_dev: one lane per (game, slot) record
+__global__ __launch_bounds__(TRAJ_LANE_THREADS) void k_traj_observe(TrajObserveArgs oa) {
+    const int i = blockIdx.x * TRAJ_LANE_THREADS + threadIdx.x;
+    if (i < oa.n) traj_observe_slot(oa, i, (int)blockIdx.y);
+}
+
+// tetris_traj_select_dev in three launches, none of which waits for another workgroup: the non-zero bytes of every workgroup's
+// SELECT_ELEMS mask bytes (16 per lane, one 16-byte load); the exclusive scan of those counts by ONE workgroup, SELECT_THREADS
+// counts per trip with a carry; the scatter, in which every workgroup repeats its count, scans its lanes' counts and writes
+// its entries from its offset on — in ascending order whatever the order the workgroups run in.
+template <int NT>
+__device__ __forceinline__ uint32_t select_block_scan(uint32_t v, uint32_t* s, uint32_t& sum) {      // -> exclusive prefix of v
+    const int t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (int off = 1; off < NT; off <<= 1) {
+        const uint32_t add = t >= off ? s[t - off] : 0u;
+        __syncthreads();
+        s[t] += add;
+        __syncthreads();
+    }
+    const uint32_t incl = s[t];
+    sum = s[NT - 1];
+    __syncthreads();
+    return incl - v;
+}
+__global__ __launch_bounds__(SELECT_THREADS) void k_select_count(TrajSelectArgs sa) {
+    __shared__ uint32_t s[SELECT_THREADS];
+    const uint32_t base = (uint32_t)blockIdx.x * (uint32_t)SELECT_ELEMS + (uint32_t)threadIdx.x * 16u;
+    uint32_t sum;
+    select_block_scan<SELECT_THREADS>((uint32_t)__builtin_popcount(select_bits(sa, base)), s, sum);
+    if (threadIdx.x == 0) sa.blocks[blockIdx.x] = (int32_t)sum;
+}
+__global__ __launch_bounds__(SELECT_THREADS) void k_select_scan(TrajSelectArgs sa) {
+    __shared__ uint32_t s[SELECT_THREADS];
+    uint32_t carry = 0u;
+    for (int first = 0; first < sa.nblocks; first += SELECT_THREADS) {
+        const int k = first + (int)threadIdx.x;
+        uint32_t sum;
+        const uint32_t excl = select_block_scan<SELECT_THREADS>(k < sa.nblocks ? (uint32_t)sa.blocks[k] : 0u, s, sum);
+        if (k < sa.nblocks) sa.blocks[k] = (int32_t)(carry + excl);
+        carry += sum;
+    }
+    if (threadIdx.x == 0) {
+        sa.blocks[sa.nblocks] = (int32_t)carry;
+        *sa.count = (int32_t)(sa.augment ? 2u * carry : carry);
+    }
+}
+__global__ __launch_bounds__(SELECT_THREADS) void k_select_scatter(TrajSelectArgs sa) {
+    __shared__ uint32_t s[SELECT_THREADS];
+    const uint32_t base = (uint32_t)blockIdx.x * (uint32_t)SELECT_ELEMS + (uint32_t)threadIdx.x * 16u;
+    const uint32_t bits = select_bits(sa, base);
+    uint32_t sum;
+    const uint32_t excl = select_block_scan<SELECT_THREADS>((uint32_t)__builtin_popcount(bits), s, sum);
+    const long long k = (long long)(uint32_t)sa.blocks[sa.nblocks];
+    select_emit(sa, base, bits, (long long)(uint32_t)sa.blocks[blockIdx.x] + excl, k);
+    // the rest of d_index, up to cap: -1
+    const long long step = (long long)gridDim.x * SELECT_THREADS;
+    for (long long p = (sa.augment ? 2 * k : k) + (long long)blockIdx.x * SELECT_THREADS + threadIdx.x; p < sa.cap; p += step) sa.index[p] = -1;
+}
+
+// tetris_traj_batch_dev.  A workgroup of one wave takes BATCH_BLOCK consecutive samples of one slot (blockIdx.y): a lane reads
+// its sample's record with three 16-byte loads — 48 contiguous bytes, one or two cache lines, wherever the index points — and
+// expands the ten column words into its row of an LDS tile that is laid out as the workgroup's slice of `visual` itself (row
+// pitch H * 10 bytes, not padded: rows start 50 / 55 words apart, at most two lanes per LDS bank while they are written, as in
+// k_observe_packed).  The mirror image is the choice of the source column of every tile column — selects between registers,
+// no second pass.  The tile leaves as 16-byte LDS reads -> 16-byte streaming stores, one contiguous run of 64 * H * 10 bytes
+// (a multiple of 16 for every H); a slice of `visual` that does not start on 16 bytes leaves as dwords or bytes.  The slot-0
+// workgroup also writes the samples' row entries.
+__global__ __launch_bounds__(BATCH_BLOCK) void k_traj_batch(TrajBatchArgs ba) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_tile[];      // BATCH_BLOCK * H * 10 bytes
+    const int lane = threadIdx.x, sl = blockIdx.y, first = blockIdx.x * BATCH_BLOCK, j = first + lane;
+    const int nb = imin(BATCH_BLOCK, ba.m - first), cells = ba.H * NCOL;
+    if (j < ba.m) {
+        const BatchEntry en = batch_entry(ba, j);
+        const Quad* rec = reinterpret_cast<const Quad*>(ba.obs + ((size_t)en.at * ba.n_slots + sl) * OBS_WORDS);
+        const Quad zero = {0u, 0u, 0u, 0u};
+        const Quad a = en.valid ? rec[0] : zero, b = en.valid ? rec[1] : zero, c = en.valid ? rec[2] : zero;
+        if (ba.visual) {
+            const bool mi = en.mirror;
+            uint32_t col[NCOL] = {mi ? c.y : a.x, mi ? c.x : a.y, mi ? b.w : a.z, mi ? b.z : a.w, mi ? b.y : b.x,
+                                  mi ? b.x : b.y, mi ? a.w : b.z, mi ? a.z : b.w, mi ? a.y : c.x, mi ? a.x : c.y};
+            if (ba.H % 2 == 0) obs_row_words(col, ba.H, s_tile + (size_t)lane * (cells / 4));
+            else obs_row_halves(col, ba.H, reinterpret_cast<uint16_t*>(s_tile) + (size_t)lane * (cells / 2));
+        }
+        uint32_t v0, v1, v2, piece;
+        batch_scalars(en, c.z, c.w, v0, v1, v2, piece);
+        batch_store_vector(ba, sl, j, v0, v1, v2, piece);
+        if (sl == 0) batch_store_entry(ba, j, en);
+    }
+    if (!ba.visual) return;
+    __syncthreads();
+    uint8_t* out = ba.visual + ((size_t)sl * ba.m + first) * (size_t)cells;
+    const uint32_t bytes = (uint32_t)nb * (uint32_t)cells;
+    const uint8_t* tile = reinterpret_cast<const uint8_t*>(s_tile);
+    uint32_t done = 0u;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    if ((((uintptr_t)out) & 15u) == 0) {
+        done = bytes & ~15u;
+        for (uint32_t k = 16u * (uint32_t)lane; k < done; k += 16u * BATCH_BLOCK)
+            __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(tile + k), reinterpret_cast<u32x4*>(out + k));
+    } else if ((((uintptr_t)out) & 3u) == 0) {
+        done = bytes & ~3u;
+        for (uint32_t k = 4u * (uint32_t)lane; k < done; k += 4u * BATCH_BLOCK)
+            *reinterpret_cast<uint32_t*>(out + k) = *reinterpret_cast<const uint32_t*>(tile + k);
+    }
+    for (uint32_t k = done + (uint32_t)lane; k < bytes; k += BATCH_BLOCK) out[k] = tile[k];
+}
+
+// ---- experience replay (tetris_replay.h)
+// tetris_replay_add_dev in three launches, none of which waits for another workgroup: a lane per game counts its mask bytes
+// (row t of the mask is read by consecutive lanes); ONE workgroup scans the N counts, SELECT_THREADS per trip with a carry, and
+// applies the cursor rule; a lane per game copies its run.  The window is read as it lies — consecutive lanes read consecutive
+// 48 S-byte records and row entries of a row t — and a lane writes a run of consecutive ring positions of its own.
+constexpr int REPLAY_THREADS = 256;      // the replay kernels that are a lane per game, position, sorted slot or output
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_add_count(ReplayAddArgs aa) {
+    const int g = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (g < aa.n) aa.offsets[g] = replay_add_count(aa, g) * (aa.augment ? 2u : 1u);
+}
+__global__ __launch_bounds__(SELECT_THREADS) void k_replay_add_scan(ReplayAddArgs aa) {
+    __shared__ uint32_t s[SELECT_THREADS];
+    uint32_t carry = 0u;
+    for (int first = 0; first < aa.n; first += SELECT_THREADS) {
+        const int g = first + (int)threadIdx.x;
+        uint32_t sum;
+        const uint32_t excl = select_block_scan<SELECT_THREADS>(g < aa.n ? aa.offsets[g] : 0u, s, sum);
+        if (g < aa.n) aa.offsets[g] = carry + excl;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) aa.offsets[aa.n] = replay_cursor_rule(aa.rp.cursor, carry, (uint32_t)aa.rp.max_size);
+}
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_add_scatter(ReplayAddArgs aa) {
+    const int g = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (g < aa.n) replay_add_game(aa, g);
+}
+
+// tetris_replay_sample_dev around its two sorts: a lane per position / sorted slot / output
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_prio_keys(ReplaySampleArgs sa) {
+    const uint32_t i = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (i < sa.max_size) replay_prio_key(sa, i);
+}
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_sample_keys(ReplaySampleArgs sa) {
+    const uint32_t s = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (s < sa.max_size) replay_sample_key(sa, s);
+}
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_emit(ReplaySampleArgs sa) {
+    const int j = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (j < sa.m || j == 0) {
+        if (sa.m == 0) sa.count[0] = 0;
+        else replay_emit(sa, j);
+    }
+}
+__global__ __launch_bounds__(REPLAY_THREADS) void k_replay_update(ReplayUpdateArgs ua) {
+    const int j = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (j < ua.m) replay_update(ua, j);
+}
+
+// One pass of the stable LSD radix sort in three launches, none of which waits for another workgroup (no look-back, no grid
+// barrier): the digit counts of every tile of SORT_TILE entries (LDS atomics), digit-major; a workgroup per digit scans its row
+// of tile counts, SORT_SCAN_SPAN per trip with a carry, and leaves the digit's total; the scatter.  In the scatter wave w of a
+// tile holds entries [512 w, 512 w + 512) in eight rounds of 64 consecutive ones.  A lane's rank among the entries of its digit
+// in its wave is the wave's counter of the digit so far (LDS, one row of counters per wave) plus the lanes below it of the
+// round with the same digit: eight ballots, one per bit of the digit, leave the mask of those lanes.  Then thread d turns the
+// four waves' counters of digit d into their places in the tile's new order — (digits below d in the tile: a scan of the tile's
+// counts) + (digit d in the waves before) — the tile is put into that order in LDS, and leaves from there: entry `at` of the
+// new order goes to (digits below d: a scan of the totals) + (digit d in the tiles before) + (its place in d's run), so
+// consecutive lanes write consecutive words of a run.  The order is tile, wave, round, lane = position in the input: the pass
+// is stable.
+static_assert(SORT_THREADS == SORT_RADIX && SORT_THREADS == 4 * 64, "four waves; a thread per digit");
+__global__ __launch_bounds__(SORT_THREADS) void k_sort_histogram(SortArgs sa) {
+    __shared__ uint32_t cnt[SORT_RADIX];
+    cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t first = (uint32_t)blockIdx.x * SORT_TILE;
+#pragma unroll
+    for (int r = 0; r < SORT_ITEMS; r++) {
+        const uint32_t e = first + (uint32_t)r * SORT_THREADS + threadIdx.x;
+        if (e < sa.total) atomicAdd(&cnt[sort_digit(sa.key_in[e], sa.pass)], 1u);
+    }
+    __syncthreads();
+    sa.hist[(size_t)threadIdx.x * sa.ntiles + blockIdx.x] = cnt[threadIdx.x];
+}
+__global__ __launch_bounds__(SORT_SCAN_SPAN) void k_sort_scan(SortArgs sa) {      // (a tile per thread and trip)
+    __shared__ uint32_t s[SORT_SCAN_SPAN];
+    uint32_t* row = sa.hist + (size_t)blockIdx.x * sa.ntiles;
+    uint32_t carry = 0u;
+    for (int first = 0; first < sa.ntiles; first += SORT_SCAN_SPAN) {
+        const int t = first + (int)threadIdx.x;
+        uint32_t sum;
+        const uint32_t excl = select_block_scan<SORT_SCAN_SPAN>(t < sa.ntiles ? row[t] : 0u, s, sum);
+        if (t < sa.ntiles) row[t] = carry + excl;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) sa.totals[blockIdx.x] = carry;
+}
+__global__ __launch_bounds__(SORT_THREADS) void k_sort_scatter(SortArgs sa) {
+    __shared__ uint32_t wcnt[SORT_THREADS / 64][SORT_RADIX];
+    __shared__ uint32_t s[SORT_THREADS], gbase[SORT_RADIX];
+    __shared__ uint32_t lkey[SORT_TILE], lpos[SORT_TILE];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+#pragma unroll
+    for (int w = 0; w < SORT_THREADS / 64; w++) wcnt[w][threadIdx.x] = 0u;
+    uint32_t sum;
+    const uint32_t below = select_block_scan<SORT_THREADS>(sa.totals[threadIdx.x], s, sum);      // (its barriers cover the zeroing)
+    const uint32_t first = (uint32_t)blockIdx.x * SORT_TILE + (uint32_t)wave * (SORT_ITEMS * 64) + (uint32_t)lane;
+    const uint64_t lower = (1ull << lane) - 1ull;
+    uint32_t key[SORT_ITEMS], pos[SORT_ITEMS], rank[SORT_ITEMS];
+#pragma unroll
+    for (int r = 0; r < SORT_ITEMS; r++) {
+        const uint32_t e = first + (uint32_t)r * 64u;
+        const bool live = e < sa.total;
+        key[r] = live ? sa.key_in[e] : 0u;
+        pos[r] = live ? sa.pos_in[e] : 0u;
+        const uint32_t d = sort_digit(key[r], sa.pass);
+        uint64_t same = __ballot(live);
+#pragma unroll
+        for (int bit = 0; bit < 8; bit++) {
+            const uint64_t set = __ballot(live && ((d >> bit) & 1u));
+            same &= ((d >> bit) & 1u) ? set : ~set;
+        }
+        // (volatile: the lanes of a wave hand the counter on from round to round without a barrier; a wave's LDS accesses
+        // complete in the order they are issued)
+        volatile uint32_t* counter = &wcnt[wave][d];
+        const uint32_t before = live ? *counter : 0u;
+        rank[r] = before + (uint32_t)__builtin_popcountll(same & lower);
+        __builtin_amdgcn_wave_barrier();                                        // every lane has read the counter
+        if (live && (same & lower) == 0ull) *counter = before + (uint32_t)__builtin_popcountll(same);
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    {   // thread d: digit d's place in the tile (a scan of the tile's counts), the waves' shares of it, and where it goes
+        const int d = threadIdx.x;
+        uint32_t c[SORT_THREADS / 64], cd = 0u;
+#pragma unroll
+        for (int w = 0; w < SORT_THREADS / 64; w++) { c[w] = wcnt[w][d]; cd += c[w]; }
+        const uint32_t local = select_block_scan<SORT_THREADS>(cd, s, sum);
+        uint32_t at = local;
+#pragma unroll
+        for (int w = 0; w < SORT_THREADS / 64; w++) { wcnt[w][d] = at; at += c[w]; }
+        gbase[d] = below + sa.hist[(size_t)d * sa.ntiles + blockIdx.x] - local;
+    }
+    __syncthreads();
+    // the tile in its new order, in LDS: consecutive lanes then write consecutive entries of a digit's run
+#pragma unroll
+    for (int r = 0; r < SORT_ITEMS; r++) {
+        const uint32_t e = first + (uint32_t)r * 64u;
+        if (e < sa.total) {
+            const uint32_t at = wcnt[wave][sort_digit(key[r], sa.pass)] + rank[r];
+            if (at < (uint32_t)SORT_TILE) { lkey[at] = key[r]; lpos[at] = pos[r]; }
+        }
+    }
+    __syncthreads();
+    const uint32_t tile_first = (uint32_t)blockIdx.x * SORT_TILE;
+    const uint32_t live = sa.total - tile_first < (uint32_t)SORT_TILE ? sa.total - tile_first : (uint32_t)SORT_TILE;
+#pragma unroll
+    for (int r = 0; r < SORT_ITEMS; r++) {
+        const uint32_t at = (uint32_t)r * SORT_THREADS + threadIdx.x;
+        if (at < live) {
+            const uint32_t k = lkey[at], dst = gbase[sort_digit(k, sa.pass)] + at;
+            if (dst < sa.total) { sa.key_out[dst] = k; sa.pos_out[dst] = lpos[at]; }
+        }
+    }
+}

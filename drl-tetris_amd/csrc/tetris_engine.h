@@ -57,7 +57,7 @@ extern unsigned long long te_path_count[PC_NCOUNTERS];
 // global_load/store, so the ~60 state accesses of a step need no per-lane 64-bit address arithmetic.
 // Memory mode of a state access.  MEM_STREAM: non-temporal (the default: a state word is touched once per launch).
 // MEM_AGENT: agent-scope (`sc1`) — the word is handed from one launch to the next WHILE both are running (chained launches,
-// tetris_hip.hip): the store is written through to memory and drops the line from the storing XCD's L2, the load skips the
+// tetris_dev_rollout.h): the store is written through to memory and drops the line from the storing XCD's L2, the load skips the
 // CU's L1 and is served through the L2 — the write-through hand-off, measured valid between any two XCDs (MI355X_MICROARCH.md,
 // inter-workgroup visibility: every store and every load of the handed-off bytes must be `sc1`).
 // MEM_AFFINE: `sc1` loads, PLAIN stores — the hand-off of k_chain_affine / k_duo_affine (direct dispatch, tetris_aql.h), which step
@@ -111,7 +111,7 @@ TE_HD void stw(uint32_t* base, uint32_t o, size_t word_off, uint32_t v, int mem 
 // Where word w of a board (or of the game words) lies, as a byte offset from the board's base: the load / store functions below
 // take it from a ROWS object.  RowStride multiplies it out at the access, one scalar multiply each (the default, what
 // load_player(s, o, ws, ...) and its like do).  RowTable holds offsets that were computed beforehand: the single-step chained kernels
-// (tetris_hip.hip: chain_body) fill one before they poll, so that neither the loads nor the stores of the step wait for a multiply.
+// (tetris_dev_rollout.h: chain_body) fill one before they poll, so that neither the loads nor the stores of the step wait for a multiply.
 struct RowStride { size_t ws; };
 template <int N>
 struct RowTable { uint32_t bytes[N]; };

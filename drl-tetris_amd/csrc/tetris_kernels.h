@@ -95,7 +95,7 @@ TE_HD void report_status(const KArgs& a, uint32_t st) {
     if (st & ST_BAD_ARGUMENT) f[F_BADARG] = 1u;
 }
 
-// ---- chained launches (tetris_hip.hip: k_chain): the hand-over of a wave's 64 games from launch E - 1 to launch E
+// ---- chained launches (tetris_dev_rollout.h: k_chain): the hand-over of a wave's 64 games from launch E - 1 to launch E
 // A wave's epoch word holds the number of the last launch that finished this wave's games (bits 0..30).  CHAIN_ABANDONED (bit 31)
 // is OR-ed into it by a wave that gave up waiting: the waves of every later launch that see the bit pass it on — they leave their
 // games untouched too — and the host, once everything has drained, finishes the games of such waves un-chained from the epoch the
@@ -261,7 +261,7 @@ TE_HD void game_load(const KArgs& a, int i, Game<P>& g) {
 
 // One env-step of the built-in rollout (SURVEY.md §8(d) synthetic workload: worker.py:91-118 with a counter-based random
 // policy): the action from g.draw0 / g.draw1, the step, the counters, the auto-reset.  game_run calls it in its loop over
-// a.steps; the single-step chained kernels (tetris_hip.hip: k_chain, k_chain_affine) call it once, with no loop around it.
+// a.steps; the single-step chained kernels (tetris_dev_rollout.h: k_chain, k_chain_affine) call it once, with no loop around it.
 template <int P>
 TE_HD void rollout_step(const Ctx& cx, const KArgs& a, size_t slot, unsigned long long step, Game<P>& g, LaneCounters& cnt) {
     TE_UNROLL

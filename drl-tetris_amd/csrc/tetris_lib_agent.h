@@ -216,7 +216,7 @@ int tetris_select_eval_dev(tetris_batch* b, const tetris_act_eval* e) {
     if ((rc = enqueue(b, Enqueue::STEPS))) return rc;
     aa.a = base_args(b, b->N, nullptr);          // (behind the gate: it may have extended the RNG tables)
     aa.a.steps = 1;
-    return launch(b, k_act_select<256>, dim3(blocks_for(b->N, ACT_BLOCK)), dim3(256), 0, aa);
+    return launch(b, k_act_select, dim3(blocks_for(b->N, ACT_BLOCK)), dim3(ACT_THREADS), 0, aa);
 }
 
 int tetris_step_eval_dev(tetris_batch* b, const tetris_act_eval* e, int ms, int flags, uint8_t* d_done, uint8_t* d_lines,
@@ -273,7 +273,7 @@ int tetris_traj_record_dev(tetris_batch* b, const tetris_traj* traj, int row, co
     TrajRecordArgs ra;
     if ((rc = traj_record_args(shape_of(b), traj, row, e, d_done, d_dead, ra))) return rc;
     if ((rc = enqueue(b, Enqueue::CALLER))) return rc;          // the caller's evaluation and step outputs -> the caller's window
-    return launch(b, k_traj_record<256>, dim3(blocks_for(b->N)), dim3(256), 0, ra);
+    return launch(b, k_traj_record, dim3(blocks_for(b->N, TRAJ_LANE_THREADS)), dim3(TRAJ_LANE_THREADS), 0, ra);
 }
 
 int tetris_traj_advantages_dev(tetris_batch* b, const tetris_traj* traj, int rows, float gamma, float lambda_adv,
@@ -283,7 +283,7 @@ int tetris_traj_advantages_dev(tetris_batch* b, const tetris_traj* traj, int row
     TrajAdvArgs aa;
     if ((rc = traj_adv_args(shape_of(b), traj, rows, gamma, lambda_adv, lambda_value, d_boot, d_adv, d_target, d_closed, aa))) return rc;
     if ((rc = enqueue(b, Enqueue::CALLER))) return rc;          // the caller's window -> the caller's advantages and targets
-    return launch(b, k_traj_advantages<TRAJ_THREADS>, dim3(blocks_for(b->N, TRAJ_BLOCK)), dim3(TRAJ_THREADS), 0, aa);
+    return launch(b, k_traj_advantages, dim3(blocks_for(b->N, TRAJ_BLOCK)), dim3(TRAJ_THREADS), 0, aa);
 }
 
 // ---------------------------------------------------------------- a window's states and sample sets (tetris_batch.h)
@@ -293,7 +293,7 @@ int tetris_traj_observe_dev(tetris_batch* b, const tetris_traj_obs* obs, int row
     TrajObserveArgs oa;
     if ((rc = traj_observe_args(shape_of(b), geo_of_batch(b), obs, row, d_player, oa))) return rc;
     if ((rc = enqueue(b, Enqueue::STATE))) return rc;
-    return launch(b, k_traj_observe<256>, dim3(blocks_for(b->N), (unsigned)b->P), dim3(256), 0, oa);
+    return launch(b, k_traj_observe, dim3(blocks_for(b->N, TRAJ_LANE_THREADS), (unsigned)b->P), dim3(TRAJ_LANE_THREADS), 0, oa);
 }
 
 int tetris_traj_select_dev(tetris_batch* b, const uint8_t* d_mask, int rows, int flags, int32_t* d_index, long long cap,
@@ -306,8 +306,8 @@ int tetris_traj_select_dev(tetris_batch* b, const uint8_t* d_mask, int rows, int
     sa.blocks = b->select_blocks.d;
     if ((rc = enqueue(b, Enqueue::STATE))) return rc;
     const dim3 grid((unsigned)sa.nblocks), block(SELECT_THREADS);
-    if ((rc = launch(b, k_select_count<SELECT_THREADS>, grid, block, 0, sa)) || (rc = launch(b, k_select_scan<SELECT_THREADS>, dim3(1), block, 0, sa))) return rc;
-    return launch(b, k_select_scatter<SELECT_THREADS>, grid, block, 0, sa);
+    if ((rc = launch(b, k_select_count, grid, block, 0, sa)) || (rc = launch(b, k_select_scan, dim3(1), block, 0, sa))) return rc;
+    return launch(b, k_select_scatter, grid, block, 0, sa);
 }
 
 // the gather of a minibatch: tetris_traj_batch_dev from a window, tetris_replay_gather_dev from the replay's ring
@@ -316,7 +316,7 @@ static int launch_traj_batch(tetris_batch* b, const TrajBatchArgs& ba) {
     const int rc = enqueue(b, Enqueue::STATE);
     if (rc) return rc;
     const size_t lds = ba.visual ? (size_t)BATCH_BLOCK * b->H * NCOL : 0;          // at most 19 840 bytes (31 rows)
-    return launch(b, k_traj_batch<BATCH_BLOCK>, dim3(blocks_for(ba.m, BATCH_BLOCK), (unsigned)b->P), dim3(BATCH_BLOCK), lds, ba);
+    return launch(b, k_traj_batch, dim3(blocks_for(ba.m, BATCH_BLOCK), (unsigned)b->P), dim3(BATCH_BLOCK), lds, ba);
 }
 
 int tetris_traj_batch_dev(tetris_batch* b, const tetris_traj* traj, const tetris_traj_obs* obs, const float* d_adv_in,
@@ -335,9 +335,9 @@ static int launch_sort(tetris_batch* b, SortArgs so, uint32_t* key, uint32_t* po
     int rc = TETRIS_OK;
     for (int pass = 0; pass < 4 && !rc; pass++) {
         sort_pass(so, pass, key, pos, okey, opos);
-        if ((rc = launch(b, k_sort_histogram<SORT_THREADS>, tiles, block, 0, so))) break;
-        if ((rc = launch(b, k_sort_scan<SORT_SCAN_SPAN>, dim3(SORT_RADIX), dim3(SORT_SCAN_SPAN), 0, so))) break;
-        rc = launch(b, k_sort_scatter<SORT_THREADS>, tiles, block, 0, so);
+        if ((rc = launch(b, k_sort_histogram, tiles, block, 0, so))) break;
+        if ((rc = launch(b, k_sort_scan, dim3(SORT_RADIX), dim3(SORT_SCAN_SPAN), 0, so))) break;
+        rc = launch(b, k_sort_scatter, tiles, block, 0, so);
     }
     return rc;
 }
@@ -352,10 +352,10 @@ int tetris_replay_add_dev(tetris_batch* b, const tetris_replay* rp, const tetris
     if ((rc = b->replay_offsets.ensure((size_t)b->N + 1, b->stream))) return rc;
     aa.offsets = b->replay_offsets.d;
     if ((rc = enqueue(b, Enqueue::STATE))) return rc;
-    const dim3 grid(blocks_for(b->N)), block(256);
-    if ((rc = launch(b, k_replay_add_count<256>, grid, block, 0, aa)) ||
-        (rc = launch(b, k_replay_add_scan<SELECT_THREADS>, dim3(1), dim3(SELECT_THREADS), 0, aa))) return rc;
-    return launch(b, k_replay_add_scatter<256>, grid, block, 0, aa);
+    const dim3 grid(blocks_for(b->N, REPLAY_THREADS)), block(REPLAY_THREADS);
+    if ((rc = launch(b, k_replay_add_count, grid, block, 0, aa)) ||
+        (rc = launch(b, k_replay_add_scan, dim3(1), dim3(SELECT_THREADS), 0, aa))) return rc;
+    return launch(b, k_replay_add_scatter, grid, block, 0, aa);
 }
 
 int tetris_replay_sample_dev(tetris_batch* b, const tetris_replay* rp, int M, float alpha, float beta, uint32_t seed, uint64_t draw,
@@ -367,10 +367,10 @@ int tetris_replay_sample_dev(tetris_batch* b, const tetris_replay* rp, int M, fl
     if ((rc = b->replay_sort.ensure(replay_scratch_words(sa.max_size), b->stream))) return rc;
     const SortArgs so = replay_sample_scratch(sa, b->replay_sort.d);
     if ((rc = enqueue(b, Enqueue::STATE))) return rc;
-    const dim3 all(blocks_for(sa.max_size)), block(256);
-    if ((rc = launch(b, k_replay_prio_keys<256>, all, block, 0, sa)) || (rc = launch_sort(b, so, sa.key_a, sa.pos_a, sa.key_b, sa.pos_b)) ||
-        (rc = launch(b, k_replay_sample_keys<256>, all, block, 0, sa)) || (rc = launch_sort(b, so, sa.key_b, sa.pos_b, sa.key_a, sa.pos_a))) return rc;
-    return launch(b, k_replay_emit<256>, dim3(std::max(1u, blocks_for(M))), block, 0, sa);
+    const dim3 all(blocks_for(sa.max_size, REPLAY_THREADS)), block(REPLAY_THREADS);
+    if ((rc = launch(b, k_replay_prio_keys, all, block, 0, sa)) || (rc = launch_sort(b, so, sa.key_a, sa.pos_a, sa.key_b, sa.pos_b)) ||
+        (rc = launch(b, k_replay_sample_keys, all, block, 0, sa)) || (rc = launch_sort(b, so, sa.key_b, sa.pos_b, sa.key_a, sa.pos_a))) return rc;
+    return launch(b, k_replay_emit, dim3(std::max(1u, blocks_for(M, REPLAY_THREADS))), block, 0, sa);
 }
 
 int tetris_replay_update_prios_dev(tetris_batch* b, const tetris_replay* rp, const int32_t* d_index, const float* d_prio_new, int M) {
@@ -380,7 +380,7 @@ int tetris_replay_update_prios_dev(tetris_batch* b, const tetris_replay* rp, con
     if ((rc = replay_update_args(shape_of(b), rp, d_index, d_prio_new, M, ua))) return rc;
     if (M == 0) return TETRIS_OK;
     if ((rc = enqueue(b, Enqueue::STATE))) return rc;
-    return launch(b, k_replay_update<256>, dim3(blocks_for(M)), dim3(256), 0, ua);
+    return launch(b, k_replay_update, dim3(blocks_for(M, REPLAY_THREADS)), dim3(REPLAY_THREADS), 0, ua);
 }
 
 int tetris_replay_gather_dev(tetris_batch* b, const tetris_replay* rp, const int32_t* d_index, int M, int steps,

@@ -1,5 +1,5 @@
 // Host side of libtetris_hip.so, part 1: the batch object with its RNG tables and staging, the launch / enqueue / scratch helpers,
-// the flag service, the run-ahead gate, finish_call and HostCall.  Included by tetris_hip.hip behind its kernels; nothing before it.
+// the flag service, the run-ahead gate, finish_call and HostCall.  Included by tetris_hip.hip behind the kernel headers (tetris_dev_*.h); no host header before it.
 
 struct tetris_batch;
 static int chain_recover(tetris_batch* b);           // (tetris_lib_rollout.h; finish_call needs it)

@@ -222,7 +222,7 @@ TE_HD void plan_step_lane(const PlanArgs& pa, int i, const uint32_t* shapes, boo
 // ---------------------------------------------------------------- deltas: simulated columns -> the network input of a planning agent
 // sherlock_utils.deltas / generate_deltas (agents/sherlock_agent/sherlock_utils.py:9-20), per game and list: the acting player's
 // field after the list minus the field before; a list whose difference adds up to less than 4 is `small_fill` everywhere; lists
-// past count are zero; sums = the sum over the lists.  The element logic below is shared by k_plan_deltas (tetris_hip.hip) and
+// past count are zero; sums = the sum over the lists.  The element logic below is shared by k_plan_deltas (tetris_dev_agent_plan.h) and
 // the host loop of tests/cpu_harness/harness_deltas.cpp, so that both give the same bits.
 struct PlanDeltaArgs {
     Geo geo;
