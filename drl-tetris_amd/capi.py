@@ -79,6 +79,13 @@ class TrajBatch(C.Structure):
                 ("d_adv", C.c_void_p), ("d_target", C.c_void_p), ("d_reward", C.c_void_p), ("d_done", C.c_void_p), ("d_valid", C.c_void_p)]
 
 
+class TrajPlan(C.Structure):
+    """mirrors `struct tetris_traj_plan` (include/tetris_hip.h)"""
+    _fields_ = [("capacity", C.c_int), ("reserved", C.c_int), ("d_rec", C.c_void_p)]
+
+
+PLAN_REC_WORDS = 112          # TETRIS_PLAN_REC_WORDS
+PLAN_BATCH_F16 = 1            # TETRIS_PLAN_BATCH_F16
 SELECT_AUGMENT = 1            # TETRIS_SELECT_AUGMENT
 class Replay(C.Structure):
     """mirrors `struct tetris_replay` (include/tetris_hip.h)"""
@@ -191,6 +198,8 @@ _SIGNATURES = {
     "tetris_traj_observe_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tetris_traj_select_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
     "tetris_traj_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "tetris_traj_record_plan_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tetris_traj_plan_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "tetris_replay_add_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_int]),
     "tetris_replay_sample_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -632,6 +641,25 @@ class TetrisBatch:
         self._check(self.lib.tetris_traj_batch_dev(self._h, C.byref(traj) if traj is not None else None,
                                                    C.byref(obs) if obs is not None else None, adv, target, index, int(m),
                                                    C.byref(out) if out is not None else None))
+
+    # -- the planning agent's windows (include/tetris_hip.h: tetris_traj_record_plan_dev, tetris_traj_plan_batch_dev)
+    def traj_plan(self, capacity, rec):
+        """The record struct of the two calls below over a raw DEVICE address: rec uint32 [T][N][112], 16-byte aligned."""
+        o = TrajPlan()
+        o.capacity, o.reserved, o.d_rec = int(capacity), 0, (rec.value if isinstance(rec, C.c_void_p) else rec)
+        return o
+
+    def traj_record_plan_dev(self, traj, plan, obs, row, e, done, dead):
+        """Row `row` of the window and of its plan records from the choosing call e = plan_eval(...) that has just been used, the
+        row of obs that traj_observe_dev wrote before it, and the step's done [N], dead [P][N].  plan None: the row arrays only."""
+        ref = lambda s: C.byref(s) if s is not None else None                     # noqa: E731
+        self._check(self.lib.tetris_traj_record_plan_dev(self._h, ref(traj), ref(plan), ref(obs), int(row), ref(e), done, dead))
+
+    def traj_plan_batch_dev(self, plan, index, m, delta=None, sums=None, small_fill=1e-3, f16=False, flags=0):
+        """delta / sums [m][H][10] float32 (f16: binary16; 16-byte aligned, either may be None) of the entries index int32 [m]
+        names (bit 31: mirrored; -1 or out of range: zeros)."""
+        self._check(self.lib.tetris_traj_plan_batch_dev(self._h, C.byref(plan) if plan is not None else None, index, int(m), float(small_fill),
+                                                        (PLAN_BATCH_F16 if f16 else 0) | int(flags), delta, sums))
 
     # -- experience replay (include/tetris_hip.h: tetris_replay_add_dev and the three after it)
     def replay(self, capacity, k_step, obs, action, prob, adv, target, reward, done, flags, prio, cursor):

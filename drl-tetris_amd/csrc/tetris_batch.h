@@ -118,6 +118,15 @@ struct TrajBatchArgs {
 };
 
 struct BatchEntry { uint32_t at; bool valid, mirror; };
+// an element v of a window's index list: entry v & 0x7FFFFFFF of `total`, mirrored with bit 31; outside [0, total): no sample
+TE_HD BatchEntry batch_index_entry(uint32_t v, uint32_t total) {
+    BatchEntry en;
+    en.at = v & ~BATCH_MIRROR;
+    en.mirror = (v & BATCH_MIRROR) != 0;
+    en.valid = en.at < total;               // (-1: 0x7FFFFFFF, never below T * N < 2^31)
+    if (!en.valid) { en.at = 0; en.mirror = false; }
+    return en;
+}
 TE_HD BatchEntry batch_entry(const TrajBatchArgs& ba, int j) {
     BatchEntry en;
     if (ba.steps > 0) {
@@ -127,12 +136,7 @@ TE_HD BatchEntry batch_entry(const TrajBatchArgs& ba, int j) {
         en.mirror = en.valid && (ba.flags[en.at] & 1u) != 0;
         return en;
     }
-    const uint32_t v = (uint32_t)ba.index[j];
-    en.at = v & ~BATCH_MIRROR;
-    en.mirror = (v & BATCH_MIRROR) != 0;
-    en.valid = en.at < ba.total;            // (-1: 0x7FFFFFFF, never below T * N < 2^31)
-    if (!en.valid) { en.at = 0; en.mirror = false; }
-    return en;
+    return batch_index_entry((uint32_t)ba.index[j], ba.total);
 }
 // augment_data's piece_swap = (1, 0, 3, 2, 4, 5, 6) (trajectory.py:89); index 7 (no piece) stays
 TE_HD uint32_t batch_piece_swap(uint32_t k) { return k < 4u ? (k ^ 1u) : k; }

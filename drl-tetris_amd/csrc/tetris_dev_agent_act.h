@@ -1,5 +1,6 @@
 // Kernels of libtetris_hip.so, part 5: the acting, window and replay half of tetris_lib_agent.h: acting on a network's evaluation,
-// trajectory windows, a window's states, sample sets and minibatches, experience replay and its radix sort.  Needs
+// trajectory windows, a window's states, sample sets and minibatches, the planning agent's windows, experience replay and its radix
+// sort.  Needs
 // tetris_dev_observe.h (obs_row_words, obs_row_halves).  Every kernel here has one named block size: its launch bounds and its
 // launch in tetris_lib_agent.h both use it.
 
@@ -265,6 +266,175 @@ __global__ __launch_bounds__(BATCH_BLOCK) void k_traj_batch(TrajBatchArgs ba) {
             *reinterpret_cast<uint32_t*>(out + k) = *reinterpret_cast<const uint32_t*>(tile + k);
     }
     for (uint32_t k = done + (uint32_t)lane; k < bytes; k += BATCH_BLOCK) out[k] = tile[k];
+}
+
+// ---- the planning agent's windows (tetris_plan_traj.h)
+// tetris_traj_record_plan_dev.  A workgroup takes PLAN_RECORD_GAMES = G consecutive games (S = threads / G slices):
+//   a. lane t < G: player, count, choice and the row's scalar arrays; `before` of the G games from the observation records
+//      (48-byte runs, 48 P bytes apart) into LDS, column-major [10][G];
+//   b. thread = (game, slice): lists k = s, s + S, ..: ten independent column loads, coalesced over the games of a slice (d_cols
+//      is game-minor), the popcounts against `before`, the kind into an LDS byte [L][G];
+//   c. thread = (game, column): the nine bit-sliced counters over the NORMAL lists — the loop of k_plan_choose's phase E, its
+//      loads coalesced over games again and served by L2 — the counts of the kinds, the chosen list's word, and all of it into an
+//      LDS image of the G records;
+//   d. the G records are G x 448 contiguous bytes of the window's row: 16-byte LDS reads -> 16-byte stores in memory order.
+// The LDS image has a pitch of PLAN_REC_PITCH = 116 words per record: a multiple of four, so the 16-byte reads of (d) stay
+// aligned, and 4 x 29, so the 32 games of a lane group, which write the same word of their records in (c), spread over eight
+// banks instead of the two a pitch of 112 gives.  LDS: 14.5 KB of records, 1.25 KB of `before`, L G bytes of kinds (8 KB at 256
+// lists).  No workgroup waits for another.
+constexpr int PLAN_REC_PITCH = PLAN_REC_WORDS + 4;
+static_assert(PLAN_RECORD_THREADS % PLAN_RECORD_GAMES == 0 && PLAN_RECORD_GAMES <= 64, "whole slices of G lanes");
+__host__ __device__ constexpr size_t plan_record_lds_bytes(int L) {
+    return ((size_t)PLAN_RECORD_GAMES * PLAN_REC_PITCH + (size_t)(NCOL + 3) * PLAN_RECORD_GAMES) * 4 + (size_t)L * PLAN_RECORD_GAMES;
+}
+__global__ __launch_bounds__(PLAN_RECORD_THREADS) void k_traj_record_plan(PlanRecordArgs ra) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t plan_record_lds[];
+    constexpr int G = PLAN_RECORD_GAMES, S = PLAN_RECORD_THREADS / G;
+    uint32_t* s_rec = plan_record_lds;                                   // [G][PLAN_REC_PITCH]
+    uint32_t* s_before = s_rec + G * PLAN_REC_PITCH;                     // [10][G]
+    int* s_player = reinterpret_cast<int*>(s_before + NCOL * G);         // [G] each
+    int *s_count = s_player + G, *s_choice = s_count + G;
+    uint8_t* s_kind = reinterpret_cast<uint8_t*>(s_choice + G);          // [L][G]
+    const int t = (int)threadIdx.x, g0 = (int)blockIdx.x * G, ng = imin(G, ra.n - g0);
+    const int P = ra.n_players, L = ra.max_lists;
+    const size_t n = (size_t)ra.n;
+    const bool packed = ra.rec != nullptr;
+    if (t < ng) {                                                                        // a
+        const int i = g0 + t, p = safe_player(ra.player, i, P);
+        const int count = packed ? plan_clamp_count(ra.count[i], L) : 0;
+        const int choice = packed ? plan_record_choice(ra.choice[i], count) : ra.choice[i];
+        s_player[t] = p; s_count[t] = count; s_choice[t] = choice;
+        plan_record_row(ra, i, p, choice);
+    }
+    if (!packed) return;
+    const uint32_t mask = plan_row_mask(ra.H);
+    for (int u = t; u < ng * NCOL; u += PLAN_RECORD_THREADS) {
+        const int g = u / NCOL, c = u - g * NCOL;
+        s_before[c * G + g] = ra.obs[(size_t)(g0 + g) * P * OBS_WORDS + c] & mask;
+    }
+    __syncthreads();
+    {                                                                                   // b
+        const int g = t % G, s = t / G, i = g0 + g;
+        if (g < ng) {
+            const int p = s_player[g], count = s_count[g];
+            uint32_t before[NCOL];
+            TE_UNROLL
+            for (int c = 0; c < NCOL; c++) before[c] = s_before[c * G + g];
+            for (int k = s; k < count; k += S) {
+                const uint32_t* src = ra.cols + ((size_t)k * P + p) * NCOL * n + i;
+                uint32_t after[NCOL];
+                TE_UNROLL
+                for (int c = 0; c < NCOL; c++) after[c] = src[(size_t)c * n] & mask;
+                s_kind[k * G + g] = (uint8_t)plan_list_kind(k, count, plan_list_sum(after, before));
+            }
+        }
+    }
+    __syncthreads();
+    for (int u = t; u < NCOL * G; u += PLAN_RECORD_THREADS) {                            // c
+        const int g = u % G, c = u / G, i = g0 + g;
+        if (g >= ng) continue;
+        const int p = s_player[g], count = s_count[g], choice = s_choice[g];
+        const uint32_t* src = ra.cols + ((size_t)p * NCOL + c) * n + i;
+        const size_t step = (size_t)P * NCOL * n;
+        uint32_t plane[CHOOSE_COUNT_PLANES];
+        TE_UNROLL
+        for (int j = 0; j < CHOOSE_COUNT_PLANES; j++) plane[j] = 0u;
+        int n_small = 0, n_normal = 0;
+#pragma unroll 4
+        for (int k = 0; k < count; k++) {
+            const uint32_t word = src[(size_t)k * step] & mask;
+            const int kind = s_kind[k * G + g];
+            n_small += kind == PLAN_LIST_SMALL;
+            n_normal += kind == PLAN_LIST_NORMAL;
+            plan_count_add(plane, kind == PLAN_LIST_NORMAL ? word : 0u);
+        }
+        const int kind = count > 0 ? (int)s_kind[choice * G + g] : (int)PLAN_LIST_PAST;
+        uint32_t aw = 0u;
+        if (kind == PLAN_LIST_NORMAL) aw = src[(size_t)choice * step] & mask;
+        uint32_t* r = s_rec + g * PLAN_REC_PITCH;
+        r[PLAN_REC_BEFORE + c] = s_before[c * G + g];
+        r[PLAN_REC_AFTER + c] = aw;
+        TE_UNROLL
+        for (int j = 0; j < CHOOSE_COUNT_PLANES; j++) r[PLAN_REC_PLANES + CHOOSE_COUNT_PLANES * c + j] = plane[j];
+        if (c == 0) {
+            r[PLAN_REC_KIND] = (uint32_t)kind;
+            r[PLAN_REC_COUNTS] = (uint32_t)n_small | ((uint32_t)n_normal << 16);
+        }
+    }
+    __syncthreads();
+    Quad* out = reinterpret_cast<Quad*>(ra.rec + (size_t)g0 * PLAN_REC_WORDS);           // d
+    for (int e = t; e < ng * PLAN_REC_QUADS; e += PLAN_RECORD_THREADS) {
+        const int g = e / PLAN_REC_QUADS, q = e - g * PLAN_REC_QUADS;
+        out[e] = *reinterpret_cast<const Quad*>(s_rec + g * PLAN_REC_PITCH + 4 * q);
+    }
+}
+
+// tetris_traj_plan_batch_dev.  A workgroup takes PLAN_BATCH_SAMPLES consecutive samples: a multiple of 8, so its run of either
+// output starts on 16 bytes for every H and both element types.  The records are gathered with 16-byte loads, 28 consecutive
+// lanes per sample — 448 contiguous bytes wherever the index points; a sample that names no entry becomes a record of zeros,
+// which expands to zeros — into an LDS image [samples][112].  Then every thread builds 16 bytes of consecutive output elements
+// from LDS, walking (sample, row, column) along without a division per element, and streams them out: a wave instruction
+// stores 1 KB contiguous, d_delta first, then d_sums.  The mirror is the choice of the record's column.  Lanes of a group read
+// at most ten distinct record words at a time (five columns of two samples: their banks differ); equal addresses broadcast.
+// The tail of a last, short workgroup whose run is no multiple of 16 bytes leaves element by element.
+struct PlanBatchShared {
+    alignas(16) uint32_t rec[PLAN_BATCH_SAMPLES * PLAN_REC_WORDS];
+    uint32_t mirror[PLAN_BATCH_SAMPLES];
+};
+template <bool SUMS>
+__device__ __forceinline__ float plan_batch_cell(const uint32_t* r, bool mirror, int y, int c, float small_fill) {
+    return SUMS ? plan_rec_sums(r, mirror, y, c, small_fill) : plan_rec_delta(r, mirror, y, c, small_fill);
+}
+template <typename T, bool SUMS>
+__device__ __forceinline__ void plan_batch_store(const PlanBatchArgs& ba, const PlanBatchShared& sh, int first, int nb, void* plane_out) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    constexpr int EPV = 16 / (int)sizeof(T);
+    const int H = ba.H, HW = H * NCOL;
+    const uint32_t total = (uint32_t)nb * (uint32_t)HW;
+    T* out = (T*)plane_out + (size_t)first * HW;
+    for (uint32_t e0 = (uint32_t)threadIdx.x * EPV; e0 < total; e0 += (uint32_t)PLAN_BATCH_THREADS * EPV) {
+        int j = (int)(e0 / (uint32_t)HW);
+        const int cell = (int)(e0 - (uint32_t)j * (uint32_t)HW);
+        int y = cell / NCOL, c = cell - y * NCOL;
+        T v[EPV];
+        TE_UNROLL
+        for (int q = 0; q < EPV; q++) {
+            v[q] = plan_encode<T>(0.0f);
+            if (e0 + (uint32_t)q < total) v[q] = plan_encode<T>(plan_batch_cell<SUMS>(sh.rec + j * PLAN_REC_WORDS, sh.mirror[j] != 0u, y, c, ba.small_fill));
+            c++;
+            if (c == NCOL) { c = 0; y++; }
+            if (y == H) { y = 0; j++; }
+        }
+        if (e0 + EPV <= total) {
+            u32x4 w;
+            w.x = pd_pack(v, 0); w.y = pd_pack(v, 1); w.z = pd_pack(v, 2); w.w = pd_pack(v, 3);
+            __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(out + e0));
+        } else {
+            TE_UNROLL
+            for (int q = 0; q < EPV; q++)
+                if (e0 + (uint32_t)q < total) out[e0 + q] = v[q];
+        }
+    }
+}
+template <typename T>
+__global__ __launch_bounds__(PLAN_BATCH_THREADS) void k_traj_plan_batch(PlanBatchArgs ba) {
+    __shared__ PlanBatchShared sh;
+    const int t = (int)threadIdx.x, first = (int)blockIdx.x * PLAN_BATCH_SAMPLES, nb = imin(PLAN_BATCH_SAMPLES, ba.m - first);
+    for (int e = t; e < nb * PLAN_REC_QUADS; e += PLAN_BATCH_THREADS) {
+        const int j = e / PLAN_REC_QUADS, q = e - j * PLAN_REC_QUADS;
+        const BatchEntry en = plan_batch_entry(ba, first + j);
+        // (an entry that names no sample has at = 0: entry 0 is loaded and dropped word by word — a select between a loaded
+        // aggregate and a constant one would go through scratch)
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 w = reinterpret_cast<const u32x4*>(ba.rec + (size_t)en.at * PLAN_REC_WORDS)[q];
+        const uint32_t keep = en.valid ? ~0u : 0u;
+        w.x &= keep; w.y &= keep; w.z &= keep; w.w &= keep;
+        *reinterpret_cast<u32x4*>(sh.rec + j * PLAN_REC_WORDS + 4 * q) = w;
+        if (q == 0) sh.mirror[j] = en.mirror ? 1u : 0u;
+    }
+    __syncthreads();
+    if (ba.delta) plan_batch_store<T, false>(ba, sh, first, nb, ba.delta);
+    if (ba.sums) plan_batch_store<T, true>(ba, sh, first, nb, ba.sums);
 }
 
 // ---- experience replay (tetris_replay.h)

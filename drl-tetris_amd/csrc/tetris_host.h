@@ -20,6 +20,7 @@
 #include "tetris_traj.h"
 #include "tetris_batch.h"
 #include "tetris_replay.h"
+#include "tetris_plan_traj.h"
 
 namespace te {
 
@@ -465,6 +466,62 @@ static inline int traj_batch_args(const HostShape& s, const tetris_traj* traj, c
     ba.prob_out = out->d_prob; ba.adv_out = out->d_adv; ba.target_out = out->d_target; ba.reward_out = out->d_reward;
     ba.done_out = out->d_done; ba.valid = out->d_valid;
     ba.steps = 0; ba.limit = 0u; ba.flags = nullptr;
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- the planning agent's windows (tetris_plan_traj.h)
+// the argument checks, then the kernel arguments
+static inline int traj_record_plan_args(const HostShape& s, const tetris_traj* traj, const tetris_traj_plan* plan, const tetris_traj_obs* obs, int row,
+                                        const tetris_plan_eval* e, const uint8_t* d_done, const uint8_t* d_dead, PlanRecordArgs& ra) {
+    if (!traj || !e) return fail(TETRIS_E_ARG, "the window or the argument struct is NULL");
+    int rc = not_on_split(s, "tetris_traj_record_plan_dev");
+    if (rc) return rc;
+    if (s.P > 2) return fail(TETRIS_E_ARG, "the reward is defined for one or two players (tetris_environment.py:135-144)");
+    if (!traj->d_action || !traj->d_prob || !traj->d_value || !traj->d_reward || !traj->d_done) return fail(TETRIS_E_ARG, "an array of the window is NULL");
+    if (row < 0 || row >= traj->capacity) return fail(TETRIS_E_ARG, "row outside the window");
+    if (!e->d_choice || !e->d_piece || !e->d_prob) return fail(TETRIS_E_ARG, "choice/piece/prob of the choosing call are NULL");
+    if (!d_done || !d_dead) return fail(TETRIS_E_ARG, "done/dead are NULL");
+    if (plan) {
+        if (!plan->d_rec) return fail(TETRIS_E_ARG, "the plan records are NULL");
+        if ((rc = traj_obs_check(s, obs))) return rc;
+        if (((uintptr_t)plan->d_rec) & 15u) return fail(TETRIS_E_ARG, "d_rec must be 16-byte aligned");
+        if (plan->capacity != traj->capacity || obs->capacity != traj->capacity) return fail(TETRIS_E_ARG, "the window, its plan records and its observation records differ in capacity");
+        if (!e->d_count || !e->d_cols) return fail(TETRIS_E_ARG, "count/cols of the choosing call are NULL");
+        if (e->max_lists < 1 || e->max_lists > PLAN_RECORD_MAX_LISTS) return fail(TETRIS_E_ARG, "1 <= max_lists <= 256");
+        if (((uintptr_t)e->d_cols) & 3u) return fail(TETRIS_E_ARG, "cols must be 4-byte aligned");
+    }
+    const size_t n = (size_t)s.N, at = (size_t)row * n;
+    memset(&ra, 0, sizeof ra);
+    ra.n = s.N; ra.n_players = s.P; ra.H = s.H; ra.max_lists = e->max_lists;
+    ra.player = e->d_player; ra.count = e->d_count; ra.cols = e->d_cols; ra.choice = e->d_choice;
+    ra.piece = e->d_piece; ra.prob_in = e->d_prob; ra.value = e->d_value;
+    ra.done = d_done; ra.dead = d_dead;
+    if (plan) {
+        ra.obs = obs->d_obs + at * (size_t)s.P * OBS_WORDS;
+        ra.rec = plan->d_rec + at * PLAN_REC_WORDS;
+    }
+    ra.action = traj->d_action + at * 4; ra.prob = traj->d_prob + at;
+    ra.value0 = traj->d_value + at; ra.value1 = traj->d_value + (size_t)traj->capacity * n + at;
+    ra.reward = traj->d_reward + at; ra.done_out = traj->d_done + at;
+    return TETRIS_OK;
+}
+
+static inline int traj_plan_batch_args(const HostShape& s, const tetris_traj_plan* plan, const int32_t* d_index, int M, float small_fill, int flags,
+                                       void* d_delta, void* d_sums, PlanBatchArgs& ba) {
+    int rc = traj_batch_rules(s, "tetris_traj_plan_batch_dev");
+    if (rc) return rc;
+    if (!plan || !plan->d_rec || !d_index) return fail(TETRIS_E_ARG, "the plan records or the index list are NULL");
+    if (!d_delta && !d_sums) return fail(TETRIS_E_ARG, "delta and sums are both NULL");
+    if (M < 0) return fail(TETRIS_E_ARG, "M < 0");
+    if (plan->capacity < 1 || (unsigned long long)plan->capacity * (unsigned long long)s.N >= (1ull << 31)) return fail(TETRIS_E_ARG, "the window must hold between 1 and 2^31 - 1 entries");
+    if (flags & ~TETRIS_PLAN_BATCH_F16) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((((uintptr_t)plan->d_rec) | ((uintptr_t)d_delta) | ((uintptr_t)d_sums)) & 15u) return fail(TETRIS_E_ARG, "d_rec / delta / sums must be 16-byte aligned");
+    memset(&ba, 0, sizeof ba);
+    ba.m = M; ba.H = s.H;
+    ba.total = (uint32_t)plan->capacity * (uint32_t)s.N;
+    ba.index = d_index; ba.rec = plan->d_rec;
+    ba.small_fill = small_fill; ba.f16 = (flags & TETRIS_PLAN_BATCH_F16) ? 1 : 0;
+    ba.delta = d_delta; ba.sums = d_sums;
     return TETRIS_OK;
 }
 

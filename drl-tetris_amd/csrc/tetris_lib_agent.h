@@ -1,5 +1,5 @@
 // Host side of libtetris_hip.so, part 4: the agent-side entry points: planning, heuristic policy, acting on an evaluation, trajectory
-// windows, window batches, experience replay.  Needs tetris_lib_batch.h and tetris_lib_rollout.h (margin, counters).
+// windows, window batches, the planning agent's windows, experience replay.  Needs tetris_lib_batch.h and tetris_lib_rollout.h (margin, counters).
 
 // ---------------------------------------------------------------- planning: action lists, simulated afterstates, list steps
 // Games per k_actions + k_plan_lists pair: bounds the slab scratch (40 x 16 slab entries of max_keys + 1 bytes per game: 128 MB
@@ -326,6 +326,30 @@ int tetris_traj_batch_dev(tetris_batch* b, const tetris_traj* traj, const tetris
     TrajBatchArgs ba;
     if ((rc = traj_batch_args(shape_of(b), traj, obs, d_adv_in, d_target_in, d_index, M, out, ba))) return rc;
     return launch_traj_batch(b, ba);
+}
+
+// ---------------------------------------------------------------- the planning agent's windows (tetris_plan_traj.h)
+int tetris_traj_record_plan_dev(tetris_batch* b, const tetris_traj* traj, const tetris_traj_plan* plan, const tetris_traj_obs* obs,
+                                int row, const tetris_plan_eval* e, const uint8_t* d_done, const uint8_t* d_dead) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    PlanRecordArgs ra;
+    if ((rc = traj_record_plan_args(shape_of(b), traj, plan, obs, row, e, d_done, d_dead, ra))) return rc;
+    if ((rc = enqueue(b, Enqueue::CALLER))) return rc;          // the caller's choice, columns and records -> the caller's windows
+    const size_t lds = ra.rec ? plan_record_lds_bytes(ra.max_lists) : plan_record_lds_bytes(0);
+    return launch(b, k_traj_record_plan, dim3(blocks_for(b->N, PLAN_RECORD_GAMES)), dim3(PLAN_RECORD_THREADS), lds, ra);
+}
+
+int tetris_traj_plan_batch_dev(tetris_batch* b, const tetris_traj_plan* plan, const int32_t* d_index, int M, float small_fill, int flags,
+                               void* d_delta, void* d_sums) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    PlanBatchArgs ba;
+    if ((rc = traj_plan_batch_args(shape_of(b), plan, d_index, M, small_fill, flags, d_delta, d_sums, ba))) return rc;
+    if (M == 0) return TETRIS_OK;
+    if ((rc = enqueue(b, Enqueue::CALLER))) return rc;          // the caller's records -> the caller's planes
+    const dim3 grid(blocks_for(M, PLAN_BATCH_SAMPLES)), block(PLAN_BATCH_THREADS);
+    return ba.f16 ? launch(b, k_traj_plan_batch<uint16_t>, grid, block, 0, ba) : launch(b, k_traj_plan_batch<float>, grid, block, 0, ba);
 }
 
 // ---------------------------------------------------------------- experience replay (tetris_replay.h)

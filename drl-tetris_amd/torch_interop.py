@@ -174,7 +174,7 @@ class TorchEnv:
 
     # ---- choosing a list from the network's phi (include/tetris_hip.h: tetris_select_lists_dev, tetris_step_lists_eval_dev): the
     # part of sherlock_agent.get_action between the network and perform_action
-    def _plan_eval(self, phi, state_eval, mode, player, seed, draw, small_fill, out_dtype, probs):
+    def _plan_eval(self, phi, state_eval, mode, player, seed, draw, small_fill, out_dtype, probs, planes=True):
         """-> (the argument struct, the outputs): the checks, simulate(finalize=False) and the reused output tensors of the two calls"""
         torch, n, H = self.torch, self.b.n_games, self.b.height
         L, _ = self._lists()
@@ -195,9 +195,9 @@ class TorchEnv:
             self.choose_piece = torch.zeros(n, dtype=torch.uint8, device=self.dev)
             self.choose_prob, self.choose_value, self.choose_entropy = torch.zeros(n, **f32), torch.zeros(2, n, **f32), torch.zeros(n, **f32)
             self._choose_planes, self._choose_probs = {}, {}
-        if out_dtype not in self._choose_planes:
+        if planes and out_dtype not in self._choose_planes:
             self._choose_planes[out_dtype] = tuple(torch.zeros(n, H, 10, dtype=out_dtype, device=self.dev) for _ in range(2))
-        delta, sums = self._choose_planes[out_dtype]
+        delta, sums = self._choose_planes[out_dtype] if planes else (None, None)
         if probs and L not in self._choose_probs:
             self._choose_probs[L] = torch.zeros(n, L, dtype=torch.float32, device=self.dev)
         pr = self._choose_probs[L] if probs else None
@@ -209,12 +209,13 @@ class TorchEnv:
                              piece=self._ptr(self.choose_piece), prob=self._ptr(self.choose_prob), probs=self._ptr(pr),
                              value=None if state_eval is None else self._ptr(self.choose_value),
                              entropy=self._ptr(self.choose_entropy) if mode == "pi" else None, delta=self._ptr(delta), sums=self._ptr(sums))
-        self._choose_last = (e, phi, state_eval, player)             # the tensors are kept alive with the struct
+        self._choose_last = (e, phi, state_eval, player)             # what Trajectory.record_plan reads (the tensors are kept alive with the struct)
         outs = (self.choose_choice, self.choose_piece, self.choose_prob, None if state_eval is None else self.choose_value,
                 self.choose_entropy if mode == "pi" else 0.0, delta, sums) + ((pr,) if probs else ())
         return e, outs
 
-    def choose_lists(self, phi, state_eval=None, mode="argmax", player=None, seed=0, draw=0, small_fill=1e-3, out_dtype=None, probs=False):
+    def choose_lists(self, phi, state_eval=None, mode="argmax", player=None, seed=0, draw=0, small_fill=1e-3, out_dtype=None, probs=False,
+                     planes=True):
         """The list of every game (lists of the last action_lists(player) call) from the network's phi [n, H, 10, K] (K = 7, or 1
         with the piece in the state vector; float32 or float16): simulate(finalize=False), then one kernel that scores every list
         with the plane of the piece the game holds, normalises and chooses by mode "argmax" or "pi" (the draw is keyed by (seed,
@@ -222,16 +223,18 @@ class TorchEnv:
         -> (choice int32 [n], piece uint8 [n], prob float32 [n] = pi(a), value float32 [2, n] or None, entropy: float32 [n] for
         "pi", else 0.0, delta [n, H, 10] = the chosen list's deltas, sums [n, H, 10] = the sum over the lists; out_dtype:
         torch.float32 (default) or torch.float16) and with probs=True also probs float32 [n, L] — device tensors, reused; choice
-        feeds step_lists unchanged.  The games are not changed; nothing waits for the GPU."""
-        e, outs = self._plan_eval(phi, state_eval, mode, player, seed, draw, small_fill, out_dtype, probs)
+        feeds step_lists unchanged.  The games are not changed; nothing waits for the GPU.  planes=False: delta and sums are not
+        asked of the kernel and None stands in their place — the form for an actor whose window keeps the packed record
+        (Trajectory(plan=True).record_plan)."""
+        e, outs = self._plan_eval(phi, state_eval, mode, player, seed, draw, small_fill, out_dtype, probs, planes)
         self.b.select_lists_dev(e)
         return outs
 
     def step_lists_eval(self, phi, state_eval=None, mode="argmax", player=None, seed=0, draw=0, small_fill=1e-3, out_dtype=None, probs=False,
-                        ms=400, auto_reset=False):
+                        ms=400, auto_reset=False, planes=True):
         """choose_lists + step_lists in one call: -> (done [n], lines [P, n], dead [P, n]) + choose_lists' outputs; auto_reset as
         for step_rt."""
-        e, outs = self._plan_eval(phi, state_eval, mode, player, seed, draw, small_fill, out_dtype, probs)
+        e, outs = self._plan_eval(phi, state_eval, mode, player, seed, draw, small_fill, out_dtype, probs, planes)
         _, K = self._lists()
         self.b.step_lists_eval_dev(e, self._ptr(self.list_lens), self._ptr(self.list_keys), self._ptr(self.done), self._ptr(self.lines),
                                    self._ptr(self.dead), max_keys=K, ms=ms, auto_reset=auto_reset)
@@ -354,10 +357,11 @@ class TorchEnv:
 
     # ---- trajectory windows (include/tetris_hip.h: tetris_traj_record_dev, tetris_traj_advantages_dev): the worker-side arithmetic
     # between perform_action and the data packet (drl_tetris/worker.py:103-112)
-    def trajectory(self, capacity, states=False):
+    def trajectory(self, capacity, states=False, plan=False):
         """A window of `capacity` rows of this batch's games: -> Trajectory (device tensors, allocated once).  states: the window
-        also holds the packed observation records (observe / select / batch)."""
-        return Trajectory(self, capacity, states)
+        also holds the packed observation records (observe / select / batch).  plan (needs states): it also holds the planning
+        agent's packed delta records (record_plan / batch_plan)."""
+        return Trajectory(self, capacity, states, plan)
 
     # ---- experience replay (include/tetris_hip.h: tetris_replay_add_dev and the three after it): the buffer of
     # sventon_agent_dqn_trainer.do_training (agents/sventon_agent/sventon_agent_dqn_trainer.py:30-100)
@@ -377,9 +381,14 @@ class Trajectory:
     their own (dual-policy re-pairing, extra rewards) fills `reward` / `done` themselves and calls advantages.
     With states=True the window also holds obs int32 [T, n, S, 12] (the words are uint32), the packed observation record of
     include/tetris_hip.h: observe(row) before the acting call of the row, then after advantages select(...) lists the finished
-    entries and batch(index) expands a minibatch of them, mirrored or not, into the trainer's arrays."""
+    entries and batch(index) expands a minibatch of them, mirrored or not, into the trainer's arrays.
+    With plan=True (a planning agent: sherlock_trajectory, sherlock_agent_ppo_trainer.do_training) the window also holds plan_rec
+    int32 [T, n, 112] (the words are uint32), the plan record of include/tetris_hip.h — 448 bytes per entry in place of two float
+    [H, 10] planes.  The loop is observe(row), action_lists, step_lists_eval(planes=False), record_plan(row); advantages, select
+    and batch serve unchanged (action[:, 0] is the list's index, action[:, 1] carries no meaning), and batch_plan(index) expands
+    delta(s, a) and delta_sum(s) of the same samples."""
 
-    def __init__(self, env, capacity, states=False):
+    def __init__(self, env, capacity, states=False, plan=False):
         torch, n = env.torch, env.b.n_games
         assert int(capacity) >= 1, "a window has at least one row"
         self.env, self.capacity = env, int(capacity)
@@ -396,6 +405,44 @@ class Trajectory:
             self._obs = env.b.traj_obs(T, p(self.obs))
             self.count = torch.zeros(1, dtype=torch.int32, device=env.dev)
             self._index, self._batches, self._rows = {}, {}, 0
+        assert states or not plan, "plan=True requires states=True (the record's `before` is the observation's)"
+        if plan:
+            from . import capi
+            self.plan_rec = torch.zeros(T, n, capi.PLAN_REC_WORDS, dtype=torch.int32, device=env.dev)
+            self._plan = env.b.traj_plan(T, p(self.plan_rec))
+            self._plan_batches = {}
+
+    def record_plan(self, row):
+        """Row `row` from the last choose_lists / step_lists_eval call of the TorchEnv (with or without planes) and the step's done /
+        dead: the list's index, piece, pi(a), values and player into the row arrays as record does, and the plan record from the
+        lists' simulated columns and the row's observation — call observe(row) before action_lists of the row.  One and two
+        players."""
+        env = self.env
+        assert hasattr(self, "plan_rec"), "the window was made without plan=True"
+        last = getattr(env, "_choose_last", None)
+        assert last is not None, "call choose_lists or step_lists_eval first"
+        env.b.traj_record_plan_dev(self._traj, self._plan, self._obs, row, last[0], env._ptr(env.done), env._ptr(env.dead))
+
+    def batch_plan(self, index, small_fill=1e-3, dtype=None):
+        """delta(s, a) and delta_sum(s) of the samples index names (as for batch; bit 31: the mirrored image, which the reference
+        does not have) -> TrajectoryPlanBatch(delta [M, H, 10, 1], sums [M, H, 10, 1]) device tensors, reused per (M, dtype); dtype:
+        torch.float32 (default) or torch.float16.  small_fill=0.0 gives the reference's numbers."""
+        from collections import namedtuple
+        env, torch = self.env, self.env.torch
+        assert hasattr(self, "plan_rec"), "the window was made without plan=True"
+        assert index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.dim() == 1
+        dtype = torch.float32 if dtype is None else dtype
+        assert dtype in (torch.float32, torch.float16), "delta / sums are float32 or float16"
+        M, H = index.numel(), env.b.height
+        if (M, dtype) not in self._plan_batches:
+            kind = namedtuple("TrajectoryPlanBatch", "delta sums")
+            self._plan_batches[(M, dtype)] = kind(*(torch.zeros(M, H, 10, 1, dtype=dtype, device=env.dev) for _ in range(2)))
+        t = self._plan_batches[(M, dtype)]
+        if M == 0:
+            return t
+        env.b.traj_plan_batch_dev(self._plan, env._ptr(index), M, delta=env._ptr(t.delta), sums=env._ptr(t.sums), small_fill=small_fill,
+                                  f16=dtype == torch.float16)
+        return t
 
     def record(self, row):
         """Row `row` from the last step_eval / step_eval_observe call of the TorchEnv: its (r, t, piece), chosen entry, values

@@ -630,6 +630,72 @@ int tetris_traj_select_dev(tetris_batch *b, const uint8_t *d_mask, int rows, int
 int tetris_traj_batch_dev(tetris_batch *b, const tetris_traj *traj, const tetris_traj_obs *obs, const float *d_adv_in,
                           const float *d_target_in, const int32_t *d_index, int M, const tetris_traj_batch *out);
 
+/* ---- trajectory windows of a planning agent: the packed deltas of a step, a minibatch of them in the trainer's form --------
+ * replaces: what the planning agent keeps per step and what its trainer reads back — the seven things
+ * sherlock_agent.get_action stores (agents/sherlock_agent/sherlock_agent.py:137-146: a_idx, piece, pi(a), v_piece, v_mean,
+ * delta(s, a), delta_sum(s)), sherlock_trajectory's add / process_trajectory (agents/datatypes/trajectory.py) and the permuted
+ * minibatch slices of sherlock_agent_ppo_trainer.do_training (sherlock_agent_ppo_trainer.py:36-63).  The reference's
+ * process_trajectory passes (v_piece, v_mean) into adv_and_targets in the same swapped order as the sventon trajectory and
+ * gives the same numbers for the same inputs, so tetris_traj_advantages_dev, tetris_traj_select_dev and tetris_traj_batch_dev
+ * serve a planning window unchanged; the two calls here add the two [H][10] planes.  Device pointers, asynchronous on the
+ * batch's stream; one and two players; the batch's games are neither read nor written.
+ *
+ * THE PLAN RECORD (struct tetris_traj_plan): d_rec is uint32 [T][N][112], 16-byte aligned: SAMPLE-major, 448 bytes per entry
+ * for every height, against the 1 600 bytes of two float32 planes of a 20-row board.  All column words are masked to rows
+ * 0..H-1.  With p, count (clamped into [0, L]) and the list kinds exactly those of tetris_plan_deltas_dev, and choice =
+ * e->d_choice[i] clamped into [0, max(count, 1) - 1]:
+ *   words 0..9     `before`: the slot-0 column words of obs->d_obs[row][i], i.e. what tetris_traj_observe_dev(row, d_player)
+ *                  stored from the state the lists were simulated on (copied, so that the record stands alone)
+ *   words 10..19   `after`: the columns of the chosen list, e->d_cols[choice][p][c][i]; zero unless that list is NORMAL
+ *   word 20        the chosen list's kind: 0 NORMAL, 1 SMALL, 2 NONE (count = 0)
+ *   word 21        n_small | n_normal << 16, counted over the lists k < count
+ *   word 22+9c+j   bit-plane j = 0..8 of column c: bit y = bit j of the number of NORMAL lists k < count whose `after` column
+ *                  c has bit y set
+ * RECORD (replaces: store_experience's append of the seven-tuple, sherlock_agent.py:137-146, worker.py:103-112) writes row
+ * `row` of the plan records and of `traj` from a tetris_plan_eval `e` that has just been used and the step's d_done [N] and
+ * d_dead [P][N].  The caller's order is tetris_traj_observe_dev(row), simulate / choose / step, then this call.  It re-reads
+ * e->d_count and e->d_cols and never e->d_phi, e->d_delta or e->d_sums: a caller that records need not ask the choosing call
+ * for the float planes.  The row arrays, as tetris_traj_record_dev writes them:
+ *   d_action[row][i] = (choice & 255, 0, e->d_piece[i], p)     a_idx in place of r; byte 1 of a planning row carries no meaning
+ *   d_prob[row][i]   = e->d_prob[i]
+ *   d_value[0][row][i], d_value[1][row][i] = e->d_value[0][i], e->d_value[1][i]; zeros when e->d_value is NULL
+ *   d_done[row][i]   = d_done[i];  d_reward[row][i] as tetris_traj_record_dev
+ * With plan NULL only the row arrays are written, obs is not read, and choice is e->d_choice[i] unclamped.
+ * TETRIS_E_ARG, and nothing is written: three or four players; a split batch; a row outside [0, T); capacities of traj, plan
+ * and obs that differ; a NULL e, traj, array of the window, e->d_choice, e->d_piece, e->d_prob, d_done or d_dead; with a plan
+ * also a NULL obs, d_obs, d_rec, e->d_count or e->d_cols, a max_lists outside [1, 256], a d_rec or d_obs that is not 16-byte
+ * aligned.
+ *
+ * BATCH (replaces: the slices delta[idx], delta_sum[idx] of sherlock_agent_ppo_trainer.do_training,
+ * sherlock_agent_ppo_trainer.py:36-63): d_index int32 [M] with the meaning it has for tetris_traj_batch_dev, at = d_index[j] &
+ * 0x7FFFFFFF = t N + n.  d_delta, d_sums: [M][H][10] float32, or IEEE binary16 (rounded to nearest even) with
+ * TETRIS_PLAN_BATCH_F16; 16-byte aligned; either may be NULL.
+ *   delta(y, c) = the value tetris_plan_deltas_dev gives a cell of a list of the record's kind whose delta is bit y of
+ *                 after[c] minus bit y of before[c] (NORMAL: that delta; SMALL: small_fill; NONE: 0)
+ *   sums(y, c)  = (float)(cnt(y, c) - n_normal * bit y of before[c]) + small_fill * (float)n_small, one float32 multiply and
+ *                 one float32 add, cnt read out of the nine planes
+ * — for a given small_fill the bits tetris_plan_deltas_dev and tetris_select_lists_dev write.
+ *   bit 31 set: output column c is taken from the record's column 9 - c (before, after, planes): the image that matches
+ *     tetris_traj_batch_dev's mirrored state and swapped piece.  THE REFERENCE HAS NO SUCH SAMPLE: its augment_data unpacks
+ *     the seven arrays of this trajectory into two and raises ValueError (trajectory.py:88-109), so process_trajectory(
+ *     augment=True) fails for a planning agent.  tetris_traj_batch_dev's mirrored action byte 1 (9 - t) carries no meaning for
+ *     a planning row either.
+ *   at outside [0, T N) — -1 among them: zeros.
+ * M = 0 succeeds and does nothing.  TETRIS_E_ARG: NULL plan, d_rec or d_index; both outputs NULL; M < 0; T N >= 2^31; an
+ * unknown flag; a d_rec, d_delta or d_sums that is not 16-byte aligned; three or four players; a split batch.              */
+#define TETRIS_PLAN_REC_WORDS 112
+typedef struct tetris_traj_plan {
+    int       capacity;    /* T */
+    int       reserved;    /* 0 */
+    uint32_t *d_rec;       /* [T][N][112], 16-byte aligned */
+} tetris_traj_plan;
+int tetris_traj_record_plan_dev(tetris_batch *b, const tetris_traj *traj, const tetris_traj_plan *plan,
+                                const tetris_traj_obs *obs, int row, const tetris_plan_eval *e,
+                                const uint8_t *d_done, const uint8_t *d_dead);
+#define TETRIS_PLAN_BATCH_F16 1   /* d_delta / d_sums are IEEE binary16 instead of float32 */
+int tetris_traj_plan_batch_dev(tetris_batch *b, const tetris_traj_plan *plan, const int32_t *d_index, int M,
+                               float small_fill, int flags, void *d_delta, void *d_sums);
+
 /* ---- experience replay: a prioritised ring on the device — add, rank sample, update_prios, k-step gather -----------------
  * replaces: agents/agent_utils/experience_replay.py as sventon_agent_dqn_trainer.do_training drives it
  * (agents/sventon_agent/sventon_agent_dqn_trainer.py:30-100) in its 'rank' sample mode (the only one the reference can run:
