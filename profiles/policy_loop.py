@@ -75,7 +75,7 @@ def rehearse():
     f = rng.random((40, N, H, 10)) < 0.55
     f[:, :, 15:17, :] |= rng.random((40, N, 2, 10)) < 0.9                  # some full rows
     cols = (f.transpose(0, 3, 1, 2).astype(np.int64) << np.arange(H)).sum(axis=-1).astype(np.int32)      # [40, 10, N]
-    from tests.test_policy_device import features
+    from tests.policy_model import features
     want = features(f.reshape(40 * N, H, 10)).reshape(40, N, 8).transpose(0, 2, 1)
     got = torch_features(torch.from_numpy(cols), H).numpy()
     assert np.array_equal(got, want), np.argwhere(got != want)[:5]

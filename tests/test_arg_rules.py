@@ -10,7 +10,7 @@ import pytest
 
 import __graft_entry__ as ge
 from tests import engines
-from tests.test_plan_device import Buf
+from tests.buffers import Buf
 
 E_ARG = -1
 N, H = 3, 8
@@ -29,7 +29,7 @@ class Ctx:
         self.map = np.arange(7, dtype=np.uint8)
         self.bad_map = np.array([0, 1, 2, 7, 4, 5, 6], np.uint8)
         # what the _dev calls take for "device" memory: 1 MiB, 16-byte aligned
-        self.dev = Buf(kind, (1 << 20,), np.uint8)
+        self.dev = Buf.full(kind, (1 << 20,), np.uint8)
         # host arrays of the synchronous calls
         self.keys = np.zeros((N, 2, 4), np.uint8)
         self.lens = np.zeros((N, 2), np.uint8)

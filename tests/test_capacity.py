@@ -41,13 +41,12 @@ import pytest
 
 from oracle import oracle as orc
 from tests import engines
-from tests.test_chain_midgame import _assert_path, _set_path
-from tests.test_plan_device import Buf, _device_lists
-from tests.test_policy_device import W_A
-from tests.test_policy_device import Buf as PBuf
-from tests.test_policy_device import Model as PolicyModel
-from tests.test_traj_device import Buf as VBuf
-from tests.test_traj_device import Window
+from tests import policy_model
+from tests.buffers import Buf
+from tests.plan_support import _device_lists
+from tests.policy_model import W_A
+from tests.seeded import _assert_path, _set_path
+from tests.traj_support import GaeWindow
 
 ERR_FIFO, ERR_STREAM, ERR_CHAIN_FELL_BACK = 1, 2, 4
 CHUNK, QUEUE = 624, 8
@@ -349,13 +348,13 @@ def test_device_steps(kind, path, case):
     auto = path.endswith("auto")
     m, rng = Model(ref, prepared, auto=auto, ms=ms), np.random.default_rng(31)
     w = Watch(eng, m)
-    d_rot, d_trans, d_pl, d_next = (Buf(kind, (n,), np.uint8) for _ in range(4))
-    d_done, d_lines, d_dead = Buf(kind, (n,), np.uint8), Buf(kind, (P, n), np.uint8), Buf(kind, (P, n), np.uint8)
-    vis, vec, pc = Buf(kind, (P, n, H, 10), np.uint8), Buf(kind, (P, n, 12), np.uint8), Buf(kind, (P, n), np.uint8)
+    d_rot, d_trans, d_pl, d_next = (Buf.full(kind, (n,), np.uint8) for _ in range(4))
+    d_done, d_lines, d_dead = Buf.full(kind, (n,), np.uint8), Buf.full(kind, (P, n), np.uint8), Buf.full(kind, (P, n), np.uint8)
+    vis, vec, pc = Buf.full(kind, (P, n, H, 10), np.uint8), Buf.full(kind, (P, n, 12), np.uint8), Buf.full(kind, (P, n), np.uint8)
     for s in range(STEPS):
         rot, trans, player = _random_rt(rng, n, P, s)
         keys, lens = rt_keys(rot, trans, player, P)
-        d_rot.set(rot), d_trans.set(trans), d_pl.set(player), d_next.set((s + 1) % P)
+        d_rot.put(rot), d_trans.put(trans), d_pl.put(player), d_next.put((s + 1) % P)
         if path.startswith("observe"):
             eng.step_rt_observe_dev(d_rot.ptr, d_trans.ptr, d_pl.ptr, d_done.ptr, d_lines.ptr, d_dead.ptr, d_next.ptr, vis.ptr, vec.ptr,
                                     pc.ptr, ms=ms, auto_reset=auto)
@@ -483,7 +482,7 @@ def test_list_steps_and_simulations(kind, case, auto):
         live = ~m.ended
         assert (c[live] >= 1).all() and (c <= L).all()
         before = eng.snapshot()
-        cols, d_done = Buf(kind, (L, P, 10, n), np.uint32), Buf(kind, (L, n), np.uint8, 77)
+        cols, d_done = Buf.full(kind, (L, P, 10, n), np.uint32), Buf.full(kind, (L, n), np.uint8, 77)
         eng.simulate_lists_dev(cnt.ptr, lens.ptr, keys.ptr, cols.ptr, max_lists=L, max_keys=K, player=pl.ptr, finalize=True, ms=ms, done=d_done.ptr)
         eng.sync()
         want, over = _simulated_model(m, c, ln, kk, player)
@@ -495,9 +494,9 @@ def test_list_steps_and_simulations(kind, case, auto):
         assert np.array_equal(eng.snapshot(), before), f"{case}, step {s}: the simulation wrote the batch's state"
         assert eng.take_errors() == 0, f"{case}, step {s}: a simulation reported a game ended by capacity"
         choice = rng.integers(0, 1 << 20, n) % np.maximum(c, 1)
-        ch = Buf(kind, (n,), np.int32)
-        ch.set(choice.astype(np.int32))
-        done, lines, dead = Buf(kind, (n,), np.uint8), Buf(kind, (P, n), np.uint8), Buf(kind, (P, n), np.uint8)
+        ch = Buf.full(kind, (n,), np.int32)
+        ch.put(choice.astype(np.int32))
+        done, lines, dead = Buf.full(kind, (n,), np.uint8), Buf.full(kind, (P, n), np.uint8), Buf.full(kind, (P, n), np.uint8)
         eng.step_lists_dev(ch.ptr, cnt.ptr, lens.ptr, keys.ptr, done.ptr, lines.ptr, dead.ptr, max_lists=L, max_keys=K, player=pl.ptr, ms=ms,
                            auto_reset=auto)
         eng.sync()
@@ -517,15 +516,15 @@ def test_list_steps_and_simulations(kind, case, auto):
 @pytest.mark.parametrize("path", ["step", "rollout_1", "rollout_4"])
 def test_policy_steps_and_rollouts(kind, path):
     """step_policy_dev with auto-reset and rollout_policy at one and four steps per launch, one player: the policy does not die,
-    so its episodes are ended by exactly this limit.  The choice comes from tests.test_policy_device.Model on the oracle."""
+    so its episodes are ended by exactly this limit.  The choice comes from tests.policy_model.Model on the oracle."""
     steps = 12
     eng, ref, prepared, ms = _batch(kind, 1, "draws")
     n = eng.n_games
-    m, pm = Model(ref, prepared, auto=True, ms=ms), PolicyModel(ref)
+    m, pm = Model(ref, prepared, auto=True, ms=ms), policy_model.Model(ref)
     w = Watch(eng, m)
-    wt = PBuf(kind, (8,), np.int16).set(W_A)
-    done, lines, dead = Buf(kind, (n,), np.uint8), Buf(kind, (1, n), np.uint8), Buf(kind, (1, n), np.uint8)
-    rot, trans = Buf(kind, (n,), np.uint8), Buf(kind, (n,), np.uint8)
+    wt = Buf.full(kind, (8,), np.int16).put(W_A)
+    done, lines, dead = Buf.full(kind, (n,), np.uint8), Buf.full(kind, (1, n), np.uint8), Buf.full(kind, (1, n), np.uint8)
+    rot, trans = Buf.full(kind, (n,), np.uint8), Buf.full(kind, (n,), np.uint8)
     S = 1 if path == "step" else int(path[-1])
     for call in range(steps // S):
         total, raised, first = np.zeros(4, np.uint64), 0, None
@@ -567,15 +566,15 @@ def test_eval_steps_and_the_recorded_row(kind, case, observe):
     eng, ref, prepared, ms = _batch(kind, P, case)
     n, H = eng.n_games, eng.height
     m, rng = Model(ref, prepared, auto=True, ms=ms), np.random.default_rng(17)
-    w, win = Watch(eng, m), Window(kind, eng, STEPS, fill=7)
-    u8 = lambda *shape: VBuf(kind, np.zeros(shape, np.uint8))      # noqa: E731
+    w, win = Watch(eng, m), GaeWindow(kind, eng, STEPS, fill=7)
+    u8 = lambda *shape: Buf(kind, np.zeros(shape, np.uint8))      # noqa: E731
     rot, trans, piece, done, lines, dead = u8(n), u8(n), u8(n), u8(n), u8(P, n), u8(P, n)
-    ev = VBuf(kind, np.zeros(n, np.float32))
+    ev = Buf(kind, np.zeros(n, np.float32))
     vis, vec, pc = u8(P, n, H, 10), u8(P, n, 12), u8(P, n)
     capacity_rows = 0
     for s in range(STEPS):
         player = np.full(n, s % P, np.uint8)
-        ae, plb, nxt = VBuf(kind, rng.random((n, 4, 10, 7)).astype(np.float32)), VBuf(kind, player), VBuf(kind, 1 - player)
+        ae, plb, nxt = Buf(kind, rng.random((n, 4, 10, 7)).astype(np.float32)), Buf(kind, player), Buf(kind, 1 - player)
         e = eng.act_eval(ae.ptr, rot.ptr, trans.ptr, n_pieces=7, mode="argmax", player=plb.ptr, piece=piece.ptr, eval=ev.ptr)
         if observe:
             eng.step_eval_observe_dev(e, done.ptr, lines.ptr, dead.ptr, nxt.ptr, vis.ptr, vec.ptr, pc.ptr, ms=ms, auto_reset=True)

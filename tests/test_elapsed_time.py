@@ -25,27 +25,22 @@ tests/test_edge_cases.py), and small `ms` lets packets pile up, so the inputs ar
 or more players only at ms >= 100, random (r, t) below; every test asserts on the ORACLE's records that no board ever has more than
 6 packets pending.  Each sweep and rollout test also asserts, again on the oracle alone, that its boards were in the regime its
 `ms` stands for (Regime, FLOORS)."""
-import functools
-
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
 from tests import engines
-from tests.test_act_eval import Call, model, pieces_of, random_maps
-from tests.test_act_eval import Buf as ValBuf
-from tests.test_chain_midgame import (N_CPU, N_GPU, PREP, Census, _assert_path, _call, _interleaved_step, _model_pool, _seeded,
-                                      _set_path)
-from tests.test_engine_vs_oracle import _DevArrays, _expected_packed
-from tests.test_plan_device import Buf as PlanBuf
-from tests.test_plan_device import _bits, _device_lists
-from tests.test_policy_device import W_A, Buf, Model, _assert_rollout
+from tests.act_support import Call, model, pieces_of, random_maps
+from tests.buffers import Buf
+from tests.plan_support import _bits, _device_lists
+from tests.policy_model import W_A, Model, _assert_rollout
+from tests.seeded import (N_CPU, N_GPU, POOL, PREP, Census, _assert_path, _call, _expected_packed, _heuristic_play, _interleaved_step,
+                          _model_pool, _seeded, _set_path)
 
 MS_ALL = (0, 1, 50, 170, 399, 401, 1000, 1500, 3001, 60000)
 MS_FEW = (50, 1500, 3001)
 N_HARNESS, N_LANES = 192, 2048 + 3      # 2051: one lane per game, the last workgroup (and wave) ragged
 MAX_PENDING = 6
-POOL = 32                               # games the heuristic model plays; tiled over the batch
 RANDOM_STEPS = 32
 
 
@@ -131,28 +126,6 @@ FLOORS = {
 
 
 # ---------------------------------------------------------------- inputs
-def _heur_steps(P, ms):
-    """steps the heuristic plays before the random ones: none for several players below 100 ms (the queue would fill), 130 at
-    3001 (1000 -> 200 -> 100 -> 50 takes 80 + 20 + 25 speed-ups, one per tick; random play ends a game after about 40 steps)"""
-    if P > 1 and ms < 100:
-        return 0
-    return 130 if ms == 3001 else 32
-
-
-@functools.lru_cache(maxsize=None)
-def _heuristic_play(P, ms):
-    """The heuristic model of tests/test_policy_device.py on a pool of 32 oracle games, a random acting player per game and step,
-    finished games reset by the built-in seed schedule -> ((rot, trans, player, done) [32] per step)"""
-    pool = engines.make("oracle", POOL, P, seeds=orc.episode_seed(np.arange(POOL), 0))
-    m = Model(pool, ms=ms)
-    rng = np.random.default_rng(1000 * P + ms)
-    out = []
-    for _ in range(_heur_steps(P, ms)):
-        player = rng.integers(0, P, POOL).astype(np.uint8)
-        r, t, _ = m.choose(W_A, player)
-        done, _, _ = m.step(r, t, player, True)
-        out.append((r.copy(), t.copy(), player, done.copy()))
-    return tuple(out)
 
 
 def _tiled_pair(kind, n, P, height=20):
@@ -297,21 +270,21 @@ def test_step_rt_dev_with_auto_reset(kind, P, ms):
     n = _n(kind)
     seeds = orc.episode_seed(np.arange(n), 0)
     eng, ref = engines.make(kind, n, P, seeds=seeds), engines.make("oracle", n, P, seeds=seeds)
-    D, rng, cen = _DevArrays(kind), np.random.default_rng(3 * ms + P), Regime()
+    rng, cen = np.random.default_rng(3 * ms + P), Regime()
     episode, ended = np.zeros(n, np.int64), 0
-    done_d, lines_d, dead_d = D.put(np.zeros(n, np.uint8)), D.put(np.zeros((P, n), np.uint8)), D.put(np.zeros((P, n), np.uint8))
+    done_d, lines_d, dead_d = Buf(kind, np.zeros(n, np.uint8)), Buf(kind, np.zeros((P, n), np.uint8)), Buf(kind, np.zeros((P, n), np.uint8))
     for s in range(64):
         rot, trans, player = _random_rt(rng, n, P)
-        r_d, t_d, p_d = D.put(rot), D.put(trans), D.put(player)
+        r_d, t_d, p_d = Buf(kind, rot), Buf(kind, trans), Buf(kind, player)
         prev = ref.observe()[0]
-        eng.step_rt_dev(D.ptr(r_d), D.ptr(t_d), D.ptr(p_d), D.ptr(done_d), D.ptr(lines_d), D.ptr(dead_d), ms=ms, auto_reset=True)
+        eng.step_rt_dev(r_d.ptr, t_d.ptr, p_d.ptr, done_d.ptr, lines_d.ptr, dead_d.ptr, ms=ms, auto_reset=True)
         want = ref.step_rt(rot, trans, player, ms=ms)
         rec = ref.observe()[0]
         cen.look(prev, rec)
         if kind == "hip":
             eng.sync()
-        assert np.array_equal(D.get(done_d), want), f"step {s}: done"
-        assert np.array_equal(D.get(lines_d).T, rec["reward"]) and np.array_equal(D.get(dead_d).T, rec["dead"]), f"step {s}: lines / dead"
+        assert np.array_equal(done_d.get(), want), f"step {s}: done"
+        assert np.array_equal(lines_d.get().T, rec["reward"]) and np.array_equal(dead_d.get().T, rec["dead"]), f"step {s}: lines / dead"
         ended += _schedule_reset(ref, want, episode, cen)
         if s % 8 == 7:
             engines.assert_same_state(eng, ref, where=f"step {s}")
@@ -329,26 +302,26 @@ def test_step_rt_observe_dev(kind, P, H, ms):
     n = _n(kind)
     seeds = orc.episode_seed(np.arange(n), 0)
     eng, ref = engines.make(kind, n, P, H, seeds=seeds), engines.make("oracle", n, P, H, seeds=seeds)
-    D, rng, cen = _DevArrays(kind), np.random.default_rng(5 * ms + 10 * P + H), Regime()
+    rng, cen = np.random.default_rng(5 * ms + 10 * P + H), Regime()
     episode, ended = np.zeros(n, np.int64), 0
-    done_d, lines_d, dead_d = D.put(np.zeros(n, np.uint8)), D.put(np.zeros((P, n), np.uint8)), D.put(np.zeros((P, n), np.uint8))
-    vis_d, vec_d, pc_d = D.put(np.zeros((P, n, H, 10), np.uint8)), D.put(np.zeros((P, n, 12), np.uint8)), D.put(np.zeros((P, n), np.uint8))
+    done_d, lines_d, dead_d = Buf(kind, np.zeros(n, np.uint8)), Buf(kind, np.zeros((P, n), np.uint8)), Buf(kind, np.zeros((P, n), np.uint8))
+    vis_d, vec_d, pc_d = Buf(kind, np.zeros((P, n, H, 10), np.uint8)), Buf(kind, np.zeros((P, n, 12), np.uint8)), Buf(kind, np.zeros((P, n), np.uint8))
     for s in range(48):
         rot, trans, player = _random_rt(rng, n, P)
         nxt = rng.integers(0, P, n).astype(np.uint8)
-        r_d, t_d, p_d, n_d = D.put(rot), D.put(trans), D.put(player), D.put(nxt)
+        r_d, t_d, p_d, n_d = Buf(kind, rot), Buf(kind, trans), Buf(kind, player), Buf(kind, nxt)
         prev = ref.observe()[0]
-        eng.step_rt_observe_dev(D.ptr(r_d), D.ptr(t_d), D.ptr(p_d), D.ptr(done_d), D.ptr(lines_d), D.ptr(dead_d), D.ptr(n_d),
-                                D.ptr(vis_d), D.ptr(vec_d), D.ptr(pc_d), ms=ms, auto_reset=True)
+        eng.step_rt_observe_dev(r_d.ptr, t_d.ptr, p_d.ptr, done_d.ptr, lines_d.ptr, dead_d.ptr, n_d.ptr,
+                                vis_d.ptr, vec_d.ptr, pc_d.ptr, ms=ms, auto_reset=True)
         want = ref.step_rt(rot, trans, player, ms=ms)
         rec = ref.observe()[0]
         cen.look(prev, rec)
         if kind == "hip":
             eng.sync()
-        assert np.array_equal(D.get(done_d), want), f"step {s}: done"
-        assert np.array_equal(D.get(lines_d).T, rec["reward"]) and np.array_equal(D.get(dead_d).T, rec["dead"]), f"step {s}: lines / dead"
+        assert np.array_equal(done_d.get(), want), f"step {s}: done"
+        assert np.array_equal(lines_d.get().T, rec["reward"]) and np.array_equal(dead_d.get().T, rec["dead"]), f"step {s}: lines / dead"
         ended += _schedule_reset(ref, want, episode, cen)
-        got = D.get(vis_d), D.get(vec_d), D.get(pc_d)
+        got = vis_d.get(), vec_d.get(), pc_d.get()
         for g, w, name in zip(got, _expected_packed(ref.observe()[0], nxt, P, H), ("visual", "vector", "piece")):
             assert np.array_equal(g, w), f"step {s}: '{name}' differs from the oracle's records"
         if s % 6 == 5:
@@ -396,8 +369,8 @@ def test_lists_simulated_and_stepped_on_the_device(kind, P, ms):
         c, ln, kk = cnt.get(), lens.get(), keys.get()
         assert (c >= 1).all()
         if s % 3 == 0:                                             # every list of every game, finalized: one oracle game per list
-            cols = PlanBuf(kind, (L, P, 10, n), np.uint32)
-            done, lines, dead = PlanBuf(kind, (L, n), np.uint8, 77), PlanBuf(kind, (L, P, n), np.uint8, 77), PlanBuf(kind, (L, P, n), np.uint8, 77)
+            cols = Buf.full(kind, (L, P, 10, n), np.uint32)
+            done, lines, dead = Buf.full(kind, (L, n), np.uint8, 77), Buf.full(kind, (L, P, n), np.uint8, 77), Buf.full(kind, (L, P, n), np.uint8, 77)
             blob = eng.snapshot()
             eng.simulate_lists_dev(cnt.ptr, lens.ptr, keys.ptr, cols.ptr, max_lists=L, max_keys=K, player=pl.ptr, finalize=True, ms=ms,
                                    done=done.ptr, lines=lines.ptr, dead=dead.ptr)
@@ -418,9 +391,9 @@ def test_lists_simulated_and_stepped_on_the_device(kind, P, ms):
             assert np.array_equal(got_done[lk, src], want_done), f"round {s}: simulated done"
             assert np.array_equal(got_lines[lk, :, src], rec["reward"]) and np.array_equal(got_dead[lk, :, src], rec["dead"]), f"round {s}"
         choice = rng.integers(-3, 60, n).astype(np.int32)          # clamped into [0, count - 1]
-        ch = PlanBuf(kind, (n,), np.int32)
-        ch.set(choice)
-        done, lines, dead = PlanBuf(kind, (n,), np.uint8), PlanBuf(kind, (P, n), np.uint8), PlanBuf(kind, (P, n), np.uint8)
+        ch = Buf.full(kind, (n,), np.int32)
+        ch.put(choice)
+        done, lines, dead = Buf.full(kind, (n,), np.uint8), Buf.full(kind, (P, n), np.uint8), Buf.full(kind, (P, n), np.uint8)
         eng.step_lists_dev(ch.ptr, cnt.ptr, lens.ptr, keys.ptr, done.ptr, lines.ptr, dead.ptr, max_lists=L, max_keys=K, player=pl.ptr, ms=ms)
         pick = np.clip(choice, 0, c - 1)
         Kh, Lh = np.zeros((n, P, K), np.uint8), np.ones((n, P), np.uint8)
@@ -451,12 +424,12 @@ def test_policy_step_and_rollout_equal_the_model(kind, P, ms):
     seeds = orc.episode_seed(np.arange(n), 0)
     b, o = engines.make(kind, n, P, seeds=seeds), engines.make("oracle", n, P, seeds=seeds)
     m, cen, rng = Model(o, ms=ms), Regime(), np.random.default_rng(17 * ms + P)
-    w, pl = Buf(kind, (8,), np.int16).set(W_A), Buf(kind, (n,), np.uint8)
-    done, lines, dead = Buf(kind, (n,), np.uint8, 7), Buf(kind, (P, n), np.uint8, 7), Buf(kind, (P, n), np.uint8, 7)
-    rot, trans = Buf(kind, (n,), np.uint8, 7), Buf(kind, (n,), np.uint8, 77)
+    w, pl = Buf.full(kind, (8,), np.int16).put(W_A), Buf.full(kind, (n,), np.uint8)
+    done, lines, dead = Buf.full(kind, (n,), np.uint8, 7), Buf.full(kind, (P, n), np.uint8, 7), Buf.full(kind, (P, n), np.uint8, 7)
+    rot, trans = Buf.full(kind, (n,), np.uint8, 7), Buf.full(kind, (n,), np.uint8, 77)
     for s in range(16):
         player = rng.integers(0, P, n).astype(np.uint8)
-        pl.set(player)
+        pl.put(player)
         b.step_policy_dev(w.ptr, done.ptr, lines.ptr, dead.ptr, rot=rot.ptr, trans=trans.ptr, player=pl.ptr, ms=ms, auto_reset=True)
         prev = o.observe()[0]
         r, t, _ = m.choose(W_A, player)
@@ -484,14 +457,14 @@ def test_policy_step_and_rollout_equal_the_model(kind, P, ms):
 @pytest.mark.parametrize("P", [1, 2])
 @pytest.mark.parametrize("ms", MS_DEV)
 def test_step_eval_dev(kind, P, ms):
-    """tetris_step_eval_dev (auto-reset; ARGMAX and EPSILON in turn) against the model of tests/test_act_eval.py choosing and the
+    """tetris_step_eval_dev (auto-reset; ARGMAX and EPSILON in turn) against the model of tests/act_support.py choosing and the
     oracle stepping at `ms`"""
     n = _n(kind)
     seeds = orc.episode_seed(np.arange(n), 0)
     a, o = engines.make(kind, n, P, seeds=seeds), engines.make("oracle", n, P, seeds=seeds)
     rng, cen = np.random.default_rng(19 * ms + P), Regime()
     ids, episode, ended = np.arange(n), np.zeros(n, np.int64), 0
-    done, lines, dead = ValBuf(kind, np.full(n, 7, np.uint8)), ValBuf(kind, np.full((P, n), 7, np.uint8)), ValBuf(kind, np.full((P, n), 7, np.uint8))
+    done, lines, dead = Buf(kind, np.full(n, 7, np.uint8)), Buf(kind, np.full((P, n), 7, np.uint8)), Buf(kind, np.full((P, n), 7, np.uint8))
     for s in range(40):
         mode = ("argmax", "epsilon")[s % 2]
         player = rng.integers(0, P, n).astype(np.uint8)
@@ -518,7 +491,7 @@ def test_step_eval_dev(kind, P, ms):
 
 # ---------------------------------------------------------------- 3. rollouts
 class RolloutCensus(Census):
-    """tests/test_chain_midgame.py's census (one oracle step per rollout_random call) that also keeps the regime"""
+    """tests/seeded.py's census (one oracle step per rollout_random call) that also keeps the regime"""
 
     def __init__(self, ref, ms):
         super().__init__(ref, ms)
@@ -531,7 +504,7 @@ class RolloutCensus(Census):
 
 
 def _prepared(P, ms):
-    """the seeding pool of tests/test_chain_midgame.py played at `ms`: 48 games; at 3001 for 130 steps, so that the drop delay
+    """the seeding pool of tests/seeded.py played at `ms`: 48 games; at 3001 for 130 steps, so that the drop delay
     is down at 50 when the rollout begins (a round of several players ends when one tops out: 12 of 48 two-player games get there)"""
     long = ms == 3001
     pool = _model_pool(P, 20, ms=ms, prep=130 if long else PREP[P], pool_size=48, survivors=0.2 if long and P > 1 else 0.75)

@@ -6,6 +6,8 @@ import pytest
 
 from oracle import oracle as orc
 from tests import engines
+from tests.buffers import Buf
+from tests.seeded import _expected_packed
 
 
 def _pair(kind, n, P, H=20, pieces=(0, 1, 2, 3, 4, 5, 6), seed_base=0):
@@ -182,29 +184,6 @@ def test_simulate_without_finalize_and_snapshot_restore(kind):
     engines.assert_same_state(eng, ref, where="locked state does not move")
 
 
-class _DevArrays:
-    """uint8 / int16 arrays the `_dev` entry points can take: numpy for the CPU harness (its "device" is host memory),
-    torch tensors on the GPU."""
-
-    def __init__(self, kind):
-        self.gpu = kind == "hip"
-        if self.gpu:
-            import torch
-            self.torch = torch
-
-    def put(self, a):
-        return self.torch.as_tensor(np.ascontiguousarray(a)).cuda() if self.gpu else np.ascontiguousarray(a).copy()
-
-    def ptr(self, t):
-        import ctypes as C
-        if t is None:
-            return None
-        return C.c_void_p(t.data_ptr()) if self.gpu else t.ctypes.data_as(C.c_void_p)
-
-    def get(self, t):
-        return t.cpu().numpy() if self.gpu else t.copy()
-
-
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
 @pytest.mark.parametrize("P", [1, 2])
 def test_device_side_auto_reset_and_masked_reset(kind, P):
@@ -214,25 +193,24 @@ def test_device_side_auto_reset_and_masked_reset(kind, P):
     n = 4096 if kind == "hip" else 320
     eng, ref = _pair(kind, n, P)
     eng.set_game_offset(1000)                                  # the schedule is keyed by GLOBAL game id
-    D = _DevArrays(kind)
     rng = np.random.default_rng(11 + P)
     episode = np.zeros(n, np.int64)
-    done_d, lines_d, dead_d = D.put(np.zeros(n, np.uint8)), D.put(np.zeros((P, n), np.uint8)), D.put(np.zeros((P, n), np.uint8))
+    done_d, lines_d, dead_d = Buf(kind, np.zeros(n, np.uint8)), Buf(kind, np.zeros((P, n), np.uint8)), Buf(kind, np.zeros((P, n), np.uint8))
     total_done = 0
     for s in range(200):
         rot, trans = rng.integers(0, 4, n).astype(np.uint8), rng.integers(0, 10, n).astype(np.uint8)
         player = rng.integers(0, P, n).astype(np.uint8)
         auto = s % 50 < 40                                     # mostly auto-reset; sometimes a separate masked reset launch
-        r_d, t_d, p_d = D.put(rot), D.put(trans), D.put(player)
-        eng.step_rt_dev(D.ptr(r_d), D.ptr(t_d), D.ptr(p_d), D.ptr(done_d), D.ptr(lines_d), D.ptr(dead_d), auto_reset=auto)
+        r_d, t_d, p_d = Buf(kind, rot), Buf(kind, trans), Buf(kind, player)
+        eng.step_rt_dev(r_d.ptr, t_d.ptr, p_d.ptr, done_d.ptr, lines_d.ptr, dead_d.ptr, auto_reset=auto)
         if not auto:
-            eng.reset_dev(D.ptr(done_d), None)                 # mask = this step's done flags, seeds from the schedule
+            eng.reset_dev(done_d.ptr, None)                 # mask = this step's done flags, seeds from the schedule
         d_ref = ref.step_rt(rot, trans, player)
         rec = ref.observe()[0]
         if kind == "hip":
             eng.sync()
-        assert np.array_equal(D.get(done_d), d_ref), s
-        assert np.array_equal(D.get(lines_d).T, rec["reward"]) and np.array_equal(D.get(dead_d).T, rec["dead"]), s
+        assert np.array_equal(done_d.get(), d_ref), s
+        assert np.array_equal(lines_d.get().T, rec["reward"]) and np.array_equal(dead_d.get().T, rec["dead"]), s
         idx = np.nonzero(d_ref)[0].astype(np.int32)
         total_done += len(idx)
         if len(idx):
@@ -244,8 +222,8 @@ def test_device_side_auto_reset_and_masked_reset(kind, P):
     # explicit device seeds for a masked subset
     mask = (np.arange(n) % 3 == 0).astype(np.uint8)
     seeds = rng.integers(-32768, 32767, n).astype(np.int16)
-    m_d, s_d = D.put(mask), D.put(seeds)
-    eng.reset_dev(D.ptr(m_d), D.ptr(s_d))
+    m_d, s_d = Buf(kind, mask), Buf(kind, seeds)
+    eng.reset_dev(m_d.ptr, s_d.ptr)
     idx = np.nonzero(mask)[0].astype(np.int32)
     ref.reset(idx, seeds[idx])
     engines.assert_same_state(eng, ref, where="masked reset with device seeds")
@@ -310,23 +288,6 @@ def test_three_and_four_players(kind, P):
     assert total_done > 0
 
 
-def _expected_packed(rec, me, P, H):
-    """state_dict + unpacker semantics (state_processors.py:23-54; state_unpack.py:88-137) computed from oracle records:
-    -> visual [P][n][H][10], vector [P][n][12], piece [P][n], slot 0 = player me[i]'s board"""
-    n = len(me)
-    visual, vector, piece = np.zeros((P, n, H, 10), np.uint8), np.zeros((P, n, 12), np.uint8), np.zeros((P, n), np.uint8)
-    for sl in range(P):
-        who = me if sl == 0 else (P - 1 - me)
-        r = rec[np.arange(n), who]
-        visual[sl] = (r["field"][:, :H, :] > 0).astype(np.uint8)
-        vector[sl, :, 0] = r["x"].astype(np.uint8); vector[sl, :, 1] = r["y"].astype(np.uint8); vector[sl, :, 2] = r["inc_count"]
-        vector[sl, :, 3] = np.minimum(25000, (r["combo_remaining"].astype(np.uint32) + 50) & 0xFFFF) // 100
-        vector[sl, :, 4] = r["combo_count"]
-        vector[sl, np.arange(n), 5 + r["next"]] = 1
-        piece[sl] = r["piece"]
-    return visual, vector, piece
-
-
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
 @pytest.mark.parametrize("P,H", [(1, 20), (2, 20), (2, 22), (1, 21), (2, 30)])
 def test_step_and_observation_in_one_launch(kind, P, H):
@@ -338,26 +299,25 @@ def test_step_and_observation_in_one_launch(kind, P, H):
     n = 4096 + 37 if kind == "hip" else 200 + 37
     seeds = orc.episode_seed(np.arange(n), 0)
     eng, ref = engines.make(kind, n, P, H, seeds=seeds), engines.make("oracle", n, P, H, seeds=seeds)
-    D = _DevArrays(kind)
     rng = np.random.default_rng(5 + 10 * P + H)
     episode = np.zeros(n, np.int64)
-    done_d, lines_d, dead_d = D.put(np.zeros(n, np.uint8)), D.put(np.zeros((P, n), np.uint8)), D.put(np.zeros((P, n), np.uint8))
-    vis_d, vec_d, pc_d = D.put(np.zeros((P, n, H, 10), np.uint8)), D.put(np.zeros((P, n, 12), np.uint8)), D.put(np.zeros((P, n), np.uint8))
+    done_d, lines_d, dead_d = Buf(kind, np.zeros(n, np.uint8)), Buf(kind, np.zeros((P, n), np.uint8)), Buf(kind, np.zeros((P, n), np.uint8))
+    vis_d, vec_d, pc_d = Buf(kind, np.zeros((P, n, H, 10), np.uint8)), Buf(kind, np.zeros((P, n, 12), np.uint8)), Buf(kind, np.zeros((P, n), np.uint8))
     total_done = 0
     for s in range(120):
         rot, trans = rng.integers(0, 4, n).astype(np.uint8), rng.integers(0, 10, n).astype(np.uint8)
         player, nxt = rng.integers(0, P, n).astype(np.uint8), rng.integers(0, P, n).astype(np.uint8)
         auto = s % 10 != 9
-        r_d, t_d, p_d, n_d = D.put(rot), D.put(trans), D.put(player), D.put(nxt)
-        eng.step_rt_observe_dev(D.ptr(r_d), D.ptr(t_d), D.ptr(p_d), D.ptr(done_d), D.ptr(lines_d), D.ptr(dead_d),
-                                D.ptr(n_d) if s % 7 else (None if P == 1 or not nxt.any() else D.ptr(n_d)),
-                                D.ptr(vis_d), D.ptr(vec_d), D.ptr(pc_d), auto_reset=auto)
+        r_d, t_d, p_d, n_d = Buf(kind, rot), Buf(kind, trans), Buf(kind, player), Buf(kind, nxt)
+        eng.step_rt_observe_dev(r_d.ptr, t_d.ptr, p_d.ptr, done_d.ptr, lines_d.ptr, dead_d.ptr,
+                                n_d.ptr if s % 7 else (None if P == 1 or not nxt.any() else n_d.ptr),
+                                vis_d.ptr, vec_d.ptr, pc_d.ptr, auto_reset=auto)
         d_ref = ref.step_rt(rot, trans, player)
         rec = ref.observe()[0]
         if kind == "hip":
             eng.sync()
-        assert np.array_equal(D.get(done_d), d_ref), s
-        assert np.array_equal(D.get(lines_d).T, rec["reward"]) and np.array_equal(D.get(dead_d).T, rec["dead"]), s
+        assert np.array_equal(done_d.get(), d_ref), s
+        assert np.array_equal(lines_d.get().T, rec["reward"]) and np.array_equal(dead_d.get().T, rec["dead"]), s
         idx = np.nonzero(d_ref)[0].astype(np.int32)
         total_done += len(idx)
         if len(idx) and auto:
@@ -365,11 +325,11 @@ def test_step_and_observation_in_one_launch(kind, P, H):
             ref.reset(idx, orc.episode_seed(idx, episode[idx]))
         me = nxt if (s % 7 or (P > 1 and nxt.any())) else np.zeros(n, np.uint8)      # a NULL next_player means player 0
         want_vis, want_vec, want_pc = _expected_packed(ref.observe()[0], me, P, H)
-        assert np.array_equal(D.get(pc_d), want_pc), s
-        assert np.array_equal(D.get(vec_d), want_vec), s
-        assert np.array_equal(D.get(vis_d), want_vis), s
+        assert np.array_equal(pc_d.get(), want_pc), s
+        assert np.array_equal(vec_d.get(), want_vec), s
+        assert np.array_equal(vis_d.get(), want_vis), s
         if not auto:                                           # the observation above showed the finished games as they ended
-            eng.reset_dev(D.ptr(done_d), None)                 # mask = this step's done flags, seeds from the schedule
+            eng.reset_dev(done_d.ptr, None)                 # mask = this step's done flags, seeds from the schedule
             if len(idx):
                 episode[idx] += 1
                 ref.reset(idx, orc.episode_seed(idx, episode[idx]))
@@ -387,13 +347,12 @@ def test_device_driven_loop_outlives_the_resident_rng_tables(kind):
     seeds = orc.episode_seed(np.arange(n), 0)
     eng = engines.make(kind, n, P, 20, (6,), seeds=seeds)
     ref = engines.make("oracle", n, P, 20, (6,), seeds=seeds)
-    D = _DevArrays(kind)
     rot = np.zeros(n, np.uint8)
-    r_d = D.put(rot)
-    t_ds = [D.put(np.full(n, 2 * k, np.uint8)) for k in range(5)]
-    done_d = D.put(np.zeros(n, np.uint8))
+    r_d = Buf(kind, rot)
+    t_ds = [Buf(kind, np.full(n, 2 * k, np.uint8)) for k in range(5)]
+    done_d = Buf(kind, np.zeros(n, np.uint8))
     for s in range(steps):
-        eng.step_rt_dev(D.ptr(r_d), D.ptr(t_ds[s % 5]), None, D.ptr(done_d), None, None, auto_reset=True)
+        eng.step_rt_dev(r_d.ptr, t_ds[s % 5].ptr, None, done_d.ptr, None, None, auto_reset=True)
         d = ref.step_rt(rot, np.full(n, 2 * (s % 5), np.uint8))
         assert not d.any()
     eng.sync()
@@ -485,19 +444,18 @@ def test_enumerate_drops_matches_oracle(kind):
     v2, y2, c2, _ = ref.enumerate_drops(idx=sub, player=1, cells=False)
     assert np.array_equal(v1, v2) and np.array_equal(y1, y2) and np.array_equal(c1, c2)
     # device-pointer form, both output layouts (game-major and rotation-minor column planes), with a ragged last workgroup
-    D = _DevArrays(kind)
     m = n - 3
     player = rng.integers(0, 2, m).astype(np.uint8)
     want = eng.enumerate_drops(idx=np.arange(m, dtype=np.int32), player=player)
     for planar in (False, True):
-        v_d, y_d, c_d = D.put(np.zeros(m * 40, np.uint8)), D.put(np.zeros(m * 40, np.int8)), D.put(np.zeros(m * 40, np.uint8))
-        a_d, p_d = D.put(np.zeros(m * 400, np.uint32).view(np.int32)), D.put(player)
-        eng.enumerate_drops_dev(m, D.ptr(v_d), D.ptr(y_d), D.ptr(c_d), D.ptr(a_d), player=D.ptr(p_d), planar=planar)
+        v_d, y_d, c_d = Buf(kind, np.zeros(m * 40, np.uint8)), Buf(kind, np.zeros(m * 40, np.int8)), Buf(kind, np.zeros(m * 40, np.uint8))
+        a_d, p_d = Buf(kind, np.zeros(m * 400, np.uint32).view(np.int32)), Buf(kind, player)
+        eng.enumerate_drops_dev(m, v_d.ptr, y_d.ptr, c_d.ptr, a_d.ptr, player=p_d.ptr, planar=planar)
         eng.sync()
         shape3 = lambda t: t.reshape(m, 10, 4).transpose(0, 2, 1) if planar else t.reshape(m, 4, 10)
-        assert np.array_equal(shape3(D.get(v_d)), want[0]) and np.array_equal(shape3(D.get(y_d)), want[1])
-        assert np.array_equal(shape3(D.get(c_d)), want[2])
-        a = D.get(a_d).view(np.uint32)
+        assert np.array_equal(shape3(v_d.get()), want[0]) and np.array_equal(shape3(y_d.get()), want[1])
+        assert np.array_equal(shape3(c_d.get()), want[2])
+        a = a_d.get().view(np.uint32)
         a = a.reshape(10, m, 10, 4).transpose(1, 3, 2, 0) if planar else a.reshape(m, 4, 10, 10)
         assert np.array_equal(a, want[3]), planar
 

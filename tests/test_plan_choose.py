@@ -14,12 +14,9 @@ import pytest
 import __graft_entry__ as ge
 from oracle import oracle as orc
 from tests import engines
-from tests.test_act_eval import Buf as VBuf
-from tests.test_act_eval import midgame, unit, words
-from tests.test_plan_deltas import Out, _crafted
-from tests.test_plan_deltas import _run as _run_deltas
-from tests.test_plan_deltas import _words
-from tests.test_plan_device import Buf, _device_lists, _numpy_deltas, _plan_env, _simulate
+from tests.act_support import midgame, pieces_of, unit, words
+from tests.buffers import Buf, bits, out
+from tests.plan_support import Call, _crafted, _device_lists, _numpy_deltas, _plan_env, _run, _simulate, _words, crafted_phi
 
 F32 = np.float32
 MODES = ("argmax", "pi")
@@ -111,46 +108,6 @@ def model(phi, piece_idx, before, after, count, fill, mode, ids=None, seed=0, dr
     return out
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=F32).view(np.uint32)
-
-
-# ---------------------------------------------------------------- calls
-class Call:
-    """The buffers of one selection (guard bytes behind every output) and the argument struct over them"""
-
-    def __init__(self, kind, b, phi, player, count, cols, L, mode, fill=1e-3, state_eval=None, seed=0, draw=0, out_f16=False, entropy=None,
-                 small_outputs_only=False, **kw):
-        N, H = b.n_games, b.height
-        self.N, self.H, self.L, self.out_f16 = N, H, L, out_f16
-        self.phi = VBuf(kind, phi)
-        self.se = None if state_eval is None else VBuf(kind, state_eval)
-        self.pl = None if player is None else VBuf(kind, np.asarray(player, np.uint8))
-        self.cnt = VBuf(kind, np.asarray(count, np.int32))
-        self.cols = cols if isinstance(cols, (Buf, VBuf)) else VBuf(kind, np.ascontiguousarray(cols).view(np.int32))
-        pdt = np.float16 if out_f16 else np.float32
-        self.out = dict(choice=Out(kind, N, np.int32), piece=Out(kind, N, np.uint8), prob=Out(kind, N, F32))
-        if not small_outputs_only:
-            self.out.update(probs=Out(kind, N * L, F32), delta=Out(kind, N * H * 10, pdt), sums=Out(kind, N * H * 10, pdt))
-        if state_eval is not None:
-            self.out["value"] = Out(kind, 2 * N, F32)
-        if mode == "pi" if entropy is None else entropy:
-            self.out["entropy"] = Out(kind, N, F32)
-        p = lambda name: self.out[name].ptr if name in self.out else None            # noqa: E731
-        args = dict(n_pieces=phi.shape[3], f16=phi.dtype == np.float16, state_eval=None if self.se is None else self.se.ptr,
-                    n_values=1 if state_eval is None else state_eval.shape[1], value_f16=state_eval is not None and state_eval.dtype == np.float16,
-                    mode=mode, player=None if self.pl is None else self.pl.ptr, seed=seed, draw=draw, small_fill=fill, max_lists=L,
-                    out_f16=out_f16, piece=p("piece"), prob=p("prob"), probs=p("probs"), value=p("value"), entropy=p("entropy"),
-                    delta=p("delta"), sums=p("sums"))
-        args.update(kw)
-        self.e = b.plan_eval(self.phi.ptr, self.cnt.ptr, self.cols.ptr, p("choice"), **args)
-
-    def get(self):
-        N, H, L = self.N, self.H, self.L
-        shapes = dict(choice=(N,), piece=(N,), prob=(N,), probs=(N, L), delta=(N, H, 10), sums=(N, H, 10), value=(2, N), entropy=(N,))
-        return {k: v.get(shapes[k]) for k, v in self.out.items()}
-
-
 def assert_outputs(got, want, where, planes=True):
     for name in ("choice", "piece"):
         assert np.array_equal(got[name], want[name]), f"{where}: '{name}' differs in games {np.nonzero(got[name] != want[name])[0][:8]}"
@@ -171,19 +128,6 @@ def assert_entropy(got, want, where):
     assert np.array_equal(np.isnan(got["entropy"]), np.isnan(want["entropy"])), where
     assert (got["entropy"][want["degenerate"] | (want["cnt"] == 0)] == 0).all(), where
     return int(q_ok.sum())
-
-
-def pieces_of(b, who):
-    return b.observe()[0]["piece"][np.arange(b.n_games), who]
-
-
-def crafted_phi(rng, N, H, K, dtype):
-    """per game: positive, all negative (a negative total, positive q) or of both signs"""
-    a = rng.random((N, H, 10, K)) + 0.05
-    kind = np.arange(N) % 3
-    a[kind == 1] *= -1.0
-    a[kind == 2] = rng.standard_normal(((kind == 2).sum(), H, 10, K))
-    return a.astype(dtype)
 
 
 # ---------------------------------------------------------------- 1. the model on crafted columns
@@ -207,8 +151,8 @@ def _crafted_case(kind, P, H, L):
         N, fill = 67, 1e-3
         b, player, count, cols, before, after = _crafted(kind, N, P, H, L, seed=100 * P + H + L)
         who = np.minimum(player, P - 1)
-        d, s, _ = _run_deltas(kind, b, player, count, cols, L, fill)
-        dh, sh, _ = _run_deltas(kind, b, player, count, cols, L, fill, f16=True)
+        d, s, _ = _run(kind, b, player, count, cols, L, fill)
+        dh, sh, _ = _run(kind, b, player, count, cols, L, fill, f16=True)
         _CRAFTED[key] = (b, player, count, cols, before, after, pieces_of(b, who), (d, s, dh, sh), {})
     return _CRAFTED[key]
 
@@ -426,13 +370,13 @@ def test_distribution_of_the_draw(kind):
     cols = _cols_of(after)
     q = model(phi, np.zeros(N, np.int64), before, after, count, 0.0, "argmax")["probs"].astype(np.float64)
     assert (q == 0).sum() >= N and ((q > 0).sum(axis=1) >= 5).all()
-    choices = Out(kind, D * N, np.int32)
+    choices = out(kind, (D, N), np.int32)
     base = Call(kind, b, phi, None, count, cols, L, "pi", fill=0.0, small_outputs_only=True, entropy=False)
     for draw in range(D):                                                  # every draw writes its own row: one read-back at the end
         base.e.draw = draw
         base.e.d_choice = choices.ptr + 4 * N * draw
         b.select_lists_dev(base.e)
-    got = choices.get((D, N))
+    got = choices.get()
     for i in range(N):
         n_k = np.bincount(got[:, i], minlength=L)
         sd = np.sqrt(D * q[i] * (1 - q[i]))
@@ -493,12 +437,12 @@ def test_step_equals_select_plus_step_lists_and_the_oracle(kind, P, auto):
     rng = np.random.default_rng(40 + P)
     ids, episode = np.arange(n), np.zeros(n, np.int64)
     ended = 0
-    outs = [dict(done=Buf(kind, (n,), np.uint8, 7), lines=Buf(kind, (P, n), np.uint8, 7), dead=Buf(kind, (P, n), np.uint8, 7)) for _ in range(2)]
+    outs = [dict(done=Buf.full(kind, (n,), np.uint8, 7), lines=Buf.full(kind, (P, n), np.uint8, 7), dead=Buf.full(kind, (P, n), np.uint8, 7)) for _ in range(2)]
     for s in range(steps):
         player = rng.integers(0, P, n)
         mode = MODES[s % 2]
         cnt, lens, keys, pl = _device_lists(kind, a, player, False, L=L, K=K)
-        cols = Buf(kind, (L, P, 10, n), np.uint32)
+        cols = Buf.full(kind, (L, P, 10, n), np.uint32)
         a.simulate_lists_dev(cnt.ptr, lens.ptr, keys.ptr, cols.ptr, max_lists=L, max_keys=K, player=pl.ptr)
         phi = (rng.random((n, 20, 10, 7)) + 0.1).astype(F32)
         count = cnt.get()
@@ -609,7 +553,7 @@ def test_torch_env_calls_equal_the_c_level_results():
         phi = crafted_phi(rng, n, 20, 7, dtype)
         se = rng.standard_normal((n, 8)).astype(dtype)
         cnt, lens, keys, pl = _device_lists("hip", c, player, False, L=L, K=K)
-        cols = Buf("hip", (L, P, 10, n), np.uint32)
+        cols = Buf.full("hip", (L, P, 10, n), np.uint32)
         c.simulate_lists_dev(cnt.ptr, lens.ptr, keys.ptr, cols.ptr, max_lists=L, max_keys=K, player=pl.ptr)
         out_f16 = dtype == np.float16
         call = Call("hip", c, phi, player, cnt.get(), cols, L, mode, state_eval=se, seed=21, draw=draw, out_f16=out_f16)
@@ -629,11 +573,11 @@ def test_torch_env_calls_equal_the_c_level_results():
             w = want[name].view(np.uint16) if want[name].dtype == np.float16 else want[name]
             assert np.array_equal(g.view(np.uint8).reshape(-1), np.ascontiguousarray(w).view(np.uint8).reshape(-1)), f"TorchEnv.choose_lists {mode} {np.dtype(dtype).name}: '{name}'"
     # step_lists_eval against the C-level call on the copy
-    done, lines, dead = Buf("hip", (n,), np.uint8), Buf("hip", (P, n), np.uint8), Buf("hip", (P, n), np.uint8)
+    done, lines, dead = Buf.full("hip", (n,), np.uint8), Buf.full("hip", (P, n), np.uint8), Buf.full("hip", (P, n), np.uint8)
     for draw in range(2):
         phi = crafted_phi(rng, n, 20, 7, np.float32)
         cnt, lens, keys, pl = _device_lists("hip", c, player, False, L=L, K=K)
-        cols = Buf("hip", (L, P, 10, n), np.uint32)
+        cols = Buf.full("hip", (L, P, 10, n), np.uint32)
         c.simulate_lists_dev(cnt.ptr, lens.ptr, keys.ptr, cols.ptr, max_lists=L, max_keys=K, player=pl.ptr)
         call = Call("hip", c, phi, player, cnt.get(), cols, L, "pi", seed=4, draw=draw)
         c.step_lists_eval_dev(call.e, lens.ptr, keys.ptr, done.ptr, lines.ptr, dead.ptr, max_keys=K, auto_reset=True)

@@ -10,99 +10,8 @@ import pytest
 import __graft_entry__ as ge
 from oracle import oracle as orc
 from tests import engines
-from tests.test_plan_device import Buf, _bits, _device_lists, _numpy_deltas, _plan_env, _simulate
-
-PAD = 64          # guard bytes behind every output buffer
-GUARD = 0xCD
-
-
-class Out:
-    """An output buffer of `count` elements of `dtype` with PAD guard bytes behind it (Buf holds the bytes)."""
-
-    def __init__(self, kind, count, dtype):
-        self.dtype, self.nbytes = np.dtype(dtype), count * np.dtype(dtype).itemsize
-        self.buf = Buf(kind, (self.nbytes + PAD,), np.uint8, GUARD)
-        self.ptr = self.buf.ptr
-        assert self.ptr % 16 == 0
-
-    def get(self, shape):
-        raw = self.buf.get()
-        assert (raw[self.nbytes:] == GUARD).all(), "wrote past the buffer"
-        return raw[: self.nbytes].view(self.dtype).reshape(shape)
-
-
-def _want(before, after, count, fill):
-    """The semantics of tetris_plan_deltas_dev in numpy.  before bool [N, H, 10], after bool [N, L, H, 10] (the acting player's
-    fields, rows 0..H-1), count int [N] -> deltas float32 [N, H, 10, L], sums float32 [N, H, 10], small uint8 [N, L]."""
-    N, L = after.shape[:2]
-    delta = after.astype(np.int32) - before[:, None].astype(np.int32)
-    s = delta.sum(axis=(2, 3))
-    valid = np.arange(L)[None, :] < np.clip(count, 0, L)[:, None]
-    small = valid & (s < 4)
-    normal = valid & ~small
-    d = np.where(normal[:, :, None, None], delta, 0).astype(np.float32)
-    d[small] = np.float32(fill)
-    isum = np.where(normal[:, :, None, None], delta, 0).sum(axis=1)                   # [N, H, 10] integers
-    fills = np.float32(fill) * small.sum(axis=1).astype(np.float32)                   # one float32 multiply
-    sums = isum.astype(np.float32) + fills[:, None, None]                             # one float32 add
-    return d.transpose(0, 2, 3, 1), sums, small.astype(np.uint8), normal
-
-
-def _words(field):
-    """bool [..., H, 10] -> uint32 column words [..., 10] (bit y = row y)"""
-    H = field.shape[-2]
-    return (field.astype(np.uint32) << np.arange(H, dtype=np.uint32)[:, None]).sum(axis=-2).astype(np.uint32)
-
-
-def _crafted(kind, N, P, H, L, seed):
-    """A scrambled batch and a d_cols buffer the test fills: per (game, list) one of five cases on the acting player's plane,
-    garbage in the other players' planes; mixed d_player (out-of-range entries included) and counts from {-1, 0, .., L, L + 5}."""
-    rng = np.random.default_rng(seed)
-    b = engines.make(kind, N, P, height=H, seeds=orc.episode_seed(np.arange(N), 7))
-    b.rollout_random(1, 18)
-    player = rng.integers(0, P + 3, N).astype(np.uint8)
-    before_all = (b.observe()[0]["field"][:, :, :H] > 0)
-    count = rng.integers(-1, L + 2, N).astype(np.int32)
-    count[count == L + 1] = L + 5
-    count[:4] = (-1, 0, L + 5, L)                                                     # every edge, whatever was drawn
-    player[4:6] = (P, P + 2)
-    who = np.minimum(player, P - 1)
-    before = before_all[np.arange(N), who]                                            # [N, H, 10]
-    cols = rng.integers(0, 2 ** 32, (L, P, 10, N), dtype=np.uint64).astype(np.uint32)
-    high = np.uint32((0xFFFFFFFF << H) & 0xFFFFFFFF)
-    for i in range(N):
-        free, used = np.argwhere(~before[i]), np.argwhere(before[i])
-        for k in range(L):
-            f = before[i].copy()
-            case = (i + k) % 5
-            if case in (1, 2):                                                        # exactly 3 / exactly 4 more cells
-                for y, x in free[rng.permutation(len(free))[: 2 + case]]:
-                    f[y, x] = True
-            elif case == 3:                                                           # two cells leave, six arrive
-                for y, x in used[rng.permutation(len(used))[:2]]:
-                    f[y, x] = False
-                for y, x in free[rng.permutation(len(free))[:6]]:
-                    f[y, x] = True
-            w = _words(f)
-            if case == 4:                                                             # random words on top, bits >= H set
-                w = w | rng.integers(0, 2 ** 32, 10, dtype=np.uint64).astype(np.uint32) | high
-            cols[k, who[i], :, i] = w
-    after = _bits(cols[:, who, :, np.arange(N)], H)                                   # [N, L, H, 10]
-    return b, player, count, cols, before, after
-
-
-def _run(kind, b, player, count, cols, L, fill, f16=False, list_major=False, with_small=True, with_sums=True):
-    N, H = b.n_games, b.height
-    dt = np.float16 if f16 else np.float32
-    pl, cnt = Buf(kind, (N,), np.uint8), Buf(kind, (N,), np.int32)
-    pl.set(player)
-    cnt.set(count)
-    dc = Buf(kind, cols.shape, np.uint32)
-    dc.set(cols)
-    d, s, sm = Out(kind, N * H * 10 * L, dt), Out(kind, N * H * 10, dt), Out(kind, N * L, np.uint8)
-    b.plan_deltas_dev(cnt.ptr, dc.ptr, d.ptr, sums=s.ptr if with_sums else None, small=sm.ptr if with_small else None, max_lists=L,
-                      player=pl.ptr, small_fill=fill, f16=f16, list_major=list_major)
-    return d.get((N, L, H, 10) if list_major else (N, H, 10, L)), s.get((N, H, 10)), sm.get((N, L))
+from tests.buffers import GUARD
+from tests.plan_support import _bits, _crafted, _device_lists, _numpy_deltas, _plan_env, _run, _simulate, _want
 
 
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)

@@ -11,54 +11,17 @@ import pytest
 import __graft_entry__ as ge
 from oracle import oracle as orc
 from tests import engines, replay
-from tests.test_python_golden import _lists
+from tests.buffers import Buf
+from tests.plan_support import _bits, _device_lists, _lists, _numpy_deltas, _plan_env, _scramble, _simulate
+from tests.replay import GOLDEN
 
 env_mod = importlib.import_module("drl-tetris_amd.environment")
 edt = importlib.import_module("drl-tetris_amd.data_types")
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ERR_LISTS = 8
-
-
-class Buf:
-    """A buffer the entry points write: numpy on the harness, a torch device tensor on the GPU; .ptr, .get() -> numpy."""
-
-    def __init__(self, kind, shape, dtype, fill=0):
-        self.kind = kind
-        if kind == "hip":
-            import torch
-            tdt = {np.uint8: torch.uint8, np.int32: torch.int32, np.uint32: torch.int32}[dtype]
-            self.t = torch.full(shape, fill, dtype=tdt, device="cuda")
-            self.ptr = self.t.data_ptr()
-            self.dtype = dtype
-            torch.cuda.synchronize()              # (the batch runs on a stream of its own)
-        else:
-            self.a = np.full(shape, fill, dtype)
-            self.ptr = self.a.ctypes.data
-
-    def get(self):
-        if self.kind == "hip":
-            import torch
-            torch.cuda.synchronize()
-            return self.t.cpu().numpy().view(self.dtype)
-        return self.a.copy()
-
-    def set(self, values):
-        if self.kind == "hip":
-            import torch
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(np.broadcast_to(values, self.t.shape)).astype(self.dtype).view(self.t.cpu().numpy().dtype)))
-            torch.cuda.synchronize()
-        else:
-            self.a[...] = values
 
 
 def _n(kind, cpu, gpu):
     return gpu if kind == "hip" else cpu
-
-
-def _scramble(b, steps, P):
-    """`steps` random-policy steps (the built-in rollout policy; finished games are reset by its seed schedule)"""
-    if steps:
-        b.rollout_random(1, steps)
 
 
 def _want_lists(b, player, keep_null, max_lists=128):
@@ -68,15 +31,6 @@ def _want_lists(b, player, keep_null, max_lists=128):
     h.restore(b.snapshot())
     raw = h.get_actions(None, player, max_lists=max_lists, max_keys=64)
     return [[list(a) for a in edt.action_list(l, remove_null=not keep_null)] for l in raw]
-
-
-def _device_lists(kind, b, player, keep_null, L=128, K=48):
-    n = b.n_games
-    cnt, lens, keys = Buf(kind, (n,), np.int32, -7), Buf(kind, (n, L), np.uint8), Buf(kind, (n, L, K), np.uint8)
-    pl = Buf(kind, (n,), np.uint8)
-    pl.set(np.asarray(player, np.uint8))
-    b.action_lists_dev(cnt.ptr, lens.ptr, keys.ptr, max_lists=L, max_keys=K, player=pl.ptr, keep_null=keep_null)
-    return cnt, lens, keys, pl
 
 
 def _check_lists(kind, b, player, keep_null, where):
@@ -183,21 +137,6 @@ def test_action_lists_on_trace_boards(kind, name):
     for player in range(P):
         for keep_null in (False, True):
             _check_lists(kind, b, np.full(len(blobs), player), keep_null, f"{name} player {player} keep_null={keep_null}")
-
-
-def _bits(cols, H):
-    """[..., 10] uint32 columns -> [..., H, 10] bool field (row y = bit y)"""
-    c = np.asarray(cols).astype(np.uint32)
-    return ((c[..., None, :] >> np.arange(H, dtype=np.uint32)[:, None]) & 1).astype(bool)
-
-
-def _simulate(kind, b, cnt, lens, keys, pl, finalize, L=128, K=48):
-    n, P = b.n_games, b.n_players
-    cols = Buf(kind, (L, P, 10, n), np.uint32)
-    done, lines, dead = Buf(kind, (L, n), np.uint8, 77), Buf(kind, (L, P, n), np.uint8, 77), Buf(kind, (L, P, n), np.uint8, 77)
-    b.simulate_lists_dev(cnt.ptr, lens.ptr, keys.ptr, cols.ptr, max_lists=L, max_keys=K, player=pl.ptr, finalize=finalize,
-                         done=done.ptr, lines=lines.ptr, dead=dead.ptr)
-    return cols.get(), done.get(), lines.get(), dead.get()
 
 
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
@@ -315,31 +254,6 @@ def test_simulate_reproduces_reference_python(kind):
     assert sim_k == len(G["sim_step"])
 
 
-def _numpy_deltas(states, sims, player, L):
-    """sherlock_utils.deltas / generate_deltas restated in numpy over the Python path's simulate_all_actions(finalize=False);
-    padded to L lists (the reference pads to the longest; the extra lists are zero either way)."""
-    out = []
-    for st, res, p in zip(states, sims, player):
-        before = np.asarray(st[p]["field"]).astype(np.float64)
-        ds = []
-        for r in res:
-            d = np.asarray(r[p]["field"]).astype(np.float64) - before
-            ds.append(np.full_like(d, 1e-3) if d.sum() < 4.0 else d)
-        a = np.zeros(before.shape + (L,))
-        a[..., : len(ds)] = np.stack(ds, axis=-1)
-        out.append(a[None])
-    d = np.concatenate(out, axis=0)
-    return d, d.sum(axis=-1, keepdims=True)
-
-
-def _plan_env(kind, n):
-    env = env_mod.tetris_environment_vector(n, None, settings={"n_players": 2, "game_size": [20, 10], "seed_source": lambda: 5},
-                                            _lib_path=ge.build_harness() if kind == "harness" else None)
-    env.backend.reset(None, seeds=orc.episode_seed(np.arange(n), 2))
-    _scramble(env.backend, 18, 2)
-    return env
-
-
 def test_columns_to_deltas_on_host_input():
     """The bitboard -> deltas function of TorchEnv.deltas, fed the harness's simulated columns as CPU tensors."""
     torch = pytest.importorskip("torch")
@@ -394,9 +308,9 @@ def test_step_lists_matches_step_keys(kind, P):
             cnt, lens, keys, pl = _device_lists(kind, a, player, False, L=L, K=K)
             c, ln, kk = cnt.get(), lens.get(), keys.get()
             choice = rng.integers(-3, 60, n).astype(np.int32)             # clamped into [0, count - 1]
-            ch = Buf(kind, (n,), np.int32)
-            ch.set(choice)
-            done, lines, dead = Buf(kind, (n,), np.uint8), Buf(kind, (P, n), np.uint8), Buf(kind, (P, n), np.uint8)
+            ch = Buf.full(kind, (n,), np.int32)
+            ch.put(choice)
+            done, lines, dead = Buf.full(kind, (n,), np.uint8), Buf.full(kind, (P, n), np.uint8), Buf.full(kind, (P, n), np.uint8)
             a.step_lists_dev(ch.ptr, cnt.ptr, lens.ptr, keys.ptr, done.ptr, lines.ptr, dead.ptr, max_lists=L, max_keys=K, player=pl.ptr,
                              auto_reset=auto)
             pick = np.clip(choice, 0, c - 1)
@@ -407,8 +321,8 @@ def test_step_lists_matches_step_keys(kind, P):
             d, li, de = r.step_keys(keys_h, lens_h)
             assert np.array_equal(done.get(), d) and np.array_equal(lines.get().T, li) and np.array_equal(dead.get().T, de), (auto, s)
             if auto and d.any():
-                m = Buf(kind, (n,), np.uint8)
-                m.set(d)
+                m = Buf.full(kind, (n,), np.uint8)
+                m.put(d)
                 r.reset_dev(m.ptr, None)
             assert np.array_equal(a.snapshot(), r.snapshot()), (auto, s)
     assert a.take_errors() == 0
@@ -473,11 +387,11 @@ def test_capacity_overflow_is_reported_per_game(kind):
     some_fit = False
     for L, K in ((4, 8), (24, 8), (40, 6)):
         pad = 64
-        cnt = Buf(kind, (n + pad,), np.int32, 0x5A5A5A5A)
-        lens = Buf(kind, (n * L + pad,), np.uint8, 0xAB)
-        keys = Buf(kind, (n * L * K + pad,), np.uint8, 0xAB)
-        pl = Buf(kind, (n,), np.uint8)
-        pl.set(player)
+        cnt = Buf.full(kind, (n + pad,), np.int32, 0x5A5A5A5A)
+        lens = Buf.full(kind, (n * L + pad,), np.uint8, 0xAB)
+        keys = Buf.full(kind, (n * L * K + pad,), np.uint8, 0xAB)
+        pl = Buf.full(kind, (n,), np.uint8)
+        pl.put(player)
         b.action_lists_dev(cnt.ptr, lens.ptr, keys.ptr, max_lists=L, max_keys=K, player=pl.ptr)
         c, ln, kk = cnt.get(), lens.get(), keys.get()
         assert (c[n:] == 0x5A5A5A5A).all() and (ln[n * L:] == 0xAB).all() and (kk[n * L * K:] == 0xAB).all(), "wrote past the buffers"

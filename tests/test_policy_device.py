@@ -1,5 +1,5 @@
 """The heuristic policy on the device (include/tetris_hip.h: tetris_rt_features_dev, tetris_policy_rt_dev,
-tetris_step_policy_dev, tetris_rollout_policy, tetris_rollout_game_totals_dev) against a CPU model written here on top of the
+tetris_step_policy_dev, tetris_rollout_policy, tetris_rollout_game_totals_dev) against a CPU model (tests/policy_model.py) on top of the
 oracle, in the way tests/golden/policies.py:GreedyRT works: every game is copied 40 times into a scratch OracleBatch, the 40
 key lists [8]*r + [2] + [3]*t + [7] are made, the eight features are computed with numpy from the observed fields as the
 header's table defines them, dotted with the weights, argmax (numpy's first maximum is the lowest candidate), step_rt on the
@@ -12,136 +12,8 @@ import pytest
 import __graft_entry__ as ge
 from oracle import oracle as orc
 from tests import engines
-
-ROT = np.repeat(np.arange(4), 10).astype(np.uint8)
-TRA = np.tile(np.arange(10), 4).astype(np.uint8)
-W_A = np.array([76, -71, -18, -51, 0, 0, 0, 0], np.int16)          # lines, holes, bumpiness, aggregate height
-W_B = np.array([34, -79, 0, -10, 0, -32, -93, -34], np.int16)      # Dellacherie-like
-W_ZERO = np.zeros(8, np.int16)
-
-
-class Buf:
-    """A buffer the entry points read or write: numpy on the harness, a torch device tensor on the GPU; .ptr, .get() -> numpy."""
-
-    def __init__(self, kind, shape, dtype, fill=0):
-        self.kind, self.dtype = kind, dtype
-        if kind == "hip":
-            import torch
-            tdt = {np.uint8: torch.uint8, np.int16: torch.int16, np.int32: torch.int32, np.uint32: torch.int32}[dtype]
-            self.t = torch.full(shape, fill, dtype=tdt, device="cuda")
-            self.ptr = self.t.data_ptr()
-            torch.cuda.synchronize()              # (the batch runs on a stream of its own)
-        else:
-            self.a = np.full(shape, fill, dtype)
-            self.ptr = self.a.ctypes.data
-
-    def get(self):
-        if self.kind == "hip":
-            import torch
-            torch.cuda.synchronize()
-            return self.t.cpu().numpy().view(self.dtype)
-        return self.a.copy()
-
-    def set(self, values):
-        v = np.ascontiguousarray(np.broadcast_to(np.asarray(values), self.get().shape)).astype(self.dtype)
-        if self.kind == "hip":
-            import torch
-            self.t.copy_(torch.from_numpy(v.view(self.t.cpu().numpy().dtype)))
-            torch.cuda.synchronize()
-        else:
-            self.a[...] = v
-        return self
-
-
-# ---------------------------------------------------------------- the model
-def features(f):
-    """f bool [M, H, W] (row 0 = top) -> int32 [M, 8], the table of include/tetris_hip.h"""
-    M, H, W = f.shape
-    full = f.all(axis=2)
-    lines = full.sum(axis=1)
-    g = np.zeros_like(f)                              # full rows removed, the rows above moved down
-    for m in range(M):
-        keep = f[m][~full[m]]
-        g[m, H - len(keep):] = keep
-    heights = np.where(g.any(axis=1), H - g.argmax(axis=1), 0)
-    below = np.cumsum(g, axis=1) > 0
-    holes = (below & ~g).sum(axis=(1, 2))
-    bump = np.abs(np.diff(heights, axis=1)).sum(axis=1)
-    agg = heights.sum(axis=1)
-    mx = heights.max(axis=1)
-    padded = np.concatenate([np.ones((M, H, 1), bool), g, np.ones((M, H, 1), bool)], axis=2)
-    rowtr = (padded[:, :, 1:] != padded[:, :, :-1]).sum(axis=(1, 2))
-    padv = np.concatenate([g, np.ones((M, 1, W), bool)], axis=1)
-    coltr = (padv[:, 1:] != padv[:, :-1]).sum(axis=(1, 2))
-    hp = np.concatenate([np.full((M, 1), H), heights, np.full((M, 1), H)], axis=1)
-    d = np.maximum(np.minimum(hp[:, :-2], hp[:, 2:]) - heights, 0)
-    wells = (d * (d + 1) // 2).sum(axis=1)
-    return np.stack([lines, holes, bump, agg, mx, rowtr, coltr, wells], axis=1).astype(np.int32)
-
-
-class Model:
-    """The policy on the oracle.  `o` is the OracleBatch it plays; weights int16 [8] or [N, 8]; ms = game time per step."""
-
-    def __init__(self, o, ids=None, ms=400):
-        self.o, self.ms = o, ms
-        self.ids = np.arange(o.n_games) if ids is None else np.asarray(ids)      # global game ids (the reset-seed schedule's key)
-        self.scratch = orc.OracleBatch(40 * o.n_games, o.n_players, o.height, 10)
-        self.episode = np.zeros(o.n_games, np.int64)
-        self.totals = np.zeros((4, o.n_games), np.int64)     # env-steps, episodes, lines, sent
-        self.decisions = self.tied = 0
-
-    def candidate_fields(self, player):
-        o, N, P, H = self.o, self.o.n_games, self.o.n_players, self.o.height
-        self.scratch.copy_from(o, src_idx=np.repeat(np.arange(N), 40).astype(np.int32))
-        keys = np.zeros((40 * N, P, 16), np.uint8)
-        lens = np.ones((40 * N, P), np.uint8)              # [0] for the others
-        pl = np.broadcast_to(np.asarray(player, np.int64), (N,))
-        for c in range(40):
-            k = [8] * int(ROT[c]) + [2] + [3] * int(TRA[c]) + [7]
-            sel = np.arange(N) * 40 + c
-            keys[sel, pl, :len(k)] = k
-            lens[sel, pl] = len(k)
-        self.scratch.make_actions(keys, lens)
-        rec, _, _ = self.scratch.observe()
-        return rec["field"][np.arange(40 * N), np.repeat(pl, 40), :H, :]      # [40 N, H, W] tile values
-
-    def features(self, player):
-        """-> int32 [N, 40, 8]"""
-        return features(self.candidate_fields(player) > 0).reshape(self.o.n_games, 40, 8)
-
-    def choose(self, weights, player):
-        """-> rot, trans, score [N]"""
-        N = self.o.n_games
-        w = np.broadcast_to(np.asarray(weights, np.int64).reshape(-1, 8), (N, 8))
-        score = (self.features(player).astype(np.int64) * w[:, None, :]).sum(axis=2)        # [N, 40]
-        best = score.argmax(axis=1)                       # lowest index on ties
-        self.decisions += N
-        self.tied += int(((score == score.max(axis=1, keepdims=True)).sum(axis=1) > 1).sum())
-        return ROT[best], TRA[best], score[np.arange(N), best].astype(np.int32)
-
-    def step(self, rot, trans, player, auto_reset, count=False):
-        """step_rt + the reset of finished games by the built-in seed schedule -> done, lines [N, P], dead [N, P] before the reset"""
-        o = self.o
-        sent0 = o.observe()[0]["lines_sent"].astype(np.int64).sum(axis=1) if count else None
-        done = o.step_rt(rot, trans, player, ms=self.ms)
-        rec = o.observe()[0]
-        lines, dead = rec["reward"].copy(), rec["dead"].copy()
-        if count:
-            self.totals[0] += 1
-            self.totals[2] += (lines.astype(np.int64) * (dead == 0)).sum(axis=1)
-            self.totals[3] += (rec["lines_sent"].astype(np.int64).sum(axis=1) - sent0) & 0xFFFF
-        d = np.nonzero(done)[0].astype(np.int32)
-        if auto_reset and len(d):
-            self.episode[d] += 1
-            self.totals[1][d] += 1
-            o.reset(d, seeds=orc.episode_seed(self.ids[d], self.episode[d]))
-        return done, lines, dead
-
-    def rollout(self, weights, steps, first_step=0):
-        P = self.o.n_players
-        for s in range(first_step, first_step + steps):
-            r, t, _ = self.choose(weights, s % P)
-            self.step(r, t, s % P, True, count=True)
+from tests.buffers import Buf
+from tests.policy_model import W_A, W_B, W_ZERO, Model, _assert_rollout
 
 
 def _pair(kind, n, P, height=20, colours=False):
@@ -190,12 +62,12 @@ def test_features_equal_the_model(kind, P, height):
     m = Model(o)
     seen_lines = seen_holes = False
     garbage_boards = 0
-    feat = Buf(kind, (40, 8, n), np.int16, -1)
-    pl = Buf(kind, (n,), np.uint8)
+    feat = Buf.full(kind, (40, 8, n), np.int16, -1)
+    pl = Buf.full(kind, (n,), np.uint8)
     for chunk in range(4):
         _mixed_play(b, m, steps // 4, rng)
         player = rng.integers(0, P, n).astype(np.uint8)
-        pl.set(player)
+        pl.put(player)
         want = m.features(player)                                   # [N, 40, 8]
         b.rt_features_dev(feat.ptr, player=pl.ptr)
         got = feat.get().transpose(2, 0, 1)
@@ -217,7 +89,7 @@ def test_features_player_null_and_colour_batches():
     b, o = _pair("harness", n, 2, colours=True)
     m = Model(o)
     _mixed_play(b, m, 40, np.random.default_rng(5))
-    feat = Buf("harness", (40, 8, n), np.int16, -1)
+    feat = Buf.full("harness", (40, 8, n), np.int16, -1)
     b.rt_features_dev(feat.ptr)
     assert np.array_equal(feat.get().transpose(2, 0, 1), m.features(0))
 
@@ -231,17 +103,17 @@ def test_choice_equals_the_model(kind, P):
     b, o = _pair(kind, n, P)
     m = Model(o)
     per_game = np.stack([W_ZERO if g % 4 == 0 else (W_A if g % 4 == 1 else (W_B if g % 4 == 2 else rng.integers(-100, 100, 8))) for g in range(n)]).astype(np.int16)
-    rot, trans, score = Buf(kind, (n,), np.uint8, 9), Buf(kind, (n,), np.uint8, 99), Buf(kind, (n,), np.int32, -5)
-    pl = Buf(kind, (n,), np.uint8)
-    w_shared, w_games = Buf(kind, (8,), np.int16), Buf(kind, (n, 8), np.int16).set(per_game)
+    rot, trans, score = Buf.full(kind, (n,), np.uint8, 9), Buf.full(kind, (n,), np.uint8, 99), Buf.full(kind, (n,), np.int32, -5)
+    pl = Buf.full(kind, (n,), np.uint8)
+    w_shared, w_games = Buf.full(kind, (8,), np.int16), Buf.full(kind, (n, 8), np.int16).put(per_game)
     m.decisions = m.tied = 0
     for chunk in range(6):
         _mixed_play(b, m, 10, rng)
         d0, t0 = m.decisions, m.tied
         player = rng.integers(0, P, n).astype(np.uint8)
-        pl.set(player)
+        pl.put(player)
         for shared in (W_A, W_B):
-            w_shared.set(shared)
+            w_shared.put(shared)
             b.policy_rt_dev(w_shared.ptr, rot.ptr, trans.ptr, score.ptr, player=pl.ptr)
             r, t, s = m.choose(shared, player)
             assert np.array_equal(rot.get(), r) and np.array_equal(trans.get(), t) and np.array_equal(score.get(), s), f"shared weights, chunk {chunk}"
@@ -266,10 +138,10 @@ def test_step_policy_equals_choice_plus_step_and_the_model(kind, P, auto_reset):
     b2, _ = _pair(kind, n, P)
     m = Model(o)
     per_game = np.stack([W_A if g % 2 else W_B for g in range(n)]).astype(np.int16)
-    w = Buf(kind, (n, 8), np.int16).set(per_game)
-    pl = Buf(kind, (n,), np.uint8)
-    out = [dict(done=Buf(kind, (n,), np.uint8, 7), lines=Buf(kind, (P, n), np.uint8, 7), dead=Buf(kind, (P, n), np.uint8, 7),
-                rot=Buf(kind, (n,), np.uint8, 7), trans=Buf(kind, (n,), np.uint8, 77)) for _ in range(2)]
+    w = Buf.full(kind, (n, 8), np.int16).put(per_game)
+    pl = Buf.full(kind, (n,), np.uint8)
+    out = [dict(done=Buf.full(kind, (n,), np.uint8, 7), lines=Buf.full(kind, (P, n), np.uint8, 7), dead=Buf.full(kind, (P, n), np.uint8, 7),
+                rot=Buf.full(kind, (n,), np.uint8, 7), trans=Buf.full(kind, (n,), np.uint8, 77)) for _ in range(2)]
     ended = 0
     for s in range(steps):
         # random (r, t) steps in between keep the boards rough, so that rounds end (without auto-reset they are reset by hand)
@@ -280,7 +152,7 @@ def test_step_policy_equals_choice_plus_step_and_the_model(kind, P, auto_reset):
             assert np.array_equal(b.step_rt(r, t, player), done) and np.array_equal(b2.step_rt(r, t, player), done)
         else:
             player = rng.integers(0, P, n).astype(np.uint8)
-            pl.set(player)
+            pl.put(player)
             a, c = out
             b.step_policy_dev(w.ptr, a["done"].ptr, a["lines"].ptr, a["dead"].ptr, rot=a["rot"].ptr, trans=a["trans"].ptr, player=pl.ptr,
                               per_game=True, auto_reset=auto_reset)
@@ -308,15 +180,6 @@ def test_step_policy_equals_choice_plus_step_and_the_model(kind, P, auto_reset):
 
 
 # ---------------------------------------------------------------- 4. / 5. rollout
-def _assert_rollout(kind, b, m, counters, label):
-    engines.assert_same_state(b, m.o, where=label)
-    n = m.o.n_games
-    tot = Buf(kind, (4, n), np.uint32, 0xFFFF)
-    b.rollout_game_totals_dev(tot.ptr)
-    b.sync()
-    assert np.array_equal(tot.get().astype(np.int64), m.totals), f"{label}: per-game totals"
-    assert np.array_equal(b.rollout_totals().astype(np.int64), m.totals.sum(axis=1)), f"{label}: rollout_totals"
-    assert np.array_equal(np.asarray(counters, np.int64), m.totals.sum(axis=1)), f"{label}: counters"
 
 
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
@@ -326,7 +189,7 @@ def test_rollout_long_one_player_crosses_two_table_chunks(kind):
     n, steps = 32, 1400
     b, o = _pair(kind, n, 1)
     m = Model(o)
-    w = Buf(kind, (8,), np.int16).set(W_B)
+    w = Buf.full(kind, (8,), np.int16).put(W_B)
     m.rollout(W_B, steps)
     draws = o.observe()[0]["piece_draws"]
     print(f"model: piece_draws min {draws.min()} max {draws.max()}, episodes ended {int(m.totals[1].sum())}, lines {int(m.totals[2].sum())}")
@@ -348,7 +211,7 @@ def test_rollout_two_players_equals_the_model(kind, weights):
     b, o = _pair(kind, n, 2)
     b8, _ = _pair(kind, n, 2)
     m = Model(o)
-    w = Buf(kind, (8,), np.int16).set(weights)
+    w = Buf.full(kind, (8,), np.int16).put(weights)
     m.rollout(weights, steps)
     print(f"model: episodes ended {int(m.totals[1].sum())}, lines {int(m.totals[2].sum())}, sent {int(m.totals[3].sum())}")
     assert m.totals[1].sum() >= 1, "no episode ended on the model: auto-reset is not inside the comparison"
@@ -372,7 +235,7 @@ def test_rollout_other_geometries_on_the_harness(P, colours, height):
     b.set_game_offset(500)
     m = Model(o, ids=np.arange(n) + 500)
     per_game = np.stack([W_A if g % 2 else W_B for g in range(n)]).astype(np.int16)
-    w = Buf("harness", (n, 8), np.int16).set(per_game)
+    w = Buf.full("harness", (n, 8), np.int16).put(per_game)
     m.rollout(per_game, steps)
     c1, _ = b.rollout_policy(w.ptr, 12, 1, per_game=True)
     c2, _ = b.rollout_policy(w.ptr, 6, 4, per_game=True, first_step=12)
@@ -424,21 +287,19 @@ def test_full_size_rollout_equals_single_steps_and_the_model(P):
     """65 536 games x 64 steps: rollout_policy (one step per launch, then fused) equals 64 x (policy_rt_dev + step_rt_dev with
     auto-reset) on a second batch for EVERY game, and the model for a sample of games run on their own (games are independent and
     keyed by global id): 336 games, the first and the last wavefront and 16 games of each of 13 more workgroups."""
-    import torch
     n, steps = 65536, 64
     seeds = orc.episode_seed(np.arange(n), 0)
     a = engines.make("hip", n, P, seeds=seeds)
     c = engines.make("hip", n, P, seeds=seeds)
-    w = Buf("hip", (8,), np.int16).set(W_B)
+    w = Buf.full("hip", (8,), np.int16).put(W_B)
     ca, _ = a.rollout_policy(w.ptr, 40, 1)
     cb, _ = a.rollout_policy(w.ptr, 3, 8, first_step=40)
     counters = ca.astype(np.int64) + cb.astype(np.int64)
-    rot, trans = Buf("hip", (n,), np.uint8), Buf("hip", (n,), np.uint8)
-    pl = Buf("hip", (n,), np.uint8)
-    done, lines, dead = Buf("hip", (n,), np.uint8), Buf("hip", (P, n), np.uint8), Buf("hip", (P, n), np.uint8)
+    rot, trans = Buf.full("hip", (n,), np.uint8), Buf.full("hip", (n,), np.uint8)
+    pl = Buf.full("hip", (n,), np.uint8)
+    done, lines, dead = Buf.full("hip", (n,), np.uint8), Buf.full("hip", (P, n), np.uint8), Buf.full("hip", (P, n), np.uint8)
     for s in range(steps):
-        pl.t.fill_(s % P)
-        torch.cuda.synchronize()
+        pl.put(s % P)
         c.policy_rt_dev(w.ptr, rot.ptr, trans.ptr, None, player=pl.ptr)
         c.step_rt_dev(rot.ptr, trans.ptr, pl.ptr, done.ptr, lines.ptr, dead.ptr, auto_reset=True)
         c.sync()
@@ -452,7 +313,7 @@ def test_full_size_rollout_equals_single_steps_and_the_model(P):
     m = Model(o, ids=sample)            # games run on their own: the reset seeds are keyed by the sampled games' global ids
     m.rollout(W_B, steps)
     _assert_same_records(a.observe(sample.astype(np.int32)), o.observe(), "sampled games against the model")
-    tot = Buf("hip", (4, n), np.uint32)
+    tot = Buf.full("hip", (4, n), np.uint32)
     a.rollout_game_totals_dev(tot.ptr)
     a.sync()
     got = tot.get().astype(np.int64)

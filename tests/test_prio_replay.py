@@ -2,7 +2,7 @@
 tetris_replay_update_prios_dev, tetris_replay_gather_dev): the ring and its cursor against the reference's own runs
 (tests/golden/replay_ring.npz, written by tests/golden/make_replay_golden.py) and against a numpy model written here from the
 header's text; ranks and selection exactly, against numpy's stable argsort; sampling keys and importance weights against the
-reference's formulas in float64; the k-step gather against the numpy model of tests/test_traj_batch.py (imported, not copied).
+reference's formulas in float64; the k-step gather against the numpy model of tests/traj_support.py (imported, not copied).
 Every test runs on the CPU harness (`-m "not gpu"`) and on the MI355X (`-m gpu`); on the harness the "device" buffers are numpy
 arrays.  The harness ranks inside a tile serially: the wave ballots of the product's sort run on the GPU only, which is why the
 sizes of test 3 sit around the wave (64), the sort's tile and its scan's span.
@@ -21,11 +21,11 @@ import pytest
 
 import __graft_entry__ as ge
 from tests import engines
-from tests.test_traj_batch import Buf, OUTPUTS, assert_outputs, model_batch, out_shapes, sync
+from tests.buffers import Buf, sync
+from tests.replay import GOLDEN
+from tests.traj_support import OUTPUTS, assert_outputs, model_batch, out_shapes
 
 F32, F64, U32, U8, I32 = np.float32, np.float64, np.uint32, np.uint8, np.int32
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-MIRROR = 1 << 31
 WEIGHT_TOL = 4 * 1.25e-7               # the docstring's number, for the 35 weights of the fixture
 
 

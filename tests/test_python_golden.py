@@ -15,8 +15,9 @@ import pytest
 
 import __graft_entry__ as ge
 from tests import engines
+from tests.plan_support import _lists
+from tests.replay import GOLDEN
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NAMES = sorted(os.path.basename(p)[len("pygolden_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN, "pygolden_*.npz")))
 DICT_KEYS = ["field", "piece", "x", "y", "incoming_lines", "combo_time", "combo_count", "nextpiece"]
 
@@ -29,10 +30,6 @@ class _Seeds:
 
     def __call__(self):
         return int(self.next)
-
-
-def _lists(keys, lens, n):
-    return [keys[i, : lens[i]].tolist() for i in range(int(n))]
 
 
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)

@@ -12,7 +12,8 @@ import pytest
 
 from oracle import oracle as orc
 from tests import engines
-from tests.test_policy_device import W_B, Buf, Model
+from tests.buffers import Buf
+from tests.policy_model import W_B, Model
 
 MAX = 0x7FFF0000            # CHAIN_EPOCH_MAX (drl-tetris_amd/csrc/tetris_kernels.h): the numbering restarts before it gets here
 FELL_BACK = 4
@@ -137,7 +138,7 @@ def test_a_restart_behind_asynchronous_work_on_the_batchs_stream(path):
     f.chained_call(40, eng.debug_chain_epoch() + 40, "undisturbed")
     rng = np.random.default_rng(7)
     r, t = rng.integers(0, 4, n).astype(np.uint8), rng.integers(0, 10, n).astype(np.uint8)
-    rot, trans = Buf("hip", (n,), np.uint8).set(r), Buf("hip", (n,), np.uint8).set(t)
+    rot, trans = Buf.full("hip", (n,), np.uint8).put(r), Buf.full("hip", (n,), np.uint8).put(t)
     eng.debug_chain_epoch(MAX - L)
     done = ref.step_rt(r, t, None)                                   # the oracle steps the same action first
     d = np.nonzero(done)[0].astype(np.int32)
@@ -314,7 +315,7 @@ def _census(preset, counts, words, where):
 
 def _assert_words(eng, kind, preset, counts, where):
     n = eng.n_games
-    tot = Buf(kind, (4, n), np.uint32, 0xFFFF)
+    tot = Buf.full(kind, (4, n), np.uint32, 0xFFFF)
     eng.rollout_game_totals_dev(tot.ptr)
     eng.sync()
     got = tot.get().astype(np.int64)
@@ -373,7 +374,7 @@ def test_rollout_policy_counts_what_the_call_did_when_per_game_words_wrap(kind, 
     m.episode = preset[W_EPISODE].astype(np.int64)
     m.rollout(W_B, K)
     _census(preset, m.totals, words, f"policy P={P} S={S}")
-    w = Buf(kind, (8,), np.int16).set(W_B)
+    w = Buf.full(kind, (8,), np.int16).put(W_B)
     c, _ = eng.rollout_policy(w.ptr, K // S, S)
     assert c.astype(np.int64).tolist() == m.totals.sum(axis=1).tolist()
     _assert_words(eng, kind, preset, m.totals, "after the call")
@@ -414,7 +415,7 @@ def test_rollout_policy_across_2_to_the_32_steps(kind, P, S):
     eng, ref = _pair(kind, n, P)
     m = Model(ref)
     m.rollout(W_B, K, first_step=first)
-    w = Buf(kind, (8,), np.int16).set(W_B)
+    w = Buf.full(kind, (8,), np.int16).put(W_B)
     c, _ = eng.rollout_policy(w.ptr, K // S, S, first_step=first)
     assert c.astype(np.int64).tolist() == m.totals.sum(axis=1).tolist()
     engines.assert_same_state(eng, ref, where="policy rollout across step 2^32")
@@ -458,12 +459,12 @@ def test_step_rt_dev_auto_reset_and_reset_dev_with_game_ids_at_the_word_boundari
     eng, ref = _pair(kind, n, P, offset=offset)
     ids, episode = _ids(n, offset), np.zeros(n, np.int64)
     rng = np.random.default_rng(offset % 1000)
-    rot, trans, pl = Buf(kind, (n,), np.uint8), Buf(kind, (n,), np.uint8), Buf(kind, (n,), np.uint8)
+    rot, trans, pl = Buf.full(kind, (n,), np.uint8), Buf.full(kind, (n,), np.uint8), Buf.full(kind, (n,), np.uint8)
     ended = 0
     for s in range(steps):
         r, t = rng.integers(0, 4, n).astype(np.uint8), rng.integers(0, 10, n).astype(np.uint8)
         player = np.full(n, s % P, np.uint8)
-        rot.set(r), trans.set(t), pl.set(player)
+        rot.put(r), trans.put(t), pl.put(player)
         eng.step_rt_dev(rot.ptr, trans.ptr, pl.ptr, None, None, None, ms=ms, auto_reset=True)
         eng.sync()
         d = np.nonzero(ref.step_rt(r, t, player, ms=ms))[0].astype(np.int32)
@@ -475,7 +476,7 @@ def test_step_rt_dev_auto_reset_and_reset_dev_with_game_ids_at_the_word_boundari
     engines.assert_same_state(eng, ref, where="step_rt_dev with auto-reset")
     _assert_seeds(eng, offset, episode, "step_rt_dev with auto-reset")
     mask = (np.arange(n) % 3 == 0).astype(np.uint8)
-    eng.reset_dev(Buf(kind, (n,), np.uint8).set(mask).ptr, None)
+    eng.reset_dev(Buf.full(kind, (n,), np.uint8).put(mask).ptr, None)
     eng.sync()
     d = np.nonzero(mask)[0].astype(np.int32)
     episode[d] += 1

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from tests.test_split_opponents_gloo import FIELDS, _actions
+from tests.split_support import CAP_N, FIELDS, N, _actions, capacity_check, capacity_side
 
 pytestmark = pytest.mark.gpu
 
@@ -57,9 +57,8 @@ def test_split_kernels_at_1500_ms_per_step():
 def _split_kernels_match_colocated_oracle(scenario, pieces, ms):
     import importlib
 
-    import tests.test_split_opponents_gloo as base
     mod = importlib.import_module("drl-tetris_amd.distributed")
-    N, STEPS = base.N, 200
+    STEPS = 200
     tg = ThreadGather(2)
     results, errors = {}, []
 
@@ -138,7 +137,6 @@ def _split_rollout_matches_oracle_rollout(N, STEPS, ms, first_step=0):
     import importlib
     import os
 
-    import tests.test_split_opponents_gloo as base
     mod = importlib.import_module("drl-tetris_amd.distributed")
     tg = ThreadGather(2)
     results, errors = {}, []
@@ -169,7 +167,7 @@ def _split_rollout_matches_oracle_rollout(N, STEPS, ms, first_step=0):
     assert int(t0[2]) + int(t1[2]) == int(want[2]) and int(t0[3]) + int(t1[3]) == int(want[3])
     for side in (0, 1):
         got, gro, glw = results[side][0]
-        for f in base.FIELDS:
+        for f in FIELDS:
             assert np.array_equal(got[f][:, 0], rec[f][:, side]), (side, f)
         assert np.array_equal(gro, ro) and np.array_equal(glw, lw)
 
@@ -179,7 +177,6 @@ def test_split_capacity_error_ends_the_round_on_both_sides(case):
     """tests/test_split_opponents_gloo.py's capacity cases through the GPU's split kernels (k_split stages, XW_ERR)."""
     import importlib
 
-    import tests.test_split_opponents_gloo as base
     mod = importlib.import_module("drl-tetris_amd.distributed")
     tg = ThreadGather(2)
     results, errors = {}, []
@@ -187,8 +184,8 @@ def test_split_capacity_error_ends_the_round_on_both_sides(case):
     def side_main(side):
         try:
             tg.bind(side)
-            so = mod.SplitOpponents(base.CAP_N, side=side, peer=1 - side, dist=tg, seeds=orc.episode_seed(np.arange(base.CAP_N), 0), pieces=(6,))
-            results[side] = base.capacity_side(so, case)
+            so = mod.SplitOpponents(CAP_N, side=side, peer=1 - side, dist=tg, seeds=orc.episode_seed(np.arange(CAP_N), 0), pieces=(6,))
+            results[side] = capacity_side(so, case)
             so.close()
         except Exception as e:          # let the other thread out of its barrier
             errors.append(e)
@@ -200,4 +197,4 @@ def test_split_capacity_error_ends_the_round_on_both_sides(case):
     for t in threads:
         t.join()
     assert not errors, errors
-    base.capacity_check(case, results)
+    capacity_check(case, results)

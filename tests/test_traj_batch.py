@@ -1,7 +1,7 @@
 """A trajectory window's states and sample sets (include/tetris_hip.h: tetris_traj_observe_dev, tetris_traj_select_dev,
 tetris_traj_batch_dev): the packed observation record, the ordered list of a mask's entries, and the expansion of a minibatch of
 entries, mirrored or not, into the trainer's arrays.  Every comparison is exact equality: nothing here rounds.  The gather is
-compared with a numpy model written here from the header's text (it owes nothing to drl-tetris_amd/csrc/tetris_batch.h), the record
+compared with a numpy model written in tests/traj_support.py from the header's text (it owes nothing to drl-tetris_amd/csrc/tetris_batch.h), the record
 with tetris_observe_packed_dev, the mirror image with the reference's own recorded `aug` dictionaries and with augment_data's
 output (tests/golden/traj_augment.npz, written by tests/golden/make_batch_golden.py), the selection with np.flatnonzero.  Every test
 runs on the CPU harness (`-m "not gpu"`) and on the MI355X (`-m gpu`); on the harness the "device" buffers are numpy arrays."""
@@ -13,94 +13,18 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as ge
-from oracle import oracle as orc
 from tests import engines
+from tests.buffers import MIRROR, Buf, sync
+from tests.replay import GOLDEN
+from tests.traj_support import OUTPUTS, PIECE_SWAP, Window, assert_outputs, model_batch, out_shapes, played
 
 F32, U32, U8, I32 = np.float32, np.uint32, np.uint8, np.int32
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-MIRROR = 1 << 31
-PIECE_SWAP = np.array([1, 0, 3, 2, 4, 5, 6, 7], U8)           # the header's piece_swap, 7 stays 7
 BLOCK = 64                                                    # samples per workgroup of the batch kernel (the issue's mapping)
 
 
 def select_elems():
     """mask bytes per workgroup of the selection kernels: the constant the harness exports"""
     return int(C.c_int.in_dll(C.CDLL(ge.build_harness()), "tetris_harness_select_elems").value)
-
-
-class Buf:
-    """A buffer the entry points read or write: numpy on the harness, a torch device tensor on the GPU; 16-byte aligned plus
-    `offset` bytes; .ptr, .get() -> numpy, .put(values)."""
-
-    def __init__(self, kind, values, offset=0):
-        values = np.ascontiguousarray(values)
-        self.kind, self.dtype, self.shape, self.nbytes, self.offset = kind, values.dtype, values.shape, values.nbytes, offset
-        if kind == "hip":
-            import torch
-            self.raw = torch.zeros(values.nbytes + offset + 16, dtype=torch.uint8).cuda()
-            self.ptr = self.raw.data_ptr() + offset
-            assert self.raw.data_ptr() % 16 == 0
-        else:
-            self.raw = np.zeros(values.nbytes + offset + 32, U8)
-            self.base = (-self.raw.ctypes.data) % 16 + offset
-            self.ptr = self.raw.ctypes.data + self.base
-        self.put(values)
-
-    def put(self, values):
-        flat = np.ascontiguousarray(values).view(U8).reshape(-1)
-        assert flat.size == self.nbytes
-        if self.kind == "hip":
-            import torch
-            self.raw[self.offset:self.offset + self.nbytes] = torch.from_numpy(flat.copy()).cuda()
-            torch.cuda.synchronize()
-        else:
-            self.raw[self.base:self.base + self.nbytes] = flat
-
-    def get(self):
-        if self.kind == "hip":
-            import torch
-            torch.cuda.synchronize()
-            flat = self.raw[self.offset:self.offset + self.nbytes].cpu().numpy()
-        else:
-            flat = self.raw[self.base:self.base + self.nbytes]
-        return flat.copy().view(self.dtype).reshape(self.shape)
-
-
-def sync(kind, b):
-    if kind == "hip":
-        b.sync()
-
-
-class Window:
-    """A window of T rows of the batch's games with its observation records, in buffers of the engine's kind"""
-
-    def __init__(self, kind, b, T, rng=None):
-        n, S = b.n_games, b.n_players
-        self.kind, self.b, self.T, self.n, self.S = kind, b, T, n, S
-        def rb(shape, dt):         # zeros, or distinct random bits
-            if rng is None:
-                return np.zeros(shape, dt)
-            return rng.integers(0, 256, shape).astype(U8) if dt == U8 else rng.integers(0, 1 << 32, shape, dtype=np.uint64).astype(U32)
-
-        obs, action = rb((T, n, S, 12), U32), rb((T, n, 4), U8)
-        if rng is not None:       # words 10 / 11 as the header defines them: four bytes; combo_count, next 0..7, piece 0..7, zero
-            obs[..., 11] = rng.integers(0, 256, (T, n, S)) | (rng.integers(0, 8, (T, n, S)) << 8) | (rng.integers(0, 8, (T, n, S)) << 16)
-            action[..., 1] = rng.integers(0, 10, (T, n))
-            action[..., 2] = rng.integers(0, 7, (T, n))
-        self.obs, self.action = Buf(kind, obs), Buf(kind, action)
-        self.prob, self.value, self.reward = Buf(kind, rb((T, n), U32)), Buf(kind, rb((2, T, n), U32)), Buf(kind, rb((T, n), U32))
-        self.done = Buf(kind, rb((T, n), U8))
-        self.adv, self.target = Buf(kind, rb((T, n), U32)), Buf(kind, rb((T, n), U32))
-        self.traj = b.traj(T, self.action.ptr, self.prob.ptr, self.value.ptr, self.reward.ptr, self.done.ptr)
-        self.tobs = b.traj_obs(T, self.obs.ptr)
-
-
-OUTPUTS = ("visual", "vector", "piece", "action", "prob", "adv", "target", "reward", "done", "valid")
-
-
-def out_shapes(S, M, H):
-    return dict(visual=((S, M, H, 10), U8), vector=((S, M, 12), U8), piece=((S, M), U8), action=((M, 3), U8), prob=((M,), U32),
-                adv=((M,), U32), target=((M,), U32), reward=((M,), U32), done=((M,), U8), valid=((M,), U8))
 
 
 def run_batch(w, index, only=None, offset=None, adv=True, target=True):
@@ -118,65 +42,7 @@ def run_batch(w, index, only=None, offset=None, adv=True, target=True):
     return {k: v.get() for k, v in outs.items()}
 
 
-# ---------------------------------------------------------------- the model, from the header's text
-def model_batch(obs, action, prob, reward, done, adv, target, index, H):
-    """obs uint32 [T, N, S, 12], action uint8 [T, N, 4], prob / reward / adv / target uint32 [T, N] (adv, target or None), done
-    uint8 [T, N]; index [M] -> the ten outputs (floats as uint32)"""
-    T, N, S, _ = obs.shape
-    e = np.asarray(index, np.int64).astype(U32)
-    at, mir = (e & U32(0x7FFFFFFF)).astype(np.int64), (e >> 31) == 1
-    valid = at < T * N
-    at, mir = np.where(valid, at, 0), mir & valid
-    M = len(e)
-    rec = obs.reshape(T * N, S, 12)[at]                                            # [M, S, 12]
-    cols = np.where(mir[:, None, None], rec[:, :, 9::-1], rec[:, :, :10])          # field column c is column 9 - c
-    visual = ((cols[:, :, None, :] >> np.arange(H, dtype=U32)[None, None, :, None]) & 1).astype(U8)
-    w10, w11 = rec[:, :, 10], rec[:, :, 11]
-    vector = np.zeros((M, S, 12), U8)
-    for k in range(4):
-        vector[:, :, k] = (w10 >> (8 * k)) & 255                                    # x, y, inc_lines, combo_time
-    vector[:, :, 4] = w11 & 255                                                     # combo_count
-    hot = (((w11 >> 8) & 255)[:, :, None] == np.arange(7)[None, None, :]).astype(U8)
-    vector[:, :, 5:] = np.where(mir[:, None, None], 1 - hot, hot)                   # piece_swap[int(p == next)]: the quirk
-    piece = ((w11 >> 16) & 255).astype(U8)
-    piece = np.where(mir[:, None], PIECE_SWAP[np.minimum(piece, 7)], piece)
-    a = action.reshape(T * N, 4)[at]
-    act = np.stack([a[:, 0], np.where(mir, 9 - a[:, 1].astype(np.int64), a[:, 1]).astype(U8), np.where(mir, PIECE_SWAP[np.minimum(a[:, 2], 7)], a[:, 2])], axis=1)
-    z = lambda x: np.where(valid.reshape((M,) + (1,) * (x.ndim - 1)), x, 0).astype(x.dtype)          # noqa: E731
-    flat = lambda x: np.zeros(M, U32) if x is None else z(x.reshape(T * N)[at])                      # noqa: E731
-    return dict(visual=z(visual).transpose(1, 0, 2, 3), vector=z(vector).transpose(1, 0, 2), piece=z(piece).T, action=z(act),
-                prob=flat(prob), adv=flat(adv), target=flat(target), reward=flat(reward), done=z(done.reshape(T * N)[at]),
-                valid=valid.astype(U8))
-
-
-def assert_outputs(got, want, where):
-    for k, v in got.items():
-        assert np.array_equal(v, want[k]), f"{where}: '{k}' differs at {np.argwhere(v != want[k])[:4].tolist()}"
-
-
 # ---------------------------------------------------------------- 1. record + expansion = the observation
-def played(kind, n, P, H, colours, seed):
-    """a batch after 30 (r, t) steps: 24 of the heuristic play of tests/test_elapsed_time.py at 400 ms (lines, combos, garbage; game
-    g starts as its pool game g % 32 and, at height 20, follows it), then 6 random ones with 10 ms and 400 ms ticks mixed;
-    finished games are reset by the seed schedule"""
-    from tests.test_elapsed_time import POOL, _heuristic_play
-    rng = np.random.default_rng(seed)
-    heur = _heuristic_play(P, 400)[:24]
-    tile = np.arange(n) % POOL
-    b = engines.make(kind, n, P, H, seeds=orc.episode_seed(tile, 0), colours=colours)
-    episode = np.zeros(n, np.int64)
-    for s in range(len(heur) + 6):
-        if s < len(heur):
-            rot, trans, player, ms = heur[s][0][tile], heur[s][1][tile], heur[s][2][tile], 400
-        else:
-            rot, trans, player = rng.integers(0, 4, n).astype(U8), rng.integers(0, 10, n).astype(U8), rng.integers(0, P, n).astype(U8)
-            ms = (10, 400)[s % 2]
-        done = b.step_rt(rot, trans, player, ms=ms)
-        idx = np.nonzero(done)[0].astype(I32)
-        if len(idx):
-            episode[idx] += 1
-            b.reset(idx, orc.episode_seed(idx % POOL, episode[idx]))
-    return b, rng
 
 
 CASES_1 = [(n, P, 20, False) for n in (1, 33, 64, 65, 257) for P in (1, 2)] + [(65, 2, 7, False), (65, 1, 7, False), (65, 2, 31, False),

@@ -1,5 +1,5 @@
 """Trajectory windows on the device (include/tetris_hip.h: tetris_traj_record_dev, tetris_traj_advantages_dev) against a model
-written here from the header's definition: numpy float32, an explicit sequential loop over the rows, every operation rounded to
+written in tests/traj_support.py from the header's definition: numpy float32, an explicit sequential loop over the rows, every operation rounded to
 float32 in the header's order.  The model owes nothing to drl-tetris_amd/csrc/tetris_traj.h.  The kernel is compared with the
 model by exact bit equality; the model is compared with the reference's own float64 numbers (tests/golden/traj_gae.npz, written
 by tests/golden/make_traj_golden.py from agents/datatypes/trajectory.py) at 4e-6 absolute — by transitivity this pins the kernel
@@ -13,84 +13,13 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as ge
-from tests import engines
+from tests import engines, replay
+from tests.buffers import Buf, bits
+from tests.traj_support import GaeWindow, model
 
 F32 = np.float32
 TILE = 16                      # rows per LDS tile of k_traj_advantages (tetris_traj.h: TRAJ_TILE)
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "traj_gae.npz")
-
-
-class Buf:
-    """A buffer the entry points read or write: numpy on the harness, a torch device tensor on the GPU; .ptr, .get() -> numpy."""
-
-    def __init__(self, kind, values):
-        values = np.ascontiguousarray(values)
-        self.kind, self.dtype, self.shape = kind, values.dtype, values.shape
-        if kind == "hip":
-            import torch
-            self.t = torch.from_numpy(values.copy()).cuda()
-            self.ptr = self.t.data_ptr()
-            torch.cuda.synchronize()              # (the batch runs on a stream of its own)
-        else:
-            self.a = values.copy()
-            self.ptr = self.a.ctypes.data
-
-    def get(self):
-        if self.kind == "hip":
-            import torch
-            torch.cuda.synchronize()
-            return self.t.cpu().numpy().view(self.dtype)
-        return self.a.copy()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=F32).view(np.uint32)
-
-
-# ---------------------------------------------------------------- the model
-def model(value, reward, done, rows, gamma, lambda_adv, lambda_value, boot=None):
-    """value float32 [2, T, n], reward float32 [T, n], done [T, n] -> adv, target float32 [rows, n], closed uint8 [rows, n]: the
-    header's recurrence, one row at a time, all games of a row side by side (elementwise float32 operations round as the
-    scalar ones do)."""
-    n = reward.shape[1]
-    g, la, lv = F32(gamma), F32(lambda_adv), F32(lambda_value)
-    gla, glv = F32(g * la), F32(g * lv)
-    zero, one = F32(0.0), F32(1.0)
-    A1, A2, W1, W2 = (np.zeros(n, F32) for _ in range(4))
-    vnext = np.zeros(n, F32) if boot is None else boot.astype(F32).copy()
-    seen = np.zeros(n, np.uint8)
-    adv, target, closed = np.zeros((rows, n), F32), np.zeros((rows, n), F32), np.zeros((rows, n), np.uint8)
-    with np.errstate(all="ignore"):
-        for t in range(rows - 1, -1, -1):
-            d = done[t] != 0
-            A1, A2, W1, W2 = (np.where(d, zero, x).astype(F32) for x in (A1, A2, W1, W2))
-            seen = np.where(d, 1, seen).astype(np.uint8)
-            v0, v1 = value[0, t].astype(F32), value[1, t].astype(F32)
-            boot_term = ((g * vnext).astype(F32) * np.where(d, zero, one).astype(F32)).astype(F32)
-            td = ((reward[t].astype(F32) + boot_term).astype(F32) - v0).astype(F32)
-            A1 = ((A1 * gla).astype(F32) + td).astype(F32)
-            W1 = ((W1 * la).astype(F32) + one).astype(F32)
-            A2 = ((A2 * glv).astype(F32) + td).astype(F32)
-            W2 = ((W2 * lv).astype(F32) + one).astype(F32)
-            adv[t] = (((A1 + v0).astype(F32) - v1).astype(F32) / W1).astype(F32)
-            target[t] = (v1 + (((A2 + v0).astype(F32) - v1).astype(F32) / W2).astype(F32)).astype(F32)
-            closed[t] = seen
-            vnext = v0
-    return adv, target, closed
-
-
-class Window:
-    """A window of T rows of the batch's games in buffers of the engine's kind, and the struct over them"""
-
-    def __init__(self, kind, b, T, value=None, reward=None, done=None, fill=0):
-        n = b.n_games
-        self.T, self.n = T, n
-        self.action = Buf(kind, np.full((T, n, 4), fill, np.uint8))
-        self.prob = Buf(kind, np.full((T, n), fill, F32))
-        self.value = Buf(kind, np.full((2, T, n), fill, F32) if value is None else value.astype(F32))
-        self.reward = Buf(kind, np.full((T, n), fill, F32) if reward is None else reward.astype(F32))
-        self.done = Buf(kind, np.full((T, n), fill, np.uint8) if done is None else done.astype(np.uint8))
-        self.traj = b.traj(T, self.action.ptr, self.prob.ptr, self.value.ptr, self.reward.ptr, self.done.ptr)
+GOLDEN = os.path.join(replay.GOLDEN, "traj_gae.npz")
 
 
 def done_columns(rng, T, n, rows, shift):
@@ -139,7 +68,7 @@ def test_advantages_equal_the_model_bit_for_bit(kind, n):
             if k % 3 == 2:                                  # rewards on every row, as a caller with shaped rewards would have
                 reward = rng.standard_normal((T, n)).astype(F32)
             boot = (2.0 * rng.standard_normal(n)).astype(F32) if (case + k) % 2 else None
-            w = Window(kind, b, T, value, reward, done)
+            w = GaeWindow(kind, b, T, value, reward, done)
             adv, target, closed = (Buf(kind, np.full((T, n), -7.0, F32)), Buf(kind, np.full((T, n), -7.0, F32)), Buf(kind, np.full((T, n), 9, np.uint8)))
             bb = None if boot is None else Buf(kind, boot)
             b.traj_advantages_dev(w.traj, rows, gamma, la, lv, None if bb is None else bb.ptr, adv.ptr, target.ptr, closed.ptr)
@@ -230,7 +159,7 @@ class _Played:
             te = ti.TorchEnv(b)
             self.tr = tr = te.trajectory(T)
         else:
-            self.w = w = Window(kind, b, T, fill=7)
+            self.w = w = GaeWindow(kind, b, T, fill=7)
             outs = dict(rot=Buf(kind, np.zeros(n, np.uint8)), trans=Buf(kind, np.zeros(n, np.uint8)), piece=Buf(kind, np.zeros(n, np.uint8)),
                         eval=Buf(kind, np.zeros(n, F32)), value=Buf(kind, np.zeros((2, n), F32)), done=Buf(kind, np.zeros(n, np.uint8)),
                         lines=Buf(kind, np.zeros((P, n), np.uint8)), dead=Buf(kind, np.zeros((P, n), np.uint8)))
@@ -318,7 +247,7 @@ def test_arguments_are_checked():
     pkg = ge.package()
     n, T = 4, 6
     b = engines.make("harness", n, 2)
-    w = Window("harness", b, T, fill=7)
+    w = GaeWindow("harness", b, T, fill=7)
     p = lambda arr: arr.ctypes.data                                                           # noqa: E731
     rot, trans, piece, ev, value = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, F32), np.zeros((2, n), F32)
     done, dead = np.zeros(n, np.uint8), np.zeros((2, n), np.uint8)

@@ -15,27 +15,17 @@ import pytest
 
 import __graft_entry__ as ge
 from oracle import oracle as orc
-from tests import engines
-from tests.test_act_eval import midgame
-from tests.test_plan_choose import Call, bits, crafted_phi
-from tests.test_plan_deltas import GUARD, PAD, Out, _crafted, _words
-from tests.test_plan_device import Buf, _device_lists
-from tests.test_traj_batch import Buf as ABuf            # 16-byte aligned, with a byte offset
+from tests import engines, replay
+from tests.act_support import midgame
+from tests.buffers import GUARD, MIRROR, Buf, bits, out
+from tests.plan_support import Call, _crafted, _device_lists, _words, crafted_phi
 
 F32, U32, U8, I32 = np.float32, np.uint32, np.uint8, np.int32
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "traj_plan.npz")
-MIRROR = 1 << 31
+GOLDEN = os.path.join(replay.GOLDEN, "traj_plan.npz")
 WORDS = 112
 
 
 # ---------------------------------------------------------------- buffers
-def put(out, values):
-    """fills an Out buffer's data (its guard bytes stay)"""
-    raw = np.full(out.nbytes + PAD, GUARD, U8)
-    raw[: out.nbytes] = np.ascontiguousarray(values).view(U8).reshape(-1)
-    out.buf.set(raw)
-
-
 class PlanWindow:
     """A window of T rows of the batch's games with its observation and plan records; every array has guard bytes behind it and
     starts as GUARD bytes throughout, so what a call did not write shows."""
@@ -46,14 +36,14 @@ class PlanWindow:
     def __init__(self, kind, b, T):
         n, S = b.n_games, b.n_players
         self.kind, self.b, self.T, self.n, self.S = kind, b, T, n, S
-        self.bufs = {k: Out(kind, int(np.prod(shape(T, n, S))), dt) for k, (shape, dt) in self.SHAPES.items()}
+        self.bufs = {k: out(kind, shape(T, n, S), dt) for k, (shape, dt) in self.SHAPES.items()}
         p = lambda k: self.bufs[k].ptr                                                           # noqa: E731
         self.traj = b.traj(T, p("action"), p("prob"), p("value"), p("reward"), p("done"))
         self.tobs = b.traj_obs(T, p("obs"))
         self.plan = b.traj_plan(T, p("rec"))
 
     def get(self, name):
-        return self.bufs[name].get(self.SHAPES[name][0](self.T, self.n, self.S))
+        return self.bufs[name].get()
 
     def untouched(self, names=None, rows=None):
         for k in names or self.SHAPES:
@@ -68,11 +58,11 @@ def run_plan_batch(kind, b, plan, index, fill, f16=False, delta=True, sums=True)
     """tetris_traj_plan_batch_dev of the index list -> {name: numpy [M, H, 10]} (guard bytes behind both outputs)"""
     M, H = len(index), b.height
     dt = np.float16 if f16 else F32
-    ib = ABuf(kind, np.asarray(index, np.int64).astype(U32).view(I32)) if M else None
-    outs = {k: Out(kind, M * H * 10, dt) for k, on in (("delta", delta), ("sums", sums)) if on}
+    ib = Buf(kind, np.asarray(index, np.int64).astype(U32).view(I32)) if M else None
+    outs = {k: out(kind, (M, H, 10), dt) for k, on in (("delta", delta), ("sums", sums)) if on}
     b.traj_plan_batch_dev(plan, ib.ptr if M else 16, M, delta=outs["delta"].ptr if delta else None, sums=outs["sums"].ptr if sums else None,
                           small_fill=fill, f16=f16)
-    return {k: v.get((M, H, 10)) for k, v in outs.items()}
+    return {k: v.get() for k, v in outs.items()}
 
 
 def raw(a):
@@ -150,8 +140,8 @@ def test_record_then_expand_equals_the_choose_calls_planes(kind, P, H, L):
         who = np.minimum(player, P - 1)
         rng = np.random.default_rng(11 * P + H + L)
         w = PlanWindow(kind, b, T)
-        pl = Buf(kind, (N,), U8)
-        pl.set(player)
+        pl = Buf.full(kind, (N,), U8)
+        pl.put(player)
         blob = b.snapshot()
         for row, mode, fill in ((0, "argmax", 1e-3), (2, "pi", 0.0), (2, "argmax", 0.0), (0, "pi", 1e-3)):
             where = f"row {row} {mode} fill {fill}"
@@ -159,7 +149,7 @@ def test_record_then_expand_equals_the_choose_calls_planes(kind, P, H, L):
             se = rng.standard_normal((N, 7)).astype(F32)
             done = (rng.random(N) < 0.5).astype(U8)
             dead = (rng.random((P, N)) < 0.5).astype(U8)
-            db, xb = ABuf(kind, done), ABuf(kind, dead)
+            db, xb = Buf(kind, done), Buf(kind, dead)
             b.traj_observe_dev(w.tobs, row, pl.ptr)
             call = Call(kind, b, phi, player, count, cols, L, mode, fill=fill, state_eval=se, seed=31, draw=row)
             half = Call(kind, b, phi, player, count, cols, L, mode, fill=fill, seed=31, draw=row, out_f16=True)
@@ -222,8 +212,8 @@ def test_the_records_words_are_the_documented_format(kind):
         choice[2], choice[0], choice[6] = 5, L + 40, -9
         cols = np.ascontiguousarray(_words(after).transpose(1, 2, 0)[:, None])                  # [L, 1, 10, N]
         w = PlanWindow(kind, b, T)
-        bufs = dict(count=ABuf(kind, count), cols=ABuf(kind, cols), choice=ABuf(kind, choice), piece=ABuf(kind, (np.arange(N) % 7).astype(U8)),
-                    prob=ABuf(kind, rng.random(N).astype(F32)), done=ABuf(kind, np.zeros(N, U8)), dead=ABuf(kind, np.zeros((1, N), U8)))
+        bufs = dict(count=Buf(kind, count), cols=Buf(kind, cols), choice=Buf(kind, choice), piece=Buf(kind, (np.arange(N) % 7).astype(U8)),
+                    prob=Buf(kind, rng.random(N).astype(F32)), done=Buf(kind, np.zeros(N, U8)), dead=Buf(kind, np.zeros((1, N), U8)))
         e = b.plan_eval(None, bufs["count"].ptr, bufs["cols"].ptr, bufs["choice"].ptr, max_lists=L, piece=bufs["piece"].ptr, prob=bufs["prob"].ptr)
         b.traj_observe_dev(w.tobs, 1, None)
         b.traj_record_plan_dev(w.traj, w.plan, w.tobs, 1, e, bufs["done"].ptr, bufs["dead"].ptr)
@@ -265,12 +255,12 @@ def test_a_recorded_step_expands_to_the_planes_taken_before_it(kind, P, auto):
         rng = np.random.default_rng(50 + P)
         ids, episode, ended = np.arange(n), np.zeros(n, np.int64), 0
         w = PlanWindow(kind, a, T)
-        done, lines, dead = Buf(kind, (n,), U8, 7), Buf(kind, (P, n), U8, 7), Buf(kind, (P, n), U8, 7)
+        done, lines, dead = Buf.full(kind, (n,), U8, 7), Buf.full(kind, (P, n), U8, 7), Buf.full(kind, (P, n), U8, 7)
         for s in range(steps):
             row, mode, fill = s % T, ("argmax", "pi")[s % 2], (1e-3, 0.0)[(s // 2) % 2]
             player = rng.integers(0, P, n)
             cnt, lens, keys, pl = _device_lists(kind, a, player, False, L=L, K=K)
-            cols = Buf(kind, (L, P, 10, n), U32)
+            cols = Buf.full(kind, (L, P, 10, n), U32)
             a.simulate_lists_dev(cnt.ptr, lens.ptr, keys.ptr, cols.ptr, max_lists=L, max_keys=K, player=pl.ptr)
             a.traj_observe_dev(w.tobs, row, pl.ptr)
             phi = (rng.random((n, 20, 10, 7)) + 0.1).astype(F32)
@@ -317,7 +307,7 @@ def test_batch_semantics(kind, H, f16):
         rec = rng.integers(0, 1 << 32, (total, WORDS), dtype=np.uint64).astype(U32)
         rec[:, 20] = rng.integers(0, 3, total)
         rec[:, 21] = rng.integers(0, 300, total) | (rng.integers(0, 300, total) << 16)
-        rb = ABuf(kind, rec)
+        rb = Buf(kind, rec)
         plan = b.traj_plan(T, rb.ptr)
         fill = 1e-3
         for M in (0, 1, 65, 1000):
@@ -392,12 +382,12 @@ def test_the_fixture_through_the_whole_path(kind):
             assert np.array_equal(b.observe()[0]["field"][:, 0, :H] > 0, before)
             cols = np.zeros((L, P, 10, E), U32)
             cols[:, 0] = _words(after).transpose(1, 2, 0)
-            bufs = [ABuf(kind, x) for x in (np.full(E, L, I32), cols, choice, piece, prob, value, done, dead)]
+            bufs = [Buf(kind, x) for x in (np.full(E, L, I32), cols, choice, piece, prob, value, done, dead)]
             e_ = b.plan_eval(None, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, max_lists=L, piece=bufs[3].ptr, prob=bufs[4].ptr, value=bufs[5].ptr)
             b.traj_observe_dev(w.tobs, t, None)
             b.traj_record_plan_dev(w.traj, w.plan, w.tobs, t, e_, bufs[6].ptr, bufs[7].ptr)
-        adv, target, closed = (ABuf(kind, np.zeros((T, E), dt)) for dt in (F32, F32, U8))
-        index, count = ABuf(kind, np.zeros(T * E, I32)), ABuf(kind, np.zeros(1, I32))
+        adv, target, closed = (Buf(kind, np.zeros((T, E), dt)) for dt in (F32, F32, U8))
+        index, count = Buf(kind, np.zeros(T * E, I32)), Buf(kind, np.zeros(1, I32))
         compared, worst = 0, [0.0, 0.0]
         for case in range(len(z["gamma"])):
             b.traj_advantages_dev(w.traj, T, float(z["gamma"][case]), float(z["gae_lambda"][case]), float(z["gve_lambda"]), None, adv.ptr, target.ptr, closed.ptr)
@@ -405,10 +395,10 @@ def test_the_fixture_through_the_whole_path(kind):
             M = int(count.get()[0])
             idx = index.get()[:M]
             assert M == T * E and (idx >= 0).all(), "every column ends in a done: every entry is closed"
-            outs = dict(visual=ABuf(kind, np.zeros((P, M, H, 10), U8)), action=ABuf(kind, np.zeros((M, 3), U8)), prob=ABuf(kind, np.zeros(M, F32)),
-                        adv=ABuf(kind, np.zeros(M, F32)), target=ABuf(kind, np.zeros(M, F32)), reward=ABuf(kind, np.zeros(M, F32)),
-                        done=ABuf(kind, np.zeros(M, U8)))
-            ib = ABuf(kind, idx)
+            outs = dict(visual=Buf(kind, np.zeros((P, M, H, 10), U8)), action=Buf(kind, np.zeros((M, 3), U8)), prob=Buf(kind, np.zeros(M, F32)),
+                        adv=Buf(kind, np.zeros(M, F32)), target=Buf(kind, np.zeros(M, F32)), reward=Buf(kind, np.zeros(M, F32)),
+                        done=Buf(kind, np.zeros(M, U8)))
+            ib = Buf(kind, idx)
             b.traj_batch_dev(w.traj, w.tobs, ib.ptr, M, b.traj_batch(**{k: v.ptr for k, v in outs.items()}), adv=adv.ptr, target=target.ptr)
             mb = {k: v.get() for k, v in outs.items()}
             pl = run_plan_batch(kind, b, w.plan, idx, 0.0)
@@ -524,7 +514,7 @@ def test_torch_env_calls_equal_the_c_level_results():
         with pytest.raises(AssertionError):
             te.trajectory(T, plan=True)
         w = PlanWindow("hip", c, T)
-        done, lines, dead = Buf("hip", (n,), U8), Buf("hip", (P, n), U8), Buf("hip", (P, n), U8)
+        done, lines, dead = Buf.full("hip", (n,), U8), Buf.full("hip", (P, n), U8), Buf.full("hip", (P, n), U8)
         for s in range(4):
             row, mode = s % T, ("pi", "argmax")[s % 2]
             player = rng.integers(0, P, n).astype(U8)
@@ -532,7 +522,7 @@ def test_torch_env_calls_equal_the_c_level_results():
             phi = crafted_phi(rng, n, 20, 7, F32)
             se = rng.standard_normal((n, 7)).astype(F32)
             cnt, lens, keys, pl = _device_lists("hip", c, player, False, L=L, K=K)
-            cols = Buf("hip", (L, P, 10, n), U32)
+            cols = Buf.full("hip", (L, P, 10, n), U32)
             c.simulate_lists_dev(cnt.ptr, lens.ptr, keys.ptr, cols.ptr, max_lists=L, max_keys=K, player=pl.ptr)
             c.traj_observe_dev(w.tobs, row, pl.ptr)
             call = Call("hip", c, phi, player, cnt.get(), cols, L, mode, state_eval=se, seed=4, draw=s)
