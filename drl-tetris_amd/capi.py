@@ -245,12 +245,6 @@ def _share_hip_runtime_with_torch():
             return
 
 
-def _missing(path, name):
-    def call(*_args):
-        raise TetrisError(f"{path} does not export {name}")
-    return call
-
-
 def load_library(lib_path=None):
     path = os.path.abspath(lib_path or DEFAULT_LIB)
     if path in _libs:
@@ -262,11 +256,6 @@ def load_library(lib_path=None):
                           "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(path)
     for name, (res, args) in _SIGNATURES.items():
-        if lib_path is not None and not hasattr(lib, name):
-            # a test build that leaves part of the ABI out (the sanitizer build of tests/cpu_harness/harness.cpp alone has no
-            # planning entry points): the name raises when called.  The product library is bound strictly below.
-            setattr(lib, name, _missing(path, name))
-            continue
         fn = getattr(lib, name)          # AttributeError here = the library does not export the ABI
         fn.restype, fn.argtypes = res, args
     if lib.tetris_record_size() != RECORD.itemsize:

@@ -5,7 +5,7 @@
 // The [N][H][10][L] deltas tensor is never formed: a list's score is a walk over the set bits of after ^ before.
 //
 // `__host__ __device__` like tetris_plan.h and tetris_act.h: tetris_hip.hip wraps these in a gfx950 kernel (k_plan_choose, tetris_dev_agent_plan.h),
-// tests/cpu_harness/harness_choose.cpp in a plain host loop.
+// tests/cpu_harness/harness_lib_agent.h in a plain host loop.
 //
 // The bodies work on one game's phi plane as a strided float32 array — w[cell * sw], cell = 10 y + x — and on its scores
 // x[k * sx]: on the GPU both are columns of a workgroup's LDS image (the lane's game fixed), on the host small arrays.  Every sum

@@ -35,3 +35,4 @@
 #include "tetris_lib_rollout.h"
 #include "tetris_lib_core.h"
 #include "tetris_lib_agent.h"
+#include "tetris_lib_compose.h"          // entry points that only call other entry points: the CPU harness includes it too

@@ -1,8 +1,8 @@
 // The host-side rules of the C ABI (include/tetris_hip.h) that do not depend on where memory lives or how work is launched: the
 // argument checks of the entry points, the filling of the kernels' argument structs, the repacking of host arrays, the mapping
 // of flag words to TETRIS_ERR_* bits, and the thread's last error.  No HIP in here.  tetris_hip.hip (hipcc) and
-// tests/cpu_harness/harness.cpp (g++, the CPU build of the same kernel bodies) both include it, so the CPU suite runs the lines
-// that ship.  Nothing here needs either side's tetris_batch: a HostShape says what the rules ask of a batch.
+// tests/cpu_harness/harness.cpp (g++, the CPU build of the same kernel bodies) both include it (and tetris_lib_compose.h), so the CPU
+// suite runs the lines that ship.  Nothing here needs either side's tetris_batch: a HostShape says what the rules ask of a batch.
 //
 // The builders fill everything of an argument struct except its embedded KArgs `a`, or take it as `base`: the caller makes it
 // with its own base_args, the product after its run-ahead gate (the gate may have extended the RNG tables).
@@ -639,6 +639,15 @@ static inline int rollout_launch_check(int launches, int steps_per_launch) {
     if (steps_per_launch > 256) return fail(TETRIS_E_ARG, "steps_per_launch must be <= 256");
     return TETRIS_OK;
 }
+// The low-water margin of the RNG tables for the launches of one call: raised to `need` draws, put back on every return path.
+// A step may consume 2 piece draws per player, and the host learns of a board that came close to the end of the tables only
+// through the flag words, up to 2 * group + 1 launches late (gate_launch): rollout_margin covers what those launches can consume.
+template <class B>          // (either side's tetris_batch)
+struct MarginGuard {
+    B* b; uint32_t saved;
+    MarginGuard(B* b, uint32_t need) : b(b), saved(b->margin) { if (b->margin < need) b->margin = need; }
+    ~MarginGuard() { b->margin = saved; }
+};
 // tetris_split_stage_dev's own rule, then those of both split calls
 static inline int split_step_check(int stage, const uint8_t* d_rot, const uint8_t* d_trans) {
     if ((stage == 0 || stage == 3) && (!d_rot || !d_trans)) return fail(TETRIS_E_ARG, "stages 0 and 3 need rot/trans (stage 3: of the NEXT step)");

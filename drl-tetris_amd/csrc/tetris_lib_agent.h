@@ -219,27 +219,6 @@ int tetris_select_eval_dev(tetris_batch* b, const tetris_act_eval* e) {
     return launch(b, k_act_select, dim3(blocks_for(b->N, ACT_BLOCK)), dim3(ACT_THREADS), 0, aa);
 }
 
-int tetris_step_eval_dev(tetris_batch* b, const tetris_act_eval* e, int ms, int flags, uint8_t* d_done, uint8_t* d_lines,
-                         uint8_t* d_dead) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = step_eval_check(flags))) return rc;
-    // two launches: the step fused behind the selection in one kernel took 1.6-2.2 times as long
-    if ((rc = tetris_select_eval_dev(b, e))) return rc;
-    return tetris_step_rt_dev_ex(b, e->d_rot, e->d_trans, e->d_player, ms, d_done, d_lines, d_dead, flags);
-}
-
-int tetris_step_eval_observe_dev(tetris_batch* b, const tetris_act_eval* e, int ms, int flags, uint8_t* d_done, uint8_t* d_lines,
-                                 uint8_t* d_dead, const uint8_t* d_next_player, uint8_t* d_visual, uint8_t* d_vector,
-                                 uint8_t* d_obs_piece) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = step_eval_observe_check(shape_of(b), flags, d_visual, d_vector, d_obs_piece))) return rc;
-    if ((rc = tetris_select_eval_dev(b, e))) return rc;
-    return tetris_step_rt_observe_dev(b, e->d_rot, e->d_trans, e->d_player, ms, d_done, d_lines, d_dead, flags, d_next_player,
-                                      d_visual, d_vector, d_obs_piece);
-}
-
 // ---------------------------------------------------------------- choosing a planning agent's list from phi (tetris_choose.h)
 int tetris_select_lists_dev(tetris_batch* b, const tetris_plan_eval* e) {
     int rc = check_batch(b);
@@ -253,16 +232,6 @@ int tetris_select_lists_dev(tetris_batch* b, const tetris_plan_eval* e) {
     const size_t lds = choose_lds_bytes(G, b->H, ca.max_lists);
     const dim3 grid(blocks_for(b->N, G)), block(CHOOSE_THREADS);
     return G == 32 ? launch(b, k_plan_choose<32>, grid, block, lds, ca) : launch(b, k_plan_choose<16>, grid, block, lds, ca);
-}
-
-int tetris_step_lists_eval_dev(tetris_batch* b, const tetris_plan_eval* e, const uint8_t* d_lens, const uint8_t* d_keys, int max_keys,
-                               int ms, int flags, uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead) {
-    int rc = check_batch(b);
-    if (rc) return rc;
-    if ((rc = step_lists_eval_check(shape_of(b), e, d_lens, d_keys, max_keys, flags))) return rc;
-    if ((rc = tetris_select_lists_dev(b, e))) return rc;
-    return tetris_step_lists_dev(b, e->d_player, e->d_choice, e->d_count, d_lens, d_keys, e->max_lists, max_keys, ms, flags, d_done,
-                                 d_lines, d_dead);
 }
 
 // ---------------------------------------------------------------- trajectory windows (tetris_traj.h)

@@ -1,0 +1,77 @@
+// The entry points that are nothing but a fixed sequence of calls to other entry points, or to helpers both sides have (check_batch,
+// shape_of, create_impl, rollout_counters_begin / _end, the checks of tetris_host.h).  No HIP in here: tetris_hip.hip and
+// tests/cpu_harness/harness.cpp both include it, last, so the CPU suite runs these lines as they ship.
+
+extern "C" {
+
+const char* tetris_last_error(void) { return last_error(); }
+int tetris_record_size(void) { return (int)sizeof(tetris_record); }
+int tetris_layout_words(void) { return NWORDS; }
+int tetris_snapshot_words(const tetris_batch* b) { return b ? NGWORDS + b->P * b->nw : 0; }
+
+int tetris_create(tetris_batch** out, int n_games, int n_players, int height, int width, const uint8_t piece_map[7],
+                  int device, const int16_t* seeds) {
+    return create_impl(out, n_games, n_players, height, width, piece_map, device, seeds, 0, 0);
+}
+
+int tetris_create_ex(tetris_batch** out, int n_games, int n_players, int height, int width, const uint8_t piece_map[7], int device,
+                     const int16_t* seeds, int flags) {
+    return create_impl(out, n_games, n_players, height, width, piece_map, device, seeds, 0, 0, flags);
+}
+
+int tetris_create_split(tetris_batch** out, int n_games, int side, int height, int width, const uint8_t piece_map[7], int device,
+                        const int16_t* seeds) {
+    return create_impl(out, n_games, 1, height, width, piece_map, device, seeds, 1, side);
+}
+
+int tetris_step_rt_dev(tetris_batch* b, const uint8_t* d_rot, const uint8_t* d_trans, const uint8_t* d_player, int ms,
+                       uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead) {
+    return tetris_step_rt_dev_ex(b, d_rot, d_trans, d_player, ms, d_done, d_lines, d_dead, 0);
+}
+
+int tetris_enumerate_drops_dev(tetris_batch* b, const int32_t* d_idx, int n, const uint8_t* d_player, uint8_t* d_valid,
+                               int8_t* d_land_y, uint8_t* d_cleared, uint32_t* d_after) {
+    return tetris_enumerate_drops_dev_ex(b, d_idx, n, d_player, d_valid, d_land_y, d_cleared, d_after, 0);
+}
+
+int tetris_step_eval_dev(tetris_batch* b, const tetris_act_eval* e, int ms, int flags, uint8_t* d_done, uint8_t* d_lines,
+                         uint8_t* d_dead) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = step_eval_check(flags))) return rc;
+    // two launches: the step fused behind the selection in one kernel took 1.6-2.2 times as long
+    if ((rc = tetris_select_eval_dev(b, e))) return rc;
+    return tetris_step_rt_dev_ex(b, e->d_rot, e->d_trans, e->d_player, ms, d_done, d_lines, d_dead, flags);
+}
+
+int tetris_step_eval_observe_dev(tetris_batch* b, const tetris_act_eval* e, int ms, int flags, uint8_t* d_done, uint8_t* d_lines,
+                                 uint8_t* d_dead, const uint8_t* d_next_player, uint8_t* d_visual, uint8_t* d_vector,
+                                 uint8_t* d_obs_piece) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = step_eval_observe_check(shape_of(b), flags, d_visual, d_vector, d_obs_piece))) return rc;
+    if ((rc = tetris_select_eval_dev(b, e))) return rc;
+    return tetris_step_rt_observe_dev(b, e->d_rot, e->d_trans, e->d_player, ms, d_done, d_lines, d_dead, flags, d_next_player,
+                                      d_visual, d_vector, d_obs_piece);
+}
+
+int tetris_step_lists_eval_dev(tetris_batch* b, const tetris_plan_eval* e, const uint8_t* d_lens, const uint8_t* d_keys, int max_keys,
+                               int ms, int flags, uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    if ((rc = step_lists_eval_check(shape_of(b), e, d_lens, d_keys, max_keys, flags))) return rc;
+    if ((rc = tetris_select_lists_dev(b, e))) return rc;
+    return tetris_step_lists_dev(b, e->d_player, e->d_choice, e->d_count, d_lens, d_keys, e->max_lists, max_keys, ms, flags, d_done,
+                                 d_lines, d_dead);
+}
+
+int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,
+                          int ms, uint64_t counters[4], float* elapsed_ms) {
+    int rc;
+    if (counters && (rc = rollout_counters_begin(b))) return rc;
+    if ((rc = tetris_rollout_launch(b, launches, steps_per_launch, policy_seed, first_step, ms, elapsed_ms))) return rc;
+    if (counters && (rc = rollout_counters_end(b, counters))) return rc;
+    return TETRIS_OK;
+}
+
+}  // extern "C"

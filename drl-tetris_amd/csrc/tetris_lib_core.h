@@ -3,8 +3,6 @@
 
 extern "C" {
 
-const char* tetris_last_error(void) { return last_error(); }
-
 int tetris_device_count(void) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -20,9 +18,6 @@ int tetris_device_name(int device, char* buf, int len) {
     return TETRIS_OK;
 }
 
-int tetris_record_size(void) { return (int)sizeof(tetris_record); }
-int tetris_layout_words(void) { return NWORDS; }
-int tetris_snapshot_words(const tetris_batch* b) { return b ? NGWORDS + b->P * b->nw : 0; }
 int tetris_table_chunks(const tetris_batch* b) { return b && b->tab ? b->tab->n_chunks : 0; }
 void* tetris_device_state(tetris_batch* b) { return b ? b->d_state : nullptr; }
 void* tetris_stream(tetris_batch* b) { return b ? (void*)b->stream : nullptr; }
@@ -275,21 +270,6 @@ int tetris_set_game_offset(tetris_batch* b, uint64_t first_game_id) {
     return TETRIS_OK;
 }
 
-int tetris_create(tetris_batch** out, int n_games, int n_players, int height, int width, const uint8_t piece_map[7],
-                  int device, const int16_t* seeds) {
-    return create_impl(out, n_games, n_players, height, width, piece_map, device, seeds, 0, 0);
-}
-
-int tetris_create_ex(tetris_batch** out, int n_games, int n_players, int height, int width, const uint8_t piece_map[7], int device,
-                     const int16_t* seeds, int flags) {
-    return create_impl(out, n_games, n_players, height, width, piece_map, device, seeds, 0, 0, flags);
-}
-
-int tetris_create_split(tetris_batch** out, int n_games, int side, int height, int width, const uint8_t piece_map[7], int device,
-                        const int16_t* seeds) {
-    return create_impl(out, n_games, 1, height, width, piece_map, device, seeds, 1, side);
-}
-
 int tetris_set_stream(tetris_batch* b, void* hip_stream, int external) {
     int rc = check_batch(b);
     if (rc) return rc;
@@ -465,11 +445,6 @@ int tetris_step_rt_observe_dev(tetris_batch* b, const uint8_t* d_rot, const uint
     return launched();
 }
 
-int tetris_step_rt_dev(tetris_batch* b, const uint8_t* d_rot, const uint8_t* d_trans, const uint8_t* d_player, int ms,
-                       uint8_t* d_done, uint8_t* d_lines, uint8_t* d_dead) {
-    return tetris_step_rt_dev_ex(b, d_rot, d_trans, d_player, ms, d_done, d_lines, d_dead, 0);
-}
-
 int tetris_reset_dev(tetris_batch* b, const uint8_t* d_mask, const int16_t* d_seeds) {
     int rc = check_batch(b);
     if (rc) return rc;
@@ -632,11 +607,6 @@ int tetris_enumerate_drops(tetris_batch* b, const int32_t* idx, int n, const uin
         (after && (rc = io.out(after, lanes * NCOL, &d_after)))) return rc;
     if ((rc = tetris_enumerate_drops_dev_ex(b, io.d_idx, n, d_player, d_valid, d_land_y, d_cleared, d_after, 0))) return rc;
     return io.finish();
-}
-
-int tetris_enumerate_drops_dev(tetris_batch* b, const int32_t* d_idx, int n, const uint8_t* d_player, uint8_t* d_valid,
-                               int8_t* d_land_y, uint8_t* d_cleared, uint32_t* d_after) {
-    return tetris_enumerate_drops_dev_ex(b, d_idx, n, d_player, d_valid, d_land_y, d_cleared, d_after, 0);
 }
 
 int tetris_timer_start(tetris_batch* b) {

@@ -1,5 +1,5 @@
 // Host side of libtetris_hip.so, part 2: chained launches and the rollout paths (plain, graph, streams, direct dispatch), chain_recover,
-// tetris_rollout_launch / tetris_rollout_random and the rollout counters.  Needs tetris_lib_batch.h.
+// tetris_rollout_launch and the rollout counters (tetris_rollout_random: tetris_lib_compose.h).  Needs tetris_lib_batch.h.
 
 // Games per wave of a chained launch: CHAIN_LANES for one player, 32 for two (k_duo: the players in adjacent half-waves).
 static int chain_lanes(const tetris_batch* b) { return b->P == 1 ? CHAIN_LANES : 32; }
@@ -125,14 +125,6 @@ static bool rollout_chained(tetris_batch* b, int steps_per_launch) {
            (b->P == 1 || (b->P == 2 && steps_per_launch == 1 && b->use_duo)) && chain_fits(b, chain_is_fused(b, steps_per_launch));
 }
 
-// The low-water margin of the RNG tables for the launches of one call: raised to `need` draws, put back on every return path.
-// A step may consume 2 piece draws per player, and the host learns of a board that came close to the end of the tables only
-// through the flag words, up to 2 * group + 1 launches late (gate_launch): rollout_margin covers what those launches can consume.
-struct MarginGuard {
-    tetris_batch* b; uint32_t saved;
-    MarginGuard(tetris_batch* b, uint32_t need) : b(b), saved(b->margin) { if (b->margin < need) b->margin = need; }
-    ~MarginGuard() { b->margin = saved; }
-};
 // run-ahead of a rollout call in launches (fused launches: fewer of them in flight)
 static int rollout_group(int steps_per_launch) { return std::max(1, steps_per_launch ? GATE_GROUP / steps_per_launch : GATE_GROUP); }
 static uint32_t rollout_margin(int steps_per_launch, int group) { return (uint32_t)(2 * steps_per_launch * (2 * group + 2) + 16); }
@@ -607,15 +599,6 @@ int tetris_rollout_launch(tetris_batch* b, int launches, int steps_per_launch, u
             return rollout_direct(b, dev, call, group, t_entry, elapsed_ms);
     }
     return rollout_streams(b, call, group, prequeue, t_entry, elapsed_ms);
-}
-
-int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,
-                          int ms, uint64_t counters[4], float* elapsed_ms) {
-    int rc;
-    if (counters && (rc = rollout_counters_begin(b))) return rc;
-    if ((rc = tetris_rollout_launch(b, launches, steps_per_launch, policy_seed, first_step, ms, elapsed_ms))) return rc;
-    if (counters && (rc = rollout_counters_end(b, counters))) return rc;
-    return TETRIS_OK;
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 // (agents/sherlock_agent/sherlock_agent.py:94-120, sherlock_utils.py:9-20).
 //
 // `__host__ __device__` like tetris_kernels.h: tetris_hip.hip / tetris_hip_multi.hip wrap these in gfx950 kernels,
-// tests/cpu_harness/harness_plan.cpp (the deltas: harness_deltas.cpp) in plain host loops.
+// tests/cpu_harness/harness_lib_agent.h in plain host loops.
 //
 // Lists of one game live at lens[i][L] and keys[i][L][K] (L = max_lists, K = max_keys), count[i] of them (-1: the game's
 // lists did not fit).  The per-(game, x, rotation) search is actions_body (k_actions), which writes "slabs": for lane
@@ -223,7 +223,7 @@ TE_HD void plan_step_lane(const PlanArgs& pa, int i, const uint32_t* shapes, boo
 // sherlock_utils.deltas / generate_deltas (agents/sherlock_agent/sherlock_utils.py:9-20), per game and list: the acting player's
 // field after the list minus the field before; a list whose difference adds up to less than 4 is `small_fill` everywhere; lists
 // past count are zero; sums = the sum over the lists.  The element logic below is shared by k_plan_deltas (tetris_dev_agent_plan.h) and
-// the host loop of tests/cpu_harness/harness_deltas.cpp, so that both give the same bits.
+// the host loop of tests/cpu_harness/harness_lib_agent.h, so that both give the same bits.
 struct PlanDeltaArgs {
     Geo geo;
     int H, n;                   // rows of a board, games

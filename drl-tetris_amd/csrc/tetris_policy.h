@@ -4,7 +4,7 @@
 // dot product with int16 weights — what tests/golden/policies.py:GreedyRT does on the CPU oracle, one game at a time.
 //
 // `__host__ __device__` like tetris_plan.h: tetris_hip.hip / tetris_hip_multi.hip wrap these in gfx950 kernels,
-// tests/cpu_harness/harness_policy.cpp in plain host loops.
+// tests/cpu_harness/harness_lib_agent.h in plain host loops.
 //
 // Two mappings over the same bodies (DESIGN.md §4 has the measurements):
 //   spread  one lane per (game, candidate), a wave = 64 consecutive games of one candidate (policy_eval_lane: 12 cached loads,

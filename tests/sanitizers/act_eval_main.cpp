@@ -1,22 +1,12 @@
 // TEST INFRASTRUCTURE — NOT PRODUCT CODE.
 //
-// A stand-alone program over the CPU harness (tests/cpu_harness/harness_act.cpp, included whole) for AddressSanitizer and
-// UBSan: tetris_select_eval_dev, tetris_step_eval_dev and tetris_step_eval_observe_dev on 65 games (a block of 64 and one more),
+// A stand-alone program over the CPU harness for AddressSanitizer and UBSan (standalone.h; built and run by the line given there):
+// tetris_select_eval_dev, tetris_step_eval_dev and tetris_step_eval_observe_dev on 65 games (a block of 64 and one more),
 // every mode, float32 and binary16 evaluations, K = 7 and 1, one and two players, with buffers of exactly the documented
 // sizes on the heap so that a read or write past an end is reported.
-//
-//   g++ -O1 -g -std=c++17 -ffp-contract=off -fopenmp -fsanitize=address,undefined -fno-omit-frame-pointer \
-//       -o act_eval_asan tests/sanitizers/act_eval_main.cpp && ./act_eval_asan
-#include "../cpu_harness/harness_act.cpp"
+#include "standalone.h"
 
-#include <cstdio>
 #include <memory>
-
-static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
-
-// one call with one bad argument per shared rule of this area (drl-tetris_amd/csrc/tetris_host.h): refused, nothing touched
-#define REFUSED(call) \
-    do { if ((call) != TETRIS_E_ARG) { fprintf(stderr, "%s: not refused\n", #call); return 1; } } while (0)
 
 static int refusals(tetris_batch* b, tetris_act_eval e, uint8_t* done, uint8_t* visual, uint8_t* vector, uint8_t* piece) {
     tetris_act_eval bad = e;

@@ -1,22 +1,11 @@
 // TEST INFRASTRUCTURE — NOT PRODUCT CODE.
 //
-// A stand-alone program over the CPU harness (tests/cpu_harness/harness_batch.cpp, included whole) for AddressSanitizer and
-// UBSan: tetris_traj_observe_dev, tetris_traj_select_dev and tetris_traj_batch_dev on 65 games (a block of 64 and one more), one
+// A stand-alone program over the CPU harness for AddressSanitizer and UBSan (standalone.h; built and run by the line given there):
+// tetris_traj_observe_dev, tetris_traj_select_dev and tetris_traj_batch_dev on 65 games (a block of 64 and one more), one
 // and two players, heights 8 and 7, every row of a window of 5 rows, selections with and without the augmented copy into lists
 // larger than, equal to and smaller than the result, and minibatches of 1, 64 and 131 entries with mirrored, repeated, -1 and
 // out-of-range ones — with buffers of exactly the documented sizes on the heap so that a read or write past an end is reported.
-//
-//   g++ -O1 -g -std=c++17 -ffp-contract=off -fopenmp -fsanitize=address,undefined -fno-omit-frame-pointer \
-//       -o batch_asan tests/sanitizers/batch_main.cpp && ./batch_asan
-#include "../cpu_harness/harness_batch.cpp"
-
-#include <cstdio>
-
-static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
-
-// one call with one bad argument per shared rule of this area (drl-tetris_amd/csrc/tetris_host.h): refused, nothing touched
-#define REFUSED(call) \
-    do { if ((call) != TETRIS_E_ARG) { fprintf(stderr, "%s: not refused\n", #call); return 1; } } while (0)
+#include "standalone.h"
 
 static int run(int P, int H) {
     const int N = 65, T = 5;

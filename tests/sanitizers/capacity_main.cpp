@@ -1,8 +1,8 @@
 // TEST INFRASTRUCTURE — NOT PRODUCT CODE.
 //
-// A stand-alone program over the CPU harness (tests/cpu_harness/harness_policy.cpp, which includes harness.cpp and the planning
-// entry points whole) for AddressSanitizer and UBSan: both capacity limits of include/tetris_hip.h where the limit is the END OF
-// THE ALLOCATION.  A fresh process has RNG tables of exactly two chunks, a vector of 2 * 65536 * 624 bytes; with
+// A stand-alone program over the CPU harness for AddressSanitizer and UBSan (standalone.h; built and run by the line given there):
+// both capacity limits of include/tetris_hip.h where the limit is the END OF THE ALLOCATION.
+// A fresh process has RNG tables of exactly two chunks, a vector of 2 * 65536 * 624 bytes; with
 // tetris_debug_table_limit(b, 2) the draw limit is the last byte of it, so a table read that the clamps of table_byte /
 // table_group_raw (tetris_engine.h) let past the limit is a heap-buffer-overflow here.  (On the GPU the tests keep the limit below
 // the allocation: tests/test_capacity.py.)  65 games (a block of 64 and one more) of one and of two players, O pieces laid side by
@@ -10,25 +10,10 @@
 // all lists before it, the policy step, and the random rollout un-fused and fused — each from the same boards, each must end games
 // with TETRIS_ERR_STREAM.  Then the queue: two players at 10 ms, 8 packets pending on player 1, 16 random steps: a ninth packet must
 // be refused (TETRIS_ERR_FIFO) without a write past qcount / qdelay.
-//
-//   g++ -O1 -g -std=c++17 -ffp-contract=off -fopenmp -fsanitize=address,undefined -fno-omit-frame-pointer \
-//       -o capacity_asan tests/sanitizers/capacity_main.cpp && \
-//   ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 ./capacity_asan
-// (detect_leaks=0 as in run.sh: the harness keeps its RNG tables for the life of the process.)
-#include "../cpu_harness/harness_policy.cpp"
-
-#include <cstdio>
-
-static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
+#include "standalone.h"
 
 static const int N = 65, H = 20, STEPS = 16, L = 64, K = 48;
 static const uint8_t O_ONLY[7] = {6, 6, 6, 6, 6, 6, 6};
-
-#define CHECK(call)                                                                              \
-    do {                                                                                         \
-        int rc_ = (call);                                                                        \
-        if (rc_) { fprintf(stderr, "%s: rc %d: %s\n", #call, rc_, tetris_last_error()); return 1; } \
-    } while (0)
 
 static int expect_bits(tetris_batch* b, uint32_t want, const char* what, int ended, uint32_t seen = 0) {
     uint32_t bits = 0;
@@ -140,10 +125,6 @@ static int queue() {
     tetris_destroy(b);
     return 0;
 }
-
-// one call with one bad argument per shared rule of this area (drl-tetris_amd/csrc/tetris_host.h): refused, nothing touched
-#define REFUSED(call) \
-    do { if ((call) != TETRIS_E_ARG) { fprintf(stderr, "%s: not refused\n", #call); return 1; } } while (0)
 
 static int refusals() {
     const int P = 2;

@@ -1,25 +1,13 @@
 // TEST INFRASTRUCTURE — NOT PRODUCT CODE.
 //
-// A stand-alone program over the CPU harness (tests/cpu_harness/harness_replay.cpp, included whole) for AddressSanitizer and
-// UBSan: tetris_replay_add_dev, tetris_replay_sample_dev, tetris_replay_update_prios_dev and tetris_replay_gather_dev on 65
+// A stand-alone program over the CPU harness for AddressSanitizer and UBSan (standalone.h; built and run by the line given there):
+// tetris_replay_add_dev, tetris_replay_sample_dev, tetris_replay_update_prios_dev and tetris_replay_gather_dev on 65
 // games, one and two players, heights 8 and 7 — adds that fit, wrap and overflow the ring, with and without the mirrored copies
 // and the optional arrays; samples of 0, 1, n and n + 7 entries from rings of 1, tile - 1, tile + 1 and 2 tile + 5 priorities of
 // random bits (NaNs among them) with cursors that say 0, a part and all of it and one that says nonsense; updates and gathers
 // with -1, max_size and out-of-range indices, every number of steps — with buffers of exactly the documented sizes on the heap,
 // so that a read or write past an end is reported.
-//
-//   g++ -O1 -g -std=c++17 -ffp-contract=off -fopenmp -fsanitize=address,undefined -fno-omit-frame-pointer \
-//       -o replay_asan tests/sanitizers/replay_main.cpp && ./replay_asan
-#include "../cpu_harness/harness_replay.cpp"
-
-#include <cstdio>
-
-static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
-
-#define REFUSED(call) \
-    do { if ((call) != TETRIS_E_ARG) { fprintf(stderr, "%s: not refused\n", #call); return 1; } } while (0)
-#define OK(call) \
-    do { if ((call) != TETRIS_OK) { fprintf(stderr, "%s: %s\n", #call, tetris_last_error()); return 1; } } while (0)
+#include "standalone.h"
 
 struct Ring {
     std::vector<uint32_t> obs;

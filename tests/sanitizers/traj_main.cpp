@@ -1,21 +1,10 @@
 // TEST INFRASTRUCTURE — NOT PRODUCT CODE.
 //
-// A stand-alone program over the CPU harness (tests/cpu_harness/harness_traj.cpp, included whole) for AddressSanitizer and
-// UBSan: tetris_step_eval_dev, tetris_traj_record_dev and tetris_traj_advantages_dev on 65 games (a block of 64 and one more), one
+// A stand-alone program over the CPU harness for AddressSanitizer and UBSan (standalone.h; built and run by the line given there):
+// tetris_step_eval_dev, tetris_traj_record_dev and tetris_traj_advantages_dev on 65 games (a block of 64 and one more), one
 // and two players, every row of a window of 19 rows and advantages over 1, 16, 17 and 19 of them, with buffers of exactly the
 // documented sizes on the heap so that a read or write past an end is reported.
-//
-//   g++ -O1 -g -std=c++17 -ffp-contract=off -fopenmp -fsanitize=address,undefined -fno-omit-frame-pointer \
-//       -o traj_asan tests/sanitizers/traj_main.cpp && ./traj_asan
-#include "../cpu_harness/harness_traj.cpp"
-
-#include <cstdio>
-
-static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
-
-// one call with one bad argument per shared rule of this area (drl-tetris_amd/csrc/tetris_host.h): refused, nothing touched
-#define REFUSED(call) \
-    do { if ((call) != TETRIS_E_ARG) { fprintf(stderr, "%s: not refused\n", #call); return 1; } } while (0)
+#include "standalone.h"
 
 static int run(int P) {
     const int N = 65, H = 8, T = 19;

@@ -1,29 +1,16 @@
 // TEST INFRASTRUCTURE — NOT PRODUCT CODE.
 //
-// A stand-alone program over the CPU harness (tests/cpu_harness/harness_policy.cpp, which includes harness.cpp and the planning
-// entry points whole) for AddressSanitizer and UBSan: the built-in rollouts with the per-game counter words at 2^32, step numbers
-// across 2^32 and game ids that wrap inside the batch (tests/test_rollout_wrap.py compares the results with the oracle; here the
+// A stand-alone program over the CPU harness for AddressSanitizer and UBSan (standalone.h; built and run by the line given there):
+// the built-in rollouts with the per-game counter words at 2^32, step numbers across 2^32
+// and game ids that wrap inside the batch (tests/test_rollout_wrap.py compares the results with the oracle; here the
 // sanitizers watch the same paths).  70 games of one, two and three players: the words G_EPISODE, G_STEPS, G_LINES, G_SENT are
 // restored to 0xFFFFFFFF - (g mod 3), the game offset is 2^32 - 40, first_step 2^32 - 7; 40 / 60 / 120 steps of tetris_rollout_random
 // at 3 000 ms (games end and are re-seeded) un-fused and fused, then 8 of tetris_rollout_policy.  counters[0] must be exactly the
 // steps of the call, whatever the words held.
-//
-//   g++ -O1 -g -std=c++17 -ffp-contract=off -fopenmp -fsanitize=address,undefined -fno-omit-frame-pointer \
-//       -o wrap_asan tests/sanitizers/wrap_main.cpp && \
-//   ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 ./wrap_asan
-// (detect_leaks=0 as in run.sh: the harness keeps its RNG tables for the life of the process.)
-#include "../cpu_harness/harness_policy.cpp"
-
-#include <cstdio>
+#include "standalone.h"
 
 static const int N = 70, H = 20;
 static const uint8_t ALL[7] = {0, 1, 2, 3, 4, 5, 6};
-
-#define CHECK(call)                                                                              \
-    do {                                                                                         \
-        int rc_ = (call);                                                                        \
-        if (rc_) { fprintf(stderr, "%s: rc %d: %s\n", #call, rc_, tetris_last_error()); return 1; } \
-    } while (0)
 
 static int expect_steps(const uint64_t c[4], uint64_t steps, const char* what) {
     if (c[0] != steps || c[1] >> 32 || c[2] >> 32 || c[3] >> 32) {
