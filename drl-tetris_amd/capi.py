@@ -96,6 +96,42 @@ class Replay(C.Structure):
 
 MIRROR_BIT = 1 << 31          # bit 31 of an index of tetris_traj_batch_dev: the mirrored sample
 
+LOSS_STATS = 16               # TETRIS_LOSS_STATS
+LOSS_F16, LOSS_VALUE_F16, LOSS_GRAD_F16 = 1, 2, 4          # TETRIS_LOSS_*
+# the slots of d_stats (include/tetris_hip.h: loss heads)
+PPO_STATS = ("n", "loss", "value_loss", "policy_loss", "entropy_loss", "entropy", "entropy_sq", "entropy_bonus", "values", "values_sq",
+             "target_values", "target_values_sq", "clip_saturation", "ratio")
+DQN_STATS = ("n", "n_weighted", "loss", "q_val", "q_val_sq", "q_target", "q_target_sq", "new_prio")
+PPO_TERMS = ("probability", "ratio", "policy_term", "entropy", "entropy_bonus", "value")
+
+
+class PpoLoss(C.Structure):
+    """mirrors `struct tetris_ppo_loss` (include/tetris_hip.h)"""
+    _fields_ = [("d_pi", C.c_void_p), ("d_v", C.c_void_p), ("d_action", C.c_void_p), ("d_prob_old", C.c_void_p), ("d_adv", C.c_void_p),
+                ("d_target", C.c_void_p), ("d_valid", C.c_void_p), ("M", C.c_int), ("n_pieces", C.c_int), ("n_values", C.c_int),
+                ("flags", C.c_int), ("clip", C.c_float), ("value_loss", C.c_float), ("policy_loss", C.c_float), ("entropy_loss", C.c_float),
+                ("entropy_floor_loss", C.c_float), ("rescaled_entropy", C.c_float), ("entropy_floor", C.c_float), ("max_entropy", C.c_float),
+                ("grad_scale", C.c_float), ("reserved", C.c_float), ("d_grad_pi", C.c_void_p), ("d_grad_v", C.c_void_p),
+                ("d_terms", C.c_void_p), ("d_stats", C.c_void_p)]
+
+
+class DqnLoss(C.Structure):
+    """mirrors `struct tetris_dqn_loss` (include/tetris_hip.h)"""
+    _fields_ = [("d_Q", C.c_void_p), ("d_action", C.c_void_p), ("d_target", C.c_void_p), ("d_weight", C.c_void_p), ("d_valid", C.c_void_p),
+                ("M", C.c_int), ("n_pieces", C.c_int), ("flags", C.c_int), ("optimistic_prios", C.c_float), ("grad_scale", C.c_float),
+                ("reserved", C.c_float), ("d_grad_Q", C.c_void_p), ("d_new_prio", C.c_void_p), ("d_q", C.c_void_p), ("d_stats", C.c_void_p)]
+
+
+def ppo_entropy_constants(ppo_epsilon):
+    """The two constants of the PPO head's entropy terms, in float64 (agents/networks/ppo_nets.py:175-180): -> (entropy_floor,
+    max_entropy) with entropy_floor = -eps log(eps / 39) - (1 - eps) log(1 - eps) and max_entropy = tools.utils.entropy of the
+    uniform distribution over the 40 actions, -sum (1/40) log(1/40 + 1e-8).  For eps <= 0 or eps >= 1, where the reference's
+    expression is NaN, the floor is 0: the floor term is switched off."""
+    eps = float(ppo_epsilon)
+    floor = -eps * np.log(eps / 39.0) - (1.0 - eps) * np.log(1.0 - eps) if 0.0 < eps < 1.0 else 0.0
+    uniform = np.full(40, 1.0 / 40.0)
+    return float(floor), float(-np.sum(uniform * np.log(uniform + 1e-8)))
+
 
 def pareto_table(theta):
     """The RANK table of the reference's pareto (tools/utils.py:88-91): (k + 1) ** -theta for rank k + 1, float32 [40]."""
@@ -206,6 +242,8 @@ _SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_replay_update_prios_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "tetris_replay_gather_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "tetris_ppo_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_dqn_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_observe_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_observe_packed_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_create_split": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -684,6 +722,49 @@ class TetrisBatch:
         ring position index[j] + s; mirrored where the entry's flag says so)."""
         self._check(self.lib.tetris_replay_gather_dev(self._h, C.byref(rp) if rp is not None else None, index, int(m), int(steps),
                                                       C.byref(out) if out is not None else None))
+
+    # -- loss heads (include/tetris_hip.h: tetris_ppo_loss_dev, tetris_dqn_loss_dev)
+    def ppo_loss(self, pi, v, action, prob_old, adv, target, grad_pi, grad_v, stats, m, n_pieces=7, n_values=1, valid=None, terms=None,
+                 f16=False, value_f16=False, grad_f16=False, clipping_parameter=0.15, value_loss=1.0, policy_loss=1.0, entropy_loss=0.0,
+                 ppo_epsilon=None, entropy_floor_loss=0.0, rescaled_entropy=0.0, entropy_floor=None, grad_scale=1.0, flags=0):
+        """The argument struct of ppo_loss_dev over raw DEVICE addresses (int / c_void_p) or None: pi, grad_pi [m][4][10][n_pieces]
+        and v, grad_v [m][n_values] float32 (f16 / value_f16 / grad_f16: binary16), action uint8 [m][3], prob_old / adv / target
+        float32 [m], valid uint8 [m], terms float32 [6][m], stats float32 [16].  The parameter names are model.train's; the
+        floor comes from ppo_epsilon (ppo_entropy_constants) unless entropy_floor gives it."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        l = PpoLoss()
+        l.d_pi, l.d_v, l.d_action, l.d_prob_old, l.d_adv, l.d_target = val(pi), val(v), val(action), val(prob_old), val(adv), val(target)
+        l.d_valid, l.M, l.n_pieces, l.n_values = val(valid), int(m), int(n_pieces), int(n_values)
+        l.flags = (LOSS_F16 if f16 else 0) | (LOSS_VALUE_F16 if value_f16 else 0) | (LOSS_GRAD_F16 if grad_f16 else 0) | int(flags)
+        l.clip, l.value_loss, l.policy_loss, l.entropy_loss = float(clipping_parameter), float(value_loss), float(policy_loss), float(entropy_loss)
+        floor, hmax = ppo_entropy_constants(0.0 if ppo_epsilon is None else ppo_epsilon)
+        l.entropy_floor_loss, l.rescaled_entropy = float(entropy_floor_loss), float(rescaled_entropy)
+        l.entropy_floor, l.max_entropy = float(floor if entropy_floor is None else entropy_floor), hmax
+        l.grad_scale, l.reserved = float(grad_scale), 0.0
+        l.d_grad_pi, l.d_grad_v, l.d_terms, l.d_stats = val(grad_pi), val(grad_v), val(terms), val(stats)
+        return l
+
+    def ppo_loss_dev(self, l):
+        """The PPO loss of a minibatch, its statistics and its gradient with respect to pi and v (l = ppo_loss(...))."""
+        self._check(self.lib.tetris_ppo_loss_dev(self._h, C.byref(l) if l is not None else None))
+
+    def dqn_loss(self, Q, action, target, grad_Q, new_prio, stats, m, n_pieces=7, weight=None, valid=None, q=None, f16=False, grad_f16=False,
+                 optimistic_prios=0.0, grad_scale=1.0, flags=0):
+        """The argument struct of dqn_loss_dev over raw DEVICE addresses or None: Q, grad_Q [m][4][10][n_pieces] float32 (f16 /
+        grad_f16: binary16), action uint8 [m][3], target / weight / new_prio / q float32 [m], valid uint8 [m], stats float32 [16]."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        l = DqnLoss()
+        l.d_Q, l.d_action, l.d_target, l.d_weight, l.d_valid = val(Q), val(action), val(target), val(weight), val(valid)
+        l.M, l.n_pieces = int(m), int(n_pieces)
+        l.flags = (LOSS_F16 if f16 else 0) | (LOSS_GRAD_F16 if grad_f16 else 0) | int(flags)
+        l.optimistic_prios, l.grad_scale, l.reserved = float(optimistic_prios), float(grad_scale), 0.0
+        l.d_grad_Q, l.d_new_prio, l.d_q, l.d_stats = val(grad_Q), val(new_prio), val(q), val(stats)
+        return l
+
+    def dqn_loss_dev(self, l):
+        """The DQN loss of a minibatch, its statistics, its gradient with respect to Q and the samples' new priorities
+        (l = dqn_loss(...))."""
+        self._check(self.lib.tetris_dqn_loss_dev(self._h, C.byref(l) if l is not None else None))
 
     def rollout_game_totals_dev(self, totals):
         """The per-game words rollout_totals sums: totals uint32 [4][N] = env-steps, episodes, lines cleared, garbage lines sent."""

@@ -1,5 +1,5 @@
 // Kernels of libtetris_hip.so, part 5: the acting, window and replay half of tetris_lib_agent.h: acting on a network's evaluation,
-// trajectory windows, a window's states, sample sets and minibatches, the planning agent's windows, experience replay and its radix
+// the trainers' loss heads, trajectory windows, a window's states, sample sets and minibatches, the planning agent's windows, experience replay and its radix
 // sort.  Needs
 // tetris_dev_observe.h (obs_row_words, obs_row_halves).  Every kernel here has one named block size: its launch bounds and its
 // launch in tetris_lib_agent.h both use it.
@@ -30,10 +30,10 @@ __device__ __forceinline__ float act_vector_element(const act_u32x4& q, int j) {
 // and piece e mod K; 40 K is a multiple of the 4 or 8 elements of a vector, so a vector lies inside one game and (K = 7) holds
 // at most two elements of the game's piece: only those are converted and stored.
 template <int NT, int K, bool F16>
-__device__ __forceinline__ void act_gather(const ActArgs& aa, int g0, int ng, ActShared& sh) {
+__device__ __forceinline__ void act_gather(const void* eval, int g0, int ng, ActShared& sh) {
     constexpr int EPV = F16 ? 8 : 4, PER_GAME = ACT_CANDIDATES * K;
     static_assert(PER_GAME % EPV == 0, "a 16-byte vector must not cross two games");
-    const act_u32x4* src = (const act_u32x4*)((const char*)aa.action_eval + (size_t)g0 * PER_GAME * (F16 ? 2 : 4));
+    const act_u32x4* src = (const act_u32x4*)((const char*)eval + (size_t)g0 * PER_GAME * (F16 ? 2 : 4));
     const int nvec = ng * (PER_GAME / EPV);
 #pragma unroll 4
     for (int v = threadIdx.x; v < nvec; v += NT) {
@@ -51,6 +51,16 @@ __device__ __forceinline__ void act_gather(const ActArgs& aa, int g0, int ng, Ac
     }
 }
 
+// the gather for K = 7 or 1 and either element type; sh.piece holds the games' pieces
+template <int NT>
+__device__ __forceinline__ void act_gather_any(const void* eval, int K, bool f16, int g0, int ng, ActShared& sh) {
+    if (K == 7) {
+        if (f16) act_gather<NT, 7, true>(eval, g0, ng, sh); else act_gather<NT, 7, false>(eval, g0, ng, sh);
+    } else {
+        if (f16) act_gather<NT, 1, true>(eval, g0, ng, sh); else act_gather<NT, 1, false>(eval, g0, ng, sh);
+    }
+}
+
 // games g0 .. g0 + ng - 1 by a workgroup of NT threads: every thread passes the barriers; thread t < ng chooses for game g0 + t
 // and writes its outputs
 template <int NT>
@@ -60,11 +70,7 @@ __device__ __forceinline__ void act_block_choose(const ActArgs& aa, int g0, int 
     if (t < ACT_BLOCK) sh.piece[t] = t < ng ? act_piece_of(geo_of(aa.a), (size_t)(g0 + t), safe_player(aa.player, g0 + t, aa.a.n_players), aa.K) : 0;
     if (t < ACT_CANDIDATES) sh.table[t] = aa.table[t];
     __syncthreads();
-    if (aa.K == 7) {
-        if (aa.eval_f16) act_gather<NT, 7, true>(aa, g0, ng, sh); else act_gather<NT, 7, false>(aa, g0, ng, sh);
-    } else {
-        if (aa.eval_f16) act_gather<NT, 1, true>(aa, g0, ng, sh); else act_gather<NT, 1, false>(aa, g0, ng, sh);
-    }
+    act_gather_any<NT>(aa.action_eval, aa.K, aa.eval_f16 != 0, g0, ng, sh);
     __syncthreads();
     const bool rank = aa.mode == ACT_RANK;
     if (rank) {                                       // lane = (game, candidate): its 39 rivals from LDS, conflict-free
@@ -85,6 +91,135 @@ __global__ __launch_bounds__(ACT_THREADS) void k_act_select(ActArgs aa) {
     __shared__ ActShared sh;
     const int g0 = blockIdx.x * ACT_BLOCK, ng = imin(ACT_BLOCK, aa.a.n - g0);
     act_block_choose<ACT_THREADS>(aa, g0, ng, sh);
+}
+
+// ---- loss heads (tetris_loss.h).  The same access pattern, there and back: a workgroup takes LOSS_BLOCK = ACT_BLOCK consecutive
+// samples, whose pieces come from the action array; act_gather streams their contiguous 64 x 40 K elements of pi / Q into the
+// first LDS plane; one lane per sample (wave 0) computes the head from its column and leaves its 40 gradient values in the second
+// plane; then the whole workgroup writes the block's gradient region as 16-byte vectors — zeros but the pieces' elements, which
+// come from LDS — in memory order, so no lane issues 40 strided stores.  The lanes' terms of the statistics are reduced across
+// wave 0 by shuffles in the order of loss_tree into the workgroup's partial row; k_loss_reduce sums the rows.  D / Dnz come
+// from k_loss_count through a device word when a valid mask or weights are given.  No workgroup waits for another.
+struct LossShared {
+    ActShared act;                  // x: the values, m: the gradients, piece: the samples' pieces
+    float gv[LOSS_BLOCK];           // PPO: the value gradients
+};
+
+// 0 | val into element j of a zeroed 16-byte vector (j is not a constant: selects, no indexed registers)
+template <bool F16>
+__device__ __forceinline__ void act_vector_put(act_u32x4& q, int j, float val) {
+    const int w = F16 ? j >> 1 : j;
+    const uint32_t bits = F16 ? (uint32_t)plan_f32_to_f16(val) << ((j & 1) * 16) : f2u(val);
+    q.x |= w == 0 ? bits : 0u; q.y |= w == 1 ? bits : 0u; q.z |= w == 2 ? bits : 0u; q.w |= w == 3 ? bits : 0u;
+}
+
+// The opposite direction of act_gather: the block's ng x 40 K gradient elements, 16 bytes per lane and store.  The elements of
+// a sample's piece are sh.m[candidate][sample], all others zero.
+template <int NT, int K, bool F16>
+__device__ __forceinline__ void loss_scatter(void* grad, int g0, int ng, const ActShared& sh) {
+    constexpr int EPV = F16 ? 8 : 4, PER = ACT_CANDIDATES * K;
+    static_assert(PER % EPV == 0, "a 16-byte vector must not cross two samples");
+    act_u32x4* dst = (act_u32x4*)((char*)grad + (size_t)g0 * PER * (F16 ? 2 : 4));
+    const int nvec = ng * (PER / EPV);
+#pragma unroll 4
+    for (int v = threadIdx.x; v < nvec; v += NT) {
+        const int e0 = v * EPV, s = e0 / PER, rem = e0 - s * PER;
+        act_u32x4 q = {0u, 0u, 0u, 0u};
+        if (K == 1) {
+#pragma unroll
+            for (int j = 0; j < EPV; j++) act_vector_put<F16>(q, j, sh.m[(rem + j) * ACT_LDS_STRIDE + s]);
+        } else {
+            int j = sh.piece[s] - rem % K;                    // the first element of the vector that belongs to the piece
+            j = j < 0 ? j + K : j;
+            if (j < EPV) act_vector_put<F16>(q, j, sh.m[((rem + j) / K) * ACT_LDS_STRIDE + s]);
+            if (EPV > K && j + K < EPV) act_vector_put<F16>(q, j + K, sh.m[((rem + j + K) / K) * ACT_LDS_STRIDE + s]);
+        }
+        __builtin_nontemporal_store(q, dst + v);
+    }
+}
+
+constexpr int LOSS_THREADS = 256;
+__global__ __launch_bounds__(LOSS_THREADS) void k_loss_head(LossArgs la) {
+    __shared__ LossShared sh;
+    static_assert(LOSS_BLOCK == 64, "wave 0 holds a lane per sample");
+    const int t = threadIdx.x, g0 = blockIdx.x * LOSS_BLOCK, ng = imin(LOSS_BLOCK, la.M - g0);
+    int k = 0, c = 0;
+    if (t < LOSS_BLOCK) {
+        if (t < ng) loss_action(la, (size_t)(g0 + t), k, c);
+        sh.act.piece[t] = k;
+    }
+    __syncthreads();
+    act_gather_any<LOSS_THREADS>(la.x, la.K, la.in_f16 != 0, g0, ng, sh.act);
+    __syncthreads();
+    if (t < LOSS_BLOCK) {                                    // wave 0, every lane: lanes past ng add zeros to the sums
+        const float D = la.count ? (float)la.count[0] : (float)la.M, Dnz = la.count ? (float)la.count[1] : (float)la.M;
+        float sum[LOSS_SUMS], gv;
+        loss_sample(la, t < ng ? (long long)(g0 + t) : (long long)la.M, k, c, D, Dnz, sh.act.x + t, ACT_LDS_STRIDE, sh.act.m + t, ACT_LDS_STRIDE, sum, gv);
+        sh.gv[t] = gv;
+#pragma unroll
+        for (int i = 0; i < LOSS_SUMS; i++) {
+            float s = sum[i];
+#pragma unroll
+            for (int off = LOSS_BLOCK / 2; off >= 1; off >>= 1) s += __shfl_down(s, off, LOSS_BLOCK);
+            if (t == 0) la.partial[(size_t)blockIdx.x * LOSS_SUMS + i] = s;
+        }
+    }
+    __syncthreads();
+    if (la.K == 7) {
+        if (la.grad_f16) loss_scatter<LOSS_THREADS, 7, true>(la.grad_x, g0, ng, sh.act); else loss_scatter<LOSS_THREADS, 7, false>(la.grad_x, g0, ng, sh.act);
+    } else {
+        if (la.grad_f16) loss_scatter<LOSS_THREADS, 1, true>(la.grad_x, g0, ng, sh.act); else loss_scatter<LOSS_THREADS, 1, false>(la.grad_x, g0, ng, sh.act);
+    }
+    if (la.head == LOSS_PPO)                                 // the block's ng x V value gradients, in memory order
+        for (int e = t; e < ng * la.V; e += LOSS_THREADS) {
+            const int s = e / la.V, kk = e - s * la.V;
+            loss_store(la.grad_v, (size_t)g0 * la.V + e, kk == imin(sh.act.piece[s], la.V - 1) ? sh.gv[s] : 0.0f, la.grad_f16);
+        }
+}
+
+// D and Dnz of the call, by one workgroup: a lane per sample and trip, the lanes' counts through LDS (integer adds)
+constexpr int LOSS_COUNT_THREADS = 1024;
+__global__ __launch_bounds__(LOSS_COUNT_THREADS) void k_loss_count(LossArgs la, uint32_t* count) {
+    __shared__ uint32_t total[2];
+    if (threadIdx.x < 2) total[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t d = 0u, dnz = 0u;
+#pragma unroll 4
+    for (int m = threadIdx.x; m < la.M; m += LOSS_COUNT_THREADS) loss_count_sample(la, (size_t)m, d, dnz);
+    atomicAdd(&total[0], d);
+    atomicAdd(&total[1], dnz);
+    __syncthreads();
+    if (threadIdx.x < 2) count[threadIdx.x] = total[threadIdx.x];
+}
+
+// the partial rows of the head's workgroups -> stats, by one workgroup, in the order of loss_reduce_serial
+__global__ __launch_bounds__(LOSS_REDUCE_LANES) void k_loss_reduce(LossArgs la, int blocks) {
+    __shared__ float slot[LOSS_SUMS][LOSS_REDUCE_LANES];
+    const int t = threadIdx.x;
+    float s[LOSS_SUMS];
+#pragma unroll
+    for (int i = 0; i < LOSS_SUMS; i++) s[i] = 0.0f;
+    for (int b = t; b < blocks; b += LOSS_REDUCE_LANES) {
+#pragma unroll
+        for (int i = 0; i < LOSS_SUMS; i++) s[i] += la.partial[(size_t)b * LOSS_SUMS + i];
+    }
+#pragma unroll
+    for (int i = 0; i < LOSS_SUMS; i++) slot[i][t] = s[i];
+    __syncthreads();
+    for (int off = LOSS_REDUCE_LANES / 2; off >= 1; off >>= 1) {
+        if (t < off) {
+#pragma unroll
+            for (int i = 0; i < LOSS_SUMS; i++) slot[i][t] += slot[i][t + off];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        float total[LOSS_SUMS];
+#pragma unroll
+        for (int i = 0; i < LOSS_SUMS; i++) total[i] = slot[i][0];
+        const float D = la.count ? (float)la.count[0] : (float)la.M, Dnz = la.count ? (float)la.count[1] : (float)la.M;
+        loss_finish(la, total, D, Dnz, la.stats);
+    }
 }
 
 // ---- trajectory windows (tetris_traj.h).  Recording is one lane per game.

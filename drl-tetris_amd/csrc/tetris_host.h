@@ -11,6 +11,7 @@
 
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "tetris_kernels.h"
 #include "tetris_plan.h"
@@ -21,6 +22,7 @@
 #include "tetris_batch.h"
 #include "tetris_replay.h"
 #include "tetris_plan_traj.h"
+#include "tetris_loss.h"
 
 namespace te {
 
@@ -630,6 +632,76 @@ static inline int replay_gather_args(const HostShape& s, const tetris_replay* rp
     ba.prob_out = out->d_prob; ba.adv_out = out->d_adv; ba.target_out = out->d_target; ba.reward_out = out->d_reward;
     ba.done_out = out->d_done; ba.valid = out->d_valid;
     ba.steps = steps; ba.limit = (uint32_t)r.max_size; ba.flags = r.flags;
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- loss heads (tetris_loss.h)
+// the rules both heads share, then the kernel arguments (all but count and partial, the caller's scratch)
+static inline int loss_common_check(int M, int K, int flags, int known_flags, const void* x, const void* grad_x) {
+    if (M < 0) return fail(TETRIS_E_ARG, "M < 0");
+    if (K != 1 && K != 7) return fail(TETRIS_E_ARG, "n_pieces must be 1 or 7");
+    if (flags & ~known_flags) return fail(TETRIS_E_ARG, "unknown flag");
+    if ((((uintptr_t)x) | ((uintptr_t)grad_x)) & 15u) return fail(TETRIS_E_ARG, "the evaluation and its gradient must be 16-byte aligned");
+    return TETRIS_OK;
+}
+static inline int ppo_loss_args(const tetris_ppo_loss* l, LossArgs& la) {
+    if (!l) return fail(TETRIS_E_ARG, "the argument struct is NULL");
+    if (!l->d_pi || !l->d_v || !l->d_action || !l->d_prob_old || !l->d_adv || !l->d_target)
+        return fail(TETRIS_E_ARG, "pi/v/action/prob_old/adv/target are NULL");
+    if (!l->d_grad_pi || !l->d_grad_v || !l->d_stats) return fail(TETRIS_E_ARG, "grad_pi/grad_v/stats are NULL");
+    int rc = loss_common_check(l->M, l->n_pieces, l->flags, TETRIS_LOSS_F16 | TETRIS_LOSS_VALUE_F16 | TETRIS_LOSS_GRAD_F16, l->d_pi, l->d_grad_pi);
+    if (rc) return rc;
+    if (l->n_values != 1 && l->n_values != l->n_pieces) return fail(TETRIS_E_ARG, "n_values must be 1 or n_pieces");
+    if (!(l->clip >= 0.0f)) return fail(TETRIS_E_ARG, "clip must be >= 0");
+    memset(&la, 0, sizeof la);
+    la.head = LOSS_PPO;
+    la.M = l->M; la.K = l->n_pieces; la.V = l->n_values;
+    la.in_f16 = (l->flags & TETRIS_LOSS_F16) ? 1 : 0; la.v_f16 = (l->flags & TETRIS_LOSS_VALUE_F16) ? 1 : 0;
+    la.grad_f16 = (l->flags & TETRIS_LOSS_GRAD_F16) ? 1 : 0;
+    la.x = l->d_pi; la.v = l->d_v; la.action = l->d_action; la.old = l->d_prob_old; la.adv = l->d_adv; la.target = l->d_target;
+    la.valid = l->d_valid;
+    la.clip = l->clip; la.c1 = l->value_loss; la.c2 = l->policy_loss; la.c3 = l->entropy_loss;
+    la.cf = l->entropy_floor_loss; la.cr = l->rescaled_entropy; la.floor = l->entropy_floor; la.hmax = l->max_entropy;
+    la.grad_scale = l->grad_scale;
+    la.grad_x = l->d_grad_pi; la.grad_v = l->d_grad_v; la.terms = l->d_terms; la.stats = l->d_stats;
+    return TETRIS_OK;
+}
+static inline int dqn_loss_args(const tetris_dqn_loss* l, LossArgs& la) {
+    if (!l) return fail(TETRIS_E_ARG, "the argument struct is NULL");
+    if (!l->d_Q || !l->d_action || !l->d_target) return fail(TETRIS_E_ARG, "Q/action/target are NULL");
+    if (!l->d_grad_Q || !l->d_new_prio || !l->d_stats) return fail(TETRIS_E_ARG, "grad_Q/new_prio/stats are NULL");
+    int rc = loss_common_check(l->M, l->n_pieces, l->flags, TETRIS_LOSS_F16 | TETRIS_LOSS_GRAD_F16, l->d_Q, l->d_grad_Q);
+    if (rc) return rc;
+    memset(&la, 0, sizeof la);
+    la.head = LOSS_DQN;
+    la.M = l->M; la.K = l->n_pieces; la.V = 1;
+    la.in_f16 = (l->flags & TETRIS_LOSS_F16) ? 1 : 0; la.grad_f16 = (l->flags & TETRIS_LOSS_GRAD_F16) ? 1 : 0;
+    la.x = l->d_Q; la.action = l->d_action; la.target = l->d_target; la.weight = l->d_weight; la.valid = l->d_valid;
+    la.optimistic = l->optimistic_prios; la.grad_scale = l->grad_scale;
+    la.grad_x = l->d_grad_Q; la.new_prio = l->d_new_prio; la.q = l->d_q; la.stats = l->d_stats;
+    return TETRIS_OK;
+}
+// whether the call counts D / Dnz on the device (otherwise both are M), and the words of scratch it needs: two counts,
+// padded to 16 bytes, then the workgroups' partial rows
+static inline bool loss_counts(const LossArgs& la) { return la.valid || la.weight; }
+static inline size_t loss_scratch_words(const LossArgs& la) { return 4 + (size_t)loss_blocks(la.M) * LOSS_SUMS; }
+// A call over host memory (the CPU build of the bodies: tests/cpu_harness), the product's three launches as three loops: the
+// counts, the blocks of LOSS_BLOCK samples, the partial rows.  tetris_lib_compose.h says which side runs what.
+static inline int loss_run_serial(LossArgs& la) {
+    if (la.M == 0) {
+        memset(la.stats, 0, LOSS_STATS * sizeof(float));
+        return TETRIS_OK;
+    }
+    const int blocks = loss_blocks(la.M);
+    std::vector<float> partial((size_t)blocks * LOSS_SUMS);
+    la.partial = partial.data();
+    uint32_t d = (uint32_t)la.M, dnz = (uint32_t)la.M;
+    if (loss_counts(la)) {
+        d = dnz = 0u;
+        for (int m = 0; m < la.M; m++) loss_count_sample(la, (size_t)m, d, dnz);
+    }
+    for (int blk = 0; blk < blocks; blk++) loss_block_serial(la, blk, (float)d, (float)dnz);
+    loss_reduce_serial(la, blocks, (float)d, (float)dnz);
     return TETRIS_OK;
 }
 

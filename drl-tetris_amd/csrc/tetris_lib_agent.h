@@ -1,5 +1,5 @@
 // Host side of libtetris_hip.so, part 4: the agent-side entry points: planning, heuristic policy, acting on an evaluation, trajectory
-// windows, window batches, the planning agent's windows, experience replay.  Needs tetris_lib_batch.h and tetris_lib_rollout.h (margin, counters).
+// windows, window batches, the planning agent's windows, experience replay, loss heads.  Needs tetris_lib_batch.h and tetris_lib_rollout.h (margin, counters).
 
 // ---------------------------------------------------------------- planning: action lists, simulated afterstates, list steps
 // Games per k_actions + k_plan_lists pair: bounds the slab scratch (40 x 16 slab entries of max_keys + 1 bytes per game: 128 MB
@@ -386,3 +386,23 @@ int tetris_replay_gather_dev(tetris_batch* b, const tetris_replay* rp, const int
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- loss heads (tetris_loss.h)
+// What tetris_ppo_loss_dev and tetris_dqn_loss_dev (tetris_lib_compose.h) run after the argument rules, at most three launches: the
+// count of D / Dnz where a mask or weights are given, the head, the statistics
+static int launch_loss(tetris_batch* b, LossArgs& la) {
+    if (la.M == 0) {
+        HIP_TRY(hipMemsetAsync(la.stats, 0, LOSS_STATS * sizeof(float), b->stream));
+        return TETRIS_OK;
+    }
+    int rc = b->loss_scratch.ensure(loss_scratch_words(la), b->stream);
+    if (rc || (rc = enqueue(b, Enqueue::STATE))) return rc;          // (the batch's scratch)
+    la.partial = reinterpret_cast<float*>(b->loss_scratch.d + 4);
+    if (loss_counts(la)) {
+        if ((rc = launch(b, k_loss_count, dim3(1), dim3(LOSS_COUNT_THREADS), 0, la, b->loss_scratch.d))) return rc;
+        la.count = b->loss_scratch.d;
+    }
+    const int blocks = loss_blocks(la.M);
+    if ((rc = launch(b, k_loss_head, dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, la))) return rc;
+    return launch(b, k_loss_reduce, dim3(1), dim3(LOSS_REDUCE_LANES), 0, la, blocks);
+}

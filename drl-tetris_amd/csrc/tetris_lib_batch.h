@@ -247,9 +247,11 @@ struct tetris_batch {
     // tetris_replay_add_dev: the entries per game and their scan; tetris_replay_sample_dev: the sort's pairs, ranks and
     // histograms (both grown on demand)
     Scratch<uint32_t> replay_offsets, replay_sort;
+    // the loss heads: the words D and Dnz and the workgroups' partial rows of the statistics (grown on demand)
+    Scratch<uint32_t> loss_scratch;
     void release_scratch() {
         plan_slabs.release(); iota.release(); plan_status.release(); policy_scores.release(); words_before.release();
-        select_blocks.release(); replay_offsets.release(); replay_sort.release();
+        select_blocks.release(); replay_offsets.release(); replay_sort.release(); loss_scratch.release();
     }
 };
 

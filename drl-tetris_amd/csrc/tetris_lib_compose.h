@@ -2,6 +2,13 @@
 // shape_of, create_impl, rollout_counters_begin / _end, the checks of tetris_host.h).  No HIP in here: tetris_hip.hip and
 // tests/cpu_harness/harness.cpp both include it, last, so the CPU suite runs these lines as they ship.
 
+// The work of a loss head behind its argument rules.  The product has launch_loss(tetris_batch*, LossArgs&) (tetris_lib_agent.h:
+// the gfx950 kernels), which as a plain function is preferred to this template and leaves it uninstantiated: the library holds no
+// CPU path.  A build whose host side defines none — the CPU harness, whose "device" memory is host memory — gets the serial form of
+// the same bodies (tetris_host.h: loss_run_serial).
+template <class B>
+static int launch_loss(B*, LossArgs& la) { return loss_run_serial(la); }
+
 extern "C" {
 
 const char* tetris_last_error(void) { return last_error(); }
@@ -63,6 +70,22 @@ int tetris_step_lists_eval_dev(tetris_batch* b, const tetris_plan_eval* e, const
     if ((rc = tetris_select_lists_dev(b, e))) return rc;
     return tetris_step_lists_dev(b, e->d_player, e->d_choice, e->d_count, d_lens, d_keys, e->max_lists, max_keys, ms, flags, d_done,
                                  d_lines, d_dead);
+}
+
+int tetris_ppo_loss_dev(tetris_batch* b, const tetris_ppo_loss* l) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    LossArgs la;
+    if ((rc = ppo_loss_args(l, la))) return rc;
+    return launch_loss(b, la);
+}
+
+int tetris_dqn_loss_dev(tetris_batch* b, const tetris_dqn_loss* l) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    LossArgs la;
+    if ((rc = dqn_loss_args(l, la))) return rc;
+    return launch_loss(b, la);
 }
 
 int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,

@@ -370,6 +370,123 @@ class TorchEnv:
         tensors, allocated once).  seed: the key of the sampling draws."""
         return Replay(self, capacity, k_step, seed)
 
+    # ---- loss heads (include/tetris_hip.h: tetris_ppo_loss_dev, tetris_dqn_loss_dev): the arithmetic of the two trainers'
+    # create_training_ops between the network's outputs and the optimiser (agents/networks/ppo_nets.py:141-196, prio_qnet.py:102-117)
+    def _loss_inputs(self, x, action, per_sample, valid):
+        """the checks both heads share -> M"""
+        torch = self.torch
+        assert x.dtype in (torch.float32, torch.float16) and x.is_cuda and x.is_contiguous(), "the evaluation is a contiguous float32 or float16 device tensor"
+        assert x.dim() == 4 and tuple(x.shape[1:3]) == (4, 10) and x.shape[3] in (1, 7), "the evaluation must be [M, 4, 10, 7 or 1]"
+        M = x.shape[0]
+        assert action.dtype == torch.uint8 and action.is_cuda and action.is_contiguous() and tuple(action.shape) == (M, 3), "action must be uint8 [M, 3]"
+        for t in per_sample:
+            assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == M, "per-sample inputs are contiguous float32 [M]"
+        if valid is not None:
+            assert valid.dtype == torch.uint8 and valid.is_cuda and valid.is_contiguous() and valid.numel() == M, "valid must be uint8 [M]"
+        return M
+
+    def _loss_buffers(self, key, M, make):
+        """One set of output tensors per head, piece count and element type, made for `capacity` samples by make(capacity): a
+        larger M replaces the set by one of that size (the old one is dropped), a smaller M uses its leading part."""
+        if getattr(self, "_loss_cache", None) is None:
+            self._loss_cache = {}
+        have = self._loss_cache.get(key)
+        if have is None or have[0] < M:
+            have = self._loss_cache[key] = (max(M, 1), make(max(M, 1)))
+        return have[1]
+
+    def ppo_head(self, pi, v, action, prob_old, adv, target, valid=None, *, clipping_parameter, value_loss, policy_loss, entropy_loss,
+                 ppo_epsilon, entropy_floor_loss, rescaled_entropy, grad_scale=1.0, terms=False):
+        """The PPO loss of a minibatch from the network's pi [M, 4, 10, K] and v [M, V] (K = 7 or 1, V = 1 or K; float32 or
+        float16): create_training_ops' loss, statistics and the gradient of the loss with respect to pi and v, scaled by grad_scale
+        (an AMP loss scale).  action uint8 [M, 3], prob_old / adv / target float32 [M] and valid uint8 [M] are the fields of
+        Trajectory.batch(...) as they come; the parameter names are model.train's, all required (entropy_floor_loss = 0 /
+        rescaled_entropy = 0 stand for the reference's params without that key; ppo_epsilon gives the entropy floor).
+        -> (stats float32 [16] in the order of capi.PPO_STATS, grad_pi like pi, grad_v like v[, terms float32 [6, M] in the order of
+        capi.PPO_TERMS]) — device tensors, reused by every call with the same K, V and element type (the leading M samples of one
+        set that grows to the largest M seen); nothing waits for the GPU."""
+        torch = self.torch
+        M = self._loss_inputs(pi, action, (prob_old, adv, target), valid)
+        assert v.dtype in (torch.float32, torch.float16) and v.is_cuda and v.is_contiguous(), "v is a contiguous float32 or float16 device tensor"
+        K = pi.shape[3]
+        assert v.dim() == 2 and v.shape[0] == M and v.shape[1] in (1, K), "v must be [M, 1 or K]"
+        V = v.shape[1]
+
+        def make(cap):
+            f32 = dict(dtype=torch.float32, device=self.dev)
+            return (torch.zeros(16, **f32), torch.zeros(cap, 4, 10, K, dtype=pi.dtype, device=self.dev),
+                    torch.zeros(cap, V, dtype=pi.dtype, device=self.dev), torch.zeros(6 * cap, **f32))
+        stats, grad_pi, grad_v, t = self._loss_buffers(("ppo", K, V, pi.dtype), M, make)
+        grad_pi, grad_v, t = grad_pi[:M], grad_v[:M], t[:6 * M].view(6, M)
+        p = self._ptr
+        l = self.b.ppo_loss(p(pi), p(v), p(action), p(prob_old), p(adv), p(target), p(grad_pi), p(grad_v), p(stats), M, n_pieces=K, n_values=V,
+                            valid=p(valid), terms=p(t) if terms else None, f16=pi.dtype == torch.float16, value_f16=v.dtype == torch.float16,
+                            grad_f16=pi.dtype == torch.float16, clipping_parameter=clipping_parameter, value_loss=value_loss,
+                            policy_loss=policy_loss, entropy_loss=entropy_loss, ppo_epsilon=ppo_epsilon, entropy_floor_loss=entropy_floor_loss,
+                            rescaled_entropy=rescaled_entropy, grad_scale=grad_scale)
+        self.b.ppo_loss_dev(l)
+        return (stats, grad_pi, grad_v, t) if terms else (stats, grad_pi, grad_v)
+
+    def dqn_head(self, Q, action, target, weight=None, valid=None, optimistic_prios=0.0, grad_scale=1.0):
+        """The DQN loss of a minibatch from the network's Q [M, 4, 10, K] (float32 or float16): the importance-weighted mean squared
+        error of Q[r, t, piece] against target (weight float32 [M] = Replay.sample's, or None), its statistics, its gradient with
+        respect to Q scaled by grad_scale, and the samples' new priorities |q - target| (+ optimistic_prios relu of it).
+        -> (stats float32 [16] in the order of capi.DQN_STATS, grad_Q like Q, new_prio float32 [M], q float32 [M]) — device tensors,
+        reused as ppo_head's are; new_prio is what Replay.update_prios(index, new_prio) takes."""
+        torch = self.torch
+        M = self._loss_inputs(Q, action, (target,) + (() if weight is None else (weight,)), valid)
+        K = Q.shape[3]
+
+        def make(cap):
+            f32 = dict(dtype=torch.float32, device=self.dev)
+            return torch.zeros(16, **f32), torch.zeros(cap, 4, 10, K, dtype=Q.dtype, device=self.dev), torch.zeros(cap, **f32), torch.zeros(cap, **f32)
+        stats, grad_Q, new_prio, q = self._loss_buffers(("dqn", K, Q.dtype), M, make)
+        grad_Q, new_prio, q = grad_Q[:M], new_prio[:M], q[:M]
+        p = self._ptr
+        l = self.b.dqn_loss(p(Q), p(action), p(target), p(grad_Q), p(new_prio), p(stats), M, n_pieces=K, weight=p(weight), valid=p(valid), q=p(q),
+                            f16=Q.dtype == torch.float16, grad_f16=Q.dtype == torch.float16, optimistic_prios=optimistic_prios,
+                            grad_scale=grad_scale)
+        self.b.dqn_loss_dev(l)
+        return stats, grad_Q, new_prio, q
+
+    def _head_function(self):
+        """the torch.autograd.Function of both losses: forward runs a head and keeps its gradients, backward hands them on"""
+        torch = self.torch
+        if getattr(self, "_head_fn", None) is None:
+            class HeadLoss(torch.autograd.Function):
+                @staticmethod
+                def forward(ctx, run, *outputs_of_the_network):
+                    loss, grads, others = run()
+                    ctx.grads = [g if g.dtype == x.dtype else g.to(x.dtype) for g, x in zip(grads, outputs_of_the_network)]
+                    ctx.mark_non_differentiable(*others)
+                    return (loss,) + tuple(others)
+
+                @staticmethod
+                def backward(ctx, grad_loss, *unused):
+                    return (None,) + tuple(g * grad_loss.to(g.dtype) for g in ctx.grads)
+            self._head_fn = HeadLoss
+        return self._head_fn
+
+    def ppo_loss(self, pi, v, action, prob_old, adv, target, valid=None, **params):
+        """ppo_head as a differentiable loss: -> (loss, stats) with loss a 0-dim float32 tensor (stats[1], copied) whose backward()
+        hands grad_pi and grad_v, times the incoming gradient, to pi and v — te.ppo_loss(*net(mb.visual, mb.vector), mb.action,
+        mb.prob, mb.adv, mb.target, mb.valid, clipping_parameter=..., ...)[0].backward(); opt.step().  The gradients are ppo_head's
+        reused tensors, not copies: call backward before the next ppo_loss of the same shape.  With grad_scale = s the gradients
+        are s times those of the returned loss (the optimiser's unscale undoes it)."""
+        def run():
+            stats, grad_pi, grad_v = self.ppo_head(pi.detach(), v.detach(), action, prob_old, adv, target, valid, **params)[:3]
+            return stats[1].clone(), (grad_pi, grad_v), (stats,)
+        return self._head_function().apply(run, pi, v)
+
+    def dqn_loss(self, Q, action, target, weight=None, valid=None, optimistic_prios=0.0, grad_scale=1.0):
+        """dqn_head as a differentiable loss: -> (loss, stats, new_prio) with loss a 0-dim float32 tensor (stats[2], copied) whose
+        backward() hands grad_Q, times the incoming gradient, to Q; then rp.update_prios(index, new_prio).  As for ppo_loss the
+        gradient is dqn_head's reused tensor."""
+        def run():
+            stats, grad_Q, new_prio, _ = self.dqn_head(Q.detach(), action, target, weight, valid, optimistic_prios, grad_scale)
+            return stats[2].clone(), (grad_Q,), (stats, new_prio)
+        return self._head_function().apply(run, Q)
+
 
 class Trajectory:
     """A trajectory window of a TorchEnv: T = capacity rows of n games, time-major device tensors

@@ -783,6 +783,92 @@ int tetris_replay_update_prios_dev(tetris_batch *b, const tetris_replay *rp, con
 int tetris_replay_gather_dev(tetris_batch *b, const tetris_replay *rp, const int32_t *d_index, int M, int steps,
                              const tetris_traj_batch *out);
 
+/* ---- loss heads: a trainer's loss, its statistics and the gradient with respect to the network's outputs ------------------
+ * replaces: the non-network arithmetic of the two trainers' create_training_ops — agents/networks/ppo_nets.py:141-196 (with
+ * N.action_entropy, network_utils.py:114-118) and agents/networks/prio_qnet.py:102-117 — and autograd's backward through it:
+ * from the network's outputs for a minibatch of M samples to the loss, the reference's statistics and d loss / d outputs, which
+ * the caller hands to the network's backward.  Not included: the regulariser (a function of the network's variables), the
+ * compressors (stateful; the caller applies them to d_adv), the optimiser.
+ * Both calls take device pointers, enqueue at most three launches on the batch's stream — a count of the valid samples when
+ * d_valid or d_weight is given, the head, the reduction of the statistics — and wait for nothing; the batch's games are neither
+ * read nor written, every batch shape serves.  The definitions, operation by operation, are in drl-tetris_amd/csrc/tetris_loss.h;
+ * float32 arithmetic, no fused multiply-adds, sums in a fixed order without atomics: a call repeated on the same inputs gives
+ * the same bits.
+ * COMMON.  K = n_pieces (7 or 1).  d_action uint8 [M][3] = (r, t, piece) as tetris_traj_batch_dev writes it; r, t and piece are
+ * limited to 3, 9 and K - 1; c = 10 r + t.  d_valid uint8 [M] or NULL: a sample with d_valid[m] == 0 contributes nothing, and
+ * its gradient rows and per-sample outputs are zeros.  D = the number of valid samples; D == 0 gives zeros everywhere (the
+ * reference's means over nothing are NaN).  The inputs pi / Q [M][4][10][K] are float32, or binary16 with TETRIS_LOSS_F16; the
+ * gradients are float32, or binary16 (rounded to nearest even) with TETRIS_LOSS_GRAD_F16; both 16-byte aligned.  Every entry of
+ * a gradient array is written: zeros outside the sample's piece.  grad_scale multiplies every gradient (an AMP loss scale).
+ * d_stats float32 [TETRIS_LOSS_STATS]; unused slots are zero.
+ * PPO (tetris_ppo_loss).  x_j = d_pi[m][j][k], val = d_v[m][min(k, V - 1)] (V = n_values, 1 or K; binary16 with
+ * TETRIS_LOSS_VALUE_F16), e = 1e-6:
+ *   p = x_c, ratio = max(p, e) / max(prob_old, e), cl = clip(ratio, 1 - clip, 1 + clip), pl = min(ratio adv, cl adv)
+ *   H = -sum_j (x_j + e) log(max(e, x_j + e)), bonus0 = H - entropy_floor_loss relu(entropy_floor - H),
+ *   bonus = bonus0 + rescaled_entropy (max_entropy - bonus0)
+ *   loss = value_loss mean((val - target)^2) - policy_loss mean(pl) - entropy_loss mean(bonus), means over the D valid samples
+ *   entropy_floor and max_entropy are the reference's two constants, computed by the caller in float64 (capi.
+ *   ppo_entropy_constants); without "entropy_floor_loss" / "rescaled_entropy" in the reference's params pass 0 for them.
+ *   d_grad_pi [M][4][10][K], d_grad_v [M][V]; TensorFlow's tie rules for maximum / minimum / clip.
+ *   d_terms float32 [6][M] or NULL: p, ratio, pl, H, bonus, val.
+ *   d_stats: 0 D, 1 loss, 2 value loss, 3 policy loss, 4 entropy loss, 5 mean H, 6 mean H^2, 7 mean bonus, 8 mean val,
+ *   9 mean val^2, 10 mean target, 11 mean target^2, 12 mean [ratio != cl] (clip_saturation), 13 mean ratio.
+ * DQN (tetris_dqn_loss).  q = d_Q[m][r][t][k], w = d_weight[m] (NULL: 1):
+ *   d_new_prio float32 [M] = |q - target| (+ optimistic_prios relu(that) when optimistic_prios != 0), 0 for invalid samples:
+ *   what tetris_replay_update_prios_dev takes.  loss = sum w (q - target)^2 / Dnz, Dnz = the number of valid samples with
+ *   w != 0 (tf.losses.mean_squared_error's default reduction), 0 when Dnz == 0.  d_grad_Q [M][4][10][K].  d_q float32 [M] or NULL.
+ *   d_stats: 0 D, 1 Dnz, 2 loss, 3 mean q, 4 mean q^2, 5 mean target, 6 mean target^2, 7 mean new_prio (means over D).
+ * TETRIS_E_ARG: a NULL argument struct; M < 0; n_pieces not 1 or 7; n_values not 1 or n_pieces; a NULL d_pi, d_v, d_action,
+ * d_prob_old, d_adv, d_target, d_grad_pi, d_grad_v or d_stats (PPO), d_Q, d_action, d_target, d_grad_Q, d_new_prio or d_stats
+ * (DQN); clip that is not >= 0; an unknown flag; an input or gradient array that is not 16-byte aligned.  M == 0 zeroes
+ * d_stats and does nothing else.                                                                                            */
+#define TETRIS_LOSS_STATS     16
+#define TETRIS_LOSS_F16       1   /* d_pi / d_Q are IEEE binary16 instead of float32 */
+#define TETRIS_LOSS_VALUE_F16 2   /* d_v is IEEE binary16 instead of float32 */
+#define TETRIS_LOSS_GRAD_F16  4   /* d_grad_pi, d_grad_v / d_grad_Q are IEEE binary16 instead of float32 */
+typedef struct tetris_ppo_loss {
+    const void    *d_pi;            /* [M][4][10][n_pieces], 16-byte aligned */
+    const void    *d_v;             /* [M][n_values] */
+    const uint8_t *d_action;        /* [M][3] */
+    const float   *d_prob_old;      /* [M] */
+    const float   *d_adv;           /* [M] */
+    const float   *d_target;        /* [M] */
+    const uint8_t *d_valid;         /* [M] or NULL */
+    int            M;
+    int            n_pieces;        /* K */
+    int            n_values;        /* V */
+    int            flags;           /* TETRIS_LOSS_* */
+    float          clip;            /* clipping_parameter */
+    float          value_loss, policy_loss, entropy_loss;      /* c1, c2, c3 */
+    float          entropy_floor_loss, rescaled_entropy;       /* 0: the term is absent */
+    float          entropy_floor, max_entropy;
+    float          grad_scale;
+    float          reserved;        /* 0 */
+    void          *d_grad_pi;       /* [M][4][10][n_pieces], 16-byte aligned */
+    void          *d_grad_v;        /* [M][n_values] */
+    float         *d_terms;         /* [6][M] or NULL */
+    float         *d_stats;         /* [TETRIS_LOSS_STATS] */
+} tetris_ppo_loss;
+typedef struct tetris_dqn_loss {
+    const void    *d_Q;             /* [M][4][10][n_pieces], 16-byte aligned */
+    const uint8_t *d_action;        /* [M][3] */
+    const float   *d_target;        /* [M] */
+    const float   *d_weight;        /* [M] or NULL */
+    const uint8_t *d_valid;         /* [M] or NULL */
+    int            M;
+    int            n_pieces;        /* K */
+    int            flags;           /* TETRIS_LOSS_F16 | TETRIS_LOSS_GRAD_F16 */
+    float          optimistic_prios;
+    float          grad_scale;
+    float          reserved;        /* 0 */
+    void          *d_grad_Q;        /* [M][4][10][n_pieces], 16-byte aligned */
+    float         *d_new_prio;      /* [M] */
+    float         *d_q;             /* [M] or NULL */
+    float         *d_stats;         /* [TETRIS_LOSS_STATS] */
+} tetris_dqn_loss;
+int tetris_ppo_loss_dev(tetris_batch *b, const tetris_ppo_loss *l);
+int tetris_dqn_loss_dev(tetris_batch *b, const tetris_dqn_loss *l);
+
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
  * t = w1 mod 10), acting player = step mod P, perform_action, auto-reset of finished games with
