@@ -103,6 +103,9 @@ PPO_STATS = ("n", "loss", "value_loss", "policy_loss", "entropy_loss", "entropy"
              "target_values", "target_values_sq", "clip_saturation", "ratio")
 DQN_STATS = ("n", "n_weighted", "loss", "q_val", "q_val_sq", "q_target", "q_target_sq", "new_prio")
 PPO_TERMS = ("probability", "ratio", "policy_term", "entropy", "entropy_bonus", "value")
+PLAN_LOSS_STATS = ("n", "loss", "value_loss", "policy_loss", "entropy_loss", "impossibility_loss", "entropy", "entropy_sq", "values",
+                   "values_sq", "target_values", "target_values_sq", "clip_saturation", "ratio", "probability")
+PLAN_LOSS_TERMS = ("probability", "ratio", "policy_term", "entropy", "impossibility", "value")
 
 
 class PpoLoss(C.Structure):
@@ -113,6 +116,16 @@ class PpoLoss(C.Structure):
                 ("entropy_floor_loss", C.c_float), ("rescaled_entropy", C.c_float), ("entropy_floor", C.c_float), ("max_entropy", C.c_float),
                 ("grad_scale", C.c_float), ("reserved", C.c_float), ("d_grad_pi", C.c_void_p), ("d_grad_v", C.c_void_p),
                 ("d_terms", C.c_void_p), ("d_stats", C.c_void_p)]
+
+
+class PlanLoss(C.Structure):
+    """mirrors `struct tetris_plan_loss` (include/tetris_hip.h)"""
+    _fields_ = [("d_phi", C.c_void_p), ("d_v", C.c_void_p), ("d_index", C.c_void_p), ("d_piece", C.c_void_p), ("d_prob_old", C.c_void_p),
+                ("d_adv", C.c_void_p), ("d_target", C.c_void_p), ("d_valid", C.c_void_p), ("M", C.c_int), ("n_pieces", C.c_int),
+                ("n_values", C.c_int), ("flags", C.c_int), ("piece_stride", C.c_int), ("small_fill", C.c_float), ("clip", C.c_float),
+                ("value_loss", C.c_float), ("policy_loss", C.c_float), ("entropy_loss", C.c_float), ("impossibility_loss", C.c_float),
+                ("grad_scale", C.c_float), ("d_grad_phi", C.c_void_p), ("d_grad_v", C.c_void_p), ("d_terms", C.c_void_p),
+                ("d_stats", C.c_void_p)]
 
 
 class DqnLoss(C.Structure):
@@ -244,6 +257,7 @@ _SIGNATURES = {
     "tetris_replay_gather_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tetris_ppo_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_dqn_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_plan_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_observe_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_observe_packed_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_create_split": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -765,6 +779,32 @@ class TetrisBatch:
         """The DQN loss of a minibatch, its statistics, its gradient with respect to Q and the samples' new priorities
         (l = dqn_loss(...))."""
         self._check(self.lib.tetris_dqn_loss_dev(self._h, C.byref(l) if l is not None else None))
+
+    def plan_loss(self, phi, v, index, piece, prob_old, adv, target, grad_phi, grad_v, stats, m, n_pieces=7, n_values=1, piece_stride=1,
+                  valid=None, terms=None, f16=False, value_f16=False, grad_f16=False, small_fill=0.0, clipping_parameter=0.15, value_loss=1.0,
+                  policy_loss=1.0, entropy_loss=0.0, impossibility_loss=0.0, grad_scale=1.0, flags=0):
+        """The argument struct of plan_loss_dev over raw DEVICE addresses (int / c_void_p) or None: phi, grad_phi [m][H][10][n_pieces]
+        and v, grad_v [m][n_values] float32 (f16 / value_f16 / grad_f16: binary16), index int32 [m] (entries of the planning window;
+        bit 31: mirrored), piece uint8 with sample j's piece at byte j * piece_stride (1: a uint8 [m] array; 3: the address of
+        byte 2 of a batch's action [m][3]), prob_old / adv / target float32 [m], valid uint8 [m], terms float32 [6][m], stats
+        float32 [16].  The parameter names are model.train's; small_fill as traj_plan_batch_dev's (0: the reference's planes)."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        l = PlanLoss()
+        l.d_phi, l.d_v, l.d_index, l.d_piece = val(phi), val(v), val(index), val(piece)
+        l.d_prob_old, l.d_adv, l.d_target, l.d_valid = val(prob_old), val(adv), val(target), val(valid)
+        l.M, l.n_pieces, l.n_values, l.piece_stride = int(m), int(n_pieces), int(n_values), int(piece_stride)
+        l.flags = (LOSS_F16 if f16 else 0) | (LOSS_VALUE_F16 if value_f16 else 0) | (LOSS_GRAD_F16 if grad_f16 else 0) | int(flags)
+        l.small_fill, l.clip = float(small_fill), float(clipping_parameter)
+        l.value_loss, l.policy_loss, l.entropy_loss, l.impossibility_loss = float(value_loss), float(policy_loss), float(entropy_loss), float(impossibility_loss)
+        l.grad_scale = float(grad_scale)
+        l.d_grad_phi, l.d_grad_v, l.d_terms, l.d_stats = val(grad_phi), val(grad_v), val(terms), val(stats)
+        return l
+
+    def plan_loss_dev(self, plan, l):
+        """The planning agent's PPO loss of a minibatch straight from the plan records (plan = traj_plan(...), l = plan_loss(...)):
+        its statistics and its gradient with respect to phi and v."""
+        ref = lambda s: C.byref(s) if s is not None else None                     # noqa: E731
+        self._check(self.lib.tetris_plan_loss_dev(self._h, ref(plan), ref(l)))
 
     def rollout_game_totals_dev(self, totals):
         """The per-game words rollout_totals sums: totals uint32 [4][N] = env-steps, episodes, lines cleared, garbage lines sent."""

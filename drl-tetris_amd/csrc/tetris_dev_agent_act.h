@@ -222,6 +222,182 @@ __global__ __launch_bounds__(LOSS_REDUCE_LANES) void k_loss_reduce(LossArgs la, 
     }
 }
 
+// ---- the planning loss head (tetris_loss.h: PLAN).  A sample is HW K contiguous elements — 5 600 bytes at H = 20, K = 7 in
+// float32 — so a workgroup takes PLAN_LOSS_BLOCK = 16 consecutive samples (a multiple of 8: its run of phi and of grad_phi starts
+// on 16 bytes for every H, K and element type), four per wave:
+//   a. lane t < 16: the sample's piece, whether it is valid, whether it is the mirrored image;
+//   b. the whole workgroup streams the block's contiguous run of phi in with 16-byte loads and drops the elements of each
+//      sample's piece into its LDS plane [sample][cell] (a vector may straddle two samples: the element walk carries sample, cell
+//      and piece index along, one division per vector); 28 consecutive lanes per sample read the record's 28 quads once, zeros
+//      for an index that names no entry;
+//   c. a wave per sample at a time: lane l holds cells l, l + 64, .. (at most PLAN_LOSS_CELLS = 5) in registers across both passes —
+//      the four sums of pass one and the entropy sum of pass two are reduced by shuffles in the order of loss_tree and handed back
+//      to every lane — and leaves g_t in the plane it read raw_t from; lane 0 writes the sample's terms;
+//   d. the workgroup streams the block's gradient run out as 16-byte non-temporal stores in memory order, zeros but the pieces'
+//      elements from LDS; the run's last elements, where it is no multiple of 16 bytes (a short last block), leave one by one.
+// Thread i < LOSS_SUMS adds the block's 16 sample terms of sum i by loss_tree into the partial row; k_loss_count and k_loss_reduce
+// serve as for the other heads.  LDS: 20 KB of planes, 7 KB of records, 1 KB of the rest.  No atomics, no workgroup waits for
+// another.
+constexpr int PLAN_LOSS_THREADS = 256;
+constexpr int PLAN_LOSS_PITCH = 320;             // floats of a sample's LDS plane (MAX_H * NCOL = 310 cells)
+static_assert(PLAN_LOSS_PITCH >= MAX_H * NCOL && PLAN_LOSS_CELLS * PLAN_LOSS_LANES >= MAX_H * NCOL, "a plane holds every height");
+static_assert(PLAN_LOSS_BLOCK % 8 == 0 && PLAN_LOSS_BLOCK % (PLAN_LOSS_THREADS / 64) == 0, "aligned runs; whole rounds of the waves");
+struct PlanLossShared {
+    alignas(16) uint32_t rec[PLAN_LOSS_BLOCK * PLAN_REC_WORDS];
+    float x[PLAN_LOSS_BLOCK * PLAN_LOSS_PITCH];      // raw_t, then g_t
+    float sum[LOSS_SUMS][PLAN_LOSS_BLOCK];
+    float gv[PLAN_LOSS_BLOCK];
+    int piece[PLAN_LOSS_BLOCK];
+    uint32_t flags[PLAN_LOSS_BLOCK];                 // bit 0: a valid sample, bit 1: the mirrored image
+};
+
+// b and d: the walk over the block's run.  PUT = false: phi -> planes; PUT = true: planes -> grad_phi.
+template <int K, bool F16, bool PUT>
+__device__ __forceinline__ void plan_loss_stream(const LossArgs& la, int g0, int ng, PlanLossShared& sh) {
+    constexpr uint32_t EPV = F16 ? 8 : 4;
+    const uint32_t PER = (uint32_t)la.H * NCOL * K, total = (uint32_t)ng * PER, nvec = total / EPV;
+    void* whole = PUT ? la.grad_x : const_cast<void*>(la.x);
+    act_u32x4* run = (act_u32x4*)((char*)whole + (size_t)g0 * PER * (F16 ? 2 : 4));
+#pragma unroll 2
+    for (uint32_t v = threadIdx.x; v < nvec; v += PLAN_LOSS_THREADS) {
+        act_u32x4 q = {0u, 0u, 0u, 0u};
+        if (!PUT) q = run[v];
+        const uint32_t e0 = v * EPV;
+        uint32_t s = e0 / PER, rem = e0 - s * PER;
+        uint32_t cell = rem / K, kk = rem - cell * K;
+#pragma unroll
+        for (int j = 0; j < (int)EPV; j++) {
+            if ((int)kk == sh.piece[s]) {
+                if (PUT) act_vector_put<F16>(q, j, sh.x[s * PLAN_LOSS_PITCH + cell]);
+                else sh.x[s * PLAN_LOSS_PITCH + cell] = act_vector_element<F16>(q, j);
+            }
+            kk++; rem++;
+            if (kk == K) { kk = 0u; cell++; }
+            if (rem == PER && j + 1 < (int)EPV) { rem = 0u; cell = 0u; kk = 0u; s++; }
+        }
+        if (PUT) __builtin_nontemporal_store(q, run + v);
+    }
+    for (uint32_t e = nvec * EPV + threadIdx.x; e < total; e += PLAN_LOSS_THREADS) {
+        const uint32_t s = e / PER, rem = e - s * PER, cell = rem / K, kk = rem - cell * K;
+        const size_t at = (size_t)g0 * PER + e;
+        if (PUT) loss_store(la.grad_x, at, (int)kk == sh.piece[s] ? sh.x[s * PLAN_LOSS_PITCH + cell] : 0.0f, F16 ? 1 : 0);
+        else if ((int)kk == sh.piece[s]) sh.x[s * PLAN_LOSS_PITCH + cell] = act_element(la.x, at, F16 ? 1 : 0);
+    }
+}
+template <bool PUT>
+__device__ __forceinline__ void plan_loss_stream_any(const LossArgs& la, int g0, int ng, PlanLossShared& sh) {
+    const bool f16 = PUT ? la.grad_f16 != 0 : la.in_f16 != 0;
+    if (la.K == 7) {
+        if (f16) plan_loss_stream<7, true, PUT>(la, g0, ng, sh); else plan_loss_stream<7, false, PUT>(la, g0, ng, sh);
+    } else {
+        if (f16) plan_loss_stream<1, true, PUT>(la, g0, ng, sh); else plan_loss_stream<1, false, PUT>(la, g0, ng, sh);
+    }
+}
+// a wave's sum in the order of loss_tree, handed to every lane
+__device__ __forceinline__ float plan_loss_wave_sum(float s) {
+#pragma unroll
+    for (int off = PLAN_LOSS_LANES / 2; off >= 1; off >>= 1) s += __shfl_down(s, off, PLAN_LOSS_LANES);
+    return __shfl(s, 0, PLAN_LOSS_LANES);
+}
+
+__global__ __launch_bounds__(PLAN_LOSS_THREADS) void k_plan_loss_head(LossArgs la) {
+    __shared__ PlanLossShared sh;
+    static_assert(PLAN_LOSS_LANES == 64, "a wave holds a lane per residue of the cell order");
+    const int t = threadIdx.x, g0 = blockIdx.x * PLAN_LOSS_BLOCK, ng = imin(PLAN_LOSS_BLOCK, la.M - g0);
+    const int HW = la.H * NCOL;
+    if (t < PLAN_LOSS_BLOCK) {                                                           // a
+        int k = 0;
+        uint32_t flags = 0u;
+        if (t < ng) {
+            const size_t m = (size_t)(g0 + t);
+            k = plan_loss_piece(la, m);
+            const BatchEntry en = batch_index_entry((uint32_t)la.index[m], la.total);
+            flags = (loss_valid(la, m) ? 1u : 0u) | (en.mirror ? 2u : 0u);
+        }
+        sh.piece[t] = k;
+        sh.flags[t] = flags;
+    }
+    __syncthreads();
+    plan_loss_stream_any<false>(la, g0, ng, sh);                                         // b
+    for (int e = t; e < ng * PLAN_REC_QUADS; e += PLAN_LOSS_THREADS) {
+        const int j = e / PLAN_REC_QUADS, q = e - j * PLAN_REC_QUADS;
+        const BatchEntry en = batch_index_entry((uint32_t)la.index[g0 + j], la.total);
+        // (an entry that names no sample has at = 0: entry 0 is loaded and dropped word by word, as in k_traj_plan_batch)
+        act_u32x4 w = reinterpret_cast<const act_u32x4*>(la.rec + (size_t)en.at * PLAN_REC_WORDS)[q];
+        const uint32_t keep = en.valid ? ~0u : 0u;
+        w.x &= keep; w.y &= keep; w.z &= keep; w.w &= keep;
+        *reinterpret_cast<act_u32x4*>(sh.rec + j * PLAN_REC_WORDS + 4 * q) = w;
+    }
+    __syncthreads();
+    const float D = la.count ? (float)la.count[0] : (float)la.M;
+    const int lane = t & (PLAN_LOSS_LANES - 1), wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    for (int s = wave; s < ng; s += PLAN_LOSS_THREADS / PLAN_LOSS_LANES) {               // c
+        const size_t m = (size_t)(g0 + s);
+        float* plane = sh.x + s * PLAN_LOSS_PITCH;
+        float sum[LOSS_SUMS], gv = 0.0f;
+#pragma unroll
+        for (int i = 0; i < LOSS_SUMS; i++) sum[i] = 0.0f;
+        if ((sh.flags[s] & 1u) && D > 0.0f) {
+            const uint32_t* r = sh.rec + s * PLAN_REC_WORDS;
+            const bool mirror = (sh.flags[s] & 2u) != 0u;
+            PlanCell pc[PLAN_LOSS_CELLS];
+            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int c = 0; c < PLAN_LOSS_CELLS; c++) {
+                const int cell = lane + c * PLAN_LOSS_LANES;
+                const bool live = cell < HW;
+                pc[c] = plan_cell(r, mirror, live ? cell : 0, live ? plane[cell] : 0.0f, la.small_fill);
+                float four[4];
+                plan_cell_terms(pc[c], four);
+#pragma unroll
+                for (int i = 0; i < 4; i++) acc[i] += live ? four[i] : 0.0f;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) acc[i] = plan_loss_wave_sum(acc[i]);
+            PlanSample ps;
+            plan_sample_policy(la, m, sh.piece[s], D, acc[0], acc[1], acc[2], ps);
+            float l[PLAN_LOSS_CELLS], above[PLAN_LOSS_CELLS], ent = 0.0f;
+#pragma unroll
+            for (int c = 0; c < PLAN_LOSS_CELLS; c++) {
+                const bool live = lane + c * PLAN_LOSS_LANES < HW;
+                const float term = plan_cell_entropy(pc[c], ps.S, l[c], above[c]);
+                ent += live ? term : 0.0f;
+            }
+            ps.Hent = -plan_loss_wave_sum(ent);
+#pragma unroll
+            for (int c = 0; c < PLAN_LOSS_CELLS; c++) {
+                const int cell = lane + c * PLAN_LOSS_LANES;
+                if (cell < HW) plane[cell] = plan_cell_grad(la, ps, pc[c], l[c], above[c]);
+            }
+            if (lane == 0) plan_sample_finish(la, m, D, ps, acc[3], sum, gv);
+        } else {
+            for (int cell = lane; cell < HW; cell += PLAN_LOSS_LANES) plane[cell] = 0.0f;
+            if (lane == 0) plan_sample_zero_terms(la, m);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < LOSS_SUMS; i++) sh.sum[i][s] = sum[i];
+            sh.gv[s] = gv;
+        }
+    }
+    if (t >= ng && t < PLAN_LOSS_BLOCK) {                    // the samples past M of a last, short block add zeros
+#pragma unroll
+        for (int i = 0; i < LOSS_SUMS; i++) sh.sum[i][t] = 0.0f;
+    }
+    __syncthreads();
+    if (t < LOSS_SUMS) {
+        float v[PLAN_LOSS_BLOCK];
+#pragma unroll
+        for (int i = 0; i < PLAN_LOSS_BLOCK; i++) v[i] = sh.sum[t][i];
+        la.partial[(size_t)blockIdx.x * LOSS_SUMS + t] = loss_tree(v, PLAN_LOSS_BLOCK);
+    }
+    plan_loss_stream_any<true>(la, g0, ng, sh);                                          // d
+    for (int e = t; e < ng * la.V; e += PLAN_LOSS_THREADS) {
+        const int s = e / la.V, kk = e - s * la.V;
+        loss_store(la.grad_v, (size_t)g0 * la.V + e, kk == imin(sh.piece[s], la.V - 1) ? sh.gv[s] : 0.0f, la.grad_f16);
+    }
+}
+
 // ---- trajectory windows (tetris_traj.h).  Recording is one lane per game.
 constexpr int TRAJ_LANE_THREADS = 256;      // k_traj_record and k_traj_observe: a lane per record
 __global__ __launch_bounds__(TRAJ_LANE_THREADS) void k_traj_record(TrajRecordArgs ra) {

@@ -681,10 +681,38 @@ static inline int dqn_loss_args(const tetris_dqn_loss* l, LossArgs& la) {
     la.grad_x = l->d_grad_Q; la.new_prio = l->d_new_prio; la.q = l->d_q; la.stats = l->d_stats;
     return TETRIS_OK;
 }
+// the planning head: the window's own rules (one or two players, no split batch, T N below 2^31), then the head's
+static inline int plan_loss_args(const HostShape& s, const tetris_traj_plan* plan, const tetris_plan_loss* l, LossArgs& la) {
+    int rc = traj_batch_rules(s, "tetris_plan_loss_dev");
+    if (rc) return rc;
+    if (!l) return fail(TETRIS_E_ARG, "the argument struct is NULL");
+    if (!plan || !plan->d_rec) return fail(TETRIS_E_ARG, "the plan records are NULL");
+    if (!l->d_phi || !l->d_v || !l->d_index || !l->d_piece || !l->d_prob_old || !l->d_adv || !l->d_target)
+        return fail(TETRIS_E_ARG, "phi/v/index/piece/prob_old/adv/target are NULL");
+    if (!l->d_grad_phi || !l->d_grad_v || !l->d_stats) return fail(TETRIS_E_ARG, "grad_phi/grad_v/stats are NULL");
+    if ((rc = loss_common_check(l->M, l->n_pieces, l->flags, TETRIS_LOSS_F16 | TETRIS_LOSS_VALUE_F16 | TETRIS_LOSS_GRAD_F16, l->d_phi, l->d_grad_phi))) return rc;
+    if (l->n_values != 1 && l->n_values != l->n_pieces) return fail(TETRIS_E_ARG, "n_values must be 1 or n_pieces");
+    if (!(l->clip >= 0.0f)) return fail(TETRIS_E_ARG, "clip must be >= 0");
+    if (l->piece_stride < 1) return fail(TETRIS_E_ARG, "piece_stride must be >= 1");
+    if (plan->capacity < 1 || (unsigned long long)plan->capacity * (unsigned long long)s.N >= (1ull << 31)) return fail(TETRIS_E_ARG, "the window must hold between 1 and 2^31 - 1 entries");
+    if (((uintptr_t)plan->d_rec) & 15u) return fail(TETRIS_E_ARG, "d_rec must be 16-byte aligned");
+    memset(&la, 0, sizeof la);
+    la.head = LOSS_PLAN;
+    la.M = l->M; la.K = l->n_pieces; la.V = l->n_values; la.H = s.H;
+    la.in_f16 = (l->flags & TETRIS_LOSS_F16) ? 1 : 0; la.v_f16 = (l->flags & TETRIS_LOSS_VALUE_F16) ? 1 : 0;
+    la.grad_f16 = (l->flags & TETRIS_LOSS_GRAD_F16) ? 1 : 0;
+    la.x = l->d_phi; la.v = l->d_v; la.old = l->d_prob_old; la.adv = l->d_adv; la.target = l->d_target; la.valid = l->d_valid;
+    la.total = (uint32_t)plan->capacity * (uint32_t)s.N; la.rec = plan->d_rec; la.index = l->d_index;
+    la.piece = l->d_piece; la.piece_stride = l->piece_stride; la.small_fill = l->small_fill;
+    la.clip = l->clip; la.c1 = l->value_loss; la.c2 = l->policy_loss; la.c3 = l->entropy_loss; la.c4 = l->impossibility_loss;
+    la.grad_scale = l->grad_scale;
+    la.grad_x = l->d_grad_phi; la.grad_v = l->d_grad_v; la.terms = l->d_terms; la.stats = l->d_stats;
+    return TETRIS_OK;
+}
 // whether the call counts D / Dnz on the device (otherwise both are M), and the words of scratch it needs: two counts,
 // padded to 16 bytes, then the workgroups' partial rows
-static inline bool loss_counts(const LossArgs& la) { return la.valid || la.weight; }
-static inline size_t loss_scratch_words(const LossArgs& la) { return 4 + (size_t)loss_blocks(la.M) * LOSS_SUMS; }
+static inline bool loss_counts(const LossArgs& la) { return la.valid || la.weight || la.index; }
+static inline size_t loss_scratch_words(const LossArgs& la) { return 4 + (size_t)loss_blocks_of(la) * LOSS_SUMS; }
 // A call over host memory (the CPU build of the bodies: tests/cpu_harness), the product's three launches as three loops: the
 // counts, the blocks of LOSS_BLOCK samples, the partial rows.  tetris_lib_compose.h says which side runs what.
 static inline int loss_run_serial(LossArgs& la) {
@@ -692,7 +720,7 @@ static inline int loss_run_serial(LossArgs& la) {
         memset(la.stats, 0, LOSS_STATS * sizeof(float));
         return TETRIS_OK;
     }
-    const int blocks = loss_blocks(la.M);
+    const int blocks = loss_blocks_of(la);
     std::vector<float> partial((size_t)blocks * LOSS_SUMS);
     la.partial = partial.data();
     uint32_t d = (uint32_t)la.M, dnz = (uint32_t)la.M;
@@ -700,7 +728,10 @@ static inline int loss_run_serial(LossArgs& la) {
         d = dnz = 0u;
         for (int m = 0; m < la.M; m++) loss_count_sample(la, (size_t)m, d, dnz);
     }
-    for (int blk = 0; blk < blocks; blk++) loss_block_serial(la, blk, (float)d, (float)dnz);
+    for (int blk = 0; blk < blocks; blk++) {
+        if (la.head == LOSS_PLAN) plan_loss_block_serial(la, blk, (float)d);
+        else loss_block_serial(la, blk, (float)d, (float)dnz);
+    }
     loss_reduce_serial(la, blocks, (float)d, (float)dnz);
     return TETRIS_OK;
 }

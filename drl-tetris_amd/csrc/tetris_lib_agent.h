@@ -388,8 +388,8 @@ int tetris_replay_gather_dev(tetris_batch* b, const tetris_replay* rp, const int
 }  // extern "C"
 
 // ---------------------------------------------------------------- loss heads (tetris_loss.h)
-// What tetris_ppo_loss_dev and tetris_dqn_loss_dev (tetris_lib_compose.h) run after the argument rules, at most three launches: the
-// count of D / Dnz where a mask or weights are given, the head, the statistics
+// What tetris_ppo_loss_dev, tetris_dqn_loss_dev and tetris_plan_loss_dev (tetris_lib_compose.h) run after the argument rules, at most
+// three launches: the count of D / Dnz where a mask, weights or a window's index list are given, the head, the statistics
 static int launch_loss(tetris_batch* b, LossArgs& la) {
     if (la.M == 0) {
         HIP_TRY(hipMemsetAsync(la.stats, 0, LOSS_STATS * sizeof(float), b->stream));
@@ -402,7 +402,9 @@ static int launch_loss(tetris_batch* b, LossArgs& la) {
         if ((rc = launch(b, k_loss_count, dim3(1), dim3(LOSS_COUNT_THREADS), 0, la, b->loss_scratch.d))) return rc;
         la.count = b->loss_scratch.d;
     }
-    const int blocks = loss_blocks(la.M);
-    if ((rc = launch(b, k_loss_head, dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, la))) return rc;
+    const int blocks = loss_blocks_of(la);
+    if (la.head == LOSS_PLAN) rc = launch(b, k_plan_loss_head, dim3((unsigned)blocks), dim3(PLAN_LOSS_THREADS), 0, la);
+    else rc = launch(b, k_loss_head, dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, la);
+    if (rc) return rc;
     return launch(b, k_loss_reduce, dim3(1), dim3(LOSS_REDUCE_LANES), 0, la, blocks);
 }

@@ -88,6 +88,14 @@ int tetris_dqn_loss_dev(tetris_batch* b, const tetris_dqn_loss* l) {
     return launch_loss(b, la);
 }
 
+int tetris_plan_loss_dev(tetris_batch* b, const tetris_traj_plan* plan, const tetris_plan_loss* l) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    LossArgs la;
+    if ((rc = plan_loss_args(shape_of(b), plan, l, la))) return rc;
+    return launch_loss(b, la);
+}
+
 int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,
                           int ms, uint64_t counters[4], float* elapsed_ms) {
     int rc;

@@ -449,6 +449,49 @@ class TorchEnv:
         self.b.dqn_loss_dev(l)
         return stats, grad_Q, new_prio, q
 
+    def plan_head(self, phi, v, traj, index, piece, prob_old, adv, target, valid=None, *, small_fill, clipping_parameter, value_loss,
+                  policy_loss, entropy_loss, impossibility_loss, grad_scale=1.0, terms=False):
+        """The planning agent's PPO loss (delta_ppo_nets.create_training_ops) of a minibatch from the network's RAW phi [M, H, 10, K]
+        (the head clips) and v [M, V] (K = 7 or 1, V = 1 or K; float32 or float16) and the plan records of traj =
+        Trajectory(plan=True): index int32 [M] as for traj.batch / batch_plan (bit 31: mirrored; an index that names no entry is an
+        invalid sample), piece uint8 [M] — mb.action[:, 2] of traj.batch(index) serves as it is, a view with a stride of 3 bytes —,
+        prob_old / adv / target float32 [M] and valid uint8 [M] as Trajectory.batch gives them.  delta and delta_sum are never
+        expanded; small_fill has batch_plan's meaning (0.0: the reference's numbers).  The parameter names are model.train's, all
+        required.  -> (stats float32 [16] in the order of capi.PLAN_LOSS_STATS, grad_phi like phi, grad_v like v[, terms float32
+        [6, M] in the order of capi.PLAN_LOSS_TERMS]) — device tensors, reused as ppo_head's are; nothing waits for the GPU."""
+        torch = self.torch
+        H = self.b.height
+        assert hasattr(traj, "plan_rec"), "the window was made without plan=True"
+        assert phi.dtype in (torch.float32, torch.float16) and phi.is_cuda and phi.is_contiguous(), "phi is a contiguous float32 or float16 device tensor"
+        assert phi.dim() == 4 and tuple(phi.shape[1:3]) == (H, 10) and phi.shape[3] in (1, 7), "phi must be [M, H, 10, 7 or 1]"
+        M, K = phi.shape[0], phi.shape[3]
+        assert v.dtype in (torch.float32, torch.float16) and v.is_cuda and v.is_contiguous(), "v is a contiguous float32 or float16 device tensor"
+        assert v.dim() == 2 and v.shape[0] == M and v.shape[1] in (1, K), "v must be [M, 1 or K]"
+        V = v.shape[1]
+        assert index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.numel() == M, "index must be int32 [M]"
+        assert piece.dtype == torch.uint8 and piece.is_cuda and piece.dim() == 1 and piece.numel() == M, "piece must be uint8 [M]"
+        stride = piece.stride(0) if M > 1 else 1
+        assert stride >= 1, "piece must not be a broadcast view"
+        for t in (prob_old, adv, target):
+            assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == M, "per-sample inputs are contiguous float32 [M]"
+        if valid is not None:
+            assert valid.dtype == torch.uint8 and valid.is_cuda and valid.is_contiguous() and valid.numel() == M, "valid must be uint8 [M]"
+
+        def make(cap):
+            f32 = dict(dtype=torch.float32, device=self.dev)
+            return (torch.zeros(16, **f32), torch.zeros(cap, H, 10, K, dtype=phi.dtype, device=self.dev),
+                    torch.zeros(cap, V, dtype=phi.dtype, device=self.dev), torch.zeros(6 * cap, **f32))
+        stats, grad_phi, grad_v, t = self._loss_buffers(("plan", K, V, phi.dtype), M, make)
+        grad_phi, grad_v, t = grad_phi[:M], grad_v[:M], t[:6 * M].view(6, M)
+        p = self._ptr
+        l = self.b.plan_loss(p(phi), p(v), p(index), p(piece), p(prob_old), p(adv), p(target), p(grad_phi), p(grad_v), p(stats), M, n_pieces=K,
+                             n_values=V, piece_stride=stride, valid=p(valid), terms=p(t) if terms else None, f16=phi.dtype == torch.float16,
+                             value_f16=v.dtype == torch.float16, grad_f16=phi.dtype == torch.float16, small_fill=small_fill,
+                             clipping_parameter=clipping_parameter, value_loss=value_loss, policy_loss=policy_loss, entropy_loss=entropy_loss,
+                             impossibility_loss=impossibility_loss, grad_scale=grad_scale)
+        self.b.plan_loss_dev(traj._plan, l)
+        return (stats, grad_phi, grad_v, t) if terms else (stats, grad_phi, grad_v)
+
     def _head_function(self):
         """the torch.autograd.Function of both losses: forward runs a head and keeps its gradients, backward hands them on"""
         torch = self.torch
@@ -477,6 +520,18 @@ class TorchEnv:
             stats, grad_pi, grad_v = self.ppo_head(pi.detach(), v.detach(), action, prob_old, adv, target, valid, **params)[:3]
             return stats[1].clone(), (grad_pi, grad_v), (stats,)
         return self._head_function().apply(run, pi, v)
+
+    def plan_loss(self, phi, v, traj, index, piece, prob_old, adv, target, valid=None, **params):
+        """plan_head as a differentiable loss: -> (loss, stats) with loss a 0-dim float32 tensor (stats[1], copied) whose backward()
+        hands grad_phi and grad_v, times the incoming gradient, to phi and v:
+            idx = index[perm[:M]]; mb = tr.batch(idx); v, phi = net(mb.visual, mb.vector)
+            loss, stats = te.plan_loss(phi, v, tr, idx, mb.action[:, 2], mb.prob, mb.adv, mb.target, mb.valid, small_fill=0.0, ...)
+            loss.backward(); opt.step()
+        As for ppo_loss the gradients are plan_head's reused tensors: call backward before the next plan_loss of the same shape."""
+        def run():
+            stats, grad_phi, grad_v = self.plan_head(phi.detach(), v.detach(), traj, index, piece, prob_old, adv, target, valid, **params)[:3]
+            return stats[1].clone(), (grad_phi, grad_v), (stats,)
+        return self._head_function().apply(run, phi, v)
 
     def dqn_loss(self, Q, action, target, weight=None, valid=None, optimistic_prios=0.0, grad_scale=1.0):
         """dqn_head as a differentiable loss: -> (loss, stats, new_prio) with loss a 0-dim float32 tensor (stats[2], copied) whose

@@ -869,6 +869,66 @@ typedef struct tetris_dqn_loss {
 int tetris_ppo_loss_dev(tetris_batch *b, const tetris_ppo_loss *l);
 int tetris_dqn_loss_dev(tetris_batch *b, const tetris_dqn_loss *l);
 
+/* ---- planning loss head: the planning agent's PPO loss, statistics and gradients straight from the plan records ------------
+ * replaces: the non-network arithmetic of delta_ppo_nets.create_training_ops (agents/networks/delta_ppo_nets.py:150-182) and
+ * autograd's backward through it, for a minibatch of M samples of a planning window.  The two [M][H][10] planes delta and
+ * delta_sum are never written: the head reads the 448-byte records of `plan` (tetris_traj_record_plan_dev) through d_index, as
+ * tetris_traj_plan_batch_dev does, and every value d_t, s_t below is the one that call gives for the same small_fill
+ * (small_fill = 0: the reference's numbers).  Not included, as for the PPO head: the regulariser, the advantage compressor, the
+ * k-step target estimator, the optimiser.  Device pointers, at most three launches on the batch's stream (the count of the
+ * valid samples, the head, the reduction of the statistics), nothing waits; one and two players; the batch's games are neither
+ * read nor written.  The definition, operation by operation, and the order of every sum are in
+ * drl-tetris_amd/csrc/tetris_loss.h (PLAN); float32, no fused multiply-adds, logf the only library call, no atomics: a call
+ * repeated on the same inputs gives the same bits.
+ *   d_phi [M][H][10][K]: the network's RAW second output (_phi_tf before the clip), float32 or binary16 (TETRIS_LOSS_F16),
+ *   16-byte aligned; K = n_pieces, 7 or 1; H = the batch's height.  d_v [M][V], V = n_values = 1 or K (TETRIS_LOSS_VALUE_F16).
+ *   d_index int32 [M]: entries of the window, bit 31 = the mirrored image; an index that names no entry (-1, >= T N) is an
+ *   invalid sample, as is one with d_valid[m] == 0 (d_valid uint8 [M] or NULL).  The piece of sample m is the byte
+ *   d_piece[m * piece_stride], limited to K - 1: piece_stride = 1 for a uint8 [M] array, 3 with d_piece = d_action + 2 of
+ *   tetris_traj_batch_dev's d_action [M][3].  d_prob_old, d_adv, d_target float32 [M].
+ * With e = 1e-6, the cells t = 10 y + c of the HW = 10 H, k the piece, x_t = clip(d_phi[m][y][c][k], e, 1):
+ *   probability = (sum x_t d_t + e) / (sum x_t s_t + e), ratio = max(probability, e) / max(prob_old, e),
+ *   cl = clip(ratio, 1 - clip, 1 + clip), pl = min(ratio adv, cl adv)
+ *   imp = sum x_t (1 - min(1, s_t));  S = sum (s_t + e), y_t = x_t s_t / S + e, Hent = -sum y_t log(max(e, y_t))
+ *   val = d_v[m][min(k, V - 1)]
+ *   loss = value_loss mean((val - target)^2) - policy_loss mean(pl) + impossibility_loss mean(imp) / HW
+ *          - entropy_loss mean(Hent), means over the D valid samples; D == 0 gives zeros everywhere
+ *   d_grad_phi [M][H][10][K] and d_grad_v [M][V], float32 or binary16 (TETRIS_LOSS_GRAD_F16), times grad_scale; every element
+ *   is written, zeros outside the piece's plane and for invalid samples.  Through the clip the gradient passes where
+ *   e <= raw <= 1 (tf.clip_by_value sends a tie to its input); the other ties as for the PPO head.
+ *   d_terms float32 [6][M] or NULL: probability, ratio, pl, Hent, imp, val (zeros for invalid samples).
+ *   d_stats: 0 D, 1 loss, 2 value loss, 3 policy loss, 4 entropy loss, 5 impossibility loss (2-5 signed as they enter the
+ *   loss), 6 mean Hent, 7 mean Hent^2, 8 mean val, 9 mean val^2, 10 mean target, 11 mean target^2, 12 clip_saturation,
+ *   13 mean ratio, 14 mean probability.
+ * TETRIS_E_ARG: a NULL l, plan, d_rec, d_phi, d_v, d_index, d_piece, d_prob_old, d_adv, d_target, d_grad_phi, d_grad_v or
+ * d_stats; M < 0; n_pieces not 1 or 7; n_values not 1 or n_pieces; clip that is not >= 0; piece_stride < 1; an unknown flag; a
+ * d_phi, d_grad_phi or d_rec that is not 16-byte aligned; a window of no rows or of 2^31 entries or more; three or four
+ * players; a split batch.  M == 0 zeroes d_stats and does nothing else.                                                      */
+typedef struct tetris_plan_loss {
+    const void    *d_phi;           /* [M][H][10][n_pieces], 16-byte aligned */
+    const void    *d_v;             /* [M][n_values] */
+    const int32_t *d_index;         /* [M] */
+    const uint8_t *d_piece;         /* sample m: d_piece[m * piece_stride] */
+    const float   *d_prob_old;      /* [M] */
+    const float   *d_adv;           /* [M] */
+    const float   *d_target;        /* [M] */
+    const uint8_t *d_valid;         /* [M] or NULL */
+    int            M;
+    int            n_pieces;        /* K */
+    int            n_values;        /* V */
+    int            flags;           /* TETRIS_LOSS_* */
+    int            piece_stride;    /* bytes between two samples' pieces, >= 1 */
+    float          small_fill;      /* as tetris_traj_plan_batch_dev's; 0: the reference's planes */
+    float          clip;            /* clipping_parameter */
+    float          value_loss, policy_loss, entropy_loss, impossibility_loss;      /* c1, c2, c3, c4 */
+    float          grad_scale;
+    void          *d_grad_phi;      /* [M][H][10][n_pieces], 16-byte aligned */
+    void          *d_grad_v;        /* [M][n_values] */
+    float         *d_terms;         /* [6][M] or NULL */
+    float         *d_stats;         /* [TETRIS_LOSS_STATS] */
+} tetris_plan_loss;
+int tetris_plan_loss_dev(tetris_batch *b, const tetris_traj_plan *plan, const tetris_plan_loss *l);
+
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
  * t = w1 mod 10), acting player = step mod P, perform_action, auto-reset of finished games with
