@@ -135,6 +135,34 @@ class DqnLoss(C.Structure):
                 ("reserved", C.c_float), ("d_grad_Q", C.c_void_p), ("d_new_prio", C.c_void_p), ("d_q", C.c_void_p), ("d_stats", C.c_void_p)]
 
 
+KSTEP_Q, KSTEP_V, KSTEP_TRUNCATE = 0, 1, 8          # TETRIS_KSTEP_*
+
+
+class KstepTarget(C.Structure):
+    """mirrors `struct tetris_kstep_target` (include/tetris_hip.h)"""
+    _fields_ = [("d_out", C.c_void_p), ("d_reward", C.c_void_p), ("d_done", C.c_void_p), ("d_index", C.c_void_p), ("M", C.c_int),
+                ("k_step", C.c_int), ("step_mask", C.c_uint64), ("max_size", C.c_int), ("mode", C.c_int), ("n_pieces", C.c_int),
+                ("n_values", C.c_int), ("used_pieces", C.c_int), ("flags", C.c_int), ("gamma", C.c_float), ("lam", C.c_float),
+                ("d_target", C.c_void_p), ("d_values", C.c_void_p), ("d_done_time", C.c_void_p)]
+
+
+def kstep_steps(k, filter=None):
+    """The steps the k-step estimator evaluates its net on (value_estimator._create_steps, agents/networks/value_estimator.py:
+    90-99): s in 1..k that no f of `filter` divides; None or an empty filter keeps all.  -> a list of ints, ascending."""
+    fs = [int(f) for f in (filter if filter is not None else [])]
+    return [s for s in range(1, int(k) + 1) if all(s % f != 0 for f in fs)]
+
+
+def kstep_mask(steps):
+    """The step_mask of replay_gather_steps_dev and kstep_target: bit s for every step s (0..63) of `steps`."""
+    mask = 0
+    for s in steps:
+        if not 0 <= int(s) <= 63:
+            raise ValueError(f"step {s} outside [0, 63]")
+        mask |= 1 << int(s)
+    return mask
+
+
 def ppo_entropy_constants(ppo_epsilon):
     """The two constants of the PPO head's entropy terms, in float64 (agents/networks/ppo_nets.py:175-180): -> (entropy_floor,
     max_entropy) with entropy_floor = -eps log(eps / 39) - (1 - eps) log(1 - eps) and max_entropy = tools.utils.entropy of the
@@ -255,6 +283,8 @@ _SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "tetris_replay_update_prios_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "tetris_replay_gather_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "tetris_replay_gather_steps_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]),
+    "tetris_kstep_target_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_ppo_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_dqn_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_plan_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -736,6 +766,37 @@ class TetrisBatch:
         ring position index[j] + s; mirrored where the entry's flag says so)."""
         self._check(self.lib.tetris_replay_gather_dev(self._h, C.byref(rp) if rp is not None else None, index, int(m), int(steps),
                                                       C.byref(out) if out is not None else None))
+
+    def replay_gather_steps_dev(self, rp, index, m, step_mask, out):
+        """The rows of step_mask's bits (kstep_mask(steps); bit s: ring position index[j] + s) of the k-step views of index int32
+        [m] into out = traj_batch(...) sized for m * n samples, n the number of bits: sample j * n + i = the i-th step."""
+        self._check(self.lib.tetris_replay_gather_steps_dev(self._h, C.byref(rp) if rp is not None else None, index, int(m),
+                                                            int(step_mask) & 0xFFFFFFFFFFFFFFFF, C.byref(out) if out is not None else None))
+
+    # -- k-step target estimator (include/tetris_hip.h: tetris_kstep_target_dev)
+    def kstep_target(self, out, reward, done, target, m, k_step, steps=None, index=None, max_size=0, values_mode=False, n_pieces=7,
+                     n_values=1, used_pieces=None, f16=False, truncate=False, gamma=0.99, lam=0.9, values=None, done_time=None, step_mask=None,
+                     mode=None, flags=0):
+        """The argument struct of kstep_target_dev over raw DEVICE addresses or None: out = Q [m][n][4][10][n_pieces] (values_mode:
+        v [m][n][n_values]) float32 (f16: binary16) for the n steps of `steps` (None: 1..k_step); ring mode: reward float32 / done
+        uint8 = the ring's arrays with index int32 [m] and max_size; array mode (index None, max_size 0): reward / done [m][k_step +
+        1]; target float32 [m], values float32 [m][n], done_time uint8 [m]."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        t = KstepTarget()
+        t.d_out, t.d_reward, t.d_done, t.d_index = val(out), val(reward), val(done), val(index)
+        t.M, t.k_step, t.max_size = int(m), int(k_step), int(max_size)
+        t.step_mask = int(step_mask) if step_mask is not None else kstep_mask(kstep_steps(k_step) if steps is None else steps)
+        t.mode = int(mode) if mode is not None else (KSTEP_V if values_mode else KSTEP_Q)
+        t.n_pieces, t.n_values = int(n_pieces), int(n_values)
+        t.used_pieces = (1 << int(n_pieces)) - 1 if used_pieces is None else int(used_pieces)
+        t.flags = (LOSS_F16 if f16 else 0) | (KSTEP_TRUNCATE if truncate else 0) | int(flags)
+        t.gamma, t.lam = float(gamma), float(lam)
+        t.d_target, t.d_values, t.d_done_time = val(target), val(values), val(done_time)
+        return t
+
+    def kstep_target_dev(self, t):
+        """The k-step targets of a minibatch from the reference net's outputs for its step rows (t = kstep_target(...))."""
+        self._check(self.lib.tetris_kstep_target_dev(self._h, C.byref(t) if t is not None else None))
 
     # -- loss heads (include/tetris_hip.h: tetris_ppo_loss_dev, tetris_dqn_loss_dev)
     def ppo_loss(self, pi, v, action, prob_old, adv, target, grad_pi, grad_v, stats, m, n_pieces=7, n_values=1, valid=None, terms=None,

@@ -115,6 +115,9 @@ struct TrajBatchArgs {
     int steps;
     uint32_t limit;                 // max_size
     const uint8_t* flags;           // [C]
+    // tetris_replay_gather_steps_dev: a non-zero step_mask (popcount = steps) makes it index[j / steps] + the (j % steps)-th set
+    // bit of the mask instead; 0: the first `steps` rows, as above
+    uint64_t step_mask;
 };
 
 struct BatchEntry { uint32_t at; bool valid, mirror; };
@@ -127,12 +130,19 @@ TE_HD BatchEntry batch_index_entry(uint32_t v, uint32_t total) {
     if (!en.valid) { en.at = 0; en.mirror = false; }
     return en;
 }
+// the position of the i-th set bit of a step mask (i < popcount(mask)), ascending
+TE_HD uint32_t batch_step_row(uint64_t mask, uint32_t i) {
+    for (uint32_t n = 0; n < i; n++) mask &= mask - 1u;
+    const uint32_t lo = (uint32_t)mask;
+    return lo ? (uint32_t)ctz32(lo) : 32u + (uint32_t)ctz32((uint32_t)(mask >> 32));
+}
 TE_HD BatchEntry batch_entry(const TrajBatchArgs& ba, int j) {
     BatchEntry en;
     if (ba.steps > 0) {
         const uint32_t base = (uint32_t)ba.index[j / ba.steps];
-        en.valid = base < ba.limit;         // (limit + k_step = C = total: base + j % steps stays inside the ring)
-        en.at = en.valid ? base + (uint32_t)(j % ba.steps) : 0u;
+        const uint32_t i = (uint32_t)(j % ba.steps);
+        en.valid = base < ba.limit;         // (limit + k_step = C = total: base + a row <= k_step stays inside the ring)
+        en.at = en.valid ? base + (ba.step_mask ? batch_step_row(ba.step_mask, i) : i) : 0u;
         en.mirror = en.valid && (ba.flags[en.at] & 1u) != 0;
         return en;
     }

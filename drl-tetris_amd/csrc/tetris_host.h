@@ -23,6 +23,7 @@
 #include "tetris_replay.h"
 #include "tetris_plan_traj.h"
 #include "tetris_loss.h"
+#include "tetris_kstep.h"
 
 namespace te {
 
@@ -467,7 +468,7 @@ static inline int traj_batch_args(const HostShape& s, const tetris_traj* traj, c
     ba.visual = out->d_visual; ba.vector = out->d_vector; ba.piece = out->d_piece; ba.action_out = out->d_action;
     ba.prob_out = out->d_prob; ba.adv_out = out->d_adv; ba.target_out = out->d_target; ba.reward_out = out->d_reward;
     ba.done_out = out->d_done; ba.valid = out->d_valid;
-    ba.steps = 0; ba.limit = 0u; ba.flags = nullptr;
+    ba.steps = 0; ba.limit = 0u; ba.flags = nullptr; ba.step_mask = 0u;
     return TETRIS_OK;
 }
 
@@ -613,14 +614,21 @@ static inline int replay_update_args(const HostShape& s, const tetris_replay* rp
     return TETRIS_OK;
 }
 
-// the gather is tetris_traj_batch_dev's kernel over the ring: ba.m = M * steps samples
-static inline int replay_gather_args(const HostShape& s, const tetris_replay* rp, const int32_t* d_index, int M, int steps, const tetris_traj_batch* out,
-                                     TrajBatchArgs& ba) {
+// the gather is tetris_traj_batch_dev's kernel over the ring: ba.m = M * steps samples — the first `steps` rows of every view
+// (step_mask 0: tetris_replay_gather_dev) or the rows of step_mask's bits (tetris_replay_gather_steps_dev; `steps` is not read)
+static inline int replay_gather_mask_args(const HostShape& s, const tetris_replay* rp, const int32_t* d_index, int M, int steps, uint64_t step_mask,
+                                          const tetris_traj_batch* out, TrajBatchArgs& ba) {
     ReplayRing r;
-    int rc = replay_ring(s, rp, "tetris_replay_gather_dev", true, r);
+    int rc = replay_ring(s, rp, step_mask ? "tetris_replay_gather_steps_dev" : "tetris_replay_gather_dev", true, r);
     if (rc) return rc;
     if (!d_index || !out) return fail(TETRIS_E_ARG, "the index list or the outputs are NULL");
     if (M < 0) return fail(TETRIS_E_ARG, "M < 0");
+    if (step_mask) {
+        if (r.k_step > 63) return fail(TETRIS_E_ARG, "a step list needs k_step <= 63");
+        if (r.k_step < 63 && (step_mask >> (r.k_step + 1))) return fail(TETRIS_E_ARG, "step_mask has a bit above k_step");
+        steps = __builtin_popcountll(step_mask);
+        if (step_mask == (steps == 64 ? ~0ull : (1ull << steps) - 1ull)) step_mask = 0u;          // the first `steps` rows
+    }
     if (steps < 1 || steps > r.k_step + 1) return fail(TETRIS_E_ARG, "steps outside [1, k_step + 1]");
     if ((unsigned long long)M * (unsigned long long)steps >= (1ull << 31)) return fail(TETRIS_E_ARG, "M * steps must be below 2^31");
     ba.m = M * steps; ba.n_slots = s.P; ba.H = s.H;
@@ -631,7 +639,24 @@ static inline int replay_gather_args(const HostShape& s, const tetris_replay* rp
     ba.visual = out->d_visual; ba.vector = out->d_vector; ba.piece = out->d_piece; ba.action_out = out->d_action;
     ba.prob_out = out->d_prob; ba.adv_out = out->d_adv; ba.target_out = out->d_target; ba.reward_out = out->d_reward;
     ba.done_out = out->d_done; ba.valid = out->d_valid;
-    ba.steps = steps; ba.limit = (uint32_t)r.max_size; ba.flags = r.flags;
+    ba.steps = steps; ba.limit = (uint32_t)r.max_size; ba.flags = r.flags; ba.step_mask = step_mask;
+    return TETRIS_OK;
+}
+
+static inline int replay_gather_args(const HostShape& s, const tetris_replay* rp, const int32_t* d_index, int M, int steps, const tetris_traj_batch* out,
+                                     TrajBatchArgs& ba) {
+    return replay_gather_mask_args(s, rp, d_index, M, steps, 0u, out, ba);
+}
+static inline int replay_gather_steps_args(const HostShape& s, const tetris_replay* rp, const int32_t* d_index, int M, uint64_t step_mask,
+                                           const tetris_traj_batch* out, TrajBatchArgs& ba) {
+    if (!step_mask) return fail(TETRIS_E_ARG, "step_mask names no step");
+    return replay_gather_mask_args(s, rp, d_index, M, 0, step_mask, out, ba);
+}
+// A gather over host memory (the CPU build of the bodies: tests/cpu_harness), the product's launch as a loop over slots and samples.
+// tetris_lib_compose.h says which side runs what.
+static inline int traj_batch_run_serial(int n_slots, const TrajBatchArgs& ba) {
+    for (int sl = 0; sl < n_slots; sl++)
+        for (int j = 0; j < ba.m; j++) batch_sample_slot(ba, j, sl);
     return TETRIS_OK;
 }
 
@@ -733,6 +758,48 @@ static inline int loss_run_serial(LossArgs& la) {
         else loss_block_serial(la, blk, (float)d, (float)dnz);
     }
     loss_reduce_serial(la, blocks, (float)d, (float)dnz);
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- k-step target estimator (tetris_kstep.h)
+// the argument rules, then the kernel arguments (all but vals, which without d_values is the caller's scratch)
+static inline int kstep_target_args(const tetris_kstep_target* t, KstepArgs& a) {
+    if (!t) return fail(TETRIS_E_ARG, "the argument struct is NULL");
+    if (!t->d_out || !t->d_reward || !t->d_done || !t->d_target) return fail(TETRIS_E_ARG, "out/reward/done/target are NULL");
+    if (t->M < 0) return fail(TETRIS_E_ARG, "M < 0");
+    if (t->k_step < 1 || t->k_step > KSTEP_MAX) return fail(TETRIS_E_ARG, "k_step must be in [1, 63]");
+    if (!t->step_mask) return fail(TETRIS_E_ARG, "step_mask names no step");
+    if ((t->step_mask & 1u) || (t->k_step < 63 && (t->step_mask >> (t->k_step + 1)))) return fail(TETRIS_E_ARG, "step_mask has a bit outside [1, k_step]");
+    if (t->mode != TETRIS_KSTEP_Q && t->mode != TETRIS_KSTEP_V) return fail(TETRIS_E_ARG, "mode must be TETRIS_KSTEP_Q or TETRIS_KSTEP_V");
+    if (t->n_pieces != 1 && t->n_pieces != 7) return fail(TETRIS_E_ARG, "n_pieces must be 1 or 7");
+    if (t->mode == TETRIS_KSTEP_V && t->n_values != 1 && t->n_values != t->n_pieces) return fail(TETRIS_E_ARG, "n_values must be 1 or n_pieces");
+    if (t->used_pieces <= 0 || (t->used_pieces >> t->n_pieces)) return fail(TETRIS_E_ARG, "used_pieces must name at least one piece and none at or above n_pieces");
+    if (t->flags & ~(TETRIS_LOSS_F16 | TETRIS_KSTEP_TRUNCATE)) return fail(TETRIS_E_ARG, "unknown flag");
+    if (t->d_index ? t->max_size < 1 : t->max_size != 0) return fail(TETRIS_E_ARG, "d_index and max_size >= 1 (the ring) or neither (arrays [M][k_step + 1])");
+    if (t->mode == TETRIS_KSTEP_Q && (((uintptr_t)t->d_out) & 15u)) return fail(TETRIS_E_ARG, "Q must be 16-byte aligned");
+    const int n = __builtin_popcountll(t->step_mask);
+    if ((unsigned long long)t->M * (unsigned long long)n >= (1ull << 31)) return fail(TETRIS_E_ARG, "M * n must be below 2^31");
+    memset(&a, 0, sizeof a);
+    a.M = t->M; a.n = n; a.k = t->k_step; a.K = t->n_pieces; a.W = t->mode == TETRIS_KSTEP_V ? t->n_values : t->n_pieces;
+    a.mode = t->mode; a.f16 = (t->flags & TETRIS_LOSS_F16) ? 1 : 0; a.truncate = (t->flags & TETRIS_KSTEP_TRUNCATE) ? 1 : 0;
+    a.used = (uint32_t)t->used_pieces; a.limit = (uint32_t)t->max_size; a.n_used = (float)__builtin_popcount((unsigned)t->used_pieces);
+    a.step_mask = t->step_mask;
+    a.x = t->d_out; a.reward = t->d_reward; a.done = t->d_done; a.index = t->d_index;
+    a.target = t->d_target; a.values = t->d_values; a.done_time = t->d_done_time;
+    for (int i = 0; i <= a.k; i++) { a.g[i] = (float)pow((double)t->gamma, (double)i); a.l[i] = (float)pow((double)t->lam, (double)i); }
+    return TETRIS_OK;
+}
+// A call over host memory (the CPU build of the bodies: tests/cpu_harness), the product's launches as loops: in Q mode the values
+// of the M n rows, then the samples.  tetris_lib_compose.h says which side runs what.
+static inline int kstep_run_serial(KstepArgs& a) {
+    if (a.M == 0) return TETRIS_OK;
+    std::vector<float> scratch;
+    if (a.mode == KSTEP_Q) {
+        if (!a.values) scratch.resize((size_t)a.M * a.n);
+        a.vals = a.values ? a.values : scratch.data();
+        for (size_t row = 0; row < (size_t)a.M * a.n; row++) kstep_value_row(a, row);
+    }
+    for (int j = 0; j < a.M; j++) kstep_sample(a, (size_t)j);
     return TETRIS_OK;
 }
 

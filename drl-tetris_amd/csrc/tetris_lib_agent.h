@@ -387,6 +387,21 @@ int tetris_replay_gather_dev(tetris_batch* b, const tetris_replay* rp, const int
 
 }  // extern "C"
 
+// ---------------------------------------------------------------- k-step target estimator (tetris_kstep.h)
+// What tetris_kstep_target_dev (tetris_lib_compose.h) runs after the argument rules: in Q mode the values of the M n rows — into
+// d_values, or into the batch's scratch where the caller wants none —, then the samples
+static int launch_kstep(tetris_batch* b, KstepArgs& a) {
+    if (a.M == 0) return TETRIS_OK;
+    int rc;
+    if (a.mode == KSTEP_Q) {
+        if (!a.values && (rc = b->kstep_values.ensure((size_t)a.M * a.n, b->stream))) return rc;
+        a.vals = a.values ? a.values : b->kstep_values.d;
+    }
+    if ((rc = enqueue(b, Enqueue::STATE))) return rc;                // (the batch's scratch)
+    if (a.mode == KSTEP_Q && (rc = launch(b, k_kstep_values, dim3((unsigned)kstep_value_blocks(a)), dim3(KSTEP_VALUE_THREADS), 0, a))) return rc;
+    return launch(b, k_kstep_estimate, dim3(blocks_for(a.M, KSTEP_THREADS)), dim3(KSTEP_THREADS), 0, a);
+}
+
 // ---------------------------------------------------------------- loss heads (tetris_loss.h)
 // What tetris_ppo_loss_dev, tetris_dqn_loss_dev and tetris_plan_loss_dev (tetris_lib_compose.h) run after the argument rules, at most
 // three launches: the count of D / Dnz where a mask, weights or a window's index list are given, the head, the statistics

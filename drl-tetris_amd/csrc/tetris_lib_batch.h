@@ -249,9 +249,11 @@ struct tetris_batch {
     Scratch<uint32_t> replay_offsets, replay_sort;
     // the loss heads: the words D and Dnz and the workgroups' partial rows of the statistics (grown on demand)
     Scratch<uint32_t> loss_scratch;
+    // tetris_kstep_target_dev in Q mode without d_values: the values of the M n rows (grown on demand)
+    Scratch<float> kstep_values;
     void release_scratch() {
         plan_slabs.release(); iota.release(); plan_status.release(); policy_scores.release(); words_before.release();
-        select_blocks.release(); replay_offsets.release(); replay_sort.release(); loss_scratch.release();
+        select_blocks.release(); replay_offsets.release(); replay_sort.release(); loss_scratch.release(); kstep_values.release();
     }
 };
 

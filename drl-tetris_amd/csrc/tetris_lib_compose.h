@@ -8,6 +8,12 @@
 // the same bodies (tetris_host.h: loss_run_serial).
 template <class B>
 static int launch_loss(B*, LossArgs& la) { return loss_run_serial(la); }
+// (the k-step target estimator likewise: launch_kstep of tetris_lib_agent.h, or kstep_run_serial; and the gather of a step list:
+// launch_traj_batch of tetris_lib_agent.h, or traj_batch_run_serial)
+template <class B>
+static int launch_kstep(B*, KstepArgs& a) { return kstep_run_serial(a); }
+template <class B>
+static int launch_traj_batch(B* b, const TrajBatchArgs& ba) { return traj_batch_run_serial(b->P, ba); }
 
 extern "C" {
 
@@ -94,6 +100,23 @@ int tetris_plan_loss_dev(tetris_batch* b, const tetris_traj_plan* plan, const te
     LossArgs la;
     if ((rc = plan_loss_args(shape_of(b), plan, l, la))) return rc;
     return launch_loss(b, la);
+}
+
+int tetris_replay_gather_steps_dev(tetris_batch* b, const tetris_replay* rp, const int32_t* d_index, int M, uint64_t step_mask,
+                                   const tetris_traj_batch* out) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    TrajBatchArgs ba;
+    if ((rc = replay_gather_steps_args(shape_of(b), rp, d_index, M, step_mask, out, ba))) return rc;
+    return launch_traj_batch(b, ba);
+}
+
+int tetris_kstep_target_dev(tetris_batch* b, const tetris_kstep_target* t) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    KstepArgs a;
+    if ((rc = kstep_target_args(t, a))) return rc;
+    return launch_kstep(b, a);
 }
 
 int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,

@@ -542,6 +542,50 @@ class TorchEnv:
             return stats[2].clone(), (grad_Q,), (stats, new_prio)
         return self._head_function().apply(run, Q)
 
+    # ---- k-step target estimator (include/tetris_hip.h: tetris_kstep_target_dev): model.compute_targets
+    # (agents/sventon_agent/sventon_agent_dqn_trainer.py:49-59, agents/networks/value_estimator.py:51-88)
+    def _kstep(self, cache, out, reward, done, index, max_size, k_step, steps, gamma, lam, truncate, used_pieces, values):
+        """the checks and the call both modes share -> target float32 [M], reused per M in `cache`"""
+        from . import capi
+        torch = self.torch
+        steps = capi.kstep_steps(k_step) if steps is None else [int(s) for s in steps]
+        n = len(steps)
+        assert n >= 1, "no step"
+        assert out.dtype in (torch.float32, torch.float16) and out.is_cuda and out.is_contiguous(), "the net's output is a contiguous float32 or float16 device tensor"
+        if values:
+            assert out.dim() == 2 and out.shape[1] in (1, 7), "v must be [M * n, 7 or 1]"
+            K = V = int(out.shape[1])
+        else:
+            assert out.dim() == 4 and tuple(out.shape[1:3]) == (4, 10) and out.shape[3] in (1, 7), "Q must be [M * n, 4, 10, 7 or 1]"
+            K, V = int(out.shape[3]), 1
+        assert out.shape[0] % n == 0, "the net's output has a row per (sample, step)"
+        M = out.shape[0] // n
+        for t, dt in ((reward, torch.float32), (done, torch.uint8)):
+            assert t.dtype == dt and t.is_cuda and t.is_contiguous()
+        if index is None:
+            assert reward.numel() == M * (k_step + 1) and done.numel() == M * (k_step + 1), "reward / done must be [M, k_step + 1]"
+        else:
+            assert index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.numel() == M
+        if M not in cache:
+            cache[M] = torch.zeros(max(M, 1), dtype=torch.float32, device=self.dev)
+        target = cache[M]
+        p = self._ptr
+        t = self.b.kstep_target(p(out), p(reward), p(done), p(target), M, k_step, steps=steps, index=p(index), max_size=max_size,
+                                values_mode=values, n_pieces=K, n_values=V, used_pieces=used_pieces, f16=out.dtype == torch.float16,
+                                truncate=truncate, gamma=gamma, lam=lam)
+        self.b.kstep_target_dev(t)
+        return target[:M]
+
+    def kstep_targets(self, out, reward, done, steps=None, k_step=None, gamma=0.99, lam=0.9, truncate=False, used_pieces=None, values=False):
+        """The k-step targets of M samples in array mode, for callers without a ring: out = Q [M * n, 4, 10, K] (values=True: v
+        [M * n, V]) float32 or float16, the net's output for the n steps of `steps` (None: 1..k_step) of every sample, sample-major;
+        reward float32 / done uint8 [M, k_step + 1], the samples' rows 0..k_step (k_step None: from reward's shape).  -> float32
+        [M], reused per M.  No host synchronisation."""
+        k = int(reward.shape[1]) - 1 if k_step is None else int(k_step)
+        if not hasattr(self, "_kstep_targets"):
+            self._kstep_targets = {}
+        return self._kstep(self._kstep_targets, out, reward, done, None, 0, k, steps, gamma, lam, truncate, used_pieces, values)
+
 
 class Trajectory:
     """A trajectory window of a TorchEnv: T = capacity rows of n games, time-major device tensors
@@ -750,10 +794,14 @@ class Replay:
     def gather(self, index, steps=1):
         """The k-step views of index (int32 device tensor [M]; -1: none) -> TrajectoryBatch(visual [S, M, steps, H, 10], vector [S,
         M, steps, 12], piece [S, M, steps], action [M, steps, 3], prob, adv, target, reward, done, valid [M, steps]) device tensors,
-        reused per (M, steps); 1 <= steps <= k_step + 1."""
+        reused per (M, steps); 1 <= steps <= k_step + 1.  steps may also be a sequence of step numbers within [0, k_step]
+        (capi.kstep_steps: the rows the target estimator's net is evaluated on): the same arrays with len(steps) in the place of
+        steps, in ascending order of the step, reused per (M, tuple of the steps)."""
         from collections import namedtuple
         env, torch = self.env, self.env.torch
         assert index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.dim() == 1
+        if not isinstance(steps, int):
+            return self._gather_steps(index, tuple(sorted({int(s) for s in steps})))
         M, K, S, H = index.numel(), int(steps), env.b.n_players, env.b.height
         assert 1 <= K <= self.k_step + 1, "steps outside [1, k_step + 1]"
         if (M, K) not in self._batches:
@@ -766,6 +814,34 @@ class Replay:
         t, out = self._batches[(M, K)]
         env.b.replay_gather_dev(self._rp, env._ptr(index), M, K, out)
         return t
+
+    def _gather_steps(self, index, steps):
+        from collections import namedtuple
+        from . import capi
+        env, torch = self.env, self.env.torch
+        M, K, S, H = index.numel(), len(steps), env.b.n_players, env.b.height
+        assert K >= 1 and 0 <= steps[0] and steps[-1] <= self.k_step <= 63, "steps outside [0, k_step], or k_step above 63"
+        if (M, steps) not in self._batches:
+            u8, f32 = dict(dtype=torch.uint8, device=env.dev), dict(dtype=torch.float32, device=env.dev)
+            kind = namedtuple("TrajectoryBatch", "visual vector piece action prob adv target reward done valid")
+            t = kind(torch.zeros(S, M, K, H, 10, **u8), torch.zeros(S, M, K, 12, **u8), torch.zeros(S, M, K, **u8), torch.zeros(M, K, 3, **u8),
+                     torch.zeros(M, K, **f32), torch.zeros(M, K, **f32), torch.zeros(M, K, **f32), torch.zeros(M, K, **f32), torch.zeros(M, K, **u8),
+                     torch.zeros(M, K, **u8))
+            self._batches[(M, steps)] = (t, env.b.traj_batch(*[env._ptr(x) for x in t]), capi.kstep_mask(steps))
+        t, out, mask = self._batches[(M, steps)]
+        env.b.replay_gather_steps_dev(self._rp, env._ptr(index), M, mask, out)
+        return t
+
+    def targets(self, index, out, steps=None, gamma=0.99, lam=0.9, truncate=False, used_pieces=None, values=False):
+        """model.compute_targets for the samples `index` (int32 device tensor [M]) from the reference net's output for their step
+        rows: out = Q [M * n, 4, 10, K] (values=True: v [M * n, V]) float32 or float16 for the n steps of `steps` (None: 1..k_step;
+        capi.kstep_steps(k, filter)) as gather(index, steps=steps) lays them out.  Rewards and dones are read in the ring behind
+        index[j]: they are not gathered.  -> float32 [M], reused per M; an index outside [0, max_size) gives 0.  No host
+        synchronisation."""
+        if not hasattr(self, "_targets"):
+            self._targets = {}
+        return self.env._kstep(self._targets, out, self.reward, self.done, index, self.max_size, self.k_step, steps, gamma, lam, truncate,
+                               used_pieces, values)
 
     def update_prios(self, index, prio):
         """prio[index[j]] = prio[j] (update_prios); -1 entries are skipped"""
