@@ -146,6 +146,26 @@ class KstepTarget(C.Structure):
                 ("d_target", C.c_void_p), ("d_values", C.c_void_p), ("d_done_time", C.c_void_p)]
 
 
+HEAD_MEAN, HEAD_MAX, HEAD_NONE = 0, 1, 2              # TETRIS_HEAD_MEAN / _MAX / _NONE
+HEAD_F16, HEAD_VALUE_F16 = 1, 2                        # TETRIS_HEAD_F16 / _VALUE_F16
+HEAD_MODES = {"mean": HEAD_MEAN, "max": HEAD_MAX}      # any other string: normalize_advantages' fall-through, HEAD_NONE
+
+
+class QHead(C.Structure):
+    """mirrors `struct tetris_q_head` (include/tetris_hip.h)"""
+    _fields_ = [("d_a", C.c_void_p), ("d_v", C.c_void_p), ("d_grad_Q", C.c_void_p), ("M", C.c_int), ("n_pieces", C.c_int),
+                ("n_values", C.c_int), ("mode", C.c_int), ("separate_piece_values", C.c_int), ("used_pieces", C.c_int), ("flags", C.c_int),
+                ("advantage_range", C.c_float), ("d_Q", C.c_void_p), ("d_V", C.c_void_p), ("d_A", C.c_void_p), ("d_grad_a", C.c_void_p),
+                ("d_grad_v", C.c_void_p)]
+
+
+class PolicyHead(C.Structure):
+    """mirrors `struct tetris_policy_head` (include/tetris_hip.h)"""
+    _fields_ = [("d_x", C.c_void_p), ("d_w", C.c_void_p), ("d_grad_pi", C.c_void_p), ("d_grad_v", C.c_void_p), ("M", C.c_int),
+                ("n_pieces", C.c_int), ("n_values", C.c_int), ("flags", C.c_int), ("d_pi", C.c_void_p), ("d_v", C.c_void_p),
+                ("d_grad_x", C.c_void_p), ("d_grad_w", C.c_void_p)]
+
+
 def kstep_steps(k, filter=None):
     """The steps the k-step estimator evaluates its net on (value_estimator._create_steps, agents/networks/value_estimator.py:
     90-99): s in 1..k that no f of `filter` divides; None or an empty filter keeps all.  -> a list of ints, ascending."""
@@ -285,6 +305,10 @@ _SIGNATURES = {
     "tetris_replay_gather_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tetris_replay_gather_steps_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]),
     "tetris_kstep_target_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_q_head_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_q_head_grad_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_policy_head_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_policy_head_grad_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_ppo_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_dqn_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_plan_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -797,6 +821,63 @@ class TetrisBatch:
     def kstep_target_dev(self, t):
         """The k-step targets of a minibatch from the reference net's outputs for its step rows (t = kstep_target(...))."""
         self._check(self.lib.tetris_kstep_target_dev(self._h, C.byref(t) if t is not None else None))
+
+    # -- output heads (include/tetris_hip.h: tetris_q_head_dev, tetris_policy_head_dev and their _grad_dev)
+    def used_pieces(self, n_pieces=7):
+        """The used_pieces mask of the batch's piece set (create_used_pieces_mask): bit p for every piece the games deal; 1 for a
+        net with one piece plane."""
+        if int(n_pieces) == 1:
+            return 1
+        mask = 0
+        for p in self.piece_map:
+            mask |= 1 << int(p)
+        return mask
+
+    def q_head(self, a, m, v=None, n_pieces=7, n_values=1, mode="mean", advantage_range=1.0, separate_piece_values=True, used_pieces=None,
+               f16=False, value_f16=False, Q=None, V=None, A=None, grad_Q=None, grad_a=None, grad_v=None, flags=0):
+        """The argument struct of q_head_dev / q_head_grad_dev over raw DEVICE addresses or None: a, Q, A, grad_Q, grad_a
+        [m][4][10][n_pieces] float32 (f16: binary16), v, grad_v [m][n_values] float32 (value_f16: binary16) or None, V float32 [m].
+        mode: "mean", "max", any other string (no normalisation) or a TETRIS_HEAD_* number; used_pieces None: the batch's piece set."""
+        val = lambda x: x.value if isinstance(x, C.c_void_p) else x               # noqa: E731
+        h = QHead()
+        h.d_a, h.d_v, h.d_grad_Q = val(a), val(v), val(grad_Q)
+        h.M, h.n_pieces, h.n_values = int(m), int(n_pieces), int(n_values)
+        h.mode = HEAD_MODES.get(mode, HEAD_NONE) if isinstance(mode, str) else int(mode)
+        h.separate_piece_values = 1 if separate_piece_values else 0
+        h.used_pieces = self.used_pieces(n_pieces) if used_pieces is None else int(used_pieces)
+        h.flags = (HEAD_F16 if f16 else 0) | (HEAD_VALUE_F16 if value_f16 else 0) | int(flags)
+        h.advantage_range = float(advantage_range)
+        h.d_Q, h.d_V, h.d_A, h.d_grad_a, h.d_grad_v = val(Q), val(V), val(A), val(grad_a), val(grad_v)
+        return h
+
+    def q_head_dev(self, h):
+        """Q, V and (where given) A of a minibatch from the raw streams a and v (h = q_head(...))."""
+        self._check(self.lib.tetris_q_head_dev(self._h, C.byref(h) if h is not None else None))
+
+    def q_head_grad_dev(self, h):
+        """grad_a and grad_v from grad_Q (h = q_head(...))."""
+        self._check(self.lib.tetris_q_head_grad_dev(self._h, C.byref(h) if h is not None else None))
+
+    def policy_head(self, m, pi, v, n_pieces=7, n_values=1, x=None, w=None, grad_pi=None, grad_v=None, grad_x=None, grad_w=None, f16=False,
+                    value_f16=False, flags=0):
+        """The argument struct of policy_head_dev / policy_head_grad_dev over raw DEVICE addresses or None: x, pi, grad_pi, grad_x
+        [m][4][10][n_pieces] float32 (f16: binary16); w, grad_w [m][n_values], n_values = 1 or n_pieces + 1, and v, grad_v
+        [m][1 or n_pieces] float32 (value_f16: binary16)."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        h = PolicyHead()
+        h.d_x, h.d_w, h.d_grad_pi, h.d_grad_v = val(x), val(w), val(grad_pi), val(grad_v)
+        h.M, h.n_pieces, h.n_values = int(m), int(n_pieces), int(n_values)
+        h.flags = (HEAD_F16 if f16 else 0) | (HEAD_VALUE_F16 if value_f16 else 0) | int(flags)
+        h.d_pi, h.d_v, h.d_grad_x, h.d_grad_w = val(pi), val(v), val(grad_x), val(grad_w)
+        return h
+
+    def policy_head_dev(self, h):
+        """pi and v of a minibatch from the logits x and the value stream w (h = policy_head(...))."""
+        self._check(self.lib.tetris_policy_head_dev(self._h, C.byref(h) if h is not None else None))
+
+    def policy_head_grad_dev(self, h):
+        """grad_x and grad_w from the stored pi, v and grad_pi, grad_v (h = policy_head(...))."""
+        self._check(self.lib.tetris_policy_head_grad_dev(self._h, C.byref(h) if h is not None else None))
 
     # -- loss heads (include/tetris_hip.h: tetris_ppo_loss_dev, tetris_dqn_loss_dev)
     def ppo_loss(self, pi, v, action, prob_old, adv, target, grad_pi, grad_v, stats, m, n_pieces=7, n_values=1, valid=None, terms=None,

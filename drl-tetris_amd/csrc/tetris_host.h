@@ -24,6 +24,7 @@
 #include "tetris_plan_traj.h"
 #include "tetris_loss.h"
 #include "tetris_kstep.h"
+#include "tetris_head.h"
 
 namespace te {
 
@@ -800,6 +801,67 @@ static inline int kstep_run_serial(KstepArgs& a) {
         for (size_t row = 0; row < (size_t)a.M * a.n; row++) kstep_value_row(a, row);
     }
     for (int j = 0; j < a.M; j++) kstep_sample(a, (size_t)j);
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- output heads (tetris_head.h)
+// the rules both heads share, then the kernel arguments.  `big` are the [M][4][10][K] arrays of the call.
+static inline int head_common_check(int M, int K, int flags, const void* const* big, int n_big) {
+    if (M < 1) return fail(TETRIS_E_ARG, "M < 1");
+    if (K != 1 && K != 7) return fail(TETRIS_E_ARG, "n_pieces must be 1 or 7");
+    if (flags & ~(TETRIS_HEAD_F16 | TETRIS_HEAD_VALUE_F16)) return fail(TETRIS_E_ARG, "unknown flag");
+    for (int i = 0; i < n_big; i++)
+        if (((uintptr_t)big[i]) & 15u) return fail(TETRIS_E_ARG, "the [M][4][10][K] arrays must be 16-byte aligned");
+    return TETRIS_OK;
+}
+static inline int q_head_args(const tetris_q_head* q, int grad, HeadArgs& h) {
+    if (!q) return fail(TETRIS_E_ARG, "the argument struct is NULL");
+    if (!q->d_a) return fail(TETRIS_E_ARG, "a is NULL");
+    if (grad ? !q->d_grad_Q || !q->d_grad_a : !q->d_Q || !q->d_V) return fail(TETRIS_E_ARG, grad ? "grad_Q/grad_a are NULL" : "Q/V are NULL");
+    if (grad && q->d_v && !q->d_grad_v) return fail(TETRIS_E_ARG, "grad_v is NULL where v is given");
+    const void* const big[3] = {q->d_a, grad ? q->d_grad_Q : q->d_Q, grad ? q->d_grad_a : q->d_A};
+    int rc = head_common_check(q->M, q->n_pieces, q->flags, big, 3);
+    if (rc) return rc;
+    if (q->d_v && q->n_values != 1 && q->n_values != q->n_pieces) return fail(TETRIS_E_ARG, "n_values must be 1 or n_pieces");
+    if (q->mode != TETRIS_HEAD_MEAN && q->mode != TETRIS_HEAD_MAX && q->mode != TETRIS_HEAD_NONE) return fail(TETRIS_E_ARG, "mode must be TETRIS_HEAD_MEAN, _MAX or _NONE");
+    if (q->used_pieces <= 0) return fail(TETRIS_E_ARG, "used_pieces names no piece");
+    if (q->used_pieces >> q->n_pieces) return fail(TETRIS_E_ARG, "used_pieces has a bit at or above n_pieces");
+    memset(&h, 0, sizeof h);
+    h.head = HEAD_Q; h.grad = grad;
+    h.M = q->M; h.K = q->n_pieces; h.W = q->d_v ? q->n_values : 0;
+    h.mode = q->mode; h.separate = q->separate_piece_values ? 1 : 0;
+    h.f16 = (q->flags & TETRIS_HEAD_F16) ? 1 : 0; h.v_f16 = (q->flags & TETRIS_HEAD_VALUE_F16) ? 1 : 0;
+    h.mask = (uint32_t)q->used_pieces; h.U = (float)__builtin_popcount((unsigned)q->used_pieces); h.rho = q->advantage_range;
+    h.x = q->d_a; h.v = q->d_v;
+    if (grad) { h.g = q->d_grad_Q; h.out = q->d_grad_a; h.out_v = q->d_v ? q->d_grad_v : nullptr; }
+    else { h.out = q->d_Q; h.out_A = q->d_A; h.V = q->d_V; }
+    return TETRIS_OK;
+}
+static inline int policy_head_args(const tetris_policy_head* p, int grad, HeadArgs& h) {
+    if (!p) return fail(TETRIS_E_ARG, "the argument struct is NULL");
+    if (!p->d_pi || !p->d_v) return fail(TETRIS_E_ARG, "pi/v are NULL");
+    if (grad ? !p->d_grad_pi || !p->d_grad_v || !p->d_grad_x || !p->d_grad_w : !p->d_x || !p->d_w)
+        return fail(TETRIS_E_ARG, grad ? "grad_pi/grad_v/grad_x/grad_w are NULL" : "x/w are NULL");
+    const void* const big[3] = {p->d_pi, grad ? p->d_grad_pi : p->d_x, grad ? p->d_grad_x : nullptr};
+    int rc = head_common_check(p->M, p->n_pieces, p->flags, big, 3);
+    if (rc) return rc;
+    if (p->n_values != 1 && p->n_values != p->n_pieces + 1) return fail(TETRIS_E_ARG, "n_values must be 1 or n_pieces + 1");
+    memset(&h, 0, sizeof h);
+    h.head = HEAD_POLICY; h.grad = grad;
+    h.M = p->M; h.K = p->n_pieces; h.W = p->n_values;
+    h.f16 = (p->flags & TETRIS_HEAD_F16) ? 1 : 0; h.v_f16 = (p->flags & TETRIS_HEAD_VALUE_F16) ? 1 : 0;
+    h.mask = (1u << p->n_pieces) - 1u; h.U = (float)p->n_pieces; h.rho = 1.0f;
+    if (grad) { h.x = p->d_pi; h.v = p->d_v; h.g = p->d_grad_pi; h.gv = p->d_grad_v; h.out = p->d_grad_x; h.out_v = p->d_grad_w; }
+    else { h.x = p->d_x; h.v = p->d_w; h.out = p->d_pi; h.out_v = p->d_v; }
+    return TETRIS_OK;
+}
+// A call over host memory (the CPU build of the bodies: tests/cpu_harness), the product's one launch as a loop over the samples.
+// tetris_lib_compose.h says which side runs what.
+static inline int head_run_serial(const HeadArgs& h) {
+    for (int m = 0; m < h.M; m++) {
+        if (h.head == HEAD_Q) head_q_sample_serial(h, (size_t)m);
+        else head_policy_sample_serial(h, (size_t)m);
+    }
     return TETRIS_OK;
 }
 

@@ -402,6 +402,16 @@ static int launch_kstep(tetris_batch* b, KstepArgs& a) {
     return launch(b, k_kstep_estimate, dim3(blocks_for(a.M, KSTEP_THREADS)), dim3(KSTEP_THREADS), 0, a);
 }
 
+// ---------------------------------------------------------------- output heads (tetris_head.h)
+// What the four head entry points (tetris_lib_compose.h) run after the argument rules: one launch, a workgroup per HEAD_BLOCK samples
+static int launch_head(tetris_batch* b, const HeadArgs& h) {
+    int rc = enqueue(b, Enqueue::CALLER);
+    if (rc) return rc;
+    const dim3 grid((unsigned)head_blocks(h.M)), block(HEAD_THREADS);
+    if (h.head == HEAD_Q) return h.grad ? launch(b, k_q_head_grad, grid, block, 0, h) : launch(b, k_q_head, grid, block, 0, h);
+    return h.grad ? launch(b, k_policy_head_grad, grid, block, 0, h) : launch(b, k_policy_head, grid, block, 0, h);
+}
+
 // ---------------------------------------------------------------- loss heads (tetris_loss.h)
 // What tetris_ppo_loss_dev, tetris_dqn_loss_dev and tetris_plan_loss_dev (tetris_lib_compose.h) run after the argument rules, at most
 // three launches: the count of D / Dnz where a mask, weights or a window's index list are given, the head, the statistics

@@ -14,6 +14,9 @@ template <class B>
 static int launch_kstep(B*, KstepArgs& a) { return kstep_run_serial(a); }
 template <class B>
 static int launch_traj_batch(B* b, const TrajBatchArgs& ba) { return traj_batch_run_serial(b->P, ba); }
+// (and the output heads: launch_head of tetris_lib_agent.h, or head_run_serial)
+template <class B>
+static int launch_head(B*, const HeadArgs& h) { return head_run_serial(h); }
 
 extern "C" {
 
@@ -117,6 +120,38 @@ int tetris_kstep_target_dev(tetris_batch* b, const tetris_kstep_target* t) {
     KstepArgs a;
     if ((rc = kstep_target_args(t, a))) return rc;
     return launch_kstep(b, a);
+}
+
+int tetris_q_head_dev(tetris_batch* b, const tetris_q_head* q) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    HeadArgs h;
+    if ((rc = q_head_args(q, 0, h))) return rc;
+    return launch_head(b, h);
+}
+
+int tetris_q_head_grad_dev(tetris_batch* b, const tetris_q_head* q) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    HeadArgs h;
+    if ((rc = q_head_args(q, 1, h))) return rc;
+    return launch_head(b, h);
+}
+
+int tetris_policy_head_dev(tetris_batch* b, const tetris_policy_head* p) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    HeadArgs h;
+    if ((rc = policy_head_args(p, 0, h))) return rc;
+    return launch_head(b, h);
+}
+
+int tetris_policy_head_grad_dev(tetris_batch* b, const tetris_policy_head* p) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    HeadArgs h;
+    if ((rc = policy_head_args(p, 1, h))) return rc;
+    return launch_head(b, h);
 }
 
 int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,

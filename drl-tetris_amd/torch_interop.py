@@ -542,6 +542,105 @@ class TorchEnv:
             return stats[2].clone(), (grad_Q,), (stats, new_prio)
         return self._head_function().apply(run, Q)
 
+    # ---- output heads (include/tetris_hip.h: tetris_q_head_dev, tetris_policy_head_dev and their _grad_dev): from a trunk's raw
+    # streams to Q / V / A (network_utils.qva_from_raw_streams) and to pi / v (ppo_nets.py:24-33), differentiable
+    def _head_streams(self, big, small, widths, what):
+        """the checks both heads share -> (M, K, width of `small` or 0)"""
+        torch = self.torch
+        assert big.dtype in (torch.float32, torch.float16) and big.is_cuda, f"{what[0]} is a float32 or float16 device tensor"
+        assert big.dim() == 4 and tuple(big.shape[1:3]) == (4, 10) and big.shape[3] in (1, 7) and big.shape[0] >= 1, f"{what[0]} must be [M, 4, 10, 7 or 1]"
+        M, K = int(big.shape[0]), int(big.shape[3])
+        if small is None:
+            return M, K, 0
+        assert small.dtype in (torch.float32, torch.float16) and small.is_cuda, f"{what[1]} is a float32 or float16 device tensor"
+        assert small.dim() == 2 and small.shape[0] == M and small.shape[1] in widths(K), f"{what[1]} must be [M, {' or '.join(str(w) for w in widths(K))}]"
+        return M, K, int(small.shape[1])
+
+    def _head_functions(self):
+        """the two torch.autograd.Functions: forward runs a head into the reused output tensors, backward its _grad entry point"""
+        torch = self.torch
+        if getattr(self, "_head_fns", None) is not None:
+            return self._head_fns
+        env, p = self, self._ptr
+
+        class QHead(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, a, v, cfg):
+                a, v = a.detach().contiguous(), None if v is None else v.detach().contiguous()
+                M, K, Kv = env._head_streams(a, v, lambda K: (1, K), ("a", "v"))
+                vdt = a.dtype if v is None else v.dtype
+
+                def make(cap):
+                    big = lambda: torch.zeros(cap, 4, 10, K, dtype=a.dtype, device=env.dev)                      # noqa: E731
+                    return big(), torch.zeros(cap, dtype=torch.float32, device=env.dev), big(), big(), torch.zeros(cap, max(Kv, 1), dtype=vdt, device=env.dev)
+                Q, V, A, grad_a, grad_v = (t[:M] for t in env._loss_buffers(("q_head", K, Kv, a.dtype, vdt), M, make))
+                kw = dict(n_pieces=K, n_values=max(Kv, 1), mode=cfg["mode"], advantage_range=cfg["advantage_range"],
+                          separate_piece_values=cfg["separate_piece_values"], used_pieces=cfg["pieces"], f16=a.dtype == torch.float16,
+                          value_f16=vdt == torch.float16)
+                env.b.q_head_dev(env.b.q_head(p(a), M, v=p(v), Q=p(Q), V=p(V), A=p(A) if cfg["A"] else None, **kw))
+                ctx.a, ctx.v, ctx.kw, ctx.grads = a, v, kw, (grad_a, grad_v)
+                ctx.mark_non_differentiable(V, A)
+                return Q, V, A
+
+            @staticmethod
+            def backward(ctx, grad_Q, *unused):
+                a, v, (grad_a, grad_v) = ctx.a, ctx.v, ctx.grads
+                grad_Q = (torch.zeros_like(a) if grad_Q is None else grad_Q.to(a.dtype)).contiguous()
+                env.b.q_head_grad_dev(env.b.q_head(p(a), a.shape[0], v=p(v), grad_Q=p(grad_Q), grad_a=p(grad_a),
+                                                   grad_v=None if v is None else p(grad_v), **ctx.kw))
+                return grad_a, None if v is None else grad_v, None
+
+        class PolicyHead(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, w):
+                x, w = x.detach().contiguous(), w.detach().contiguous()
+                M, K, W = env._head_streams(x, w, lambda K: (1, K + 1), ("x", "w"))
+                V = 1 if W == 1 else K
+
+                def make(cap):
+                    big = lambda: torch.zeros(cap, 4, 10, K, dtype=x.dtype, device=env.dev)                      # noqa: E731
+                    return big(), torch.zeros(cap, V, dtype=w.dtype, device=env.dev), big(), torch.zeros(cap, W, dtype=w.dtype, device=env.dev)
+                pi, v, grad_x, grad_w = (t[:M] for t in env._loss_buffers(("policy_head", K, W, x.dtype, w.dtype), M, make))
+                kw = dict(n_pieces=K, n_values=W, f16=x.dtype == torch.float16, value_f16=w.dtype == torch.float16)
+                env.b.policy_head_dev(env.b.policy_head(M, p(pi), p(v), x=p(x), w=p(w), **kw))
+                ctx.out, ctx.kw, ctx.grads = (pi, v), kw, (grad_x, grad_w)
+                return pi, v
+
+            @staticmethod
+            def backward(ctx, grad_pi, grad_v):
+                (pi, v), (grad_x, grad_w) = ctx.out, ctx.grads
+                grad_pi = (torch.zeros_like(pi) if grad_pi is None else grad_pi.to(pi.dtype)).contiguous()
+                grad_v = (torch.zeros_like(v) if grad_v is None else grad_v.to(v.dtype)).contiguous()
+                env.b.policy_head_grad_dev(env.b.policy_head(pi.shape[0], p(pi), p(v), grad_pi=p(grad_pi), grad_v=p(grad_v), grad_x=p(grad_x),
+                                                             grad_w=p(grad_w), **ctx.kw))
+                return grad_x, grad_w
+        self._head_fns = (QHead, PolicyHead)
+        return self._head_fns
+
+    def q_head(self, a, v=None, mode="mean", advantage_range=1.0, separate_piece_values=True, pieces=None, A=False):
+        """The DQN nets' output head (qva_from_raw_streams as base_architecture.py:53-62 calls it) from a trunk's raw streams: a =
+        _A [M, 4, 10, K] and v = _V [M, 1 or K] or None (prio_qnet's full_network=False: 0), float32 or float16, K = 7 or 1.
+        mode "mean" / "max" / anything else (no normalisation), advantage_range and separate_piece_values are the reference's
+        settings; pieces = the used-piece mask (bit p), None: the batch's piece set.  -> (Q like a, V float32 [M][, A like a with
+        A=True]), differentiable through Q with respect to a and v; V and A carry no gradient (the trainers differentiate Q only).
+            te.select_eval(te.q_head(*qnet(visual, vector))[0], ...); te.dqn_loss(te.q_head(*qnet(mb.visual, mb.vector))[0], ...)
+        Device tensors, reused by every call with the same K, width of v and element types (the leading M samples of one set that
+        grows to the largest M seen): use Q — select, loss, targets — before the next q_head of the same shapes; backward needs only
+        a and v, which it recomputes from.  Nothing waits for the GPU."""
+        cfg = dict(mode=mode, advantage_range=float(advantage_range), separate_piece_values=bool(separate_piece_values),
+                   pieces=self.b.used_pieces(a.shape[3]) if pieces is None else int(pieces), A=bool(A))
+        Q, V, A_out = self._head_functions()[0].apply(a, v, cfg)
+        return (Q, V, A_out) if A else (Q, V)
+
+    def policy_head(self, x, w):
+        """The PPO nets' output head (ppo_nets.py:24-33) from a trunk's raw streams: x = the logits [M, 4, 10, K] as keyboard_conv's
+        concat lays them out, w = the value stream [M, 1 or K + 1], float32 or float16.  -> (pi like x: action_softmax over the 40
+        (r, t) of each piece; v [M, 1 or K] like w: tanh of w_0 plus the mean-free piece values), the shapes ppo_loss takes:
+            te.ppo_loss(*te.policy_head(*net(mb.visual, mb.vector)), mb.action, mb.prob, mb.adv, mb.target, mb.valid, ...)
+        Differentiable with respect to x and w.  Device tensors, reused as q_head's are; backward reads the stored pi and v: call it
+        before the next policy_head of the same shapes.  Nothing waits for the GPU."""
+        return self._head_functions()[1].apply(x, w)
+
     # ---- k-step target estimator (include/tetris_hip.h: tetris_kstep_target_dev): model.compute_targets
     # (agents/sventon_agent/sventon_agent_dqn_trainer.py:49-59, agents/networks/value_estimator.py:51-88)
     def _kstep(self, cache, out, reward, done, index, max_size, k_step, steps, gamma, lam, truncate, used_pieces, values):

@@ -991,6 +991,84 @@ typedef struct tetris_kstep_target {
 } tetris_kstep_target;
 int tetris_kstep_target_dev(tetris_batch *b, const tetris_kstep_target *a);
 
+/* ---- output heads: from a trunk's raw streams to Q / V / A and to pi / v, with their backward -------------------------------
+ * replaces: the output-head arithmetic of the reference's networks and autograd's backward through it.  DQN nets:
+ * qva_from_raw_streams (agents/networks/network_utils.py:100-104) as base_architecture.py:53-62 calls it — advantage_range * _A
+ * through normalize_advantages (network_utils.py:8-35) in mode "mean" or "max" with the used-piece mask, tanh, Q = _V + A,
+ * V = q_to_v(Q).  PPO nets (ppo_nets.py:24-33): pi = action_softmax (network_utils.py:120-125) over the 40 (r, t) of each piece,
+ * v = normalize_advantages(_V, tanh, axis=3, inplace=True) of the [M, K + 1] value stream.  Not included: the trunk,
+ * keyboard_conv's convolution and its slice / concat (the caller hands over [M][4][10][K]), the input side.  The definition,
+ * operation by operation and with the order of every sum, is in drl-tetris_amd/csrc/tetris_head.h; float32, no fused
+ * multiply-adds, tanhf and expf the only library calls, no atomics: a call repeated on the same inputs gives the same bits.
+ * Device pointers, ONE launch per call on the batch's stream, nothing waits; the batch's games are neither read nor written,
+ * every batch shape serves.  The output of a forward call is what tetris_select_eval_dev, tetris_ppo_loss_dev,
+ * tetris_dqn_loss_dev and tetris_kstep_target_dev take.
+ *   Big arrays — d_a, d_Q, d_A, d_grad_Q, d_grad_a; d_x, d_pi, d_grad_pi, d_grad_x — are [M][4][10][K], K = n_pieces = 7 or 1,
+ *   float32, or all of them binary16 with TETRIS_HEAD_F16 (what autograd under AMP hands over), 16-byte aligned.  The per-sample
+ *   value arrays — d_v, d_grad_v of the Q head; d_w, d_v, d_grad_v, d_grad_w of the policy head — are float32, or all binary16
+ *   with TETRIS_HEAD_VALUE_F16.  Outputs are rounded to nearest even.  Every element of every output is written, nothing past M.
+ * Q HEAD (tetris_q_head).  a = advantage_range d_a.  d_v [M][n_values], n_values = 1 or K, or NULL: the reference's constant 0
+ *   of full_network=False (prio_qnet); n_values is then not read.  mask_k = bit k of used_pieces, U its popcount; K = 1 takes
+ *   used_pieces = 1.  mode TETRIS_HEAD_MEAN: d = a - (sum_k mask_k mean_j a_jk) / U, for every piece, used or not.
+ *   TETRIS_HEAD_MAX: lo = the minimum of all 40 K elements; mx_k = the maximum over j of a used piece, lo for an unused one;
+ *   separate_piece_values != 0: d_jk = a_jk - mx_k; otherwise d = a - (sum_k mask_k mx_k) / U.  TETRIS_HEAD_NONE: d = a.
+ *   A = tanh(d), Q_jk = v[min(k, n_values - 1)] + A_jk, V = (sum_k mask_k max_j Q_jk) / U of the Q that was stored.
+ *   tetris_q_head_dev reads d_a, d_v; writes d_Q, d_V float32 [M] and, unless NULL, d_A.
+ *   tetris_q_head_grad_dev reads d_a, d_grad_Q (and d_v for its presence only: A is recomputed from d_a); writes d_grad_a and,
+ *   when d_v is given, d_grad_v [M][n_values]: the gradient of sum grad_Q Q.  V and A are forward-only: no gradient flows through
+ *   them (the reference's trainers differentiate Q only).  Ties of a maximum or of the minimum share the gradient equally
+ *   (TensorFlow's reduce_max / reduce_min, torch's amax / amin).
+ * POLICY HEAD (tetris_policy_head).  d_x: the logits; d_w [M][n_values], n_values = W = 1 or K + 1.
+ *   pi_jk = exp(x_jk - max_j x_jk) / sum_j exp(x_jk - max_j x_jk).  W = 1: v_0 = tanh(w_0).  W = K + 1:
+ *   v_(k-1) = tanh(w_0 + (w_k - mean_{k=1..K} w_k)), d_v [M][K] — the mean over all K entries, used or not, as in the reference.
+ *   tetris_policy_head_dev reads d_x, d_w; writes d_pi, d_v.  tetris_policy_head_grad_dev reads the stored d_pi, d_v and d_grad_pi,
+ *   d_grad_v; writes d_grad_x, d_grad_w [M][W].
+ * TETRIS_E_ARG, with nothing written: a NULL argument struct or a NULL array the call reads or writes (d_A and, for the Q head,
+ * d_v / d_grad_v may be NULL; d_grad_v is required where d_v is given); M < 1; n_pieces not 1 or 7; n_values not 1 or K (Q head,
+ * d_v given), not 1 or K + 1 (policy head); an unknown mode; used_pieces empty or with a bit at or above n_pieces; an unknown
+ * flag; a big array that is not 16-byte aligned.                                                                             */
+#define TETRIS_HEAD_MEAN      0
+#define TETRIS_HEAD_MAX       1
+#define TETRIS_HEAD_NONE      2
+#define TETRIS_HEAD_F16       1   /* the [M][4][10][K] arrays are IEEE binary16 instead of float32 */
+#define TETRIS_HEAD_VALUE_F16 2   /* the per-sample value arrays are IEEE binary16 instead of float32 */
+typedef struct tetris_q_head {
+    const void    *d_a;             /* [M][4][10][n_pieces], 16-byte aligned */
+    const void    *d_v;             /* [M][n_values] or NULL */
+    const void    *d_grad_Q;        /* backward: [M][4][10][n_pieces], 16-byte aligned */
+    int            M;
+    int            n_pieces;        /* K */
+    int            n_values;        /* Kv */
+    int            mode;            /* TETRIS_HEAD_MEAN / _MAX / _NONE */
+    int            separate_piece_values;
+    int            used_pieces;     /* bit k: piece k is used; 0x7F (K = 7) or 1 (K = 1) for all */
+    int            flags;           /* TETRIS_HEAD_F16 | TETRIS_HEAD_VALUE_F16 */
+    float          advantage_range;
+    void          *d_Q;             /* forward: [M][4][10][n_pieces], 16-byte aligned */
+    float         *d_V;             /* forward: [M] */
+    void          *d_A;             /* forward: like d_Q, or NULL */
+    void          *d_grad_a;        /* backward: like d_a */
+    void          *d_grad_v;        /* backward: [M][n_values], with d_v */
+} tetris_q_head;
+typedef struct tetris_policy_head {
+    const void    *d_x;             /* forward: [M][4][10][n_pieces], 16-byte aligned */
+    const void    *d_w;             /* forward: [M][n_values] */
+    const void    *d_grad_pi;       /* backward: like d_pi */
+    const void    *d_grad_v;        /* backward: like d_v */
+    int            M;
+    int            n_pieces;        /* K */
+    int            n_values;        /* W: 1 or K + 1 */
+    int            flags;           /* TETRIS_HEAD_F16 | TETRIS_HEAD_VALUE_F16 */
+    void          *d_pi;            /* [M][4][10][n_pieces], 16-byte aligned: written forward, read backward */
+    void          *d_v;             /* [M][W == 1 ? 1 : K]: written forward, read backward */
+    void          *d_grad_x;        /* backward: like d_x */
+    void          *d_grad_w;        /* backward: [M][n_values] */
+} tetris_policy_head;
+int tetris_q_head_dev(tetris_batch *b, const tetris_q_head *h);
+int tetris_q_head_grad_dev(tetris_batch *b, const tetris_q_head *h);
+int tetris_policy_head_dev(tetris_batch *b, const tetris_policy_head *h);
+int tetris_policy_head_grad_dev(tetris_batch *b, const tetris_policy_head *h);
+
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
  * t = w1 mod 10), acting player = step mod P, perform_action, auto-reset of finished games with
