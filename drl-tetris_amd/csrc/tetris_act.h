@@ -5,7 +5,7 @@
 // greedy) and the trajectory's side outputs.
 //
 // `__host__ __device__` like tetris_plan.h and tetris_policy.h: tetris_hip.hip wraps these in a gfx950 kernel (k_act_select,
-// tetris_dev_agent_act.h), tests/cpu_harness/harness_lib_agent.h in a plain host loop.
+// tetris_dev_act.h), tests/cpu_harness/harness_lib_agent.h in a plain host loop.
 //
 // The bodies work on one game's 40 candidate values as a strided float32 array — x[c * sx] — and, for the two sampling modes, on
 // 40 weights m[c * sm] of the same shape: on the GPU both are columns of a workgroup's LDS image (stride ACT_LDS_STRIDE, the

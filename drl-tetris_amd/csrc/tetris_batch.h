@@ -5,7 +5,7 @@
 // `aug` (environment/env_utils/state_processors.py:44-53) and unpacker(mirrored=True) (agents/agent_utils/state_unpack.py:88-105).
 //
 // `__host__ __device__` like tetris_traj.h: tetris_hip.hip wraps these in gfx950 kernels (k_traj_observe, k_select_count,
-// k_select_scan, k_select_scatter, k_traj_batch: tetris_dev_agent_act.h), tests/cpu_harness/harness_lib_agent.h in plain host loops.
+// k_select_scan, k_select_scatter, k_traj_batch: tetris_dev_traj.h), tests/cpu_harness/harness_lib_agent.h in plain host loops.
 #pragma once
 #include "tetris_kernels.h"
 

@@ -1,6 +1,6 @@
 // Kernels of libtetris_hip.so, part 4: the planning and policy half of tetris_lib_agent.h: a planning agent's action lists, its
 // afterstate deltas and its choice from phi, and the heuristic policy's evaluation and pick.  (The planning and policy STEP kernels
-// are compiled for every player count and live in tetris_game_kernel.h.)
+// are compiled for every player count and live in tetris_game_kernel.h.)  Needs tetris_dev_vec.h.
 
 // tetris_action_lists_dev: the slabs k_actions wrote for games g0 .. g0 + m - 1 -> the caller's [N][L][K] lists, one wave per
 // game (plan_compact_serial is the serial form of the same steps): prefix sum of the 40 slab counts in the reference's order,
@@ -114,7 +114,6 @@ __device__ __forceinline__ T pd_element(T v_fill, T v_zero, T v_one, T v_mone, i
 
 template <typename T, bool LIST_MAJOR>
 __global__ __launch_bounds__(PD_BLOCK) void k_plan_deltas(PlanDeltaArgs da) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     constexpr int EPL = 16 / (int)sizeof(T);                  // elements of one 16-byte store
     __shared__ __attribute__((aligned(16))) uint32_t s_after[NCOL * PD_LS];
     __shared__ __attribute__((aligned(16))) uint8_t s_kind[PD_BLOCK];

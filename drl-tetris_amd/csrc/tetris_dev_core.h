@@ -77,7 +77,6 @@ __global__ __launch_bounds__(ENUM_BLOCK) void k_enumerate(Geo geo, int n, const 
     if (PLANAR) {
         // rotation-minor planes: the lane's four placements are adjacent, so each result array takes ONE 4-byte store per lane and
         // each afterstate column ONE 16-byte store (13 stores per lane instead of 52; a wave's store = 1 KB contiguous)
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         Placement pl[4];
         uint32_t v_ok = 0, v_y = 0, v_cl = 0;
         TE_UNROLL

@@ -1,8 +1,8 @@
 // Kernels of libtetris_hip.so, part 1: observations.  The tile helpers that turn a board's ten column words into its byte plane
 // in LDS and stream the tile out, the observation kernels of tetris_lib_core.h's entry points, and the step that leaves its
-// observation behind.  First of the tetris_dev_*.h headers of tetris_hip.hip because k_duo (tetris_dev_rollout.h) builds its
-// observation with obs_build and obs_stream, and k_traj_batch (tetris_dev_agent_act.h) its tile with obs_row_words / obs_row_halves.
-// Needs tetris_game_kernel.h (d_shape_table).
+// observation behind.  First of the kernel headers of tetris_hip.hip because k_duo (tetris_dev_rollout.h) builds its
+// observation with obs_build and obs_stream, and k_traj_batch (tetris_dev_traj.h) its tile with obs_row_words / obs_row_halves.
+// Needs tetris_game_kernel.h (d_shape_table) and tetris_dev_vec.h.
 
 template <int P, bool TINT>
 __global__ __launch_bounds__(256) void k_observe(Geo geo, int n, const int32_t* idx, int H, tetris_record* rec, uint8_t* round_over,
@@ -13,7 +13,7 @@ __global__ __launch_bounds__(256) void k_observe(Geo geo, int n, const int32_t* 
 
 // One board's ten column words -> its row of a workgroup's LDS tile, for even heights: the byte planes are built as words in
 // registers — two rows = 20 cells = 5 words per loop trip, columns indexed statically — and go to LDS as dwords.  Shared by
-// k_observe_packed (below) and k_traj_batch (tetris_dev_agent_act.h).  `col` is used up.
+// k_observe_packed (below) and k_traj_batch (tetris_dev_traj.h).  `col` is used up.
 __device__ __forceinline__ void obs_row_words(uint32_t (&col)[NCOL], int H, uint32_t* row) {
     for (int yp = 0; yp < H / 2; yp++) {
         uint32_t lo[NCOL], hi[NCOL];                 // cells of rows 2 yp and 2 yp + 1
@@ -107,7 +107,6 @@ __global__ __launch_bounds__(BLOCK) void k_observe_packed(Geo geo, int n, const 
         // image: one 16-byte LDS read per 16-byte streaming store, no index arithmetic
         uint32_t* dst = (uint32_t*)(visual + ((size_t)sl * n + first) * (size_t)(H * NCOL));
         const uint32_t words = (uint32_t)nb * (uint32_t)nw;
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         if ((((uintptr_t)dst) & 15u) == 0) {
             const uint32_t whole = words & ~3u;
             for (uint32_t g = 4u * threadIdx.x; g < whole; g += 4u * BLOCK)
@@ -168,7 +167,6 @@ __device__ __forceinline__ void obs_stream(const KArgs& a, const uint32_t* rows,
     const int nw = a.H * NCOL / 4;
     uint32_t* dst = (uint32_t*)(a.obs_visual + ((size_t)sl * a.n + first) * (size_t)(a.H * NCOL));
     const uint32_t words = (uint32_t)nb * (uint32_t)nw;
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     if (((((uintptr_t)dst) | ((uintptr_t)rows)) & 15u) == 0) {
         const uint32_t whole = words & ~3u;
         for (uint32_t k = 4u * (uint32_t)lane; k < whole; k += 4u * 64u)

@@ -7,7 +7,7 @@
 // [M, K + 1] value stream (sventon_architectures.py:50).
 //
 // `__host__ __device__` like tetris_loss.h: tetris_hip.hip wraps these in gfx950 kernels (k_q_head, k_q_head_grad, k_policy_head,
-// k_policy_head_grad: tetris_dev_agent_act.h), the CPU harness (tests/cpu_harness) runs them through head_run_serial
+// k_policy_head_grad: tetris_dev_head.h), the CPU harness (tests/cpu_harness) runs them through head_run_serial
 // (tetris_host.h) in plain host loops.  float32 throughout, -ffp-contract=off (no fused multiply-adds), the division correctly
 // rounded, tanhf and expf the only library calls; every expression below is evaluated in the order it is written, so host and
 // device give the same bits but for tanhf and expf.  No atomics: the same call twice gives the same bits.

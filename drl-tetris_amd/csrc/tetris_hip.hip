@@ -24,11 +24,17 @@
 
 // ============================================================================ device side
 #include "tetris_game_kernel.h"          // the step kernels of both translation units; `using namespace te;` for all that follows
+#include "tetris_dev_vec.h"              // no kernel: the 16-byte vector helpers of the headers below
 #include "tetris_dev_observe.h"
 #include "tetris_dev_rollout.h"
 #include "tetris_dev_core.h"
 #include "tetris_dev_agent_plan.h"
-#include "tetris_dev_agent_act.h"
+#include "tetris_dev_act.h"
+#include "tetris_dev_loss.h"             // (act_gather of tetris_dev_act.h)
+#include "tetris_dev_kstep.h"
+#include "tetris_dev_head.h"
+#include "tetris_dev_traj.h"
+#include "tetris_dev_replay.h"           // (select_block_scan of tetris_dev_traj.h)
 
 // ============================================================================ host side (they launch the kernels above)
 #include "tetris_lib_batch.h"

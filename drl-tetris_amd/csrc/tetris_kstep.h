@@ -4,7 +4,7 @@
 // (agents/networks/network_utils.py:95-98) for the value of a step.
 //
 // `__host__ __device__` like tetris_loss.h: tetris_hip.hip wraps these in gfx950 kernels (k_kstep_values, k_kstep_estimate:
-// tetris_dev_agent_act.h), the CPU harness (tests/cpu_harness) runs them through kstep_run_serial (tetris_host.h) in plain host loops.
+// tetris_dev_kstep.h), the CPU harness (tests/cpu_harness) runs them through kstep_run_serial (tetris_host.h) in plain host loops.
 // float32 throughout, -ffp-contract=off (no fused multiply-adds), the division correctly rounded, no library call on the device;
 // every expression below is evaluated in the order it is written, so host and device give the same bits.
 //

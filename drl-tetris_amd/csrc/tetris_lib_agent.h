@@ -87,10 +87,12 @@ int tetris_plan_deltas_dev(tetris_batch* b, const uint8_t* d_player, const int32
     if ((rc = plan_deltas_args(shape_of(b), geo_of_batch(b), d_player, d_count, d_cols, max_lists, small_fill, flags, d_deltas, d_sums, d_small, da))) return rc;
     if ((rc = enqueue(b, Enqueue::STATE))) return rc;
     const dim3 grid(blocks_for(b->N, 128) * 128u), block(PD_BLOCK);     // whole groups of 8 XCDs x 16 games
-    const bool major = (flags & TETRIS_DELTAS_LIST_MAJOR) != 0;
-    if (flags & TETRIS_DELTAS_F16)
-        return major ? launch(b, k_plan_deltas<uint16_t, true>, grid, block, 0, da) : launch(b, k_plan_deltas<uint16_t, false>, grid, block, 0, da);
-    return major ? launch(b, k_plan_deltas<float, true>, grid, block, 0, da) : launch(b, k_plan_deltas<float, false>, grid, block, 0, da);
+    with_flag((flags & TETRIS_DELTAS_F16) != 0, [&](auto F16) {
+        with_flag((flags & TETRIS_DELTAS_LIST_MAJOR) != 0, [&](auto MAJOR) {
+            hipLaunchKernelGGL((k_plan_deltas<std::conditional_t<F16(), uint16_t, float>, MAJOR()>), grid, block, 0, b->stream, da);
+        });
+    });
+    return launched();
 }
 
 }  // extern "C"
@@ -231,7 +233,8 @@ int tetris_select_lists_dev(tetris_batch* b, const tetris_plan_eval* e) {
     const int G = choose_games_per_block(b->H, ca.max_lists);
     const size_t lds = choose_lds_bytes(G, b->H, ca.max_lists);
     const dim3 grid(blocks_for(b->N, G)), block(CHOOSE_THREADS);
-    return G == 32 ? launch(b, k_plan_choose<32>, grid, block, lds, ca) : launch(b, k_plan_choose<16>, grid, block, lds, ca);
+    with_flag(G == 32, [&](auto WIDE) { hipLaunchKernelGGL((k_plan_choose<WIDE() ? 32 : 16>), grid, block, lds, b->stream, ca); });
+    return launched();
 }
 
 // ---------------------------------------------------------------- trajectory windows (tetris_traj.h)
@@ -318,7 +321,8 @@ int tetris_traj_plan_batch_dev(tetris_batch* b, const tetris_traj_plan* plan, co
     if (M == 0) return TETRIS_OK;
     if ((rc = enqueue(b, Enqueue::CALLER))) return rc;          // the caller's records -> the caller's planes
     const dim3 grid(blocks_for(M, PLAN_BATCH_SAMPLES)), block(PLAN_BATCH_THREADS);
-    return ba.f16 ? launch(b, k_traj_plan_batch<uint16_t>, grid, block, 0, ba) : launch(b, k_traj_plan_batch<float>, grid, block, 0, ba);
+    with_flag(ba.f16 != 0, [&](auto F16) { hipLaunchKernelGGL((k_traj_plan_batch<std::conditional_t<F16(), uint16_t, float>>), grid, block, 0, b->stream, ba); });
+    return launched();
 }
 
 // ---------------------------------------------------------------- experience replay (tetris_replay.h)

@@ -3,7 +3,7 @@
 // the outputs — of the PPO trainer (agents/networks/ppo_nets.py:141-196, create_training_ops, with N.action_entropy,
 // network_utils.py:114-118) and of the DQN trainer (agents/networks/prio_qnet.py:102-117).
 //
-// `__host__ __device__` like tetris_act.h: tetris_hip.hip wraps these in gfx950 kernels (k_loss_head, tetris_dev_agent_act.h),
+// `__host__ __device__` like tetris_act.h: tetris_hip.hip wraps these in gfx950 kernels (k_loss_head, tetris_dev_loss.h),
 // the CPU harness (tests/cpu_harness) through loss_run_serial (tetris_host.h) in plain host loops.  A body works on one sample's 40 values x[j * sx] of its piece's
 // plane — a column of the workgroup's LDS image on the GPU — and leaves the 40 gradient values in g[j * sg].  float32
 // throughout, -ffp-contract=off, every sum in index order, logf the only library call; every expression below is evaluated in

@@ -5,7 +5,7 @@
 // (sherlock_agent_ppo_trainer.py:36-63).
 //
 // `__host__ __device__` like tetris_traj.h and tetris_choose.h: tetris_hip.hip wraps these in gfx950 kernels (k_traj_record_plan,
-// k_traj_plan_batch: tetris_dev_agent_act.h), tests/cpu_harness/harness_lib_agent.h in plain host loops.  The values of the
+// k_traj_plan_batch: tetris_dev_traj.h), tests/cpu_harness/harness_lib_agent.h in plain host loops.  The values of the
 // planes are plan_delta_value / plan_sums_value (tetris_plan.h) on integers read out of the record, so the expansion gives the
 // bits tetris_plan_deltas_dev and tetris_select_lists_dev write for the same small_fill.
 #pragma once

@@ -5,7 +5,7 @@
 // experience_replay.py:42-74, 108-141).  The gather is tetris_batch.h's own (batch_entry with ba.steps > 0).
 //
 // `__host__ __device__` like tetris_batch.h: tetris_hip.hip wraps these in gfx950 kernels (k_replay_*, k_sort_*:
-// tetris_dev_agent_act.h), tests/cpu_harness/harness_lib_agent.h in plain host loops, tile by tile.
+// tetris_dev_replay.h), tests/cpu_harness/harness_lib_agent.h in plain host loops, tile by tile.
 #pragma once
 #include <math.h>
 

@@ -4,7 +4,7 @@
 // 111-141) as that call uses it: the TD errors on v(s | piece), the target on mean v.
 //
 // `__host__ __device__` like tetris_act.h: tetris_hip.hip wraps these in gfx950 kernels (k_traj_record, k_traj_advantages,
-// tetris_dev_agent_act.h), tests/cpu_harness/harness_lib_agent.h in plain host loops.
+// tetris_dev_traj.h), tests/cpu_harness/harness_lib_agent.h in plain host loops.
 //
 // The backward recurrence is one game's state in six registers (TrajScan) and one function per row (traj_scan_row) that takes
 // the row's four inputs as values: the kernel feeds it from a workgroup's LDS tiles, the host from the window itself.  Every
