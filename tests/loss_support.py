@@ -7,7 +7,7 @@ import collections
 
 import numpy as np
 
-from tests.buffers import Buf, out
+from tests.buffers import GUARD, Buf, out
 
 F32, F64 = np.float32, np.float64
 E32 = F32(1e-6)
@@ -291,7 +291,175 @@ def same_bits(got, want):
     return np.array_equal((got + got.dtype.type(0)).view(u), (want + want.dtype.type(0)).view(u))
 
 
+def written(a, want=None):
+    """no element of an output buffer still holds the guard bytes it was filled with — but where `want`, the array the output is
+    then compared with, holds that very pattern: of 65536 float16 values one does (-23.2), and a large gradient array meets it"""
+    held = (a.view(np.uint8).reshape(-1, a.dtype.itemsize) == GUARD).all(axis=1)
+    if want is not None:
+        held &= ~(np.ascontiguousarray(want).view(np.uint8).reshape(-1, want.dtype.itemsize) == GUARD).all(axis=1)
+    return not held.any()
+
+
 def sum_bound(x):
     """the standard bound on the error of a float32 sum of the terms x in any order: (n - 1) 2^-24 sum |x_i|"""
     x = np.asarray(x, F64)
     return (max(len(x), 1) - 1) * U24 * np.abs(x).sum()
+
+
+# ---------------------------------------------------------------- the stated order of a statistic's sum
+BLOCK = 64                # samples of a block of the PPO / DQN heads (the planning head: plan_loss_support.BLOCK = 16)
+SLOTS = 256               # LOSS_REDUCE_LANES of the header's sentence
+
+
+def tree(v):
+    """loss_tree over axis 0 of a copy of v (2^k rows): v[i] += v[i + off] for off = n/2, n/4, .., 1 -> row 0"""
+    v = v.copy()
+    off = v.shape[0] // 2
+    assert 2 * off == v.shape[0] or v.shape[0] == 1, "a tree takes a power of two"
+    while off >= 1:
+        v[:off] = v[:off] + v[off:2 * off]
+        off //= 2
+    return v[0]
+
+
+def stated_sum(terms, block, order="stated"):
+    """The one model of "the order of a statistic's sum is fixed" (drl-tetris_amd/csrc/tetris_loss.h, STATISTICS), over axis 0 of
+    terms [M] or [M, n], in the terms' float type: the samples of a block of `block` by the tree (samples past M add zeros), block
+    b's row into slot b mod 256 — a slot starts at +0 — in ascending b, the 256 slots by the same tree.  Vectorised: the rows of a
+    trip b = 256 i .. 256 i + 255 are added to the slots at once, trips in ascending i.
+    `order` other than "stated" gives what a departure from the sentence would: "slotless" adds the rows in ascending b into one
+    accumulator, "descending" adds them into their slots in descending b.  (Only the test of this model itself uses these.)"""
+    terms = np.asarray(terms)
+    flat = terms.reshape(terms.shape[0], -1)
+    M, n = flat.shape
+    nb = (M + block - 1) // block
+    padded = np.zeros((nb * block, n), flat.dtype)
+    padded[:M] = flat
+    rows = tree(padded.reshape(nb, block, n).transpose(1, 0, 2))                 # [nb, n]: the blocks' partial rows
+    if order == "slotless":
+        total = np.zeros(n, flat.dtype)
+        for b in range(nb):
+            total = total + rows[b]
+    else:
+        slots = np.zeros((SLOTS, n), flat.dtype)
+        trips = range(0, nb, SLOTS)
+        for first in (trips if order == "stated" else reversed(trips)):
+            part = rows[first:first + SLOTS]
+            slots[:len(part)] = slots[:len(part)] + part
+        total = tree(slots)
+    assert total.dtype == terms.dtype
+    return total.reshape(terms.shape[1:])
+
+
+def stated_bound(x, block):
+    """The bound on the error of a float32 sum of the terms x in the stated order.  Any path from a term to the total passes
+    log2(block) additions of the block's tree (6 for PPO / DQN, 4 for the planning head), then the additions of its slot — one per
+    trip, ceil(blocks / 256) of them, the first onto +0 —, then the 8 of the slots' tree; each addition rounds its result by at
+    most 2^-24 of it, and no partial result exceeds sum |x_i| (1 + depth 2^-24).  To first order, which at depth <= 17 leaves out
+    less than 2^-44 sum |x_i|, the error is at most depth 2^-24 sum |x_i|: (14 + ceil(blocks / 256)) 2^-24 sum |x_i| for a block
+    of 64.  At M = 32833 (514 blocks, 3 trips) that is 1.0e-6 sum |x_i|, against 3.0e-5 sum |x_i| for one sample of equal terms and
+    2.0e-3 sum |x_i| of the bound that holds for any order."""
+    x = np.asarray(x, F64)
+    blocks = (max(len(x), 1) + block - 1) // block
+    depth = int(np.log2(block)) + (blocks + SLOTS - 1) // SLOTS + 8
+    assert 2 ** int(np.log2(block)) == block
+    return depth * U24 * np.abs(x).sum()
+
+
+def loop_sum(terms, block):
+    """The same sentence as plain Python loops over one column of float32 terms, a scalar at a time: for every block, for every
+    level of the tree, for every pair.  (Slow: for the test of stated_sum.)"""
+    M = len(terms)
+    nb = (M + block - 1) // block
+    slots = [F32(0.0)] * SLOTS
+    for b in range(nb):                                              # ascending b
+        v = [terms[b * block + t] if b * block + t < M else F32(0.0) for t in range(block)]
+        off = block // 2
+        while off >= 1:
+            for i in range(off):
+                v[i] = F32(v[i] + v[i + off])
+            off //= 2
+        slots[b % SLOTS] = F32(slots[b % SLOTS] + v[0])
+    off = SLOTS // 2
+    while off >= 1:
+        for i in range(off):
+            slots[i] = F32(slots[i] + slots[i + off])
+        off //= 2
+    return slots[0]
+
+
+def ppo_stated_stats(terms, D, prm):
+    """float32 [16]: the PPO statistics from the eleven per-sample float32 terms [M, 11] (ppo_model's `terms`), summed in the stated
+    order and finished as the header's STATISTICS and PPO paragraphs write it, every operation in float32: c1 (total / D) and so on"""
+    assert terms.dtype == F32 and terms.shape[1] == 11
+    total = stated_sum(terms, BLOCK)
+    stats = np.zeros(16, F32)
+    D = F32(D)
+    if not D > 0:
+        return stats
+    c1, c2, c3 = F32(prm.c1), F32(prm.c2), F32(prm.c3)
+    vl, pol, ent = c1 * (total[0] / D), (-c2) * (total[1] / D), (-c3) * (total[2] / D)
+    stats[:5] = D, (vl + pol) + ent, vl, pol, ent
+    stats[5:14] = [total[col] / D for col in (3, 4, 2, 5, 6, 7, 8, 9, 10)]
+    return stats
+
+
+def dqn_stated_stats(terms, D, Dnz):
+    """float32 [16]: the DQN statistics from the six per-sample float32 terms [M, 6] in the stated order"""
+    assert terms.dtype == F32 and terms.shape[1] == 6
+    total = stated_sum(terms, BLOCK)
+    stats = np.zeros(16, F32)
+    D, Dnz = F32(D), F32(Dnz)
+    if not D > 0:
+        return stats
+    stats[:3] = D, Dnz, (total[0] / Dnz if Dnz > 0 else F32(0.0))
+    stats[3:8] = [total[col] / D for col in (1, 2, 3, 4, 5)]
+    return stats
+
+
+# ---------------------------------------------------------------- batches whose loops take more than one trip
+COUNT_LANES = 1024        # the lanes of the one workgroup that counts D and Dnz: a lane's trips are m, m + 1024, ..
+CARRY_SIZES = (1025, 5123, 16385, 32833)      # 64 x 16 + 1, 5 x 1024 + 3, 64 x 256 + 1, 64 x 513 + 1
+
+
+def carry_mask(rng, M, block, last_valid, span):
+    """A valid mask for a batch whose count loop and whose reduction take more than one trip: the first sample invalid, every
+    19th, the whole block 3, with `span` 1024 consecutive samples (every lane of the count has one trip that counts nothing; they
+    start inside a block and inside a trip: at 1500, or at 0 where M leaves no other room), the last sample as `last_valid` says;
+    any non-zero byte counts as valid."""
+    rows = np.arange(M)
+    valid = np.ones(M, np.uint8)
+    valid[0] = 0
+    valid[rows % 19 == 8] = 0
+    valid[3 * block:4 * block] = 0
+    if span:
+        first = 1500 if M >= 1500 + COUNT_LANES + block else 0
+        valid[first:first + COUNT_LANES] = 0
+    valid[M - 1] = 1 if last_valid else 0
+    valid[valid != 0] = rng.integers(1, 256, int((valid != 0).sum()))
+    return valid
+
+
+def weigh_the_full_slots(target, block):
+    """Where a slot of the stated order takes three rows or more (more than 512 blocks), the targets of the blocks that share the
+    fullest slots times 1024, in place.  Only in those slots can the order of a slot's rows show, and only in a last bit; 255 other
+    slots of equal weight would round most such bits away in the slots' tree.  So the sums of T, T^2 and (val - T)^2 or
+    w (q - T)^2 tell the stated order from another."""
+    M = len(target)
+    nb = (M + block - 1) // block
+    trips = (nb + SLOTS - 1) // SLOTS
+    if trips >= 3:
+        b = np.arange(M) // block
+        target[b % SLOTS < nb - SLOTS * (trips - 1)] *= F32(1024.0)
+    return target
+
+
+def assert_carry_mask(ok, block, last_valid, span):
+    """what carry_mask promises, stated on the model's `ok`"""
+    M = len(ok)
+    assert not ok[0] and ok[M - 1] == last_valid
+    nb = M // block
+    assert (~ok[:nb * block].reshape(nb, block)).all(axis=1).any(), "no block without a valid sample"
+    if span:
+        gaps = np.diff(np.concatenate([[-1], np.nonzero(ok)[0], [M]])) - 1
+        assert gaps.max() >= COUNT_LANES, "no 1024 consecutive samples without a valid one"

@@ -12,8 +12,9 @@ import numpy as np
 
 from oracle import oracle as orc
 from tests import engines, replay
-from tests.buffers import GUARD, MIRROR, Buf, out
-from tests.loss_support import E32, F32, F64, U24, same_bits, sum_bound          # noqa: F401  (re-exported to the test file)
+from tests.buffers import MIRROR, Buf, out
+from tests.loss_support import (E32, F32, F64, U24, assert_carry_mask, carry_mask, same_bits, stated_bound, stated_sum,        # noqa: F401
+                                sum_bound, weigh_the_full_slots, written)                             # (re-exported to the test file)
 from tests.plan_support import _crafted, _words
 
 U8, U32, I32 = np.uint8, np.uint32, np.int32
@@ -104,26 +105,21 @@ def plan_model(ft, phi, v, delta, sums, piece, old, adv, target, ok, prm, grad_s
     return res
 
 
-def block_sum(terms):
-    """the across-sample order: blocks of 16 samples by the tree (samples past M add zeros), block b into slot b mod 256 in
-    ascending b, the slots by the tree -> [12] in the terms' float type"""
-    M = terms.shape[0]
-    nb = (M + BLOCK - 1) // BLOCK
-    padded = np.zeros((nb * BLOCK,) + terms.shape[1:], terms.dtype)
-    padded[:M] = terms
-    v = padded.reshape(nb, BLOCK, -1).copy()
-    off = BLOCK // 2
-    while off >= 1:
-        v[:, :off] = v[:, :off] + v[:, off:2 * off]
-        off //= 2
-    slots = np.zeros((256, terms.shape[1]), terms.dtype)
-    for b_ in range(nb):
-        slots[b_ % 256] = slots[b_ % 256] + v[b_, 0]
-    off = 128
-    while off >= 1:
-        slots[:off] = slots[:off] + slots[off:2 * off]
-        off //= 2
-    return slots[0]
+def plan_stated_stats(terms, D, prm, H):
+    """float32 [16]: the statistics from the twelve per-sample float32 terms [M, 12] (plan_model's `terms`), summed in the stated
+    order (loss_support.stated_sum with blocks of 16) and finished as the definition writes it, every operation in float32"""
+    assert terms.dtype == F32 and terms.shape[1] == 12
+    total = stated_sum(terms, BLOCK)
+    stats = np.zeros(16, F32)
+    D = F32(D)
+    if not D > 0:
+        return stats
+    c1, c2, c3, c4 = (F32(z) for z in prm[1:])
+    vl, pol, ent = c1 * (total[0] / D), (-c2) * (total[1] / D), (-c3) * (total[2] / D)
+    imp = c4 * ((total[11] / D) / F32(10 * H))
+    stats[:6] = D, ((vl + pol) + imp) + ent, vl, pol, ent, imp
+    stats[6:15] = [total[col] / D for col in range(2, 11)]
+    return stats
 
 
 def expand(plane, k, K, dtype):
@@ -392,8 +388,3 @@ class PlanLossCall:
 
     def get(self):
         return {name: buf.get() for name, buf in self.out.items()}
-
-
-def written(a):
-    """no element of an output buffer still holds the guard bytes it was filled with"""
-    return not (a.view(U8).reshape(-1, a.dtype.itemsize) == GUARD).all(axis=1).any()

@@ -1,7 +1,9 @@
 """The trainer's loss heads on the device (include/tetris_hip.h: tetris_ppo_loss_dev, tetris_dqn_loss_dev) against the model of
 tests/loss_support.py, written from the header's definitions: bit equality in float32 for everything that does not pass through
 the logarithm, the same formulas in float64 with a derived tolerance for what does, the float64 model's gradients against torch
-autograd of the reference's expressions, the statistics against float64 sums with the standard summation bound, the argument
+autograd of the reference's expressions, the statistics against float64 sums with the standard summation bound and bit for bit
+against the sum in the order the header states, all of this again at batch sizes where the single-workgroup loops behind the
+heads (the count of D, the reduction of the blocks' rows) go round more than once, the scratch buffer across sizes, the argument
 rules, and on the GPU the TorchEnv wrappers inside a small training step.  Every test but the last group runs on the CPU harness
 (`-m "not gpu"`) and on the MI355X (`-m gpu`); on the harness the "device" buffers are numpy arrays."""
 import importlib
@@ -12,10 +14,10 @@ import pytest
 
 import __graft_entry__ as ge
 from tests import engines
-from tests.buffers import GUARD
-from tests.loss_support import (DQN_STATS, F32, F64, PARAM_SETS, PPO_STATS, U24, DqnCall, Params, PpoCall, dqn_inputs, dqn_model,
-                                entropy_constants, expand, expand_v, ppo_inputs, ppo_model, same_bits, sum_bound, torch_dqn_loss,
-                                torch_ppo_loss)
+from tests.loss_support import (BLOCK, CARRY_SIZES, DQN_STATS, F32, F64, PARAM_SETS, PPO_STATS, U24, DqnCall, Params, PpoCall, assert_carry_mask,
+                                carry_mask, dqn_inputs, dqn_model, dqn_stated_stats, entropy_constants, expand, expand_v, loop_sum, ppo_inputs,
+                                ppo_model, ppo_stated_stats, same_bits, stated_bound, stated_sum, sum_bound, torch_dqn_loss, torch_ppo_loss,
+                                weigh_the_full_slots, written)
 
 SIZES = (1, 33, 64, 65, 257)          # one sample, a partial wave, a block, a block and one, several blocks with a partial last
 KV = ((7, 1), (7, 7), (1, 1))
@@ -57,16 +59,34 @@ def batch_of():
         b.close()
 
 
-def written(a):
-    """no element of an output buffer still holds the guard bytes it was filled with"""
-    return not (a.view(np.uint8).reshape(-1, a.dtype.itemsize) == GUARD).all(axis=1).any()
-
-
 def grad_scale_for(gt):
     return 1.0 if np.dtype(gt) == np.float32 else 1024.0          # (float16 gradients: the range an AMP loss scale is for)
 
 
 # ---------------------------------------------------------------- 1. bit equality
+def ppo_bits(kind, b, inp, gt):
+    """A PPO call with entropy_loss = 0 against the float32 model: the per-sample outputs bit for bit, every entry written, zeros
+    outside the piece's plane, nothing past M (Buf.get checks the guard bytes), D exact -> (outputs, model)"""
+    M, K, V = inp["pi"].shape[0], inp["pi"].shape[3], inp["v"].shape[1]
+    prm = Params(0.15, 0.3, 1.0, 0.0, 0.05, 1.0, 2.0)
+    gs = grad_scale_for(gt)
+    call = PpoCall(kind, b, inp, prm, grad_dtype=gt, grad_scale=gs)
+    b.ppo_loss_dev(call.l)
+    got = call.get()
+    m = ppo_model(F32, inp["pi"], inp["v"], inp["action"], inp["old"], inp["adv"], inp["target"], inp["valid"], prm, gs)
+    for row, name in ((0, "p"), (1, "ratio"), (2, "pl"), (5, "val")):
+        assert same_bits(got["terms"][row], m[name]), f"'{name}' differs in samples {np.nonzero(got['terms'][row] != m[name])[0][:8]}"
+    want, want_v = expand(m["g"], m["k"], K, gt), expand_v(m["gv"], m["k"], V, gt)
+    assert written(got["grad_pi"], want) and written(got["grad_v"], want_v) and written(got["terms"]) and written(got["stats"])
+    assert same_bits(got["grad_v"], want_v), "grad_v"
+    assert same_bits(got["grad_pi"], want), f"grad_pi differs in samples {np.unique(np.nonzero(got['grad_pi'] != want)[0])[:8]}"
+    other = np.ones((M, 40, K), bool)
+    other[np.arange(M), :, m["k"]] = False
+    assert not got["grad_pi"].reshape(M, 40, K)[other].any(), "a non-zero outside the piece's plane"
+    assert got["stats"][0] == m["D"] and got["stats"][4] == 0.0
+    return got, m
+
+
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
 @pytest.mark.parametrize("shape", shapes(), ids=shape_id)
 def test_ppo_equals_the_model_bit_for_bit(kind, shape, batch_of):
@@ -75,22 +95,7 @@ def test_ppo_equals_the_model_bit_for_bit(kind, shape, batch_of):
     M, K, V, dt, gt, masked = shape
     rng = np.random.default_rng(100 * M + 10 * K + V)
     inp = ppo_inputs(rng, M, K, V, dt, masked)
-    prm = Params(0.15, 0.3, 1.0, 0.0, 0.05, 1.0, 2.0)
-    gs = grad_scale_for(gt)
-    call = PpoCall(kind, batch_of(kind), inp, prm, grad_dtype=gt, grad_scale=gs)
-    batch_of(kind).ppo_loss_dev(call.l)
-    got = call.get()
-    m = ppo_model(F32, inp["pi"], inp["v"], inp["action"], inp["old"], inp["adv"], inp["target"], inp["valid"], prm, gs)
-    for row, name in ((0, "p"), (1, "ratio"), (2, "pl"), (5, "val")):
-        assert same_bits(got["terms"][row], m[name]), f"'{name}' differs in samples {np.nonzero(got['terms'][row] != m[name])[0][:8]}"
-    assert written(got["grad_pi"]) and written(got["grad_v"]) and written(got["terms"]) and written(got["stats"])
-    assert same_bits(got["grad_v"], expand_v(m["gv"], m["k"], V, gt)), "grad_v"
-    want = expand(m["g"], m["k"], K, gt)
-    assert same_bits(got["grad_pi"], want), f"grad_pi differs in samples {np.unique(np.nonzero(got['grad_pi'] != want)[0])[:8]}"
-    other = np.ones((M, 40, K), bool)
-    other[np.arange(M), :, m["k"]] = False
-    assert not got["grad_pi"].reshape(M, 40, K)[other].any(), "a non-zero outside the piece's plane"
-    assert got["stats"][0] == m["D"] and got["stats"][4] == 0.0
+    got, m = ppo_bits(kind, batch_of(kind), inp, gt)
     if M == 257:                                                  # every branch occurred
         ok, ratio, cl, A = m["ok"], m["ratio"], m["cl"], m["A"]
         for sign in (A > 0, A < 0):
@@ -105,6 +110,22 @@ def test_ppo_equals_the_model_bit_for_bit(kind, shape, batch_of):
             assert not ok[0] and not ok[M - 1] and not ok[64:192].all() and ok.sum() > 200
 
 
+def dqn_bits(kind, b, inp, gt, optimistic, gs):
+    """A DQN call against the float32 model: q, new_prio and all of grad_Q bit for bit, every entry written, nothing past M, D and
+    Dnz exact -> (the call, outputs, model)"""
+    K = inp["Q"].shape[3]
+    call = DqnCall(kind, b, inp, grad_dtype=gt, optimistic=optimistic, grad_scale=gs)
+    b.dqn_loss_dev(call.l)
+    got = call.get()
+    m = dqn_model(F32, inp["Q"], inp["action"], inp["target"], inp["weight"], inp["valid"], optimistic, gs)
+    want = expand(m["g"], m["k"], K, gt)
+    assert written(got["grad_Q"], want) and all(written(a) for name, a in got.items() if name != "grad_Q")
+    assert same_bits(got["q"], m["q"]) and same_bits(got["new_prio"], m["prio"])
+    assert same_bits(got["grad_Q"], want), f"grad_Q differs in samples {np.unique(np.nonzero(got['grad_Q'] != want)[0])[:8]}"
+    assert got["stats"][0] == m["D"] and got["stats"][1] == m["Dnz"]
+    return call, got, m
+
+
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
 @pytest.mark.parametrize("shape", [s[:2] + s[3:] for s in shapes() if s[2] == 1], ids=lambda s: f"M{s[0]}-K{s[1]}-{np.dtype(s[2]).name}-grad_{np.dtype(s[3]).name}")
 def test_dqn_equals_the_model_bit_for_bit(kind, shape, batch_of):
@@ -113,16 +134,7 @@ def test_dqn_equals_the_model_bit_for_bit(kind, shape, batch_of):
     M, K, dt, gt, masked = shape
     rng = np.random.default_rng(7 * M + K)
     inp = dqn_inputs(rng, M, K, dt, masked, weighted=masked or M == 65)
-    optimistic, gs = (0.25 if M % 2 else 0.0), grad_scale_for(gt)
-    call = DqnCall(kind, batch_of(kind), inp, grad_dtype=gt, optimistic=optimistic, grad_scale=gs)
-    batch_of(kind).dqn_loss_dev(call.l)
-    got = call.get()
-    m = dqn_model(F32, inp["Q"], inp["action"], inp["target"], inp["weight"], inp["valid"], optimistic, gs)
-    assert all(written(a) for a in got.values())
-    assert same_bits(got["q"], m["q"]) and same_bits(got["new_prio"], m["prio"])
-    want = expand(m["g"], m["k"], K, gt)
-    assert same_bits(got["grad_Q"], want), f"grad_Q differs in samples {np.unique(np.nonzero(got['grad_Q'] != want)[0])[:8]}"
-    assert got["stats"][0] == m["D"] and got["stats"][1] == m["Dnz"]
+    _, got, m = dqn_bits(kind, batch_of(kind), inp, gt, 0.25 if M % 2 else 0.0, grad_scale_for(gt))
     if M == 257 and masked:
         assert (m["ok"] & (inp["weight"] == 0)).any() and not m["ok"][0] and not m["ok"][M - 1] and not m["ok"][64:192].all()
         a = inp["action"]
@@ -262,15 +274,38 @@ def test_the_float64_model_against_torch_autograd_dqn(weighted, K):
 
 
 # ---------------------------------------------------------------- 4. statistics
-def stat_check(name, got, terms, coef, D, term_err=0.0):
-    """got against coef * sum(terms) / D in float64: the summation bound of the float32 sum in any order plus the terms' own
-    error, through the division and the product (two roundings, and one more for a sum of such statistics)"""
+def stat_check(name, got, terms, coef, D, term_err=0.0, bound=None):
+    """got against coef * sum(terms) / D in float64: the summation bound of the float32 sum — in any order, or `bound`, that of
+    the stated order (loss_support.stated_bound) — plus the terms' own error, through the division and the product (two roundings,
+    and one more for a sum of such statistics)"""
     terms = np.asarray(terms, F64)
     want = coef * terms.sum() / D
-    tol = abs(coef) * (sum_bound(terms) + len(terms) * term_err) / D + 3 * U24 * abs(want) + 1e-45
+    tol = abs(coef) * ((sum_bound(terms) if bound is None else bound) + len(terms) * term_err) / D + 3 * U24 * abs(want) + 1e-45
     print(f"{name}: got {got:.9g}, want {want:.9g}, difference {abs(got - want):.3g}, allowed {tol:.3g}")
     assert abs(got - want) <= tol, name
     return want, tol
+
+
+def ppo_stats_in_the_stated_order(got, m32, prm):
+    """Every PPO statistic bit for bit: the sum of its per-sample float32 terms in the stated order, then loss_finish's division and
+    products in float32.  The terms that carry the float32 model's bits come from the model (dv^2, pl, val, val^2, T, T^2,
+    [ratio != cl], ratio); H and bonus, which pass through the logarithm, are the rows the call itself wrote to `terms` — the header
+    sums the very values it writes, and section 2 holds those rows against float64 —, and H^2 is the float32 square of that H."""
+    t = m32["terms"].copy()
+    H, bonus = got["terms"][3], got["terms"][4]
+    t[:, 2], t[:, 3], t[:, 4] = bonus, H, H * H
+    want = ppo_stated_stats(t, m32["D"], prm)
+    for slot, name in enumerate(PPO_STATS):
+        assert same_bits(got["stats"][slot], want[slot]), f"'{name}' is {got['stats'][slot]!r}, the sum in the stated order gives {want[slot]!r}"
+    assert not got["stats"][len(PPO_STATS):].any()
+
+
+def dqn_stats_in_the_stated_order(got, m32):
+    """Every DQN statistic bit for bit: the float32 model's per-sample terms summed in the stated order, divided in float32"""
+    want = dqn_stated_stats(m32["terms"], m32["D"], m32["Dnz"])
+    for slot, name in enumerate(DQN_STATS):
+        assert same_bits(got["stats"][slot], want[slot]), f"'{name}' is {got['stats'][slot]!r}, the sum in the stated order gives {want[slot]!r}"
+    assert not got["stats"][len(DQN_STATS):].any()
 
 
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
@@ -278,7 +313,8 @@ def stat_check(name, got, terms, coef, D, term_err=0.0):
 def test_ppo_statistics(kind, shape, batch_of):
     """Every statistic against the float64 sum of the model's per-sample terms: the float32 model's for the terms that carry its
     bits (section 1), the float64 model's with the per-term tolerance of section 2 for H, H^2 and bonus; (n - 1) 2^-24 sum |x_i|
-    holds for any order of the sum.  D and clip_saturation D are integers.  A second call gives the same bits everywhere."""
+    holds for any order of the sum.  Then every statistic bit for bit against the sum in the stated order
+    (ppo_stats_in_the_stated_order).  D and clip_saturation D are integers.  A second call gives the same bits everywhere."""
     M, K, V, dt, gt, masked = shape
     rng = np.random.default_rng(50 * M + K + V)
     inp = ppo_inputs(rng, M, K, V, dt, masked)
@@ -312,6 +348,7 @@ def test_ppo_statistics(kind, shape, batch_of):
     stat_check("entropy_bonus", stats["entropy_bonus"], t64[:, 2], 1.0, D, tol_b)
     for name, col in (("values", 5), ("values_sq", 6), ("target_values", 7), ("target_values_sq", 8), ("clip_saturation", 9), ("ratio", 10)):
         stat_check(name, stats[name], t32[:, col], 1.0, D)
+    ppo_stats_in_the_stated_order(got, m32, prm)
     batch_of(kind).ppo_loss_dev(call.l)
     again = call.get()
     for name in got:
@@ -321,6 +358,8 @@ def test_ppo_statistics(kind, shape, batch_of):
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
 @pytest.mark.parametrize("shape", [s[:2] + s[3:] for s in shapes(types=1) if s[2] == 1], ids=lambda s: f"M{s[0]}-K{s[1]}-{np.dtype(s[2]).name}-grad_{np.dtype(s[3]).name}")
 def test_dqn_statistics(kind, shape, batch_of):
+    """Every statistic against the float64 sum of the float32 model's per-sample terms within the bound of any order, then bit for
+    bit against the sum in the stated order (dqn_stats_in_the_stated_order); a second call gives the same bits everywhere."""
     M, K, dt, gt, masked = shape
     inp = dqn_inputs(np.random.default_rng(9 * M + K), M, K, dt, masked, weighted=True)
     call = DqnCall(kind, batch_of(kind), inp, grad_dtype=gt, optimistic=0.5, grad_scale=128.0)
@@ -338,10 +377,181 @@ def test_dqn_statistics(kind, shape, batch_of):
     for name, col in (("q_val", 1), ("q_val_sq", 2), ("q_target", 3), ("q_target_sq", 4), ("new_prio", 5)):
         if D:
             stat_check(name, stats[name], t[:, col], 1.0, D)
+    dqn_stats_in_the_stated_order(got, m)
     batch_of(kind).dqn_loss_dev(call.l)
     again = call.get()
     for name in got:
         assert got[name].tobytes() == again[name].tobytes(), f"'{name}' of a second call differs"
+
+
+# ---------------------------------------------------------------- 4a. the model of the stated order
+@pytest.mark.parametrize("block", [BLOCK, 16], ids=["block64", "block16"])
+def test_the_model_of_the_stated_order(block):
+    """loss_support.stated_sum against the sentence of tetris_loss.h (STATISTICS) written as plain scalar loops, on 515 blocks
+    with a short last one (slots 0, 1 and 2 take three rows): the same bits in every column.  And the sentence is not idle at
+    that size: adding the same rows without slots, or into their slots in descending b, gives other bits in some column."""
+    rng = np.random.default_rng(block)
+    M = 515 * block - block // 2 - 1
+    terms = rng.standard_normal((M, 6)) * 10.0 ** rng.uniform(-1, 1, (M, 1))
+    # (only slots 0, 1 and 2 hold three rows, and only there can the order of a slot's rows show; their nine blocks weigh 1024
+    # times the others, so that a last bit of theirs is not rounded away on the way through the slots' tree)
+    heavy = np.isin(np.arange(M) // block, [0, 1, 2, 256, 257, 258, 512, 513, 514])
+    terms = np.where(heavy[:, None], 1024.0 * terms, terms).astype(F32)
+    stated = stated_sum(terms, block)
+    assert stated.dtype == F32 and stated.shape == (6,)
+    for col in range(6):
+        assert same_bits(stated[col], loop_sum(terms[:, col], block)), f"column {col}"
+        assert same_bits(stated[col], stated_sum(terms[:, col], block)), "a single column"
+    assert (stated != stated_sum(terms, block, "slotless")).any(), "the slots change nothing"
+    assert (stated != stated_sum(terms, block, "descending")).any(), "the order of a slot's rows changes nothing"
+    few = terms[:3 * block + 1]                                   # fewer blocks than slots: every slot holds one row or none
+    assert same_bits(stated_sum(few, block), stated_sum(few, block, "descending"))
+
+
+# ---------------------------------------------------------------- 4b. batches whose loops take a second trip
+def carry_shapes():
+    """(M, K, V, input type, gradient type, last_valid, span) at the sizes of loss_support.CARRY_SIZES — the count of D and Dnz is
+    one workgroup of 1024 lanes that strides over M, the reduction of the blocks' partial rows one of 256 lanes that strides over
+    the blocks of 64:
+      M = 1025 = 16 x 64 + 1    one lane of the count has a second trip; 17 blocks
+      M = 5123 = 5 x 1024 + 3   lanes 0-2 count six samples, the others five; 81 blocks
+      M = 16385 = 256 x 64 + 1  17 trips of the count; 257 blocks: slot 0 takes a second row, and the last block holds one sample
+      M = 32833 = 513 x 64 + 1  33 trips; 514 blocks: slots 0 and 1 take a third row
+    Every size with every (K, V), the element type pairs going round.  Every call carries a valid mask (loss_support.carry_mask):
+    the second (K, V) of a size has its last sample — at every size the only one of its block — valid, the others invalid; from
+    M = 5123 on every mask has 1024 consecutive invalid samples, so D lies more than 1024 below M.  At M = 1025 such a run leaves
+    one sample at most, so no D there can lie more than 1024 from M without being 0: the third (K, V) takes the run, with the
+    last sample valid (D = 1), and the other two do without."""
+    res = []
+    pairs = list(itertools.product(TYPES, TYPES))
+    for n, (M, (i, (K, V))) in enumerate(itertools.product(CARRY_SIZES, enumerate(KV))):
+        dt, gt = pairs[n % 4]
+        res.append((M, K, V, dt, gt, i == 1 or (M == 1025 and i == 2), M > 1025 or i == 2))
+    return res
+
+
+def carry_id(s):
+    return f"M{s[0]}-K{s[1]}-V{s[2]}-{np.dtype(s[3]).name}-grad_{np.dtype(s[4]).name}-last_{'valid' if s[5] else 'invalid'}" + ("-run1024" if s[6] else "")
+
+
+def check_carry_counts(M, ok, D, last_valid, span):
+    """the mask is what the case needs, and a count that drops or doubles a trip of 1024 lanes cannot land on this D"""
+    assert_carry_mask(ok, BLOCK, last_valid, span)
+    assert D == ok.sum() and D % 1024 != 0
+    if M > 1025:
+        assert M - D > 1024
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("shape", carry_shapes(), ids=carry_id)
+def test_ppo_equals_the_model_bit_for_bit_across_the_carries(kind, shape, batch_of):
+    """Section 1's comparison (ppo_bits) at the sizes of carry_shapes: every per-sample output and both gradient arrays bit for
+    bit, D exact; and with entropy_loss = 0 every statistic in the stated order."""
+    M, K, V, dt, gt, last_valid, span = shape
+    rng = np.random.default_rng(100 * M + 10 * K + V)
+    inp = ppo_inputs(rng, M, K, V, dt, True)
+    inp["valid"] = carry_mask(rng, M, BLOCK, last_valid, span)
+    weigh_the_full_slots(inp["target"], BLOCK)
+    got, m = ppo_bits(kind, batch_of(kind), inp, gt)
+    check_carry_counts(M, m["ok"], got["stats"][0], last_valid, span)
+    ppo_stats_in_the_stated_order(got, m, Params(0.15, 0.3, 1.0, 0.0, 0.05, 1.0, 2.0))
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("shape", carry_shapes(), ids=carry_id)
+def test_ppo_statistics_across_the_carries(kind, shape, batch_of):
+    """With every loss coefficient non-zero: D exact; H and bonus of every sample against float64 within section 2's tolerances
+    (so that summing the written rows is not circular); every statistic bit for bit in the stated order; entropy_sq also against
+    the float64 sum with the bound of the stated order (loss_support.stated_bound) and section 4's per-term error of H^2 — at
+    M = 32833 that bound is a thirtieth of one sample's share, where the any-order bound exceeds a whole block's —; a second call
+    gives the same bytes in every output."""
+    M, K, V, dt, gt, last_valid, span = shape
+    rng = np.random.default_rng(50 * M + K + V)
+    inp = ppo_inputs(rng, M, K, V, dt, True)
+    inp["valid"] = carry_mask(rng, M, BLOCK, last_valid, span)
+    weigh_the_full_slots(inp["target"], BLOCK)
+    prm = PARAM_SETS[2]
+    b = batch_of(kind)
+    call = PpoCall(kind, b, inp, prm, grad_dtype=gt, grad_scale=128.0)
+    b.ppo_loss_dev(call.l)
+    got = call.get()
+    args = (inp["pi"], inp["v"], inp["action"], inp["old"], inp["adv"], inp["target"], inp["valid"], prm, 128.0)
+    m32, m64 = ppo_model(F32, *args), ppo_model(F64, *args)
+    ok, D = m32["ok"], m32["D"]
+    assert written(got["terms"]) and written(got["stats"])        # (the gradient arrays: the test above)
+    check_carry_counts(M, ok, got["stats"][0], last_valid, span)
+    assert got["stats"][0] == D
+    scale = np.abs(m64["H"]) + prm.cf * np.abs(m64["floor"] - m64["H"]) + prm.cr * (3.7 + np.abs(m64["bonus0"])) + np.abs(m64["bonus"])
+    tol_b = abs(1 - prm.cr) * (1 + prm.cf) * TOL_H + 4 * 6 * U24 * scale
+    assert (np.abs(m64["H"] - m64["floor"])[ok] >= 1e-3).all(), "an entropy of the inputs lies within 1e-3 of the floor"
+    assert (np.abs(got["terms"][3] - m64["H"]) < TOL_H).all() and (np.abs(got["terms"][4] - m64["bonus"]) <= tol_b).all()
+    ppo_stats_in_the_stated_order(got, m32, prm)
+    t64 = m64["terms"][ok]
+    stat_check("entropy_sq", float(got["stats"][6]), t64[:, 4], 1.0, D, 2 * 3.7 * TOL_H + TOL_H ** 2 + U24 * 13.7, bound=stated_bound(t64[:, 4], BLOCK))
+    b.ppo_loss_dev(call.l)
+    again = call.get()
+    for name in got:
+        assert got[name].tobytes() == again[name].tobytes(), f"'{name}' of a second call differs"
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("shape", carry_shapes(), ids=carry_id)
+def test_dqn_across_the_carries(kind, shape, batch_of):
+    """The DQN head at the sizes of carry_shapes, with the mask of each case and weights, every sixth of them 0 (the three cases of
+    a size differ in K, in the element types and in the mask; V is no argument of this head): q, new_prio and all of grad_Q bit for
+    bit, D and Dnz exact, every statistic bit for bit in the stated order, and a second call with the same bytes."""
+    M, K, _, dt, gt, last_valid, span = shape
+    rng = np.random.default_rng(9 * M + K)
+    inp = dqn_inputs(rng, M, K, dt, True, True)
+    inp["valid"] = carry_mask(rng, M, BLOCK, last_valid, span)
+    weigh_the_full_slots(inp["target"], BLOCK)
+    call, got, m = dqn_bits(kind, batch_of(kind), inp, gt, 0.5, 128.0)
+    check_carry_counts(M, m["ok"], got["stats"][0], last_valid, span)
+    zero_weight = m["ok"] & (inp["weight"] == 0)
+    assert got["stats"][1] == m["Dnz"] == m["D"] - zero_weight.sum() and (zero_weight.any() or m["D"] == 1)
+    dqn_stats_in_the_stated_order(got, m)
+    batch_of(kind).dqn_loss_dev(call.l)
+    again = call.get()
+    for name in got:
+        assert got[name].tobytes() == again[name].tobytes(), f"'{name}' of a second call differs"
+
+
+# ---------------------------------------------------------------- 4c. the scratch buffer across sizes
+def same_outputs(a, b, what):
+    for name in a:
+        assert a[name].tobytes() == b[name].tobytes(), f"{what}: '{name}' differs"
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("head", ["ppo", "dqn"])
+def test_the_scratch_buffer_grows_between_calls(kind, head):
+    """On a batch of its own, so that the first call finds no scratch: a call at M = 33 (one partial row), one at M = 32833 (514
+    rows: the scratch is replaced while the first call may still run) and the first again, enqueued one after the other — the
+    outputs are read only after the third.  The third call's outputs are the first's byte for byte, the large call's are those
+    of the same call on a fresh batch, and no error is pending."""
+    rng = np.random.default_rng(33)
+    if head == "ppo":
+        small, large = (ppo_inputs(rng, M, 7, 7, np.float32, True) for M in (33, CARRY_SIZES[-1]))
+        make = lambda b, inp: PpoCall(kind, b, inp, PARAM_SETS[2], grad_scale=128.0)                     # noqa: E731
+    else:
+        small, large = (dqn_inputs(rng, M, 7, np.float32, True, True) for M in (33, CARRY_SIZES[-1]))
+        make = lambda b, inp: DqnCall(kind, b, inp, optimistic=0.5, grad_scale=128.0)                    # noqa: E731
+    b, fresh = engines.make(kind, 4, 1), engines.make(kind, 4, 1)
+    try:
+        calls = [make(b, small), make(b, large), make(b, small)]
+        for call in calls:
+            (b.ppo_loss_dev if head == "ppo" else b.dqn_loss_dev)(call.l)
+        first, big, third = (call.get() for call in calls)
+        assert all(written(a) for got in (first, big, third) for a in got.values())
+        assert first["stats"][0] == (small["valid"] != 0).sum() and big["stats"][0] == (large["valid"] != 0).sum() > 30000
+        same_outputs(third, first, "the small call after the large one")
+        alone = make(fresh, large)
+        (fresh.ppo_loss_dev if head == "ppo" else fresh.dqn_loss_dev)(alone.l)
+        same_outputs(big, alone.get(), "the large call after a small one")
+        assert b.take_errors() == 0 and fresh.take_errors() == 0
+    finally:
+        b.close()
+        fresh.close()
 
 
 # ---------------------------------------------------------------- 5. argument rules

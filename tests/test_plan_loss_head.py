@@ -1,8 +1,9 @@
 """The planning loss head on the device (include/tetris_hip.h: tetris_plan_loss_dev) against the model of
 tests/plan_loss_support.py, written from the definition: bit equality in float32 for everything that does not pass through the
 logarithm, the same formulas in float64 with a derived tolerance for what does, the float64 model's gradients against torch
-autograd of the reference's expressions, the statistics against float64 sums with the standard summation bound, determinism, the
-reference's own recorded planes, the argument rules, and on the GPU the TorchEnv wrappers inside a small training step.  The
+autograd of the reference's expressions, the statistics against float64 sums with the standard summation bound and bit for bit
+against the sum in the stated order, determinism, all of this again at batch sizes where the count of D and the reduction of the
+blocks' rows go round more than once, the scratch buffer across sizes, the reference's own recorded planes, the argument rules, and on the GPU the TorchEnv wrappers inside a small training step.  The
 records are made by the library's own calls (record_plan over crafted lists) and the model is fed what batch_plan expands from
 them.  Every test but the torch ones runs on the CPU harness (`-m "not gpu"`) and on the MI355X (`-m gpu`); on the harness the
 "device" buffers are numpy arrays."""
@@ -15,9 +16,9 @@ import pytest
 import __graft_entry__ as ge
 from tests import engines
 from tests.buffers import MIRROR
-from tests.plan_loss_support import (E32, F32, F64, PARAM_SETS, STATS, U24, PlanLossCall, PlanParams, block_sum, crafted_window, entropy_tolerances,
-                                     expand, expand_v, golden_window, named, ok_of, plan_inputs, plan_model, same_bits, sample_index, sum_bound,
-                                     torch_plan_loss, with_old, written)
+from tests.plan_loss_support import (BLOCK, E32, F32, F64, PARAM_SETS, STATS, U24, PlanLossCall, PlanParams, assert_carry_mask, carry_mask,
+                                     crafted_window, entropy_tolerances, expand, expand_v, golden_window, named, ok_of, plan_inputs, plan_model,
+                                     plan_stated_stats, same_bits, sample_index, stated_bound, sum_bound, torch_plan_loss, weigh_the_full_slots, with_old, written)
 
 SIZES = (1, 3, 16, 17, 33)            # one sample, a few, a block of 16, a block and one, two blocks and one
 HEIGHTS = (20, 7)                     # 200 cells: four cells in some lanes, three in others; 70 cells: lanes with one and with none
@@ -59,13 +60,18 @@ def grad_scale_for(gt):
     return 1.0 if np.dtype(gt) == np.float32 else 1024.0          # (float16 gradients: the range an AMP loss scale is for)
 
 
-def prepare(kind, window_of, shape, seed, prm, ties=True):
-    """inputs, index list, the planes batch_plan gives, ok, with prob_old placed around the model's probabilities"""
+def prepare(kind, window_of, shape, seed, prm, ties=True, carry=None):
+    """inputs, index list, the planes batch_plan gives, ok, with prob_old placed around the model's probabilities.  carry =
+    (last_valid, span): the mask of plan_loss_support.carry_mask over blocks of 16, and the indices of block 5 name no entry."""
     M, H, K, V, dt, gt, masked, fill = shape
     w = window_of(kind, H)
     rng = np.random.default_rng(seed)
     index = sample_index(rng, M, w.total)
     inp = plan_inputs(rng, M, H, K, V, dt, masked, ties=ties)
+    if carry:
+        inp["valid"] = carry_mask(rng, M, BLOCK, *carry)
+        weigh_the_full_slots(inp["target"], BLOCK)
+        index[5 * BLOCK:6 * BLOCK] = np.resize([-1, w.total, (w.total + 5) | MIRROR, 0x7FFFFFFF], BLOCK)
     delta, sums = w.planes(index, fill)
     ok = ok_of(inp, index, w.total)
     m = plan_model(F32, inp["phi"], inp["v"], delta, sums, inp["piece"], inp["old"], inp["adv"], inp["target"], ok, prm)
@@ -78,28 +84,40 @@ def model(ft, inp, delta, sums, ok, prm, gs=1.0):
 
 
 # ---------------------------------------------------------------- 1. bit equality
-@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
-@pytest.mark.parametrize("shape", shapes(), ids=shape_id)
-def test_equals_the_model_bit_for_bit(kind, shape, window_of):
-    """entropy_loss = 0: probability, ratio, pl, the impossibility sum, val, grad_v and all of grad_phi carry the model's bits.
-    Every entry of both gradient arrays is written, zeros outside the piece's plane, nothing past M (guard bytes)."""
+BITS_PRM = PlanParams(0.15, 0.3, 1.0, 0.0, 0.25)                 # entropy_loss = 0: grad_phi carries the float32 model's bits
+
+
+def plan_bits(kind, window_of, shape, carry=None):
+    """A call with entropy_loss = 0 against the float32 model: the per-sample outputs and both gradient arrays bit for bit, every
+    entry written, zeros outside the piece's plane and for samples that are not valid, nothing past M (Buf.get checks the guard
+    bytes), D exact -> (outputs, model, window, inputs, index, ok)"""
     M, H, K, V, dt, gt, masked, fill = shape
-    prm = PlanParams(0.15, 0.3, 1.0, 0.0, 0.25)
-    w, inp, index, delta, sums, ok = prepare(kind, window_of, shape, 100 * M + 10 * K + V + H, prm)
+    prm = BITS_PRM
+    w, inp, index, delta, sums, ok = prepare(kind, window_of, shape, 100 * M + 10 * K + V + H, prm, carry=carry)
     gs = grad_scale_for(gt)
     got = PlanLossCall(kind, w.b, w.plan, inp, index, prm, fill, grad_dtype=gt, grad_scale=gs, stride3=M % 2 == 1).run(w.b)
     m = model(F32, inp, delta, sums, ok, prm, gs)
     for row, name in ((0, "probability"), (1, "ratio"), (2, "pl"), (4, "I"), (5, "val")):
         assert same_bits(got["terms"][row], m[name]), f"'{name}' differs in samples {np.nonzero(got['terms'][row] != m[name])[0][:8]}"
-    assert all(written(a) for a in got.values())
-    assert same_bits(got["grad_v"], expand_v(m["gv"], m["k"], V, gt)), "grad_v"
-    want = expand(m["g"], m["k"], K, gt)
+    want, want_v = expand(m["g"], m["k"], K, gt), expand_v(m["gv"], m["k"], V, gt)
+    assert written(got["grad_phi"], want) and written(got["grad_v"], want_v) and written(got["terms"]) and written(got["stats"])
+    assert same_bits(got["grad_v"], want_v), "grad_v"
     assert same_bits(got["grad_phi"], want), f"grad_phi differs in samples {np.unique(np.nonzero(got['grad_phi'] != want)[0])[:8]}"
     other = np.ones((M, 10 * H, K), bool)
     other[np.arange(M), :, m["k"]] = False
     assert not got["grad_phi"].reshape(M, 10 * H, K)[other].any(), "a non-zero outside the piece's plane"
     assert not got["grad_phi"][~ok].any() and not got["terms"][:, ~ok].any(), "a sample that is not valid"
     assert got["stats"][0] == m["D"] == ok.sum() and got["stats"][4] == 0.0
+    return got, m, w, inp, index, ok
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("shape", shapes(), ids=shape_id)
+def test_equals_the_model_bit_for_bit(kind, shape, window_of):
+    """entropy_loss = 0: probability, ratio, pl, the impossibility sum, val, grad_v and all of grad_phi carry the model's bits.
+    Every entry of both gradient arrays is written, zeros outside the piece's plane, nothing past M (guard bytes)."""
+    M, K = shape[0], shape[2]
+    got, m, w, inp, index, ok = plan_bits(kind, window_of, shape)
     if M == 33:                                                   # every branch occurred
         ratio, cl, A, s, raw = m["ratio"], m["cl"], m["A"], m["s"][ok], m["raw"][ok]
         for sign in (A > 0, A < 0):
@@ -226,23 +244,38 @@ def test_the_tie_rules_against_torch_autograd(tie, window_of):
 
 
 # ---------------------------------------------------------------- 4. statistics
-def stat_check(name, got, terms, coef, D, term_err=0.0):
-    """got against coef * sum(terms) / D in float64: the summation bound of the float32 sum in any order plus the terms' own
-    error, through the divisions and the product (three roundings, and one more for a sum of such statistics)"""
+def stat_check(name, got, terms, coef, D, term_err=0.0, bound=None):
+    """got against coef * sum(terms) / D in float64: the summation bound of the float32 sum — in any order, or `bound`, that of
+    the stated order (loss_support.stated_bound) — plus the terms' own error, through the divisions and the product (three
+    roundings, and one more for a sum of such statistics)"""
     terms = np.asarray(terms, F64)
     want = coef * terms.sum() / D
-    tol = abs(coef) * (sum_bound(terms) + np.sum(term_err)) / D + 4 * U24 * abs(want) + 1e-45
+    tol = abs(coef) * ((sum_bound(terms) if bound is None else bound) + np.sum(term_err)) / D + 4 * U24 * abs(want) + 1e-45
     print(f"{name}: got {got:.9g}, want {want:.9g}, difference {abs(got - want):.3g}, allowed {tol:.3g}")
     assert abs(got - want) <= tol, name
     return want, tol
+
+
+def stats_in_the_stated_order(got, m32, prm, H):
+    """Every statistic bit for bit: the sum of its per-sample float32 terms in the stated order (loss_support.stated_sum with
+    blocks of 16), then the definition's divisions and products in float32.  The terms that carry the float32 model's bits come
+    from the model; Hent, which passes through the logarithm, is the row the call itself wrote to `terms` — the head sums the
+    very value it writes, and section 2 holds that row against float64 —, and Hent^2 is the float32 square of that Hent."""
+    t = m32["terms"].copy()
+    Hent = got["terms"][3]
+    t[:, 2], t[:, 3] = Hent, Hent * Hent
+    want = plan_stated_stats(t, m32["D"], prm, H)
+    for slot, name in enumerate(STATS):
+        assert same_bits(got["stats"][slot], want[slot]), f"'{name}' is {got['stats'][slot]!r}, the sum in the stated order gives {want[slot]!r}"
+    assert not got["stats"][len(STATS):].any()
 
 
 @pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
 @pytest.mark.parametrize("shape", shapes(types=1), ids=shape_id)
 def test_statistics_and_determinism(kind, shape, window_of):
     """Every statistic against the float64 sum of the model's per-sample terms — the float32 model's for the terms that carry its
-    bits (section 1), the float64 model's with the per-sample tolerance of section 2 for Hent and Hent^2 —; the sums that carry
-    the model's bits are also compared bit for bit in the stated order (block_sum).  D counts the mask and the indices that name
+    bits (section 1), the float64 model's with the per-sample tolerance of section 2 for Hent and Hent^2 —; then every statistic
+    bit for bit against the sum in the stated order (stats_in_the_stated_order).  D counts the mask and the indices that name
     no entry.  A second call gives the same bytes in every output."""
     M, H, K, V, dt, gt, masked, fill = shape
     prm = PARAM_SETS[1]
@@ -272,12 +305,7 @@ def test_statistics_and_determinism(kind, shape, window_of):
     for name, col in (("values", 4), ("values_sq", 5), ("target_values", 6), ("target_values_sq", 7), ("clip_saturation", 8), ("ratio", 9),
                       ("probability", 10)):
         stat_check(name, stats[name], t32[:, col], 1.0, D)
-    total = block_sum(m32["terms"])                               # the stated order, for the sums without a logarithm
-    Df = F32(D)
-    for slot, col in ((8, 4), (9, 5), (10, 6), (11, 7), (12, 8), (13, 9), (14, 10)):
-        assert same_bits(got["stats"][slot], total[col] / Df), f"'{STATS[slot]}' is not the sum in the stated order"
-    assert same_bits(got["stats"][2], F32(prm.c1) * (total[0] / Df)) and same_bits(got["stats"][3], (-F32(prm.c2)) * (total[1] / Df))
-    assert same_bits(got["stats"][5], F32(prm.c4) * ((total[11] / Df) / F32(10 * H)))
+    stats_in_the_stated_order(got, m32, prm, H)
     again = call.run(w.b)
     for name in got:
         assert got[name].tobytes() == again[name].tobytes(), f"'{name}' of a second call differs"
@@ -307,6 +335,127 @@ def test_no_samples_zeroes_the_statistics(kind, window_of):
     inp = plan_inputs(np.random.default_rng(4), 1, 20, 7, 1, np.float32, False)
     got = PlanLossCall(kind, w.b, w.plan, inp, [0], PARAM_SETS[0], 0.0, m=0).run(w.b)
     assert written(got["stats"]) and not got["stats"].any() and not written(got["grad_phi"]) and not written(got["grad_v"])
+
+
+# ---------------------------------------------------------------- 5. batches whose loops take a second trip
+CARRY_SIZES = (1025, 4097, 5123, 8209)
+
+
+def carry_shapes():
+    """(shape as in shapes(), (last_valid, span)) at the sizes where the single-workgroup loops behind the head go round again — the
+    count of D is one workgroup of 1024 lanes that strides over M, the reduction of the blocks' partial rows one of 256 lanes that
+    strides over the blocks of 16:
+      M = 1025 = 64 x 16 + 1    one lane of the count has a second trip; 65 blocks
+      M = 4097 = 256 x 16 + 1   5 trips of the count; 257 blocks: slot 0 takes a second row, and the last block holds one sample
+      M = 5123 = 5 x 1024 + 3   lanes 0-2 count six samples, the others five; 321 blocks: slots 0-64 take a second row
+      M = 8209 = 513 x 16 + 1   9 trips; 514 blocks: slots 0 and 1 take a third row
+    Every size with every (K, V); the heights, the element type pairs and small_fill go round.  Every call carries a valid mask
+    (plan_loss_support.carry_mask over blocks of 16) and an index list with repeats and with entries that name nothing, a whole
+    block of them: the second (K, V) of a size has its last sample valid, the others invalid; from M = 4097 on every mask has 1024
+    consecutive invalid samples, so D lies more than 1024 below M.  At M = 1025 such a run leaves one sample at most, so no D
+    there can lie more than 1024 from M without being 0: the third (K, V) takes the run, with the last sample valid (D = 1)."""
+    res = []
+    pairs = list(itertools.product(TYPES, TYPES))
+    for n, (M, (i, (K, V))) in enumerate(itertools.product(CARRY_SIZES, enumerate(KV))):
+        dt, gt = pairs[n % 4]
+        res.append(((M, HEIGHTS[(n + 1) % 2], K, V, dt, gt, True, FILLS[(n // 2) % 2]), (i == 1 or (M == 1025 and i == 2), M > 1025 or i == 2)))
+    assert {s[0][7] for s in res} == set(FILLS) and all({s[0][1] for s in res if s[0][0] == M} == set(HEIGHTS) for M in CARRY_SIZES)
+    return res
+
+
+def carry_id(case):
+    return shape_id(case[0]).replace("-masked", "") + f"-last_{'valid' if case[1][0] else 'invalid'}" + ("-run1024" if case[1][1] else "")
+
+
+def check_carry_inputs(w, inp, index, ok, D, carry):
+    """the mask and the index list are what the case needs, and a count that drops or doubles a trip of 1024 lanes cannot land on
+    this D"""
+    M = len(ok)
+    assert_carry_mask(ok, BLOCK, *carry)
+    is_named = named(index, w.total)
+    assert not is_named[5 * BLOCK:6 * BLOCK].any() and (inp["valid"][5 * BLOCK:6 * BLOCK] != 0).any() == (M > 1025 or not carry[1])
+    assert len(np.unique(index[is_named])) < is_named.sum(), "no entry is named twice"
+    assert D == 1 or ((index[ok] & MIRROR).any() and not (index[ok] & MIRROR).all())
+    assert D == ok.sum() and D % 1024 != 0
+    if M > 1025:
+        assert M - D > 1024
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("case", carry_shapes(), ids=carry_id)
+def test_equals_the_model_bit_for_bit_across_the_carries(kind, case, window_of):
+    """Section 1's comparison (plan_bits) at the sizes of carry_shapes: every per-sample output and both gradient arrays bit for
+    bit, D exact; and every statistic in the stated order."""
+    shape, carry = case
+    got, m, w, inp, index, ok = plan_bits(kind, window_of, shape, carry)
+    check_carry_inputs(w, inp, index, ok, got["stats"][0], carry)
+    stats_in_the_stated_order(got, m, BITS_PRM, shape[1])
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+@pytest.mark.parametrize("case", carry_shapes(), ids=carry_id)
+def test_statistics_and_determinism_across_the_carries(kind, case, window_of):
+    """With every loss coefficient non-zero: D exact; Hent of every sample against float64 within section 2's tolerance (so that
+    summing the written row is not circular); every statistic bit for bit in the stated order — at these sizes the slots of the
+    order take more than one row —; entropy_sq also against the float64 sum with the bound of the stated order
+    (loss_support.stated_bound) and section 4's per-sample error of Hent^2; a second call gives the same bytes in every output."""
+    shape, carry = case
+    M, H, K, V, dt, gt, masked, fill = shape
+    prm = PARAM_SETS[1]
+    w, inp, index, delta, sums, ok = prepare(kind, window_of, shape, 50 * M + K + V + H, prm, carry=carry)
+    call = PlanLossCall(kind, w.b, w.plan, inp, index, prm, fill, grad_dtype=gt, grad_scale=128.0)
+    got = call.run(w.b)
+    m32, m64 = model(F32, inp, delta, sums, ok, prm, 128.0), model(F64, inp, delta, sums, ok, prm, 128.0)
+    D = m32["D"]
+    assert written(got["terms"]) and written(got["stats"])        # (the gradient arrays: the test above)
+    check_carry_inputs(w, inp, index, ok, got["stats"][0], carry)
+    assert got["stats"][0] == D
+    tol_H = entropy_tolerances(m64, gt)[0]
+    assert (np.abs(got["terms"][3] - m64["Hent"]) <= tol_H).all()
+    stats_in_the_stated_order(got, m32, prm, H)
+    t64, tol_H = m64["terms"][ok], tol_H[ok]
+    stat_check("entropy_sq", float(got["stats"][7]), t64[:, 3], 1.0, D, 2 * np.abs(t64[:, 2]) * tol_H + tol_H ** 2 + U24 * t64[:, 3],
+               bound=stated_bound(t64[:, 3], BLOCK))
+    again = call.run(w.b)
+    for name in got:
+        assert got[name].tobytes() == again[name].tobytes(), f"'{name}' of a second call differs"
+
+
+@pytest.mark.parametrize("kind", engines.ENGINE_PARAMS)
+def test_the_scratch_buffer_grows_between_calls(kind):
+    """On a window of its own, so that the first call finds no scratch: a call at M = 33 (three partial rows), one at M = 8209 (514
+    rows: the scratch is replaced while the first call may still run) and the first again, enqueued one after the other — the
+    outputs are read only after the third.  The third call's outputs are the first's byte for byte, the large call's are those
+    of the same call on a fresh window with the same records, and no error is pending."""
+    H, K, prm = 7, 7, PARAM_SETS[1]
+    made = {}
+
+    def own_window(kind_, H_):
+        return made.setdefault("w", crafted_window(kind_, H_))
+    fresh = None
+    try:
+        prepared = [prepare(kind, own_window, (M, H, K, K, np.float32, np.float32, True, 1e-3), 7 * M, prm) for M in (33, CARRY_SIZES[-1])]
+        w = made["w"]
+        (_, small, small_index, *_), (_, large, large_index, *_) = prepared
+        calls = [PlanLossCall(kind, w.b, w.plan, inp, index, prm, 1e-3, grad_scale=128.0)
+                 for inp, index in ((small, small_index), (large, large_index), (small, small_index))]
+        for call in calls:
+            w.b.plan_loss_dev(w.plan, call.l)
+        first, big, third = (call.get() for call in calls)
+        assert all(written(a) for got in (first, big, third) for a in got.values())
+        assert first["stats"][0] == prepared[0][5].sum() and big["stats"][0] == prepared[1][5].sum() > 8000
+        for name in first:
+            assert third[name].tobytes() == first[name].tobytes(), f"the small call after the large one: '{name}' differs"
+        fresh = crafted_window(kind, H)
+        assert fresh.bufs["rec"].get().tobytes() == w.bufs["rec"].get().tobytes()
+        alone = PlanLossCall(kind, fresh.b, fresh.plan, large, large_index, prm, 1e-3, grad_scale=128.0).run(fresh.b)
+        for name in big:
+            assert big[name].tobytes() == alone[name].tobytes(), f"the large call after a small one: '{name}' differs"
+        assert w.b.take_errors() == 0 and fresh.b.take_errors() == 0
+    finally:
+        for win in (made.get("w"), fresh):
+            if win is not None:
+                win.b.close()
 
 
 # ---------------------------------------------------------------- 6. the reference's own planes
