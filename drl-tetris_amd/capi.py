@@ -166,6 +166,22 @@ class PolicyHead(C.Structure):
                 ("d_grad_x", C.c_void_p), ("d_grad_w", C.c_void_p)]
 
 
+INPUT_ITEMS = {"cumsum": 1, "shadow": 2, "height": 3, "holes": 4}          # TETRIS_INPUT_CUMSUM / _SHADOW / _HEIGHT / _HOLES
+INPUT_F16, INPUT_CHANNELS_LAST, INPUT_PAD = 1, 2, 4                        # TETRIS_INPUT_*
+
+
+class NetInput(C.Structure):
+    """mirrors `struct tetris_net_input` (include/tetris_hip.h)"""
+    _fields_ = [("obs", C.c_void_p), ("replay", C.c_void_p), ("d_index", C.c_void_p), ("row", C.c_int), ("M", C.c_int), ("steps", C.c_int),
+                ("n_items", C.c_int), ("step_mask", C.c_uint64), ("items", C.c_int * 4), ("flags", C.c_int), ("reserved", C.c_int),
+                ("d_visual", C.c_void_p), ("d_vector", C.c_void_p), ("d_piece", C.c_void_p), ("d_valid", C.c_void_p)]
+
+
+def input_shape(height, n_items, pad=True):
+    """(C, Hp, Wp) of the visual output of net_input_dev: 1 + n_items channels, H + 2 rows and 12 columns with pad, else H and 10."""
+    return 1 + int(n_items), int(height) + (2 if pad else 0), W + (2 if pad else 0)
+
+
 def kstep_steps(k, filter=None):
     """The steps the k-step estimator evaluates its net on (value_estimator._create_steps, agents/networks/value_estimator.py:
     90-99): s in 1..k that no f of `filter` divides; None or an empty filter keeps all.  -> a list of ints, ascending."""
@@ -309,6 +325,7 @@ _SIGNATURES = {
     "tetris_q_head_grad_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_policy_head_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_policy_head_grad_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_net_input_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_ppo_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_dqn_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_plan_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -878,6 +895,34 @@ class TetrisBatch:
     def policy_head_grad_dev(self, h):
         """grad_x and grad_w from the stored pi, v and grad_pi, grad_v (h = policy_head(...))."""
         self._check(self.lib.tetris_policy_head_grad_dev(self._h, C.byref(h) if h is not None else None))
+
+    # -- network inputs (include/tetris_hip.h: tetris_net_input_dev)
+    def net_input(self, m, obs=None, replay=None, index=None, row=0, steps=1, step_mask=0, items=("cumsum", "shadow", "height", "holes"), pad=True,
+                  f16=False, channels_last=False, visual=None, vector=None, piece=None, valid=None, flags=0):
+        """The argument struct of net_input_dev over raw DEVICE addresses or None.  The source is obs = traj_obs(...) with index int32
+        [m] (bit 31: mirrored; out of range: no sample) or with index None and a row (m = n_games), or replay = replay(...) with
+        index int32 [m] and steps (a count) or step_mask (kstep_mask(steps)): m * n samples.  items: names or TETRIS_INPUT_* codes in
+        channel order.  Outputs: visual [S][m][C][Hp][Wp] (channels_last: [S][m][Hp][Wp][C]) and vector [S][m][12] float32 (f16:
+        binary16), piece uint8 [S][m], valid uint8 [m]; (C, Hp, Wp) = input_shape(height, len(items), pad).  The struct keeps obs /
+        replay alive."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        n = NetInput()
+        n._keep = (obs, replay)
+        n.obs = C.addressof(obs) if obs is not None else None
+        n.replay = C.addressof(replay) if replay is not None else None
+        n.d_index, n.row, n.M, n.steps, n.step_mask = val(index), int(row), int(m), int(steps), int(step_mask) & 0xFFFFFFFFFFFFFFFF
+        codes = [INPUT_ITEMS[i] if isinstance(i, str) else int(i) for i in items]
+        n.n_items = len(codes)
+        for i, code in enumerate(codes[:4]):
+            n.items[i] = code
+        n.flags = (INPUT_F16 if f16 else 0) | (INPUT_CHANNELS_LAST if channels_last else 0) | (INPUT_PAD if pad else 0) | int(flags)
+        n.d_visual, n.d_vector, n.d_piece, n.d_valid = val(visual), val(vector), val(piece), val(valid)
+        return n
+
+    def net_input_dev(self, n):
+        """The padded plane stack, the float vector, piece and valid of a set of samples straight from their packed records
+        (n = net_input(...))."""
+        self._check(self.lib.tetris_net_input_dev(self._h, C.byref(n) if n is not None else None))
 
     # -- loss heads (include/tetris_hip.h: tetris_ppo_loss_dev, tetris_dqn_loss_dev)
     def ppo_loss(self, pi, v, action, prob_old, adv, target, grad_pi, grad_v, stats, m, n_pieces=7, n_values=1, valid=None, terms=None,

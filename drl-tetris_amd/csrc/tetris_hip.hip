@@ -35,6 +35,7 @@
 #include "tetris_dev_head.h"
 #include "tetris_dev_traj.h"
 #include "tetris_dev_replay.h"           // (select_block_scan of tetris_dev_traj.h)
+#include "tetris_dev_input.h"
 
 // ============================================================================ host side (they launch the kernels above)
 #include "tetris_lib_batch.h"

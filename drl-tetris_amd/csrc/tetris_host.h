@@ -25,6 +25,7 @@
 #include "tetris_loss.h"
 #include "tetris_kstep.h"
 #include "tetris_head.h"
+#include "tetris_input.h"
 
 namespace te {
 
@@ -862,6 +863,58 @@ static inline int head_run_serial(const HeadArgs& h) {
         if (h.head == HEAD_Q) head_q_sample_serial(h, (size_t)m);
         else head_policy_sample_serial(h, (size_t)m);
     }
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- network inputs (tetris_input.h)
+// the argument rules, then the kernel arguments.  The sample's source goes through the rules of the call it is taken from:
+// traj_obs_check for a window, replay_gather_mask_args for the ring (with no output of its own).
+static inline int input_args(const HostShape& s, const tetris_net_input* in, InputArgs& ia) {
+    if (!in) return fail(TETRIS_E_ARG, "the argument struct is NULL");
+    int rc = traj_batch_rules(s, "tetris_net_input_dev");
+    if (rc) return rc;
+    if (in->obs && in->replay) return fail(TETRIS_E_ARG, "obs and replay are both given");
+    memset(&ia, 0, sizeof ia);
+    if (in->replay) {
+        const tetris_traj_batch none = {};
+        if ((rc = replay_gather_mask_args(s, in->replay, in->d_index, in->M, in->steps, in->step_mask, &none, ia.ba))) return rc;
+    } else {
+        if ((rc = traj_obs_check(s, in->obs))) return rc;
+        if (!in->d_index) {
+            if (in->row < 0 || in->row >= in->obs->capacity) return fail(TETRIS_E_ARG, "row outside the window");
+            if (in->M != s.N) return fail(TETRIS_E_ARG, "the row form takes M = N samples");
+        }
+        if (in->M < 0) return fail(TETRIS_E_ARG, "M < 0");
+        ia.ba.m = in->M; ia.ba.n_slots = s.P; ia.ba.H = s.H;
+        ia.ba.total = (uint32_t)in->obs->capacity * (uint32_t)s.N;
+        ia.ba.index = in->d_index; ia.ba.obs = in->obs->d_obs;
+        ia.row_base = in->d_index ? 0u : (uint32_t)in->row * (uint32_t)s.N;
+    }
+    if (in->n_items < 0 || in->n_items > INPUT_MAX_ITEMS) return fail(TETRIS_E_ARG, "n_items must be in [0, 4]");
+    uint32_t seen = 0u;
+    for (int i = 0; i < in->n_items; i++) {
+        const int code = in->items[i];
+        if (code < TETRIS_INPUT_CUMSUM || code > TETRIS_INPUT_HOLES) return fail(TETRIS_E_ARG, "unknown item code");
+        if (seen & (1u << code)) return fail(TETRIS_E_ARG, "an item code is named twice");
+        seen |= 1u << code;
+        ia.chan |= (uint32_t)code << (4 * (i + 1));
+    }
+    if (in->flags & ~(TETRIS_INPUT_F16 | TETRIS_INPUT_CHANNELS_LAST | TETRIS_INPUT_PAD)) return fail(TETRIS_E_ARG, "unknown flag");
+    ia.f16 = (in->flags & TETRIS_INPUT_F16) ? 1 : 0; ia.last = (in->flags & TETRIS_INPUT_CHANNELS_LAST) ? 1 : 0;
+    ia.pad = (in->flags & TETRIS_INPUT_PAD) ? 1 : 0;
+    if ((((uintptr_t)in->d_visual) | ((uintptr_t)in->d_vector)) & (ia.f16 ? 1u : 3u)) return fail(TETRIS_E_ARG, "visual / vector must be aligned to their element type");
+    ia.C = 1 + in->n_items; ia.Hp = s.H + (ia.pad ? 2 : 0); ia.Wp = NCOL + (ia.pad ? 2 : 0);
+    ia.E = ia.C * ia.Hp * ia.Wp;
+    ia.dA = (uint32_t)(ia.last ? ia.Wp * ia.C : ia.Hp * ia.Wp); ia.dB = (uint32_t)(ia.last ? ia.C : ia.Wp);
+    ia.mE = input_magic((uint32_t)ia.E); ia.mA = input_magic(ia.dA); ia.mB = input_magic(ia.dB);
+    ia.visual = in->d_visual; ia.vector = in->d_vector; ia.piece = in->d_piece; ia.valid = in->d_valid;
+    return TETRIS_OK;
+}
+// A call over host memory (the CPU build of the bodies: tests/cpu_harness), the product's one launch as a loop over slots and
+// samples.  tetris_lib_compose.h says which side runs what.
+static inline int input_run_serial(const InputArgs& ia) {
+    for (int sl = 0; sl < ia.ba.n_slots; sl++)
+        for (int j = 0; j < ia.ba.m; j++) input_sample_slot(ia, j, sl);
     return TETRIS_OK;
 }
 

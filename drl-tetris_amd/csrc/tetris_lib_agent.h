@@ -1,5 +1,5 @@
 // Host side of libtetris_hip.so, part 4: the agent-side entry points: planning, heuristic policy, acting on an evaluation, trajectory
-// windows, window batches, the planning agent's windows, experience replay, loss heads.  Needs tetris_lib_batch.h and tetris_lib_rollout.h (margin, counters).
+// windows, window batches, the planning agent's windows, experience replay, loss heads, output heads, network inputs.  Needs tetris_lib_batch.h and tetris_lib_rollout.h (margin, counters).
 
 // ---------------------------------------------------------------- planning: action lists, simulated afterstates, list steps
 // Games per k_actions + k_plan_lists pair: bounds the slab scratch (40 x 16 slab entries of max_keys + 1 bytes per game: 128 MB
@@ -414,6 +414,26 @@ static int launch_head(tetris_batch* b, const HeadArgs& h) {
     const dim3 grid((unsigned)head_blocks(h.M)), block(HEAD_THREADS);
     if (h.head == HEAD_Q) return h.grad ? launch(b, k_q_head_grad, grid, block, 0, h) : launch(b, k_q_head, grid, block, 0, h);
     return h.grad ? launch(b, k_policy_head_grad, grid, block, 0, h) : launch(b, k_policy_head, grid, block, 0, h);
+}
+
+// ---------------------------------------------------------------- network inputs (tetris_input.h)
+// What tetris_net_input_dev (tetris_lib_compose.h) runs after the argument rules: one launch, a workgroup per INPUT_BLOCK samples
+// of a slot
+static int launch_input(tetris_batch* b, const InputArgs& ia) {
+    if (ia.ba.m == 0) return TETRIS_OK;
+    const int rc = enqueue(b, Enqueue::CALLER);          // the caller's records -> the caller's planes
+    if (rc) return rc;
+    const dim3 grid((unsigned)input_blocks(ia.ba.m), (unsigned)b->P), block(INPUT_THREADS);
+    // (an image of at most 32 rows — every height but 31 with the pad — fits 32-bit column words; one channel is the same memory in both layouts)
+    with_flag(ia.f16 != 0, [&](auto F16) {
+        with_flag(ia.last != 0 && ia.C > 1, [&](auto LAST) {
+            with_flag(ia.Hp > 32, [&](auto WIDE) {
+                hipLaunchKernelGGL((k_net_input<std::conditional_t<F16(), uint16_t, float>, LAST(), std::conditional_t<WIDE(), uint64_t, uint32_t>>),
+                                   grid, block, 0, b->stream, ia);
+            });
+        });
+    });
+    return launched();
 }
 
 // ---------------------------------------------------------------- loss heads (tetris_loss.h)

@@ -17,6 +17,9 @@ static int launch_traj_batch(B* b, const TrajBatchArgs& ba) { return traj_batch_
 // (and the output heads: launch_head of tetris_lib_agent.h, or head_run_serial)
 template <class B>
 static int launch_head(B*, const HeadArgs& h) { return head_run_serial(h); }
+// (and the network inputs: launch_input of tetris_lib_agent.h, or input_run_serial)
+template <class B>
+static int launch_input(B*, const InputArgs& ia) { return input_run_serial(ia); }
 
 extern "C" {
 
@@ -152,6 +155,14 @@ int tetris_policy_head_grad_dev(tetris_batch* b, const tetris_policy_head* p) {
     HeadArgs h;
     if ((rc = policy_head_args(p, 1, h))) return rc;
     return launch_head(b, h);
+}
+
+int tetris_net_input_dev(tetris_batch* b, const tetris_net_input* in) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    InputArgs ia;
+    if ((rc = input_args(shape_of(b), in, ia))) return rc;
+    return launch_input(b, ia);
 }
 
 int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,

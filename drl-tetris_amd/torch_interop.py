@@ -686,6 +686,53 @@ class TorchEnv:
         return self._kstep(self._kstep_targets, out, reward, done, None, 0, k, steps, gamma, lam, truncate, used_pieces, values)
 
 
+    # ---- network inputs (include/tetris_hip.h: tetris_net_input_dev): the cast, apply_visual_pad and visual_stack
+    # (agents/networks/network_utils.py:71-93) of a network's first layer, straight from packed observation records
+    def _net_input(self, cache, key, lead, source, items, pad, dtype, channels_last):
+        """the checks and the call the three wrappers share: `lead` = the sample dimensions ([M] or [M, steps]); source = the
+        keywords of capi's net_input that name the records -> (visual, vector, piece, valid), reused per (key, lead, settings)"""
+        from . import capi
+        torch = self.torch
+        assert dtype in (torch.float32, torch.float16), "the inputs are float32 or float16"
+        items = tuple(items)
+        assert len(items) <= 4 and len(set(items)) == len(items) and all(i in capi.INPUT_ITEMS for i in items), \
+            f"items: up to four distinct names of {tuple(capi.INPUT_ITEMS)}"
+        S = self.b.n_players
+        Cn, Hp, Wp = capi.input_shape(self.b.height, len(items), pad)
+        full = (key, tuple(lead), items, bool(pad), dtype, bool(channels_last))
+        if full not in cache:
+            f, u8 = dict(dtype=dtype, device=self.dev), dict(dtype=torch.uint8, device=self.dev)
+            k = len(lead)
+            if channels_last:          # the memory of a torch channels_last tensor, handed out in the logical (channels-first) shape
+                visual = torch.zeros(S, *lead, Hp, Wp, Cn, **f).permute(*range(1 + k), 3 + k, 1 + k, 2 + k)
+            else:
+                visual = torch.zeros(S, *lead, Cn, Hp, Wp, **f)
+            cache[full] = (visual, torch.zeros(S, *lead, 12, **f), torch.zeros(S, *lead, **u8), torch.zeros(*lead, **u8))
+        out = cache[full]
+        visual, vector, piece, valid = out
+        if visual.numel() == 0:
+            return out
+        p = self._ptr
+        self.b.net_input_dev(self.b.net_input(items=items, pad=pad, f16=dtype == torch.float16, channels_last=channels_last, visual=p(visual),
+                                              vector=p(vector), piece=p(piece), valid=p(valid), **source))
+        return out
+
+    def net_input(self, player=None, items=("cumsum", "shadow", "height", "holes"), pad=True, dtype=None, channels_last=False):
+        """The network's input of the games' current state for an actor without a window, perspective of player (uint8 [n] or None:
+        player 0): the records of tetris_traj_observe_dev into a private one-row buffer, then their padded plane stacks — two
+        launches, no uint8 planes in between.  -> (visual [S, n, C, Hp, Wp], vector [S, n, 12], piece uint8 [S, n], valid uint8 [n]),
+        as Trajectory.inputs(row=...) gives them; reused device tensors, nothing waits for the GPU.  One and two players."""
+        torch, n = self.torch, self.b.n_games
+        self._check_player(player)
+        if getattr(self, "_input_obs", None) is None:
+            assert self.b.n_players <= 2, "the packed observation is defined for one or two players"
+            self._input_rec = torch.zeros(1, n, self.b.n_players, 12, dtype=torch.int32, device=self.dev)
+            self._input_obs, self._inputs = self.b.traj_obs(1, self._ptr(self._input_rec)), {}
+        self.b.traj_observe_dev(self._input_obs, 0, self._ptr(player))
+        return self._net_input(self._inputs, "row", (n,), dict(m=n, obs=self._input_obs, row=0), items, pad,
+                               torch.float32 if dtype is None else dtype, channels_last)
+
+
 class Trajectory:
     """A trajectory window of a TorchEnv: T = capacity rows of n games, time-major device tensors
         action uint8 [T, n, 4] (r, t, piece, acting player), prob float32 [T, n] (the chosen entry), value float32 [2, T, n]
@@ -829,6 +876,29 @@ class Trajectory:
         env.b.traj_batch_dev(self._traj, self._obs, env._ptr(index), M, out, adv=env._ptr(self.adv), target=env._ptr(self.target))
         return t
 
+    def inputs(self, index=None, row=None, items=("cumsum", "shadow", "height", "holes"), pad=True, dtype=None, channels_last=False):
+        """The network's first-layer inputs of a set of the window's entries straight from their packed records (tetris_net_input_dev:
+        the cast to float, apply_visual_pad and visual_stack of agents/networks/network_utils.py:71-93; batch's uint8 planes are
+        never written): index as for batch (int32 device tensor [M]; bit 31 = mirrored, -1 = none), or row = a row of the window in
+        game order, M = n — the actor's form: observe(row), then inputs(row=row).  items: the reference's `items` list, in channel
+        order, () for the plain float planes; pad=False: the legacy encoder's pad_visuals=False; dtype torch.float32 (default) or
+        torch.float16.  -> (visual [S, M, C, Hp, Wp], vector [S, M, 12] of dtype, piece uint8 [S, M], valid uint8 [M]) device tensors,
+        reused per shape and settings; C = 1 + len(items), Hp = H + 2 and Wp = 12 with pad.  channels_last=True: the same logical
+        shape as a permuted view of [S, M, Hp, Wp, C], so visual[s] is a torch channels_last tensor (the reference's NHWC)."""
+        env, torch = self.env, self.env.torch
+        assert hasattr(self, "obs"), "the window was made without states=True"
+        assert (index is None) != (row is None), "either an index list or a row"
+        if not hasattr(self, "_inputs"):
+            self._inputs = {}
+        dtype = torch.float32 if dtype is None else dtype
+        if index is None:
+            assert 0 <= int(row) < self.capacity, "row outside the window"
+            n = env.b.n_games
+            return env._net_input(self._inputs, "row", (n,), dict(m=n, obs=self._obs, row=int(row)), items, pad, dtype, channels_last)
+        assert index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.dim() == 1
+        M = index.numel()
+        return env._net_input(self._inputs, "index", (M,), dict(m=M, obs=self._obs, index=env._ptr(index)), items, pad, dtype, channels_last)
+
 
 class Replay:
     """The prioritised experience replay of a TorchEnv (agents/agent_utils/experience_replay.py in its rank mode), on the device:
@@ -930,6 +1000,28 @@ class Replay:
         t, out, mask = self._batches[(M, steps)]
         env.b.replay_gather_steps_dev(self._rp, env._ptr(index), M, mask, out)
         return t
+
+    def inputs(self, index, steps=1, items=("cumsum", "shadow", "height", "holes"), pad=True, dtype=None, channels_last=False):
+        """The network's first-layer inputs of the k-step views of index, straight from the ring's records (tetris_net_input_dev):
+        index and steps — a count, or a sequence of step numbers — as for gather.  -> (visual [S, M, steps, C, Hp, Wp], vector [S, M,
+        steps, 12], piece uint8 [S, M, steps], valid uint8 [M, steps]) as Trajectory.inputs gives them; reused device tensors."""
+        from . import capi
+        env, torch = self.env, self.env.torch
+        assert index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.dim() == 1
+        M = index.numel()
+        if isinstance(steps, int):
+            K = int(steps)
+            assert 1 <= K <= self.k_step + 1, "steps outside [1, k_step + 1]"
+            source = dict(steps=K)
+        else:
+            steps = tuple(sorted({int(s) for s in steps}))
+            K = len(steps)
+            assert K >= 1 and 0 <= steps[0] and steps[-1] <= self.k_step <= 63, "steps outside [0, k_step], or k_step above 63"
+            source = dict(step_mask=capi.kstep_mask(steps))
+        if not hasattr(self, "_inputs"):
+            self._inputs = {}
+        return env._net_input(self._inputs, steps, (M, K), dict(m=M, replay=self._rp, index=env._ptr(index), **source), items, pad,
+                              torch.float32 if dtype is None else dtype, channels_last)
 
     def targets(self, index, out, steps=None, gamma=0.99, lam=0.9, truncate=False, used_pieces=None, values=False):
         """model.compute_targets for the samples `index` (int32 device tensor [M]) from the reference net's output for their step

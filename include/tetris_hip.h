@@ -1069,6 +1069,69 @@ int tetris_q_head_grad_dev(tetris_batch *b, const tetris_q_head *h);
 int tetris_policy_head_dev(tetris_batch *b, const tetris_policy_head *h);
 int tetris_policy_head_grad_dev(tetris_batch *b, const tetris_policy_head *h);
 
+/* ---- network inputs: the padded plane stack and the float vector of a network's first layer, from packed records ------------
+ * replaces: the fixed arithmetic every architecture of the reference does between the uint8 planes of a state and its first
+ * learned layer (resblock, resblock_kbd: agents/networks/builders/sventon_architectures.py:25-29; the legacy encoder:
+ * legacy_build_blocks.py:31) — the cast to float, apply_visual_pad (agents/networks/network_utils.py:71-77) and visual_stack
+ * (network_utils.py:79-93) — taken straight from the 48-byte observation records of a window or of the replay ring: the uint8
+ * planes tetris_traj_batch_dev / tetris_replay_gather_dev would write are never written.  Not included: conv_shape_vector's
+ * tiling of the vector over the image (a broadcast), every learned layer, bfloat16.  The definition, operation by operation, is
+ * in drl-tetris_amd/csrc/tetris_input.h.  Device pointers, ONE launch on the batch's stream, nothing waits, the batch's games are
+ * neither read nor written; one and two players.
+ * SOURCES (struct tetris_net_input): how sample j of the call finds its record — the rules of the calls named, not restated.
+ *   a window's index list   obs, d_index int32 [M]: entry d_index[j] & 0x7FFFFFFF of the window, mirrored with bit 31, no sample
+ *                           outside [0, T N) (-1 among them): tetris_traj_batch_dev's.  M samples.
+ *   a row of a window       obs, d_index NULL, row in [0, T), M == N: sample j is entry row N + j, game order, not mirrored — the
+ *                           actor's form: tetris_traj_observe_dev(obs, row, d_player), then this call.
+ *   the replay ring         replay (obs NULL), d_index int32 [M], and step_mask != 0 (tetris_replay_gather_steps_dev's rows,
+ *                           n = its popcount) or else steps (tetris_replay_gather_dev's, n = steps): sample j n + i is ring
+ *                           position d_index[j] + the i-th row, mirrored by bit 0 of d_flags there, no sample for an index
+ *                           outside [0, max_size).  M n samples: every output below has M n in the place of M.
+ * OUTPUTS, each NULL to skip it; float32, or binary16 with TETRIS_INPUT_F16, aligned to the element:
+ *   d_visual  [S][M][C][Hp][Wp], or [S][M][Hp][Wp][C] with TETRIS_INPUT_CHANNELS_LAST (the reference's NHWC; the memory of a torch
+ *             channels_last tensor).  C = 1 + n_items; with TETRIS_INPUT_PAD Hp = H + 2, Wp = 12, without Hp = H, Wp = 10.
+ *   d_vector  [S][M][12]: the float of each byte tetris_traj_batch_dev writes to d_vector (the mirrored one-hot quirk kept).
+ *   d_piece   uint8 [S][M], d_valid uint8 [M]: as tetris_traj_batch_dev writes them.
+ * With f[y][c] the byte tetris_traj_batch_dev gives for the sample (bit y of column c, or of column 9 - c when mirrored; bits
+ * at and above H of a record word reach no channel), the image P is, with TETRIS_INPUT_PAD,
+ *   P[0][x] = 0 for x in 1..10;  P[y][0] = P[y][11] = 1 for every y in 0..H+1;  P[H+1][x] = 1;  P[1+y][1+c] = f[y][c]
+ * (a zero row on top, then ones left, right and below: the second pad covers the first pad's row), and P = f without.  Channel
+ * 0 is P; channel 1 + i is items[i], in the caller's order (the reference's `items` list):
+ *   TETRIS_INPUT_CUMSUM  cumsum[y][x] = sum over y' <= y of P[y'][x]      TETRIS_INPUT_SHADOW  min(cumsum, 1)
+ *   TETRIS_INPUT_HEIGHT  y                                                TETRIS_INPUT_HOLES   shadow - P
+ * Every value is an integer in [0, 33]: exact in both element types.  A sample that is no sample is zeros in every output —
+ * height and the walls included — and d_valid = 0.  16-byte stores are used where the address allows, narrower ones elsewhere.
+ * TETRIS_E_ARG, with nothing written: a NULL argument struct; three or four players; a split batch; obs and replay both
+ * given or both NULL; obs: d_obs NULL or not 16-byte aligned, T N outside [1, 2^31); d_index NULL: row outside [0, T) or
+ * M != N; M < 0; replay: tetris_replay_gather_dev's rules (tetris_replay_gather_steps_dev's with step_mask != 0), a NULL d_index
+ * among them; n_items outside [0, 4]; an item code that is unknown or named twice; an unknown flag; d_visual or d_vector not
+ * aligned to the element type.                                                                                                */
+#define TETRIS_INPUT_CUMSUM 1
+#define TETRIS_INPUT_SHADOW 2
+#define TETRIS_INPUT_HEIGHT 3
+#define TETRIS_INPUT_HOLES  4
+#define TETRIS_INPUT_F16           1   /* d_visual / d_vector are IEEE binary16 instead of float32 */
+#define TETRIS_INPUT_CHANNELS_LAST 2   /* d_visual is [S][M][Hp][Wp][C] instead of [S][M][C][Hp][Wp] */
+#define TETRIS_INPUT_PAD           4   /* apply_visual_pad: Hp = H + 2, Wp = 12 */
+typedef struct tetris_net_input {
+    const tetris_traj_obs *obs;        /* a window's records, or NULL with replay */
+    const tetris_replay   *replay;     /* the ring, or NULL with obs */
+    const int32_t         *d_index;    /* [M]; NULL with obs: the row form */
+    int                    row;        /* the row form: [0, T) */
+    int                    M;
+    int                    steps;      /* the ring, step_mask == 0: [1, k_step + 1] */
+    int                    n_items;    /* [0, 4] */
+    uint64_t               step_mask;  /* the ring: bit s selects row s; 0: the first `steps` rows */
+    int                    items[4];   /* TETRIS_INPUT_CUMSUM / _SHADOW / _HEIGHT / _HOLES, channel order */
+    int                    flags;      /* TETRIS_INPUT_F16 | _CHANNELS_LAST | _PAD */
+    int                    reserved;   /* 0 */
+    void                  *d_visual;   /* [S][M][C][Hp][Wp] or [S][M][Hp][Wp][C] */
+    void                  *d_vector;   /* [S][M][12] */
+    uint8_t               *d_piece;    /* [S][M] */
+    uint8_t               *d_valid;    /* [M] */
+} tetris_net_input;
+int tetris_net_input_dev(tetris_batch *b, const tetris_net_input *in);
+
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
  * t = w1 mod 10), acting player = step mod P, perform_action, auto-reset of finished games with
