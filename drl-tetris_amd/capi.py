@@ -177,6 +177,17 @@ class NetInput(C.Structure):
                 ("d_visual", C.c_void_p), ("d_vector", C.c_void_p), ("d_piece", C.c_void_p), ("d_valid", C.c_void_p)]
 
 
+KBD_F16 = 1                                            # TETRIS_KBD_F16
+KBD_BLOCK, KBD_W_SAMPLES = 16, 256                     # drl-tetris_amd/csrc/tetris_kbd.h: samples per workgroup, per partial of grad_w
+
+
+class KbdConv(C.Structure):
+    """mirrors `struct tetris_kbd_conv` (include/tetris_hip.h)"""
+    _fields_ = [("d_x", C.c_void_p), ("d_w", C.c_void_p), ("d_bias", C.c_void_p), ("d_grad_out", C.c_void_p), ("M", C.c_int),
+                ("n_pieces", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("flags", C.c_int), ("reserved", C.c_int),
+                ("d_out", C.c_void_p), ("d_grad_x", C.c_void_p), ("d_grad_w", C.c_void_p), ("d_grad_b", C.c_void_p)]
+
+
 def input_shape(height, n_items, pad=True):
     """(C, Hp, Wp) of the visual output of net_input_dev: 1 + n_items channels, H + 2 rows and 12 columns with pad, else H and 10."""
     return 1 + int(n_items), int(height) + (2 if pad else 0), W + (2 if pad else 0)
@@ -326,6 +337,9 @@ _SIGNATURES = {
     "tetris_policy_head_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_policy_head_grad_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_net_input_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_kbd_conv_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_kbd_conv_grad_x_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_kbd_conv_grad_w_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_ppo_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_dqn_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_plan_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -923,6 +937,32 @@ class TetrisBatch:
         """The padded plane stack, the float vector, piece and valid of a set of samples straight from their packed records
         (n = net_input(...))."""
         self._check(self.lib.tetris_net_input_dev(self._h, C.byref(n) if n is not None else None))
+
+    # -- keyboard convolution (include/tetris_hip.h: tetris_kbd_conv_dev, _grad_x_dev, _grad_w_dev)
+    def kbd_conv(self, m, height, channels, n_pieces=7, x=None, w=None, bias=None, grad_out=None, out=None, grad_x=None, grad_w=None,
+                 grad_b=None, f16=False, flags=0):
+        """The argument struct of the three kbd_conv calls over raw DEVICE addresses or None: x, grad_x [m][height][12][channels],
+        w [height][3][channels][4 n_pieces], out, grad_out [m][4][10][n_pieces] float32 (f16: binary16); bias, grad_b float32
+        [4 n_pieces]; grad_w float32 like w."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        k = KbdConv()
+        k.d_x, k.d_w, k.d_bias, k.d_grad_out = val(x), val(w), val(bias), val(grad_out)
+        k.M, k.n_pieces, k.height, k.channels = int(m), int(n_pieces), int(height), int(channels)
+        k.flags = (KBD_F16 if f16 else 0) | int(flags)
+        k.d_out, k.d_grad_x, k.d_grad_w, k.d_grad_b = val(out), val(grad_x), val(grad_w), val(grad_b)
+        return k
+
+    def kbd_conv_dev(self, k):
+        """out = keyboard_conv(x) of a minibatch (k = kbd_conv(...))."""
+        self._check(self.lib.tetris_kbd_conv_dev(self._h, C.byref(k) if k is not None else None))
+
+    def kbd_conv_grad_x_dev(self, k):
+        """grad_x from grad_out and w (k = kbd_conv(...))."""
+        self._check(self.lib.tetris_kbd_conv_grad_x_dev(self._h, C.byref(k) if k is not None else None))
+
+    def kbd_conv_grad_w_dev(self, k):
+        """grad_w and grad_b from x and grad_out (k = kbd_conv(...))."""
+        self._check(self.lib.tetris_kbd_conv_grad_w_dev(self._h, C.byref(k) if k is not None else None))
 
     # -- loss heads (include/tetris_hip.h: tetris_ppo_loss_dev, tetris_dqn_loss_dev)
     def ppo_loss(self, pi, v, action, prob_old, adv, target, grad_pi, grad_v, stats, m, n_pieces=7, n_values=1, valid=None, terms=None,

@@ -26,6 +26,7 @@
 #include "tetris_kstep.h"
 #include "tetris_head.h"
 #include "tetris_input.h"
+#include "tetris_kbd.h"
 
 namespace te {
 
@@ -915,6 +916,66 @@ static inline int input_args(const HostShape& s, const tetris_net_input* in, Inp
 static inline int input_run_serial(const InputArgs& ia) {
     for (int sl = 0; sl < ia.ba.n_slots; sl++)
         for (int j = 0; j < ia.ba.m; j++) input_sample_slot(ia, j, sl);
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- keyboard convolution (tetris_kbd.h)
+// the argument rules of the three entry points, then the kernel arguments (all but the scratch, the launcher's)
+static inline bool kbd_overlap(const void* p, size_t np, const void* q, size_t nq) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && a < b + nq && b < a + np;
+}
+static inline int kbd_args(const tetris_kbd_conv* k, int op, KbdArgs& a) {
+    if (!k) return fail(TETRIS_E_ARG, "the argument struct is NULL");
+    if (op == KBD_FWD ? !k->d_x || !k->d_w || !k->d_bias || !k->d_out
+        : op == KBD_GRAD_X ? !k->d_grad_out || !k->d_w || !k->d_grad_x
+                           : !k->d_x || !k->d_grad_out || !k->d_grad_w || !k->d_grad_b)
+        return fail(TETRIS_E_ARG, op == KBD_FWD ? "x/w/bias/out are NULL" : op == KBD_GRAD_X ? "grad_out/w/grad_x are NULL" : "x/grad_out/grad_w/grad_b are NULL");
+    if (k->M < 1) return fail(TETRIS_E_ARG, "M < 1");
+    if (k->n_pieces < 1 || k->n_pieces > 7) return fail(TETRIS_E_ARG, "n_pieces must be in [1, 7]");
+    if (k->height < 4 || k->height > 33) return fail(TETRIS_E_ARG, "height must be in [4, 33]");
+    if (k->channels < 32 || k->channels > 512 || k->channels % 32) return fail(TETRIS_E_ARG, "channels must be a multiple of 32 in [32, 512]");
+    if (k->flags & ~TETRIS_KBD_F16) return fail(TETRIS_E_ARG, "unknown flag");
+    const size_t es = (k->flags & TETRIS_KBD_F16) ? 2 : 4, O = 4 * (size_t)k->n_pieces;
+    const size_t nx = (size_t)k->M * k->height * KBD_W * k->channels * es, nw = (size_t)k->height * KBD_D * k->channels * O,
+                 no = (size_t)k->M * KBD_T * O * es;
+    // the arrays of the call: {pointer, bytes}, inputs first
+    const void* in[3] = {nullptr, nullptr, nullptr};
+    const void* out[2] = {nullptr, nullptr};
+    size_t in_n[3] = {0, 0, 0}, out_n[2] = {0, 0};
+    if (op == KBD_FWD) { in[0] = k->d_x; in_n[0] = nx; in[1] = k->d_w; in_n[1] = nw * es; in[2] = k->d_bias; in_n[2] = O * 4; out[0] = k->d_out; out_n[0] = no; }
+    else if (op == KBD_GRAD_X) { in[0] = k->d_grad_out; in_n[0] = no; in[1] = k->d_w; in_n[1] = nw * es; out[0] = k->d_grad_x; out_n[0] = nx; }
+    else { in[0] = k->d_x; in_n[0] = nx; in[1] = k->d_grad_out; in_n[1] = no; out[0] = k->d_grad_w; out_n[0] = nw * 4; out[1] = k->d_grad_b; out_n[1] = O * 4; }
+    for (int i = 0; i < 3; i++)
+        if (((uintptr_t)in[i]) & 15u) return fail(TETRIS_E_ARG, "the arrays must be 16-byte aligned");
+    for (int i = 0; i < 2; i++)
+        if (((uintptr_t)out[i]) & 15u) return fail(TETRIS_E_ARG, "the arrays must be 16-byte aligned");
+    for (int o = 0; o < 2; o++) {
+        for (int i = 0; i < 3; i++)
+            if (kbd_overlap(out[o], out_n[o], in[i], in_n[i])) return fail(TETRIS_E_ARG, "an output overlaps an input");
+        if (o == 1 && kbd_overlap(out[0], out_n[0], out[1], out_n[1])) return fail(TETRIS_E_ARG, "the outputs overlap");
+    }
+    memset(&a, 0, sizeof a);
+    a.op = op; a.M = k->M; a.K = k->n_pieces; a.O = 4 * k->n_pieces; a.Hp = k->height; a.C = k->channels;
+    a.f16 = (k->flags & TETRIS_KBD_F16) ? 1 : 0;
+    if (op == KBD_FWD) { a.x = k->d_x; a.w = k->d_w; a.bias = k->d_bias; a.out = k->d_out; }
+    else if (op == KBD_GRAD_X) { a.g = k->d_grad_out; a.w = k->d_w; a.out = k->d_grad_x; }
+    else { a.x = k->d_x; a.g = k->d_grad_out; a.grad_w = k->d_grad_w; a.grad_b = k->d_grad_b; }
+    return TETRIS_OK;
+}
+// A call over host memory (the CPU build of the bodies: tests/cpu_harness), the product's launches as loops over samples or over
+// the rows of grad_w.  tetris_lib_compose.h says which side runs what.
+static inline int kbd_run_serial(const KbdArgs& a) {
+    if (a.op == KBD_FWD) {
+        for (int m = 0; m < a.M; m++) kbd_forward_sample_serial(a, (size_t)m);
+    } else if (a.op == KBD_GRAD_X) {
+        for (int m = 0; m < a.M; m++) kbd_grad_x_sample_serial(a, (size_t)m);
+    } else {
+        for (int h = 0; h < a.Hp; h++)
+            for (int d = 0; d < KBD_D; d++)
+                for (int c = 0; c < a.C; c++) kbd_grad_w_row_serial(a, h, d, c);
+        kbd_grad_b_serial(a);
+    }
     return TETRIS_OK;
 }
 

@@ -416,6 +416,35 @@ static int launch_head(tetris_batch* b, const HeadArgs& h) {
     return h.grad ? launch(b, k_policy_head_grad, grid, block, 0, h) : launch(b, k_policy_head, grid, block, 0, h);
 }
 
+// ---------------------------------------------------------------- keyboard convolution (tetris_kbd.h)
+// What the three keyboard-convolution entry points (tetris_lib_compose.h) run after the argument rules, two launches each: the
+// forward and grad_x repack w into the batch's scratch and then run the product; grad_w writes a partial per chunk of
+// KBD_W_SAMPLES samples there and then adds them up
+static int launch_kbd(tetris_batch* b, const KbdArgs& in) {
+    KbdArgs a = in;
+    const size_t packed = (size_t)a.Hp * KBD_D * KBD_OP * a.C, per = packed + KBD_OP;      // elements of the repacked w; floats of a partial with its bias row
+    a.chunks = kbd_w_chunks(a.M);
+    const size_t words = a.op == KBD_GRAD_W ? (size_t)a.chunks * per : a.f16 ? packed / 2 : packed;
+    int rc = b->kbd_scratch.ensure(words, b->stream);
+    if (rc || (rc = enqueue(b, Enqueue::STATE))) return rc;          // (the batch's scratch)
+    a.packed = b->kbd_scratch.d; a.partial = reinterpret_cast<float*>(b->kbd_scratch.d);
+    const dim3 block(KBD_THREADS);
+    with_flag(a.f16 != 0, [&](auto F16) {
+        if (a.op == KBD_FWD) {
+            hipLaunchKernelGGL((k_kbd_pack<F16(), true>), dim3(blocks_for(packed, KBD_THREADS)), block, 0, b->stream, a, (void*)b->kbd_scratch.d);
+            hipLaunchKernelGGL((k_kbd_fwd<F16(), KBD_BLOCK>), dim3((unsigned)kbd_blocks(a.M)), dim3(KBD_FWD_THREADS), 0, b->stream, a);
+        } else if (a.op == KBD_GRAD_X) {
+            hipLaunchKernelGGL((k_kbd_pack<F16(), false>), dim3(blocks_for(packed, KBD_THREADS)), block, 0, b->stream, a, (void*)b->kbd_scratch.d);
+            hipLaunchKernelGGL((k_kbd_grad_x<F16(), KBD_BLOCK>), dim3((unsigned)kbd_blocks(a.M)), block, 0, b->stream, a);
+        } else {
+            const dim3 grid((unsigned)a.chunks, (unsigned)a.Hp, (unsigned)((a.C + KBD_W_CHANNELS - 1) / KBD_W_CHANNELS));
+            hipLaunchKernelGGL((k_kbd_grad_w<F16()>), grid, block, 0, b->stream, a);
+            hipLaunchKernelGGL(k_kbd_grad_w_reduce, dim3(blocks_for(per, KBD_THREADS)), block, 0, b->stream, a);
+        }
+    });
+    return launched();
+}
+
 // ---------------------------------------------------------------- network inputs (tetris_input.h)
 // What tetris_net_input_dev (tetris_lib_compose.h) runs after the argument rules: one launch, a workgroup per INPUT_BLOCK samples
 // of a slot

@@ -251,7 +251,10 @@ struct tetris_batch {
     Scratch<uint32_t> loss_scratch;
     // tetris_kstep_target_dev in Q mode without d_values: the values of the M n rows (grown on demand)
     Scratch<float> kstep_values;
+    // the keyboard convolution: w repacked for the matrix unit (forward, grad_x) or grad_w's partial sums (grown on demand)
+    Scratch<uint32_t> kbd_scratch;
     void release_scratch() {
+        kbd_scratch.release();
         plan_slabs.release(); iota.release(); plan_status.release(); policy_scores.release(); words_before.release();
         select_blocks.release(); replay_offsets.release(); replay_sort.release(); loss_scratch.release(); kstep_values.release();
     }

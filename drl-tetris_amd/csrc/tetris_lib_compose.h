@@ -20,6 +20,9 @@ static int launch_head(B*, const HeadArgs& h) { return head_run_serial(h); }
 // (and the network inputs: launch_input of tetris_lib_agent.h, or input_run_serial)
 template <class B>
 static int launch_input(B*, const InputArgs& ia) { return input_run_serial(ia); }
+// (and the keyboard convolution: launch_kbd of tetris_lib_agent.h, or kbd_run_serial)
+template <class B>
+static int launch_kbd(B*, const KbdArgs& a) { return kbd_run_serial(a); }
 
 extern "C" {
 
@@ -163,6 +166,30 @@ int tetris_net_input_dev(tetris_batch* b, const tetris_net_input* in) {
     InputArgs ia;
     if ((rc = input_args(shape_of(b), in, ia))) return rc;
     return launch_input(b, ia);
+}
+
+int tetris_kbd_conv_dev(tetris_batch* b, const tetris_kbd_conv* k) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    KbdArgs a;
+    if ((rc = kbd_args(k, KBD_FWD, a))) return rc;
+    return launch_kbd(b, a);
+}
+
+int tetris_kbd_conv_grad_x_dev(tetris_batch* b, const tetris_kbd_conv* k) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    KbdArgs a;
+    if ((rc = kbd_args(k, KBD_GRAD_X, a))) return rc;
+    return launch_kbd(b, a);
+}
+
+int tetris_kbd_conv_grad_w_dev(tetris_batch* b, const tetris_kbd_conv* k) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    KbdArgs a;
+    if ((rc = kbd_args(k, KBD_GRAD_W, a))) return rc;
+    return launch_kbd(b, a);
 }
 
 int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,

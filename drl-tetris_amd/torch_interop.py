@@ -35,6 +35,26 @@ def columns_to_deltas(cols, player, before, count, height, out=None, small_fill=
     return out, out.sum(dim=-1, keepdim=True)
 
 
+def kbd_weight_from_conv2d(weight):
+    """torch's conv2d kernel [O, C, Hp, 3] (OIHW) -> the keyboard convolution's [Hp, 3, C, O] (HWIO, the reference variable's own
+    layout: a checkpoint's kernel needs no transpose), contiguous."""
+    return weight.permute(2, 3, 1, 0).contiguous()
+
+
+def kbd_weight_to_conv2d(weight):
+    """[Hp, 3, C, O] (HWIO) -> torch's conv2d kernel [O, C, Hp, 3] (OIHW), contiguous."""
+    return weight.permute(3, 2, 0, 1).contiguous()
+
+
+def keyboard_conv_init(Hp, C, K, device=None, generator=None):
+    """The reference's initialisation of keyboard_conv (agents/networks/builders/build_blocks.py:76-77): -> (weight float32
+    [Hp, 3, C, 4 K], all zeros; bias float32 [4 K] drawn from a normal distribution of mean 0 and standard deviation 1e-5)."""
+    import torch
+    weight = torch.zeros(int(Hp), 3, int(C), 4 * int(K), dtype=torch.float32, device=device)
+    bias = torch.randn(4 * int(K), dtype=torch.float32, generator=generator) * 1e-5
+    return weight, bias.to(device) if device is not None else bias
+
+
 class TorchEnv:
     def __init__(self, batch, device=None):
         import torch
@@ -640,6 +660,70 @@ class TorchEnv:
         Differentiable with respect to x and w.  Device tensors, reused as q_head's are; backward reads the stored pi and v: call it
         before the next policy_head of the same shapes.  Nothing waits for the GPU."""
         return self._head_functions()[1].apply(x, w)
+
+    # ---- keyboard convolution (include/tetris_hip.h: tetris_kbd_conv_dev and its _grad_x_dev / _grad_w_dev): the network's last
+    # learned layer (agents/networks/builders/build_blocks.py:68-83), differentiable
+    def _kbd_input(self, x):
+        """x [M, C, Hp, 12] as the library reads it: itself when its memory is channels_last (NHWC), else one layout copy"""
+        torch = self.torch
+        return x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+
+    def _kbd_function(self):
+        torch = self.torch
+        if getattr(self, "_kbd_fn", None) is not None:
+            return self._kbd_fn
+        env, p = self, self._ptr
+
+        class KeyboardConv(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, weight, bias):
+                assert x.dtype in (torch.float32, torch.float16) and x.is_cuda, "x is a float32 or float16 device tensor"
+                assert x.dim() == 4 and x.shape[3] == 12 and x.shape[0] >= 1, "x must be [M, C, Hp, 12]"
+                M, Cn, Hp = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+                assert weight.dim() == 4 and tuple(weight.shape[:3]) == (Hp, 3, Cn) and weight.shape[3] % 4 == 0, "weight must be [Hp, 3, C, 4 K]"
+                K = int(weight.shape[3]) // 4
+                assert bias.dtype == torch.float32 and tuple(bias.shape) == (4 * K,) and bias.is_cuda, "bias is a float32 device tensor [4 K]"
+                xl = env._kbd_input(x.detach())
+                w = weight.detach().to(x.dtype).contiguous()
+                b32 = bias.detach().contiguous()
+
+                def make(cap):
+                    return (torch.zeros(cap, 4, 10, K, dtype=x.dtype, device=env.dev),
+                            torch.zeros(cap, Cn, Hp, 12, dtype=x.dtype, device=env.dev).contiguous(memory_format=torch.channels_last),
+                            torch.zeros(Hp, 3, Cn, 4 * K, dtype=torch.float32, device=env.dev), torch.zeros(4 * K, dtype=torch.float32, device=env.dev))
+                out, grad_x, grad_w, grad_b = env._loss_buffers(("kbd_conv", Hp, Cn, K, x.dtype), M, make)
+                kw = dict(m=M, height=Hp, channels=Cn, n_pieces=K, f16=x.dtype == torch.float16)
+                env.b.kbd_conv_dev(env.b.kbd_conv(x=p(xl), w=p(w), bias=p(b32), out=p(out), **kw))
+                ctx.x, ctx.w, ctx.kw, ctx.grads, ctx.types = xl, w, kw, (grad_x[:M], grad_w, grad_b), (weight.dtype, bias.dtype)
+                return out[:M]
+
+            @staticmethod
+            def backward(ctx, grad_out):
+                (grad_x, grad_w, grad_b), (wdt, bdt) = ctx.grads, ctx.types
+                g = grad_out.to(ctx.x.dtype).contiguous()
+                need_x, need_w, need_b = ctx.needs_input_grad
+                if need_x:
+                    env.b.kbd_conv_grad_x_dev(env.b.kbd_conv(w=p(ctx.w), grad_out=p(g), grad_x=p(grad_x), **ctx.kw))
+                if need_w or need_b:
+                    env.b.kbd_conv_grad_w_dev(env.b.kbd_conv(x=p(ctx.x), grad_out=p(g), grad_w=p(grad_w), grad_b=p(grad_b), **ctx.kw))
+                return (grad_x if need_x else None, grad_w.to(wdt) if need_w else None, grad_b.to(bdt) if need_b else None)
+        self._kbd_fn = KeyboardConv
+        return self._kbd_fn
+
+    def keyboard_conv(self, x, weight, bias):
+        """The reference's keyboard_conv (agents/networks/builders/build_blocks.py:68-83, without its activation, which q_head and
+        policy_head apply): a "valid" convolution of the trunk's output x [M, C, Hp, 12] with a kernel as tall as the image and three
+        columns wide, and the four channel slices concatenated along the rotation axis, on the matrix cores.  x float32 or
+        float16, C a multiple of 32 in 32..512, Hp in 4..33; weight [Hp, 3, C, 4 K] (HWIO: kbd_weight_from_conv2d gives it from a
+        conv2d kernel), cast to x's type when it is a float32 master weight; bias float32 [4 K], K in 1..7.  -> [M, 4, 10, K] in
+        x's type, differentiable with respect to x, weight and bias (grad_w and grad_b in the parameters' types):
+            out = te.select_eval(te.q_head(te.keyboard_conv(trunk(visual, vector), w, b))[0], mode="argmax")
+        x is read in place when its memory is channels_last (tr.inputs(channels_last=True) and a channels_last trunk give that);
+        otherwise it is COPIED once with .contiguous(memory_format=torch.channels_last), forward and for grad_w.  Device tensors,
+        reused by every call with the same Hp, C, K and element type (the leading M samples of one set that grows to the largest M
+        seen): use the output — heads, select, loss — and call backward before the next keyboard_conv of the same shapes; the
+        gradients handed back are reused likewise.  Nothing waits for the GPU."""
+        return self._kbd_function().apply(x, weight, bias)
 
     # ---- k-step target estimator (include/tetris_hip.h: tetris_kstep_target_dev): model.compute_targets
     # (agents/sventon_agent/sventon_agent_dqn_trainer.py:49-59, agents/networks/value_estimator.py:51-88)

@@ -1132,6 +1132,53 @@ typedef struct tetris_net_input {
 } tetris_net_input;
 int tetris_net_input_dev(tetris_batch *b, const tetris_net_input *in);
 
+/* ---- keyboard convolution: the network's last learned layer, forward and gradients, on the matrix cores --------------------
+ * replaces: keyboard_conv (agents/networks/builders/build_blocks.py:68-83) as resblock_kbd ends in it
+ * (agents/networks/builders/sventon_architectures.py:71-73) — tf.layers.conv2d with a "valid" kernel as tall as the image and
+ * three columns wide (build_blocks.py:69-78), the n_rot = 4 channel slices and their concat along the rotation axis
+ * (build_blocks.py:79-80) — and autograd's backward through it.  Not included: kbd_activation (build_blocks.py:81-82; it stays
+ * with tetris_q_head_dev / tetris_policy_head_dev), the residual blocks and every other learned layer, conv_shape_vector and the
+ * peephole concats, bfloat16, an image width other than 12, the optimiser and the regulariser.  The definition is in
+ * drl-tetris_amd/csrc/tetris_kbd.h.  Device pointers, asynchronous on the batch's stream, nothing waits; the batch's games are
+ * neither read nor written, every batch shape serves; the batch's scratch holds the repacked kernel and grad_w's partial sums,
+ * so calls on one batch are ordered by its stream.
+ *   K = n_pieces in 1..7, O = 4 K, o = r K + k; Hp = height in 4..33 (the padded image's rows), C = channels, a multiple of 32
+ *   in 32..512.  d_x [M][Hp][12][C] (NHWC: the memory of a torch channels_last tensor [M, C, Hp, 12]); d_w [Hp][3][C][O] (HWIO,
+ *   the reference variable's layout); d_bias float32 [O]; d_out, d_grad_out [M][4][10][K]; d_grad_x like d_x; d_grad_w float32
+ *   like d_w; d_grad_b float32 [O].  d_x, d_w, d_out, d_grad_out and d_grad_x are float32, or all binary16 with TETRIS_KBD_F16.
+ *     out[m][r][t][k]    = bias[o] + sum_h sum_d sum_c x[m][h][t + d][c] w[h][d][c][o]                 d in 0..2, t in 0..9
+ *     grad_x[m][h][j][c] = sum over d with 0 <= j - d <= 9, sum_o grad_out[m][r][j - d][k] w[h][d][c][o]
+ *     grad_w[h][d][c][o] = sum_m sum_t x[m][h][t + d][c] grad_out[m][r][t][k];   grad_b[o] = sum_m sum_t grad_out[m][r][t][k]
+ *   Products and sums in float32, one rounding to nearest even on the way out; the order of the sums is the matrix unit's and is
+ *   not specified; no atomics: a call repeated on the same inputs gives the same bytes.  Every element of every output is
+ *   written, nothing past it.
+ *   tetris_kbd_conv_dev reads d_x, d_w, d_bias; writes d_out.  tetris_kbd_conv_grad_x_dev reads d_grad_out, d_w; writes d_grad_x.
+ *   tetris_kbd_conv_grad_w_dev reads d_x, d_grad_out; writes d_grad_w and d_grad_b.  Arrays a call neither reads nor writes may
+ *   be NULL.
+ * TETRIS_E_ARG, with nothing written: a NULL argument struct or a NULL array the call reads or writes; M < 1; n_pieces outside
+ * [1, 7]; height outside [4, 33]; channels no multiple of 32 or outside [32, 512]; an unknown flag; an array of the call that is
+ * not 16-byte aligned; an output of the call that overlaps one of its inputs.                                                  */
+#define TETRIS_KBD_F16 1   /* d_x, d_w, d_out, d_grad_out and d_grad_x are IEEE binary16 instead of float32 */
+typedef struct tetris_kbd_conv {
+    const void    *d_x;             /* [M][height][12][channels], 16-byte aligned */
+    const void    *d_w;             /* [height][3][channels][4 n_pieces], 16-byte aligned */
+    const float   *d_bias;          /* [4 n_pieces], 16-byte aligned */
+    const void    *d_grad_out;      /* backward: [M][4][10][n_pieces], 16-byte aligned */
+    int            M;
+    int            n_pieces;        /* K: 1..7 */
+    int            height;          /* Hp: 4..33 */
+    int            channels;        /* C: a multiple of 32 in 32..512 */
+    int            flags;           /* TETRIS_KBD_F16 */
+    int            reserved;        /* 0 */
+    void          *d_out;           /* forward: [M][4][10][n_pieces], 16-byte aligned */
+    void          *d_grad_x;        /* like d_x */
+    float         *d_grad_w;        /* like d_w, float32 */
+    float         *d_grad_b;        /* [4 n_pieces] */
+} tetris_kbd_conv;
+int tetris_kbd_conv_dev(tetris_batch *b, const tetris_kbd_conv *k);
+int tetris_kbd_conv_grad_x_dev(tetris_batch *b, const tetris_kbd_conv *k);
+int tetris_kbd_conv_grad_w_dev(tetris_batch *b, const tetris_kbd_conv *k);
+
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
  * t = w1 mod 10), acting player = step mod P, perform_action, auto-reset of finished games with
