@@ -188,6 +188,29 @@ class KbdConv(C.Structure):
                 ("d_out", C.c_void_p), ("d_grad_x", C.c_void_p), ("d_grad_w", C.c_void_p), ("d_grad_b", C.c_void_p)]
 
 
+RES_F16 = 1                                            # TETRIS_RES_F16
+RES_JOIN_NONE, RES_JOIN_ADD, RES_JOIN_TRUNCATE_ADD = 0, 1, 2               # TETRIS_RES_JOIN_*
+RES_ACT_NONE, RES_ACT_ELU = 0, 1                       # TETRIS_RES_ACT_*
+RES_JOINS = {None: RES_JOIN_NONE, "none": RES_JOIN_NONE, "add": RES_JOIN_ADD, "truncate_add": RES_JOIN_TRUNCATE_ADD}
+RES_ACTS = {None: RES_ACT_NONE, "none": RES_ACT_NONE, "elu": RES_ACT_ELU}
+RES_ROWS, RES_W_SAMPLES = 8, 64                        # drl-tetris_amd/csrc/tetris_res.h: image rows per workgroup, samples per partial of grad_w
+
+
+class ResLayer(C.Structure):
+    """mirrors `struct tetris_res_layer` (include/tetris_hip.h)"""
+    _fields_ = [("d_x", C.c_void_p), ("d_w", C.c_void_p), ("d_bias", C.c_void_p), ("d_y", C.c_void_p), ("d_grad_out", C.c_void_p),
+                ("M", C.c_int), ("height", C.c_int), ("in_channels", C.c_int), ("out_channels", C.c_int), ("join", C.c_int),
+                ("activation", C.c_int), ("flags", C.c_int), ("reserved", C.c_int),
+                ("d_out", C.c_void_p), ("d_grad_x", C.c_void_p), ("d_grad_w", C.c_void_p), ("d_grad_b", C.c_void_p)]
+
+
+def res_out_channels(in_channels, out_channels, join):
+    """Cout of a residual layer: Co without a join, max(Ci, Co) with "add", min(Ci, Co) with "truncate_add" (peephole_join,
+    agents/networks/network_utils.py:52-64)."""
+    j = RES_JOINS.get(join, join)
+    return int(out_channels) if j == RES_JOIN_NONE else max(int(in_channels), int(out_channels)) if j == RES_JOIN_ADD else min(int(in_channels), int(out_channels))
+
+
 def input_shape(height, n_items, pad=True):
     """(C, Hp, Wp) of the visual output of net_input_dev: 1 + n_items channels, H + 2 rows and 12 columns with pad, else H and 10."""
     return 1 + int(n_items), int(height) + (2 if pad else 0), W + (2 if pad else 0)
@@ -340,6 +363,9 @@ _SIGNATURES = {
     "tetris_kbd_conv_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_kbd_conv_grad_x_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_kbd_conv_grad_w_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_res_layer_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_res_layer_grad_x_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tetris_res_layer_grad_w_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_ppo_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_dqn_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tetris_plan_loss_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -963,6 +989,34 @@ class TetrisBatch:
     def kbd_conv_grad_w_dev(self, k):
         """grad_w and grad_b from x and grad_out (k = kbd_conv(...))."""
         self._check(self.lib.tetris_kbd_conv_grad_w_dev(self._h, C.byref(k) if k is not None else None))
+
+    # -- residual layer (include/tetris_hip.h: tetris_res_layer_dev, _grad_x_dev, _grad_w_dev)
+    def res_layer(self, m, height, in_channels, out_channels, join="add", activation="elu", x=None, w=None, bias=None, y=None,
+                  grad_out=None, out=None, grad_x=None, grad_w=None, grad_b=None, f16=False, flags=0):
+        """The argument struct of the three res_layer calls over raw DEVICE addresses or None: x, grad_x [m][height][12][in_channels],
+        w [3][3][in_channels][out_channels], out, y, grad_out [m][height][12][res_out_channels(...)] float32 (f16: binary16); bias,
+        grad_b float32 [out_channels]; grad_w float32 like w.  join "none" / "add" / "truncate_add" and activation "none" / "elu"
+        (or None, or the header's numbers)."""
+        val = lambda a: a.value if isinstance(a, C.c_void_p) else a               # noqa: E731
+        r = ResLayer()
+        r.d_x, r.d_w, r.d_bias, r.d_y, r.d_grad_out = val(x), val(w), val(bias), val(y), val(grad_out)
+        r.M, r.height, r.in_channels, r.out_channels = int(m), int(height), int(in_channels), int(out_channels)
+        r.join, r.activation = int(RES_JOINS.get(join, join)), int(RES_ACTS.get(activation, activation))
+        r.flags = (RES_F16 if f16 else 0) | int(flags)
+        r.d_out, r.d_grad_x, r.d_grad_w, r.d_grad_b = val(out), val(grad_x), val(grad_w), val(grad_b)
+        return r
+
+    def res_layer_dev(self, r):
+        """out = act(join(x, conv3x3(x))) of a minibatch (r = res_layer(...))."""
+        self._check(self.lib.tetris_res_layer_dev(self._h, C.byref(r) if r is not None else None))
+
+    def res_layer_grad_x_dev(self, r):
+        """grad_x from grad_out, w and, with ELU, y (r = res_layer(...))."""
+        self._check(self.lib.tetris_res_layer_grad_x_dev(self._h, C.byref(r) if r is not None else None))
+
+    def res_layer_grad_w_dev(self, r):
+        """grad_w and grad_b from x, grad_out and, with ELU, y (r = res_layer(...))."""
+        self._check(self.lib.tetris_res_layer_grad_w_dev(self._h, C.byref(r) if r is not None else None))
 
     # -- loss heads (include/tetris_hip.h: tetris_ppo_loss_dev, tetris_dqn_loss_dev)
     def ppo_loss(self, pi, v, action, prob_old, adv, target, grad_pi, grad_v, stats, m, n_pieces=7, n_values=1, valid=None, terms=None,

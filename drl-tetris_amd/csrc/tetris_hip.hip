@@ -34,6 +34,7 @@
 #include "tetris_dev_kstep.h"
 #include "tetris_dev_head.h"
 #include "tetris_dev_kbd.h"
+#include "tetris_dev_res.h"             // (the fragments of tetris_dev_kbd.h)
 #include "tetris_dev_traj.h"
 #include "tetris_dev_replay.h"           // (select_block_scan of tetris_dev_traj.h)
 #include "tetris_dev_input.h"

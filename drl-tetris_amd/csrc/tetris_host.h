@@ -27,6 +27,7 @@
 #include "tetris_head.h"
 #include "tetris_input.h"
 #include "tetris_kbd.h"
+#include "tetris_res.h"
 
 namespace te {
 
@@ -975,6 +976,82 @@ static inline int kbd_run_serial(const KbdArgs& a) {
             for (int d = 0; d < KBD_D; d++)
                 for (int c = 0; c < a.C; c++) kbd_grad_w_row_serial(a, h, d, c);
         kbd_grad_b_serial(a);
+    }
+    return TETRIS_OK;
+}
+
+// ---------------------------------------------------------------- residual layer (tetris_res.h)
+// the argument rules of the three entry points, then the kernel arguments (all but the scratch, the launcher's)
+static inline int res_args(const tetris_res_layer* r, int op, ResArgs& a) {
+    if (!r) return fail(TETRIS_E_ARG, "the argument struct is NULL");
+    if (r->M < 1) return fail(TETRIS_E_ARG, "M < 1");
+    if (r->height < 4 || r->height > 33) return fail(TETRIS_E_ARG, "height must be in [4, 33]");
+    if (r->in_channels < 8 || r->in_channels > RES_MAX_C || r->in_channels % 8) return fail(TETRIS_E_ARG, "in_channels must be a multiple of 8 in [8, 512]");
+    if (r->out_channels < 32 || r->out_channels > RES_MAX_C || r->out_channels % 32) return fail(TETRIS_E_ARG, "out_channels must be a multiple of 32 in [32, 512]");
+    if (r->join != TETRIS_RES_JOIN_NONE && r->join != TETRIS_RES_JOIN_ADD && r->join != TETRIS_RES_JOIN_TRUNCATE_ADD) return fail(TETRIS_E_ARG, "unknown join");
+    if (r->activation != TETRIS_RES_ACT_NONE && r->activation != TETRIS_RES_ACT_ELU) return fail(TETRIS_E_ARG, "unknown activation");
+    if (r->flags & ~TETRIS_RES_F16) return fail(TETRIS_E_ARG, "unknown flag");
+    const bool elu = r->activation == TETRIS_RES_ACT_ELU;
+    if (op == RES_FWD ? !r->d_x || !r->d_w || !r->d_bias || !r->d_out
+        : op == RES_GRAD_X ? !r->d_grad_out || !r->d_w || !r->d_grad_x || (elu && !r->d_y)
+                           : !r->d_x || !r->d_grad_out || !r->d_grad_w || !r->d_grad_b || (elu && !r->d_y))
+        return fail(TETRIS_E_ARG, op == RES_FWD ? "x/w/bias/out are NULL" : op == RES_GRAD_X ? "grad_out/w/grad_x (ELU: y) are NULL" : "x/grad_out/grad_w/grad_b (ELU: y) are NULL");
+    const size_t es = (r->flags & TETRIS_RES_F16) ? 2 : 4, Ci = (size_t)r->in_channels, Co = (size_t)r->out_channels;
+    const size_t Cout = (size_t)res_cout(r->in_channels, r->out_channels, r->join), pos = (size_t)r->M * r->height * RES_W;
+    const size_t nx = pos * Ci * es, nw = RES_TAPS * Ci * Co, no = pos * Cout * es;
+    // the arrays of the call: {pointer, bytes}, inputs first
+    const void* in[3] = {nullptr, nullptr, nullptr};
+    const void* out[2] = {nullptr, nullptr};
+    size_t in_n[3] = {0, 0, 0}, out_n[2] = {0, 0};
+    if (op == RES_FWD) { in[0] = r->d_x; in_n[0] = nx; in[1] = r->d_w; in_n[1] = nw * es; in[2] = r->d_bias; in_n[2] = Co * 4; out[0] = r->d_out; out_n[0] = no; }
+    else if (op == RES_GRAD_X) { in[0] = r->d_grad_out; in_n[0] = no; in[1] = r->d_w; in_n[1] = nw * es; if (elu) { in[2] = r->d_y; in_n[2] = no; } out[0] = r->d_grad_x; out_n[0] = nx; }
+    else { in[0] = r->d_x; in_n[0] = nx; in[1] = r->d_grad_out; in_n[1] = no; if (elu) { in[2] = r->d_y; in_n[2] = no; } out[0] = r->d_grad_w; out_n[0] = nw * 4; out[1] = r->d_grad_b; out_n[1] = Co * 4; }
+    for (int i = 0; i < 3; i++)
+        if (((uintptr_t)in[i]) & 15u) return fail(TETRIS_E_ARG, "the arrays must be 16-byte aligned");
+    for (int i = 0; i < 2; i++)
+        if (((uintptr_t)out[i]) & 15u) return fail(TETRIS_E_ARG, "the arrays must be 16-byte aligned");
+    for (int o = 0; o < 2; o++) {
+        for (int i = 0; i < 3; i++)
+            if (kbd_overlap(out[o], out_n[o], in[i], in_n[i])) return fail(TETRIS_E_ARG, "an output overlaps an input");
+        if (o == 1 && kbd_overlap(out[0], out_n[0], out[1], out_n[1])) return fail(TETRIS_E_ARG, "the outputs overlap");
+    }
+    memset(&a, 0, sizeof a);
+    a.op = op; a.M = r->M; a.Hp = r->height; a.Ci = r->in_channels; a.Co = r->out_channels; a.Cout = (int)Cout; a.Cz = imin(a.Co, a.Cout);
+    a.join = r->join; a.elu = elu ? 1 : 0; a.f16 = a.f16_in = (r->flags & TETRIS_RES_F16) ? 1 : 0;
+    if (op == RES_FWD) { a.x = r->d_x; a.w = r->d_w; a.bias = r->d_bias; a.out = r->d_out; }
+    else if (op == RES_GRAD_X) { a.g = r->d_grad_out; a.y = r->d_y; a.w = r->d_w; a.out = r->d_grad_x; }
+    else { a.x = r->d_x; a.g = r->d_grad_out; a.y = r->d_y; a.grad_w = r->d_grad_w; a.grad_b = r->d_grad_b; }
+    return TETRIS_OK;
+}
+// A call over host memory (the CPU build of the bodies: tests/cpu_harness), the product's launches as loops over image rows or over
+// the rows of grad_w.  The arrays read are widened to float32 once, and e is formed once (res_e of a formed e is that e), so the
+// serial forms' inner loops are plain float32.  tetris_lib_compose.h says which side runs what.
+static inline int res_run_serial(const ResArgs& in) {
+    ResArgs a = in;
+    const size_t pos = (size_t)a.M * a.Hp * RES_W;
+    std::vector<float> x, w, e;
+    auto widen = [&](const void* p, size_t n, std::vector<float>& v) {
+        v.resize(n);
+        for (size_t i = 0; i < n; i++) v[i] = act_element(p, i, in.f16);
+    };
+    if (a.op != RES_GRAD_X) { widen(in.x, pos * a.Ci, x); a.x = x.data(); }
+    if (a.op != RES_GRAD_W) { widen(in.w, (size_t)RES_TAPS * a.Ci * a.Co, w); a.w = w.data(); }
+    if (a.op != RES_FWD) {
+        e.resize(pos * a.Cout);
+        for (size_t i = 0; i < e.size(); i++) e[i] = res_e_at(in, i);
+        a.g = e.data(); a.y = nullptr; a.elu = 0;
+    }
+    a.f16_in = 0;
+    if (a.op == RES_FWD) {
+        for (int m = 0; m < a.M; m++)
+            for (int h = 0; h < a.Hp; h++) res_forward_row_serial(a, (size_t)m, h);
+    } else if (a.op == RES_GRAD_X) {
+        for (int m = 0; m < a.M; m++)
+            for (int h = 0; h < a.Hp; h++) res_grad_x_row_serial(a, (size_t)m, h);
+    } else {
+        for (int t = 0; t < RES_TAPS; t++)
+            for (int ci = 0; ci < a.Ci; ci++) res_grad_w_row_serial(a, t / 3, t % 3, ci);
+        res_grad_b_serial(a);
     }
     return TETRIS_OK;
 }

@@ -445,6 +445,37 @@ static int launch_kbd(tetris_batch* b, const KbdArgs& in) {
     return launched();
 }
 
+// ---------------------------------------------------------------- residual layer (tetris_res.h)
+// What the three residual-layer entry points (tetris_lib_compose.h) run after the argument rules, two launches each: the forward
+// and grad_x repack w into the batch's scratch and then run the product; grad_w writes a partial per chunk of RES_W_SAMPLES samples
+// there and then adds them up
+static int launch_res(tetris_batch* b, const ResArgs& in) {
+    ResArgs a = in;
+    if (a.op == RES_FWD) { a.N = a.Cz; a.K = a.Ci; } else { a.N = a.Ci; a.K = a.Cz; }
+    a.NP = res_pad32(a.N); a.KP = res_pad32(a.K);
+    a.chunks = res_w_chunks(a.M);
+    const size_t packed = (size_t)RES_TAPS * a.NP * a.KP, per = (size_t)RES_TAPS * a.Ci * a.Co + (size_t)a.Co;      // elements of the repacked w; floats of a partial with its bias row
+    const size_t words = a.op == RES_GRAD_W ? (size_t)a.chunks * per : a.f16 ? packed / 2 : packed;
+    int rc = b->res_scratch.ensure(words, b->stream);
+    if (rc || (rc = enqueue(b, Enqueue::STATE))) return rc;          // (the batch's scratch)
+    a.packed = b->res_scratch.d; a.partial = reinterpret_cast<float*>(b->res_scratch.d);
+    const dim3 block(RES_THREADS), conv_grid((unsigned)((size_t)a.M * res_bands(a.Hp)), (unsigned)((a.NP + RES_NB - 1) / RES_NB));
+    with_flag(a.f16 != 0, [&](auto F16) {
+        if (a.op == RES_FWD) {
+            hipLaunchKernelGGL((k_res_pack<F16(), true>), dim3(blocks_for(packed, RES_THREADS)), block, 0, b->stream, a, (void*)b->res_scratch.d);
+            hipLaunchKernelGGL((k_res_conv<F16(), true>), conv_grid, block, 0, b->stream, a);
+        } else if (a.op == RES_GRAD_X) {
+            hipLaunchKernelGGL((k_res_pack<F16(), false>), dim3(blocks_for(packed, RES_THREADS)), block, 0, b->stream, a, (void*)b->res_scratch.d);
+            hipLaunchKernelGGL((k_res_conv<F16(), false>), conv_grid, block, 0, b->stream, a);
+        } else {
+            const dim3 grid((unsigned)a.chunks, (unsigned)((a.Ci + RES_W_CHANNELS - 1) / RES_W_CHANNELS), (unsigned)(a.Co / RES_W_CHANNELS));
+            hipLaunchKernelGGL((k_res_grad_w<F16()>), grid, block, 0, b->stream, a);
+            hipLaunchKernelGGL(k_res_grad_w_reduce, dim3(blocks_for(per, RES_THREADS)), block, 0, b->stream, a);
+        }
+    });
+    return launched();
+}
+
 // ---------------------------------------------------------------- network inputs (tetris_input.h)
 // What tetris_net_input_dev (tetris_lib_compose.h) runs after the argument rules: one launch, a workgroup per INPUT_BLOCK samples
 // of a slot

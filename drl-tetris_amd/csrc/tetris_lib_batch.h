@@ -253,8 +253,10 @@ struct tetris_batch {
     Scratch<float> kstep_values;
     // the keyboard convolution: w repacked for the matrix unit (forward, grad_x) or grad_w's partial sums (grown on demand)
     Scratch<uint32_t> kbd_scratch;
+    // the residual layer: likewise
+    Scratch<uint32_t> res_scratch;
     void release_scratch() {
-        kbd_scratch.release();
+        kbd_scratch.release(); res_scratch.release();
         plan_slabs.release(); iota.release(); plan_status.release(); policy_scores.release(); words_before.release();
         select_blocks.release(); replay_offsets.release(); replay_sort.release(); loss_scratch.release(); kstep_values.release();
     }

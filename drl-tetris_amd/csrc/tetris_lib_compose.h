@@ -23,6 +23,9 @@ static int launch_input(B*, const InputArgs& ia) { return input_run_serial(ia); 
 // (and the keyboard convolution: launch_kbd of tetris_lib_agent.h, or kbd_run_serial)
 template <class B>
 static int launch_kbd(B*, const KbdArgs& a) { return kbd_run_serial(a); }
+// (and the residual layer: launch_res of tetris_lib_agent.h, or res_run_serial)
+template <class B>
+static int launch_res(B*, const ResArgs& a) { return res_run_serial(a); }
 
 extern "C" {
 
@@ -190,6 +193,30 @@ int tetris_kbd_conv_grad_w_dev(tetris_batch* b, const tetris_kbd_conv* k) {
     KbdArgs a;
     if ((rc = kbd_args(k, KBD_GRAD_W, a))) return rc;
     return launch_kbd(b, a);
+}
+
+int tetris_res_layer_dev(tetris_batch* b, const tetris_res_layer* r) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    ResArgs a;
+    if ((rc = res_args(r, RES_FWD, a))) return rc;
+    return launch_res(b, a);
+}
+
+int tetris_res_layer_grad_x_dev(tetris_batch* b, const tetris_res_layer* r) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    ResArgs a;
+    if ((rc = res_args(r, RES_GRAD_X, a))) return rc;
+    return launch_res(b, a);
+}
+
+int tetris_res_layer_grad_w_dev(tetris_batch* b, const tetris_res_layer* r) {
+    int rc = check_batch(b);
+    if (rc) return rc;
+    ResArgs a;
+    if ((rc = res_args(r, RES_GRAD_W, a))) return rc;
+    return launch_res(b, a);
 }
 
 int tetris_rollout_random(tetris_batch* b, int launches, int steps_per_launch, uint32_t policy_seed, uint64_t first_step,

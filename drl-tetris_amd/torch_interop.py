@@ -37,7 +37,8 @@ def columns_to_deltas(cols, player, before, count, height, out=None, small_fill=
 
 def kbd_weight_from_conv2d(weight):
     """torch's conv2d kernel [O, C, Hp, 3] (OIHW) -> the keyboard convolution's [Hp, 3, C, O] (HWIO, the reference variable's own
-    layout: a checkpoint's kernel needs no transpose), contiguous."""
+    layout: a checkpoint's kernel needs no transpose), contiguous.  The permute is the same for any kernel size: a residual
+    layer's [Co, Ci, 3, 3] becomes its [3, 3, Ci, Co], and kbd_weight_to_conv2d takes it back."""
     return weight.permute(2, 3, 1, 0).contiguous()
 
 
@@ -53,6 +54,34 @@ def keyboard_conv_init(Hp, C, K, device=None, generator=None):
     weight = torch.zeros(int(Hp), 3, int(C), 4 * int(K), dtype=torch.float32, device=device)
     bias = torch.randn(4 * int(K), dtype=torch.float32, generator=generator) * 1e-5
     return weight, bias.to(device) if device is not None else bias
+
+
+def residual_layer_init(Ci, Co, device=None, generator=None):
+    """The reference's initialisation of a residual layer (agents/networks/builders/build_blocks.py:28, 50): -> (weight float32
+    [3, 3, Ci, Co] (HWIO) drawn glorot-uniform, |w| <= sqrt(6 / (fan_in + fan_out)) with fan_in = 9 Ci and fan_out = 9 Co; bias
+    float32 [Co], all zeros)."""
+    import torch
+    limit = (6.0 / (9 * int(Ci) + 9 * int(Co))) ** 0.5
+    weight = (torch.rand(3, 3, int(Ci), int(Co), dtype=torch.float32, generator=generator) * 2.0 - 1.0) * limit
+    bias = torch.zeros(int(Co), dtype=torch.float32)
+    return (weight.to(device), bias.to(device)) if device is not None else (weight, bias)
+
+
+def pad_channels(x, multiple=8):
+    """x [M, C, Hp, 12] -> [M, C', Hp, 12] in channels_last memory, C' = C rounded up to `multiple`, the new channels zero: what
+    TorchEnv.residual_layer's rule Ci % 8 == 0 asks of the reference's first layer (1..5 channels from tr.inputs) and of its
+    second block's input (128 + len(vector)).  A zero channel stays zero through the ADD join and ELU where it lies at or past Co (the
+    join passes it through, and elu(0) = 0) and adds nothing where it lies below; whatever weights face it multiply zeros, so a padded
+    trunk computes the unpadded trunk's numbers in the real channels; the rows of the first kernel that face the padding
+    get a zero gradient.  x itself when C is a multiple already and its memory is channels_last."""
+    import torch
+    M, Cn, Hp, Wd = x.shape
+    Cp = -(-int(Cn) // int(multiple)) * int(multiple)
+    if Cp == Cn and x.is_contiguous(memory_format=torch.channels_last):
+        return x
+    out = torch.zeros(M, Cp, Hp, Wd, dtype=x.dtype, device=x.device).contiguous(memory_format=torch.channels_last)
+    out[:, :Cn] = x
+    return out
 
 
 class TorchEnv:
@@ -724,6 +753,107 @@ class TorchEnv:
         seen): use the output — heads, select, loss — and call backward before the next keyboard_conv of the same shapes; the
         gradients handed back are reused likewise.  Nothing waits for the GPU."""
         return self._kbd_function().apply(x, weight, bias)
+
+    # ---- residual layer (include/tetris_hip.h: tetris_res_layer_dev and its _grad_x_dev / _grad_w_dev): one layer of the trunk's
+    # residual_block (agents/networks/builders/build_blocks.py:8-64), differentiable
+    def _res_function(self):
+        torch = self.torch
+        if getattr(self, "_res_fn", None) is not None:
+            return self._res_fn
+        from . import capi
+        env, p = self, self._ptr
+
+        class ResidualLayer(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, weight, bias, join, activation, slot):
+                assert x.dtype in (torch.float32, torch.float16) and x.is_cuda, "x is a float32 or float16 device tensor"
+                assert x.dim() == 4 and x.shape[3] == 12 and x.shape[0] >= 1, "x must be [M, Ci, Hp, 12]"
+                M, Ci, Hp = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+                assert weight.dim() == 4 and tuple(weight.shape[:3]) == (3, 3, Ci), "weight must be [3, 3, Ci, Co]"
+                Co = int(weight.shape[3])
+                assert bias.dtype == torch.float32 and tuple(bias.shape) == (Co,) and bias.is_cuda, "bias is a float32 device tensor [Co]"
+                Cout = capi.res_out_channels(Ci, Co, join)
+                xl = env._kbd_input(x.detach())
+                w = weight.detach().to(x.dtype).contiguous()
+                b32 = bias.detach().contiguous()
+
+                def make(cap):
+                    last = lambda c: torch.zeros(cap, c, Hp, 12, dtype=x.dtype, device=env.dev).contiguous(memory_format=torch.channels_last)      # noqa: E731
+                    return (last(Cout), last(Ci), torch.zeros(3, 3, Ci, Co, dtype=torch.float32, device=env.dev), torch.zeros(Co, dtype=torch.float32, device=env.dev))
+                base = ("res_layer", Hp, Ci, Co, join, activation, x.dtype)
+                ctx.pending = None
+                if slot is None:
+                    # a set of its own for every forward of these shapes whose backward is still to come (they end in the
+                    # reverse order, so the count is a stack), and never the set whose output this layer reads
+                    pending = env._res_pending.get(base, 0)
+                    out = env._loss_buffers(base + (("auto", pending),), M, make)[0]
+                    index = pending + 1 if out.data_ptr() == xl.data_ptr() else pending
+                    slot = ("auto", index)
+                    if any(ctx.needs_input_grad[:3]):
+                        ctx.pending = base
+                        env._res_pending[base] = index + 1
+                out, grad_x, grad_w, grad_b = env._loss_buffers(base + (slot,), M, make)
+                kw = dict(m=M, height=Hp, in_channels=Ci, out_channels=Co, join=join, activation=activation, f16=x.dtype == torch.float16)
+                env.b.res_layer_dev(env.b.res_layer(x=p(xl), w=p(w), bias=p(b32), out=p(out), **kw))
+                ctx.x, ctx.w, ctx.y, ctx.kw, ctx.grads, ctx.types = xl, w, out, kw, (grad_x[:M], grad_w, grad_b), (weight.dtype, bias.dtype)
+                return out[:M]
+
+            @staticmethod
+            def backward(ctx, grad_out):
+                (grad_x, grad_w, grad_b), (wdt, bdt) = ctx.grads, ctx.types
+                g = grad_out.to(ctx.x.dtype).contiguous(memory_format=torch.channels_last)
+                need_x, need_w, need_b = ctx.needs_input_grad[:3]
+                if ctx.pending is not None:
+                    env._res_pending[ctx.pending] = max(env._res_pending.get(ctx.pending, 0) - 1, 0)
+                    ctx.pending = None
+                if need_x:
+                    env.b.res_layer_grad_x_dev(env.b.res_layer(w=p(ctx.w), y=p(ctx.y), grad_out=p(g), grad_x=p(grad_x), **ctx.kw))
+                if need_w or need_b:
+                    env.b.res_layer_grad_w_dev(env.b.res_layer(x=p(ctx.x), y=p(ctx.y), grad_out=p(g), grad_w=p(grad_w), grad_b=p(grad_b), **ctx.kw))
+                return (grad_x if need_x else None, grad_w.to(wdt) if need_w else None, grad_b.to(bdt) if need_b else None, None, None, None)
+        self._res_fn, self._res_pending = ResidualLayer, {}
+        return self._res_fn
+
+    def residual_release(self):
+        """Forget the forwards of residual_layer whose backward never came (a graph that was dropped): their buffer sets are
+        handed out again."""
+        if getattr(self, "_res_pending", None) is not None:
+            self._res_pending.clear()
+
+    def residual_layer(self, x, weight, bias, join="add", activation="elu", slot=None):
+        """One layer of the reference's residual_block (agents/networks/builders/build_blocks.py:43-57): conv2d(3 x 3, 'same'),
+        peephole_join(mode=join) (agents/networks/network_utils.py:52-64), activation, fused on the matrix cores.  x [M, Ci, Hp, 12]
+        float32 or float16, Ci a multiple of 8 in 8..512 (pad_channels gives that), Hp in 4..33; weight [3, 3, Ci, Co] (HWIO:
+        kbd_weight_from_conv2d gives it from a conv2d kernel, residual_layer_init draws it), Co a multiple of 32 in 32..512, cast to
+        x's type when it is a float32 master weight; bias float32 [Co]; join "add" / "truncate_add" / None; activation "elu" / None.
+        -> a channels_last tensor [M, Cout, Hp, 12] in x's type, Cout = max(Ci, Co) / min(Ci, Co) / Co, differentiable with respect
+        to x, weight and bias (grad_w and grad_b in the parameters' types).  x is read in place when its memory is channels_last
+        (tr.inputs(channels_last=True), pad_channels and this function's own output give that), so layers chain without copies and
+        the last one feeds keyboard_conv without one; otherwise it is COPIED once.  Device tensors, reused per shape, settings and
+        element type (the leading M samples of one set that grows to the largest M seen).  Backward reads each layer's stored
+        input and output, so layers whose shapes agree must not share a set: with slot=None (the default) a forward that
+        needs a gradient takes a set of its own until its backward has run — the sets are counted per shape, and the same ones
+        come round in the next step —, and a forward without one alternates between two sets so that a chain never writes what
+        it reads.  A graph that is dropped without backward keeps its sets until residual_release().  slot=<any hashable> names
+        the set instead; then the caller keeps layers of equal shape apart.  Nothing waits for the GPU."""
+        from . import capi
+        assert join in capi.RES_JOINS and activation in capi.RES_ACTS, "join is 'add', 'truncate_add' or None; activation 'elu' or None"
+        return self._res_function().apply(x, weight, bias, join or "none", activation or "none", slot)
+
+    def residual_block(self, x, params, output_activation="elu", output_n_filters=None, slot=None):
+        """The reference's residual_block with its defaults (peepholes=True, no pools, no dropout, no normalisation): params is a
+        list of (weight [3, 3, Ci, Co], bias [Co]), one per layer; every layer is ADD + ELU, the last one takes output_activation
+        and, when output_n_filters is given (it must be the last weight's Co), TRUNCATE_ADD.  -> [M, Cout, Hp, 12], channels_last.
+        slot=None: every layer finds its own buffer set (residual_layer); slot=k: the layers take the sets k, k + 1, ..."""
+        n = len(params)
+        for i, (weight, bias) in enumerate(params):
+            last = i == n - 1
+            join = "truncate_add" if last and output_n_filters is not None else "add"
+            if last and output_n_filters is not None:
+                assert int(weight.shape[3]) == int(output_n_filters), "the last layer's Co is output_n_filters"
+            x = self.residual_layer(x, weight, bias, join=join, activation=output_activation if last else "elu",
+                                    slot=None if slot is None else slot + i)
+        return x
 
     # ---- k-step target estimator (include/tetris_hip.h: tetris_kstep_target_dev): model.compute_targets
     # (agents/sventon_agent/sventon_agent_dqn_trainer.py:49-59, agents/networks/value_estimator.py:51-88)

@@ -1179,6 +1179,63 @@ int tetris_kbd_conv_dev(tetris_batch *b, const tetris_kbd_conv *k);
 int tetris_kbd_conv_grad_x_dev(tetris_batch *b, const tetris_kbd_conv *k);
 int tetris_kbd_conv_grad_w_dev(tetris_batch *b, const tetris_kbd_conv *k);
 
+/* ---- residual layer: one layer of the trunk — 3 x 3 'same' convolution, peephole join, ELU — forward and gradients, on the
+ * matrix cores -----------------------------------------------------------------------------------------------------------------
+ * replaces: one layer of residual_block (agents/networks/builders/build_blocks.py:8-64) — tf.layers.conv2d(3 x 3, 'same'),
+ * peephole_join(x, y, mode = "add" | "truncate_add") (agents/networks/network_utils.py:52-64), elu — and autograd's backward
+ * through it.  Not included: normalization = "layer", dropout and pools, strides and filter sizes other than 3 x 3, the 5 x 5
+ * pooled value stream, conv_shape_vector and the concat in front of the second block, bfloat16, an image width other than 12,
+ * fusing consecutive layers, the optimiser.  The definition is in drl-tetris_amd/csrc/tetris_res.h.  Device pointers, asynchronous
+ * on the batch's stream, nothing waits; the batch's games are neither read nor written, every batch shape serves; the batch's
+ * scratch holds the repacked kernel and grad_w's partial sums, so calls on one batch are ordered by its stream.
+ *   Hp = height in 4..33, 12 columns; Ci = in_channels, a multiple of 8 in 8..512; Co = out_channels, a multiple of 32 in 32..512;
+ *   Cout = Co (TETRIS_RES_JOIN_NONE), max(Ci, Co) (_ADD), min(Ci, Co) (_TRUNCATE_ADD).  d_x, d_grad_x [M][Hp][12][Ci] (NHWC: the
+ *   memory of a torch channels_last tensor [M, Ci, Hp, 12]); d_w [3][3][Ci][Co] (HWIO, the reference variable's layout); d_bias
+ *   float32 [Co]; d_out, d_y, d_grad_out [M][Hp][12][Cout], d_y being d_out as the forward wrote it; d_grad_w float32 like d_w;
+ *   d_grad_b float32 [Co].  d_x, d_w, d_out, d_y, d_grad_out and d_grad_x are float32, or all binary16 with TETRIS_RES_F16.
+ *     z[m][h][j][o] = bias[o] + sum_(a, b in 0..2) sum_ci x[m][h + a - 1][j + b - 1][ci] w[a][b][ci][o]      x = 0 outside the image
+ *     p[c]   = (c < Co ? z[c] : 0) + (join != NONE and c < Ci ? x[m][h][j][c] : 0);   out[c] = ELU ? (p > 0 ? p : expm1f(p)) : p
+ *     e[c]   = round(grad_out[c] (ELU and y[c] <= 0 ? y[c] + 1 : 1)) to the element type;   gz[o] = o < min(Co, Cout) ? e[o] : 0
+ *     grad_x[m][h][j][ci] = sum_(a, b) sum_o gz[m][h - a + 1][j - b + 1][o] w[a][b][ci][o] + (join != NONE and ci < Cout ? e[ci] : 0)
+ *     grad_w[a][b][ci][o] = sum_m sum_h sum_j x[m][h + a - 1][j + b - 1][ci] gz[m][h][j][o];   grad_b[o] = sum_m sum_h sum_j gz[m][h][j][o]
+ *   Products and sums in float32, p unrounded into the activation, one rounding to nearest even on the way out; the order of the
+ *   sums is the matrix unit's and is not specified; no atomics: a call repeated on the same inputs gives the same bytes.  Every
+ *   element of every output is written, nothing past it; the zero border is never a read.
+ *   tetris_res_layer_dev reads d_x, d_w, d_bias; writes d_out.  tetris_res_layer_grad_x_dev reads d_grad_out, d_w and, with ELU,
+ *   d_y; writes d_grad_x.  tetris_res_layer_grad_w_dev reads d_x, d_grad_out and, with ELU, d_y; writes d_grad_w and d_grad_b.
+ *   Arrays a call neither reads nor writes may be NULL.
+ * TETRIS_E_ARG, with nothing written: a NULL argument struct or a NULL array the call reads or writes; M < 1; height outside
+ * [4, 33]; in_channels no multiple of 8 or outside [8, 512]; out_channels no multiple of 32 or outside [32, 512]; an unknown join,
+ * activation or flag; an array of the call that is not 16-byte aligned; an output of the call that overlaps one of its inputs.   */
+#define TETRIS_RES_F16 1   /* d_x, d_w, d_out, d_y, d_grad_out and d_grad_x are IEEE binary16 instead of float32 */
+#define TETRIS_RES_JOIN_NONE 0
+#define TETRIS_RES_JOIN_ADD 1
+#define TETRIS_RES_JOIN_TRUNCATE_ADD 2
+#define TETRIS_RES_ACT_NONE 0
+#define TETRIS_RES_ACT_ELU 1
+typedef struct tetris_res_layer {
+    const void    *d_x;             /* [M][height][12][in_channels], 16-byte aligned */
+    const void    *d_w;             /* [3][3][in_channels][out_channels], 16-byte aligned */
+    const float   *d_bias;          /* [out_channels], 16-byte aligned */
+    const void    *d_y;             /* backward with ELU: the forward's d_out, 16-byte aligned */
+    const void    *d_grad_out;      /* backward: like d_out, 16-byte aligned */
+    int            M;
+    int            height;          /* Hp: 4..33 */
+    int            in_channels;     /* Ci: a multiple of 8 in 8..512 */
+    int            out_channels;    /* Co: a multiple of 32 in 32..512 */
+    int            join;            /* TETRIS_RES_JOIN_* */
+    int            activation;      /* TETRIS_RES_ACT_* */
+    int            flags;           /* TETRIS_RES_F16 */
+    int            reserved;        /* 0 */
+    void          *d_out;           /* forward: [M][height][12][Cout], 16-byte aligned */
+    void          *d_grad_x;        /* like d_x */
+    float         *d_grad_w;        /* like d_w, float32 */
+    float         *d_grad_b;        /* [out_channels] */
+} tetris_res_layer;
+int tetris_res_layer_dev(tetris_batch *b, const tetris_res_layer *r);
+int tetris_res_layer_grad_x_dev(tetris_batch *b, const tetris_res_layer *r);
+int tetris_res_layer_grad_w_dev(tetris_batch *b, const tetris_res_layer *r);
+
 /* Built-in synthetic rollout = the worker loop of drl_tetris/worker.py:91-118 with a random policy
  * (SURVEY.md §8d): per env-step  Philox4x32-10(policy_seed; game, step) -> (r = w0 & 3,
  * t = w1 mod 10), acting player = step mod P, perform_action, auto-reset of finished games with
